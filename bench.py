@@ -1,6 +1,6 @@
 """ELBO-gradient updates/sec on a 1M-row mini-batch (BASELINE.json's metric), MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling both|weak|strong] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--config cfg2] [--scaling both|weak|strong]
 
 Default workload = BASELINE config 2 (the configuration the metric is quoted on): Bayesian
 linear regression, 1M x 256 float32 mini-batch, reparameterisation-trick ELBO, S = 8, Adam.
@@ -18,21 +18,30 @@ id, barrier, max over ranks); the data path's one collective is bsc_allreduce_su
 --scaling strong: ONE global mini-batch of the configured size (the metric's "1M-row mini-batch at
 1/2/4/8 GPUs") is split into N row blocks.  --scaling weak: every rank holds its own full-size
 mini-batch, `value` counts 1M-row mini-batch equivalents per second over all ranks.  Default
-(`both`): at N > 1 the line carries BOTH -- `value` / `scaling` = the metric's reading (strong) and
-`value_weak` beside it; at N = 1 the two coincide.
+(`both`): at N > 1 `value` / `scaling` = the metric's reading (strong), with --full `value_weak`
+beside it; at N = 1 the two coincide.
 
 What `value` is on config 2 (the metric's configuration): the update loop ROTATES over --batches
 (default 3) distinct mini-batches resident in HBM, a different one every step, as an SVI loop over
 fresh subsamples does (README.md:69-79) -- nothing of a step's 1.03 GB is left in the 256 MiB
 Infinity Cache for the next.  The same loop over ONE resident mini-batch (alternating sweeps, each
-pass starting in the rows the previous one left on-die) is timed beside it: `value_same_batch`,
-`roofline.same_batch`.
+pass starting in the rows the previous one left on-die) is timed beside it with --full:
+`value_same_batch`, `roofline.same_batch`.
 
-The timed region is EXACTLY K steps between barrier + synchronize; it is repeated (same K) until
---min-timed-s of it has been measured, `ms_per_step` / `value` are the MEDIAN block's and
-`timed_blocks` gives min / median / max.
+The timed region is EXACTLY K steps between barrier + synchronize, timed once: `ms_per_step` is
+its time / K.  --min-timed-s T repeats the block (same K) until T s of it have been measured;
+`ms_per_step` / `value` are then the MEDIAN block's and `timed_blocks` gives min / median / max.
 
-Prints ONE JSON line on rank 0 (DESIGN.md section 7).
+A plain run sets up, warms up (spin-up launches + W steps), times the K steps and prints the line.
+Everything else is --full: event pairs inside the timed region (allreduce_us, finish_us), the
+roofline burst after it, the same-batch loop, the read ceiling and the plugin-surface loop of
+config 2, the weak reading beside the strong one at N > 1, and the cpu_baseline legs.
+
+--dump-outputs DIR writes what the timed loop's last step computed (the arrays a caller of the
+driver reads off it) as DIR/<name>.npy, float32 / float64, at most 64 MB in all.  The inputs are
+seeded, so the same arguments give the same inputs run after run.
+
+Prints ONE JSON line on rank 0 (DESIGN.md section 6).
 """
 import argparse
 import json
@@ -65,8 +74,9 @@ def parse_args(argv=None):
     ap.add_argument("--batches", type=int, default=3,
                     help="cfg2: distinct resident mini-batches the update loop rotates over (1 = the same "
                          "mini-batch every step)")
-    ap.add_argument("--min-timed-s", type=float, default=0.25,
-                    help="repeat the timed block of K steps until this much of it has been measured")
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="repeat the timed block of K steps until this much of it has been measured (0: one block, "
+                         "exactly K timed steps)")
     ap.add_argument("--max-blocks", type=int, default=100)
     ap.add_argument("--rows", type=int, default=None,
                     help="mini-batch rows (cfg4: documents): per GPU when weak, global when strong; "
@@ -113,7 +123,16 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic", default="survey", choices=["survey", "device"],
                     help="survey: the SURVEY 8(d) numpy RandomState inputs (host-generated, seconds); "
                          "device: torch.randn on the GPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: event pairs in the timed region, the roofline "
+                         "burst, config 2's same-batch loop, read ceiling and plugin-surface loop, the weak reading at "
+                         "N > 1 and the cpu_baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------
@@ -195,6 +214,38 @@ class Workload:
 
     def step(self):
         raise NotImplementedError
+
+    def outputs(self):         # {name: array} of the last step, as a caller of the driver reads them
+        raise NotImplementedError
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write {name: array} as out_dir/<name>.npy, float64 where the array is float64 (or integer), float32 otherwise.
+    Past `limit` bytes in all, the budget is shared out smallest array first: an array that fits its even share of
+    what is left is written whole, a larger one as a fixed seeded sample of its elements (flat indices drawn by
+    default_rng(0), sorted), out_dir/<name>_sample.npy.  Returns the file names."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    written, left = [], limit
+    order = sorted(host, key=lambda n: (host[n].nbytes, n))
+    for i, name in enumerate(order):
+        a = host[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written.append(name + ".npy")
+    return written
 
 
 class Cfg2(Workload):
@@ -328,6 +379,13 @@ class Cfg2(Workload):
 
     def result(self):
         return {"final_elbo": float(self.model.elbo.item())}
+
+    def outputs(self):
+        if self.engine is not None:     # the plugin surface hands back its own parameter layout
+            e = self.engine
+            return {"lam": e.lam, "grad": e.grad, "elbo": [e.elbo]}
+        m = self.model
+        return {"lam": m.lam.cpu().numpy(), "grad": m.grad.cpu().numpy(), "elbo": m.elbo.cpu().numpy()}
 
     def roofline(self, avg_s):
         algo = 4.0 * self.rows * self.D + 4.0 * self.rows      # X and y read once per launch
@@ -486,6 +544,10 @@ class Cfg3(Workload):
     def result(self):
         return {"final_elbo": float(self.model.elbo.item()), "final_bound_term": float(self.model.lse.item())}
 
+    def outputs(self):
+        m = self.model
+        return {"eta": m.eta.cpu().numpy(), "elbo": m.elbo.cpu().numpy(), "bound_term": m.lse.cpu().numpy()}
+
     def roofline(self, avg_s):
         if self.mfma_split:
             # forward on three terms (6 products), backward on two (3): 4.5 bf16 products per f32 product on average.
@@ -572,6 +634,10 @@ class Cfg5(Workload):
 
     def result(self):
         return {"final_elbo": float(self.model.elbo.item())}
+
+    def outputs(self):
+        m = self.model
+        return {"lam": m.lam.cpu().numpy(), "grad": m.grad.cpu().numpy(), "elbo": m.elbo.cpu().numpy()}
 
     def roofline(self, avg_s):
         # 32 flop/B: the fp32-MFMA time (209 us) exceeds the HBM time (129 us) -> MFMA binds
@@ -665,6 +731,10 @@ class Cfg4(Workload):
 
     def result(self):
         return {"final_elbo": float(self.model.elbo.item()), "lambda_sum": float(self.model.lam.sum().item())}
+
+    def outputs(self):
+        m = self.model
+        return {"lam": m.lam.cpu().numpy(), "elbo": m.elbo.cpu().numpy()}
 
     def roofline(self, avg_s):
         split = self.mfma_split
@@ -792,17 +862,18 @@ def run_rank(args):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return [float(v) for v in t]
 
-    def measure(wl, spin_up=True, burst=True):
+    def measure(wl, spin_up=True, burst=True, capture=False):
         """Spin-up, W warm-up steps, then timed blocks of EXACTLY K steps each (barrier + synchronize on both
-        sides, max over ranks), repeated until --min-timed-s has been measured; then the dominant kernel's
-        burst.  Returns a dict."""
+        sides, max over ranks), repeated until --min-timed-s has been measured; with --full, then the dominant
+        kernel's burst.  `capture`: the last step's outputs are copied to the host (m["outputs"]) before anything
+        else runs.  Returns a dict."""
         spin_launches = int(args.spin_up_ms / wl.kernel_ms) if (spin_up and args.spin_up_ms > 0) else 0
         for _ in range(spin_launches):
             wl.spin()
         for _ in range(args.warmup):
             wl.step()
         torch.cuda.synchronize()
-        timing = not args.no_kernel_timing
+        timing = args.full and not args.no_kernel_timing
         ctx.profile(max(1, args.time_every) if timing else 0)
         blocks, n_blocks = [], 1
         while len(blocks) < n_blocks:
@@ -819,6 +890,7 @@ def run_rank(args):
                 n_blocks = max(1, min(args.max_blocks, int(-(-args.min_timed_s // max(first, 1e-9)))))
         in_region = {s: ctx.profile_read(s) for s in (0, 1, 2)} if timing else {}
         ctx.profile(0)
+        outputs = wl.outputs() if capture else None
         # dedicated burst AFTER the timed region: every launch of the dominant kernel timed on the
         # launch stream, so roofline.avg_launch_us rests on >= 50 samples whatever --steps was
         burst_ms, burst_n, pairs = 0.0, 0, (0.0, 0)
@@ -842,7 +914,7 @@ def run_rank(args):
         blocks = sorted(reduce_max(blocks))
         median = blocks[len(blocks) // 2] if len(blocks) % 2 else 0.5 * (blocks[len(blocks) // 2 - 1] + blocks[len(blocks) // 2])
         return {"blocks": blocks, "median_s": median, "in_region": in_region, "burst": (burst_ms, burst_n),
-                "burst_pairs": pairs, "spin_launches": spin_launches}
+                "burst_pairs": pairs, "spin_launches": spin_launches, "outputs": outputs}
 
     def block_stats(m):
         k = args.steps
@@ -852,7 +924,8 @@ def run_rank(args):
 
     import copy
     if args.scaling == "both":
-        modes = ["strong", "weak"] if world > 1 else ["weak"]
+        # (the weak reading beside the strong one is --full)
+        modes = (["strong", "weak"] if args.full else ["strong"]) if world > 1 else ["weak"]
     else:
         modes = [args.scaling]
     runs = {}
@@ -862,20 +935,24 @@ def run_rank(args):
         margs = copy.copy(args)
         margs.scaling = mode
         wl = WORKLOADS[args.config](margs, ctx, torch, rank, world)
-        m = measure(wl)
+        head_run = mode == modes[0]
+        m = measure(wl, capture=head_run and rank == 0 and args.dump_outputs is not None)
+        if m["outputs"] is not None:
+            dump_outputs(m["outputs"], args.dump_outputs)
         m["units_per_step"], m["describe"], m["config"] = wl.units_per_step, wl.describe, wl.config
-        if mode == modes[0]:
+        if head_run:
             m["roofline_wl"] = wl
             # config 2: the same loop over ONE resident mini-batch (alternating sweeps) beside the rotation
-            if args.config == "cfg2" and getattr(wl, "rotate", False):
+            if args.full and args.config == "cfg2" and getattr(wl, "rotate", False):
                 wl.set_mode("same")
                 m["same"] = measure(wl, spin_up=False)
                 wl.set_mode("rotate")
-            m["read_ceiling"] = ctx.read_probe(getattr(wl, "X_all", wl.X)) if (rank == 0 and args.config == "cfg2") else None
+            m["read_ceiling"] = (ctx.read_probe(getattr(wl, "X_all", wl.X))
+                                 if (args.full and rank == 0 and args.config == "cfg2") else None)
             m["extra"] = wl.result()
-            # config 2 by default: the same loop once more with the model written on the reference's plugin surface
+            # config 2 with --full: the same loop once more with the model written on the reference's plugin surface
             # (row P of the coverage table: recognition must reach the same kernels at the same speed)
-            if (args.config == "cfg2" and world == 1 and args.via == "driver" and not args.unfused
+            if (args.full and args.config == "cfg2" and world == 1 and args.via == "driver" and not args.unfused
                     and not args.reproducible and not args.no_via_plugin):
                 try:
                     route = wl.attach_plugin_engine()
@@ -951,6 +1028,7 @@ def run_rank(args):
                          exchange_note if exchange_note else
                          ("gloo (rehearsal: all ranks on one GPU)" if world > 1 else "none (one rank)")),
             "spin_up_launches": head["spin_launches"],
+            "full": bool(args.full),
         }
         if "plugin" in head:
             pl = head["plugin"]
@@ -978,7 +1056,7 @@ def run_rank(args):
             out["scaling_note"] = ("value = ONE global mini-batch of the configured size split over the ranks "
                                    "(the metric's reading); value_weak = one full-size mini-batch PER rank")
         out.update(head["extra"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = rwl.cpu_baseline(args.cpu_budget_s)
             except Exception as e:

@@ -163,9 +163,9 @@ def _bench(extra, env_extra=None, timeout=600):
 def test_bench_bare_two_ranks_rehearsal():
     """`python bench.py --gpus 2` from a bare shell: the parent spawns the ranks itself."""
     out = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--rows", "40000", "--no-cpu-baseline",
-                  "--spin-up-ms", "5", "--burst", "8"], {"BSC_BENCH_REHEARSAL": "1"})
-    # default --scaling both: value = ONE global mini-batch of the configured size split over the ranks (the metric's
-    # reading), value_weak = a full-size mini-batch per rank, both from the one invocation
+                  "--spin-up-ms", "5", "--burst", "8", "--full"], {"BSC_BENCH_REHEARSAL": "1"})
+    # default --scaling both with --full: value = ONE global mini-batch of the configured size split over the ranks (the
+    # metric's reading), value_weak = a full-size mini-batch per rank, both from the one invocation
     assert out["n_gpus"] == 2 and out["steps"] == 6 and out["scaling"] == "strong"
     assert out["config"]["rows_per_gpu"] == 20000 and out["config"]["global_rows"] == 40000 and out["value"] > 0
     assert out["value_weak"] > 0 and out["config_weak"]["rows_per_gpu"] == 40000
@@ -183,7 +183,7 @@ def test_bench_bare_two_ranks_rehearsal():
 
 def test_bench_world1_rccl_line():
     out = _bench(["--steps", "6", "--warmup", "2", "--rows", "40000", "--no-cpu-baseline", "--rccl-world1",
-                  "--spin-up-ms", "5", "--time-every", "1", "--burst", "50"])
+                  "--spin-up-ms", "5", "--time-every", "1", "--burst", "50", "--full"])
     assert out["rccl_ranks"] == 1 and out["allreduce_us"] is not None and out["allreduce_us"] > 0
     assert out["roofline"]["launches"] == 50 and out["roofline"]["bound"] == "hbm"
     assert out["finish_us"] is not None

@@ -6,8 +6,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/lines
 rm -rf $O && mkdir -p $O
 for cfg in cfg2 cfg3 cfg4 cfg5; do
-  timeout -k 10 300 python3 $R/bench.py --config $cfg > $O/bench_line_$cfg.json 2> $O/bench_line_$cfg.err
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -- python3 $R/bench.py --config $cfg --no-cpu-baseline > $O/prof_$cfg.log 2>&1
+  timeout -k 10 300 python3 $R/bench.py --full --config $cfg > $O/bench_line_$cfg.json 2> $O/bench_line_$cfg.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -- python3 $R/bench.py --full --config $cfg --no-cpu-baseline > $O/prof_$cfg.log 2>&1
   f=$(find $O/prof_$cfg -name "*kernel_stats.csv" | head -1)
   cp $f $O/kernel_stats_bench_$cfg.csv
   echo "$cfg done" >> $O/progress.txt

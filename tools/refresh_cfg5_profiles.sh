@@ -7,8 +7,8 @@ tag=$1
 O=$R/gpurun_out/${tag}_cfg5
 rm -rf $O && mkdir -p $O
 for terms in 0 2; do
-  timeout -k 10 300 python3 $R/bench.py --config cfg5 --mfma-split $terms > $O/bench_line_cfg5_split$terms.json 2> $O/bench_line_cfg5_split$terms.err
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --config cfg5 --mfma-split $terms --no-cpu-baseline > $O/bench_line_prof_cfg5_split$terms.json 2> $O/prof.log
+  timeout -k 10 300 python3 $R/bench.py --full --config cfg5 --mfma-split $terms > $O/bench_line_cfg5_split$terms.json 2> $O/bench_line_cfg5_split$terms.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --config cfg5 --mfma-split $terms --no-cpu-baseline > $O/bench_line_prof_cfg5_split$terms.json 2> $O/prof.log
   f=$(find $O/prof -name "*kernel_stats.csv" | head -1)
   cp $f $O/kernel_stats_bench_cfg5_split$terms.csv
   rm -rf $O/prof

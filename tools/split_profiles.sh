@@ -9,8 +9,8 @@ rm -rf $O && mkdir -p $O
 for run in "cfg3 2" "cfg4 2" "cfg4 3" "cfg5 2"; do
   set -- $run
   cfg=$1; terms=$2
-  timeout -k 10 300 python3 $R/bench.py --config $cfg --mfma-split $terms --no-cpu-baseline > $O/bench_line_${cfg}_split$terms.json 2> $O/bench_line_${cfg}_split$terms.err
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --config $cfg --mfma-split $terms --no-cpu-baseline > $O/bench_line_prof_${cfg}_split$terms.json 2> $O/prof.log
+  timeout -k 10 300 python3 $R/bench.py --full --config $cfg --mfma-split $terms --no-cpu-baseline > $O/bench_line_${cfg}_split$terms.json 2> $O/bench_line_${cfg}_split$terms.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --config $cfg --mfma-split $terms --no-cpu-baseline > $O/bench_line_prof_${cfg}_split$terms.json 2> $O/prof.log
   f=$(find $O/prof -name "*kernel_stats.csv" | head -1)
   cp $f $O/kernel_stats_bench_${cfg}_split$terms.csv
   rm -rf $O/prof
