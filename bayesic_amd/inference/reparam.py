@@ -13,6 +13,16 @@ run in reverse over the resident data.  Everything parameter-sized (S x P number
     d/d mu        = mean_s  g_s,                g_s = d log p / d z at z_s
     d/d rho       = mean_s  g_s * eps_s * e^{rho} + 1
 
+``guide="full"``: q(z) = N(mu, L L^T), L lower-triangular with L_ii = e^{rho_i} (full-rank ADVI, Kucukelbir et al.),
+lam = [mu (P) | L packed row-major, lower triangle incl. the diagonal (P(P+1)/2), rho_i in the diagonal slots]:
+
+    z_s = mu + L eps_s,   d/d mu = mean_s g_s,   d/d L_ij = mean_s g_si eps_sj (j < i),
+    d/d rho_i = mean_s g_si eps_si e^{rho_i} + 1,   ELBO = mean_s log p(data, z_s) + sum(rho) + P/2 (1 + log 2 pi)
+
+On the general route the draws and the gradient are host float64 numpy; on the fused route the finish is
+``bsc_blr_fullrank_update`` (svi/blr.py, ``covariance="full"``; it orders z as [w | xi], so the latents must list the
+weights first).  The state kept on the device (``resident``) is mean-field only: a full guide steps on the host.
+
 Noise is Philox4x32-10 keyed as in ``ScoreFunctionVI`` (and bsc_blr_noise's stream layout is
 NOT assumed: this engine shares draws with ScoreFunctionVI, so the two estimators can be compared
 on identical noise).
@@ -91,6 +101,8 @@ class ReparamVI(object):
                   the walk of the next step overlaps the device's work on this one; ``elbo`` / ``grad`` / ``lam``
                   read back on access (as on the fused route).  Without it every step waits for the device twice
                   (the draws come back, the gradient comes back) and the host does the update in numpy.
+    guide       : "diag" (mean-field, the default) or "full" (module docstring; ``lam`` then in the full layout, in the
+                  order of ``latents``; the default ``lam0`` has mu = 0, rho = log 0.05 and zero off-diagonal entries)
     replay      : resident engines only (default on).  From its third step on the engine re-issues the RECORDED list of
                   C-ABI calls of a step -- draws to gradient, every launch whose arguments do not change -- instead of
                   walking the expression again (``DeviceBackend.replay_call``): the walk costs ~28 us of Python per
@@ -99,7 +111,7 @@ class ReparamVI(object):
     """
 
     def __init__(self, log_joint, latents, data, n_samples, seed=0, lr=1e-2, backend=None,
-                 lam0=None, noise=None, graph=False, route="auto", resident=None, replay=True):
+                 lam0=None, noise=None, graph=False, route="auto", resident=None, replay=True, guide="diag"):
         from ..algebra.backend import resolve_backend
         self.backend = resolve_backend(backend)
         if log_joint.ndim != 1:
@@ -112,11 +124,22 @@ class ReparamVI(object):
                 raise ValueError("latent %s must be [samples, size] (ndim 2)" % v.name)
         self.P = sum(n for _, n in self.latents)
         self.S, self.seed, self.lr = int(n_samples), int(seed), float(lr)
+        if guide not in ("diag", "full"):
+            raise ValueError("guide must be 'diag' or 'full', got %r" % (guide,))
+        self.guide = guide
         self._fused = None
-        self._lam = np.zeros(2 * self.P)
-        if lam0 is None:
-            self._lam[self.P:] = math.log(0.05)
+        P = self.P
+        if guide == "full":
+            self._tril = np.tril_indices(P)                 # the packed order: row-major lower triangle
+            self._diag_slots = P + np.arange(P) * (np.arange(P) + 1) // 2 + np.arange(P)
+            self._lam = np.zeros(P + P * (P + 1) // 2)
+            if lam0 is None:
+                self._lam[self._diag_slots] = math.log(0.05)
         else:
+            self._lam = np.zeros(2 * P)
+            if lam0 is None:
+                self._lam[P:] = math.log(0.05)
+        if lam0 is not None:
             self._lam[:] = np.asarray(lam0, np.float64)
         self.m1, self.m2 = np.zeros_like(self._lam), np.zeros_like(self._lam)
         self._t = 0
@@ -146,6 +169,13 @@ class ReparamVI(object):
             if why is not None and route == "fused":
                 raise ValueError("route='fused': %s" % why)
         self._resident = None
+        if guide == "full" and self._fused is None:
+            if resident:
+                raise ValueError("resident=True: the state kept on the device is mean-field only (guide='diag')")
+            if self._pass_plan is not None:
+                self.route += " (stepped on the host)"
+                self.route_reason += "; the resident pass route is mean-field only, so guide='full' steps on the host"
+            resident = False
         if resident is None:        # the pass route keeps its state on the device wherever it can
             resident = self._pass_plan is not None and self._noise is None and hasattr(self.backend, "ctx")
         if resident and self._fused is None:
@@ -307,6 +337,16 @@ class ReparamVI(object):
         c0, c_xi, s_q, k_w, beta, xi_name = plan.family
         self._order = [v.name for v, _ in self.latents]          # [W, xi] or [xi, W]
         self._w_first = self._order[0] == plan.W
+        if self.guide == "full":
+            if not self._w_first:
+                return ("the full-rank finish factors Cov(z) over z = [w | xi] (a triangular L is tied to the order); "
+                        "list the weights first in `latents` for the fused route")
+            # [mu | packed L] over [w | xi]: the latents' order IS svi/blr.py's full layout
+            self._fused = BLRReparamSVI(X, y, n_samples=self.S, seed=self.seed, lr=self.lr, ctx=self.backend.ctx,
+                                        lam0=self._lam, family=(c0, c_xi, s_q, k_w, beta), covariance="full")
+            self._fused_D = D
+            self.route = "fused: bsc_blr_data_pass + bsc_blr_fullrank_update"
+            return None
         self._fused = BLRReparamSVI(X, y, n_samples=self.S, seed=self.seed, lr=self.lr, ctx=self.backend.ctx,
                                     lam0=self._to_blr_layout(self._lam), family=(c0, c_xi, s_q, k_w, beta))
         self._fused_D = D
@@ -329,10 +369,14 @@ class ReparamVI(object):
             return np.concatenate([m, [a], rho, [b]])
         return np.concatenate([[a], m, [b], rho])
 
+    def _from_fused(self, v):
+        v = v.cpu().numpy()
+        return v if self.guide == "full" else self._from_blr_layout(v)
+
     @property
     def lam(self):
         if self._fused is not None:
-            return self._from_blr_layout(self._fused.lam.cpu().numpy())
+            return self._from_fused(self._fused.lam)
         if getattr(self, "_resident", None) is not None:
             return self._resident["lam"].cpu().numpy()
         return self._lam
@@ -373,7 +417,7 @@ class ReparamVI(object):
     @property
     def grad(self):
         if self._fused is not None:
-            return self._from_blr_layout(self._fused.grad.cpu().numpy()) if self._fused.t else None
+            return self._from_fused(self._fused.grad) if self._fused.t else None
         if getattr(self, "_resident", None) is not None:
             st = self._resident
             return None if st["gmu"] is None else np.concatenate([st["gmu"].cpu().numpy(), st["grho"].cpu().numpy()])
@@ -494,8 +538,40 @@ class ReparamVI(object):
                             for v, n in self.latents], axis=1)
         return f, g
 
+    def unpack(self, lam=None):
+        """(mu [P], L [P, P]) of a full-guide lam (default: the current one); L_ii = e^{rho_i}."""
+        lam = self.lam if lam is None else np.asarray(lam, np.float64)
+        P = self.P
+        L = np.zeros((P, P))
+        L[self._tril] = lam[P:]
+        d = np.arange(P)
+        L[d, d] = np.exp(L[d, d])
+        return np.array(lam[:P]), L
+
+    def covariance(self):
+        """Cov_q(z) in the order of ``latents`` (P x P, float64): L L^T, or diag(e^{2 rho}) for the mean-field guide."""
+        if self.guide == "full":
+            _, L = self.unpack()
+            return L @ L.T
+        return np.diag(np.exp(2.0 * self.lam[self.P:]))
+
+    def _estimate_full(self, step):
+        P, S = self.P, self.S
+        lam = self.lam
+        mu, L = self.unpack(lam)
+        rho = lam[self._diag_slots]
+        eps = self.draw(step)
+        f, g = self.log_joint_and_gradient(mu[None, :] + eps @ L.T)
+        elbo = f.mean() + rho.sum() + 0.5 * P * (1.0 + _LOG_2PI)
+        gL = (g.T @ eps) / S                                     # d / d L_ij = mean_s g_si eps_sj
+        d = np.arange(P)
+        gL[d, d] = (g * eps).mean(axis=0) * np.exp(rho) + 1.0    # the diagonal through rho (the mean-field expression)
+        return elbo, np.concatenate([g.mean(axis=0), gL[self._tril]])
+
     def estimate(self, step):
         """(ELBO estimate, pathwise gradient) at the current lam with the noise of step `step`."""
+        if self.guide == "full":
+            return self._estimate_full(step)
         P = self.P
         mu, rho = self.lam[:P], self.lam[P:]
         eps = self.draw(step)

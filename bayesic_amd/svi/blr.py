@@ -9,6 +9,13 @@ bayesic/distribution/base.py:47-69.
 Model:  y_n ~ N(x_n.w, s2),  w | s2 ~ N(0, s2 I),  s2 ~ InvGamma(alpha0, beta0)
 q:      w ~ N(m, diag e^{2 rho}),  log s2 ~ N(a, e^{2b});  lam = [m, rho, a, b].
 
+``covariance="full"``: q(z) = N(mu, L L^T) over z = [w | xi] (P = D + 1), L lower-triangular with
+L_ii = e^{rho_i}; lam = [mu (P) | L packed row-major, lower triangle incl. the diagonal, rho_i in the
+diagonal slots] (include/bayesic_hip.h, bsc_blr_fullrank_update).  The data pass is the same; the finish
+is bsc_blr_fullrank_update, always behind data_pass() -> all_reduce(), so S > 8, ``reproducible=True``
+and the RCCL exchange are the mean-field driver's.  A mean-field guide cannot represent the posterior
+correlation of w that correlated features induce and shrinks its marginal variances; the full guide can.
+
 ``sweep="alternate"`` (default): the passes over a resident mini-batch alternate their direction
 so that each starts in the rows the previous one left in the Infinity Cache (158 instead of 164 us
 at 1M x 256; a shard below 256 MiB is read from the cache entirely).  ``sweep="stream"`` always walks
@@ -50,11 +57,17 @@ class BLRReparamSVI:
 
     def __init__(self, X, y, n_total=None, n_samples=8, seed=1234, lr=1e-2, alpha0=1.0,
                  beta0=1.0, ctx=None, group=None, lam0=None, fused=True, reproducible=False,
-                 sweep="alternate", family=None):
+                 sweep="alternate", family=None, covariance="diag"):
         """``family`` = (c0, c_xi, s_q, k_w, beta): the log-joint per draw as a member of
         f(w, xi; Q) = c0 + c_xi xi + e^{-xi} (-s_q Q / 2 - k_w |w|^2 / 2 - beta) instead of the
         Normal-InverseGamma model above (bsc_blr_fused_update_general) -- what ``inference.ReparamVI``
-        passes when it has recognised such a model in a symbolic log-joint."""
+        passes when it has recognised such a model in a symbolic log-joint.
+
+        ``covariance``: "diag" (the mean-field guide, default) or "full" (module docstring; ``lam0`` then in the
+        full layout, default: the mean-field default's mu and rho with zero off-diagonal entries)."""
+        if covariance not in ("diag", "full"):
+            raise ValueError("covariance must be 'diag' or 'full', got %r" % (covariance,))
+        self.covariance_kind = covariance
         self.ctx = ctx or default_context()
         dev = self.ctx.device
         self.X = X if isinstance(X, torch.Tensor) else self.ctx.to_device(X, torch.float32)
@@ -110,21 +123,30 @@ class BLRReparamSVI:
         D, S = self.D, self.S
         f64 = torch.float64
         # double-buffered state: index t & 1 is current at the start of step t+1
-        self._lam = torch.zeros((2, 2 * D + 2), dtype=f64, device=dev)
+        P = D + 1
+        n_lam = P + P * (P + 1) // 2 if covariance == "full" else 2 * D + 2
+        self._lam = torch.zeros((2, n_lam), dtype=f64, device=dev)
         if lam0 is None:
-            self._lam[0, D:2 * D] = math.log(0.1)
-            self._lam[0, 2 * D + 1] = math.log(0.1)
+            if covariance == "full":
+                diag = torch.arange(P, device=dev)
+                self._lam[0, P + diag * (diag + 1) // 2 + diag] = math.log(0.1)
+            else:
+                self._lam[0, D:2 * D] = math.log(0.1)
+                self._lam[0, 2 * D + 1] = math.log(0.1)
         else:
-            self._lam[0].copy_(torch.as_tensor(lam0, dtype=f64))
+            lam0 = torch.as_tensor(lam0, dtype=f64)
+            if covariance == "full" and lam0.numel() != n_lam:
+                raise ValueError("lam0 has %d entries; covariance='full' at D = %d needs %d" % (lam0.numel(), D, n_lam))
+            self._lam[0].copy_(lam0)
         # noise ring: NOISE_BLOCK steps are drawn per launch, two blocks resident
         self._ring = 2 * self.NOISE_BLOCK
         self._eps = torch.zeros((self._ring, S * (D + 1)), dtype=f64, device=dev)
         self._noise_upto = 0   # noise of Philox steps [0, _noise_upto) has been requested
         self._W = torch.zeros((2, S * D), dtype=torch.float32, device=dev)
         self._xi = torch.zeros((2, S), dtype=f64, device=dev)
-        self.m1 = torch.zeros(2 * D + 2, dtype=f64, device=dev)
-        self.m2 = torch.zeros(2 * D + 2, dtype=f64, device=dev)
-        self.grad = torch.zeros(2 * D + 2, dtype=f64, device=dev)
+        self.m1 = torch.zeros(n_lam, dtype=f64, device=dev)
+        self.m2 = torch.zeros(n_lam, dtype=f64, device=dev)
+        self.grad = torch.zeros(n_lam, dtype=f64, device=dev)
         self.elbo = torch.zeros(1, dtype=f64, device=dev)
         self.stats = torch.zeros(S * (D + 1), dtype=f64, device=dev)  # [Q | G]
         if self.reproducible:
@@ -221,10 +243,36 @@ class BLRReparamSVI:
     # -- unfused phases (also the multi-sample-group path) ---------------------
     def sample(self, step):
         c = self.cur
+        if self.covariance_kind == "full":
+            return self._sample_full(step)
         self._ensure_noise(step)        # (bsc_blr_sample rewrites this row with the same values)
         self.ctx.call("bsc_blr_sample", self._lam[c], self.D, self.S, self.seed, step,
                       self._eps[step % self._ring], self._W[c], self._xi[c])
         self._drawn = True
+
+    def _sample_full(self, step):
+        """The first draw z_s = mu + L eps_s of the full guide (every later one comes out of the finish): once per
+        model, in float64 on the host from bsc_blr_noise's draws."""
+        import numpy as np
+        c, D, S = self.cur, self.D, self.S
+        self._ensure_noise(step)
+        eps = self._eps[step % self._ring].cpu().numpy().reshape(S, D + 1)
+        m, L = self._unpack_full(self._lam[c].cpu().numpy())
+        z = m[None, :] + eps @ L.T
+        self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :D], np.float32).reshape(-1)))
+        self._xi[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, D])))
+        self._drawn = True
+
+    def _unpack_full(self, lam):
+        """[mu | packed L] -> (mu [P], dense L [P, P]) with L_ii = e^{rho_i}."""
+        import numpy as np
+        P = self.D + 1
+        rows, cols = np.tril_indices(P)            # row-major lower triangle: the packed order
+        L = np.zeros((P, P))
+        L[rows, cols] = lam[P:]
+        d = np.arange(P)
+        L[d, d] = np.exp(L[d, d])
+        return np.array(lam[:P], np.float64), L
 
     def data_pass(self):
         if self.reproducible:
@@ -257,12 +305,27 @@ class BLRReparamSVI:
         # stats = ((V0 + V1) + V2) + ... in shard order: one n-ary add, the same on every rank count
         self.ctx.call("bsc_elemwise", 0, 1, 1, i64([n]), self.stats, i64([1]), V, ptrs, i64([1] * V))
 
+    def _nig_family(self):
+        """Config 2 as a member of the family (bsc_blr_fused_update's coefficients)."""
+        scale = self.n_total / self.batch_rows
+        half = 0.5 * (scale * self.batch_rows + self.D)
+        return (-half * math.log(2.0 * math.pi) + self.alpha0 * math.log(self.beta0) - math.lgamma(self.alpha0),
+                -half - self.alpha0, scale, 1.0, self.beta0)
+
     def _finish(self, stats):
         """Fused gradient + Adam + next draw; flips the double buffer."""
         c, n = self.cur, 1 - self.cur
         t = self.t + 1                  # Adam step count; Philox step of the NEXT draw
         self._ensure_noise(t)
-        if self.family is None:
+        if self.covariance_kind == "full":
+            family = self._nig_family() if self.family is None else self.family
+            self.ctx.call("bsc_blr_fullrank_update", stats,
+                          self._lam[c], self._lam[n], self.m1, self.m2,
+                          self._eps[self.t % self._ring], self._W[c], self._xi[c], self.D, self.S,
+                          *family, t, self.lr, 0.9, 0.999, 1e-8, self.seed, t,
+                          self._eps[t % self._ring], 1, self._W[n], self._xi[n], self.elbo,
+                          self.grad)
+        elif self.family is None:
             self.ctx.call("bsc_blr_fused_update", stats,
                           self._lam[c], self._lam[n], self.m1, self.m2,
                           self._eps[self.t % self._ring], self._W[c], self._xi[c], self.D, self.S,
@@ -302,7 +365,8 @@ class BLRReparamSVI:
         """One ELBO-gradient update; asynchronous on the context stream."""
         if not self._drawn:
             self.sample(self.t)  # Philox step index == number of completed updates
-        if self.fused and self.world == 1 and not self.exchange.rccl and self.S <= 8 and not self.reproducible:
+        if self.fused and self.world == 1 and not self.exchange.rccl and self.S <= 8 and not self.reproducible \
+                and self.covariance_kind == "diag":
             if self.one_launch:
                 self._pass_update()         # the pass with the finish in its tail: one launch (falls back inside the library)
             else:
@@ -316,6 +380,20 @@ class BLRReparamSVI:
 
     # -- host views -----------------------------------------------------------
     def params(self):
+        """diag: m, rho, a, b.  full: m = mu [P] and the dense lower-triangular L [P, P] (w first, xi last)."""
         lam = self.lam.cpu().numpy()
         D = self.D
+        if self.covariance_kind == "full":
+            m, L = self._unpack_full(lam)
+            return dict(m=m, L=L)
         return dict(m=lam[:D], rho=lam[D:2 * D], a=lam[2 * D], b=lam[2 * D + 1])
+
+    def covariance(self):
+        """Cov_q(z) = L L^T over z = [w | xi] (P x P, host float64) of the full guide; the diagonal
+        e^{2 rho}, e^{2 b} of the mean-field one."""
+        import numpy as np
+        if self.covariance_kind == "full":
+            _, L = self._unpack_full(self.lam.cpu().numpy())
+            return L @ L.T
+        p = self.params()
+        return np.diag(np.exp(2.0 * np.concatenate([p["rho"], [p["b"]]])))

@@ -342,6 +342,30 @@ int bsc_blr_fused_update_general(bsc_ctx* ctx, const double* stats, const double
                                  uint32_t next_step, double* eps_next, int32_t eps_next_ready, float* W_next,
                                  double* xi_next, double* elbo, double* grad);
 
+/* The finish of bsc_blr_fused_update_general for a FULL-COVARIANCE Gaussian guide (full-rank ADVI, Kucukelbir et al.):
+ * q(z) = N(mu, L L^T) over z = [w (D) | xi], P = D + 1, L lower-triangular with L_ii = e^{rho_i}.
+ *     lam = [mu (P) | L packed row-major, lower triangle incl. the diagonal (P(P+1)/2)]
+ * row i of L starts at lam[P + i(i+1)/2] and its diagonal slot holds rho_i (33 410 doubles at D = 256); m1, m2 and
+ * grad have lam's layout.  Same family f(w, xi; Q) and arguments as bsc_blr_fused_update_general; per update, with
+ * eps_s in bsc_blr_noise's [S, D+1] layout (stream 0 for w, stream 1 for xi) and g_s = d f / d z at
+ * z_s = mu + L eps_s (the w part at the float32-rounded W):
+ *     ELBO = mean_s f_s + sum_i rho_i + P/2 (1 + log 2 pi)
+ *     d / d mu = mean_s g_s,   d / d L_ij = mean_s g_si eps_sj (j < i),   d / d rho_i = mean_s g_si eps_si e^{rho_i} + 1
+ * then Adam ascent on every entry (bsc_blr_fused_update's hyper-parameters and bias correction) and, when the *_next
+ * buffers are set, the next draw z'_s = mu' + L' eps'_s into W_next (float32 [S, D]) and xi_next [S].
+ * eps_next_ready = 0: the noise of next_step is drawn into eps_next first (one bsc_blr_noise launch).  With every
+ * off-diagonal entry zero the update equals the mean-field one on the same noise, term by term.
+ * stats = [Q (S) | G (S*D)] as the data pass and the all-reduce leave them (NULL is refused: the pending partials of
+ * bsc_blr_data_pass_partial are not read).  One launch of (D + 2) / 2 workgroups, workgroup k owning rows k and
+ * D - k of L; fixed-order sums, no atomics: reproducible bit for bit.  The caller double-buffers lam and the draws.
+ * Requires D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64. */
+int bsc_blr_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                            double* m2, const double* eps, const float* W, const double* xi, int32_t D, int32_t S,
+                            double c0, double c_xi, double s_q, double k_w, double beta, int64_t t, double lr,
+                            double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
+                            double* eps_next, int32_t eps_next_ready, float* W_next, double* xi_next, double* elbo,
+                            double* grad);
+
 /* ---- parameter updates --------------------------------------------------- */
 
 /* Adam ascent on a flat float64 vector; t is the 1-based step count. */
