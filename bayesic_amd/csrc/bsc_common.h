@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/bayesic_hip.h"
+#include "bsc_special.h"   // bsc_digamma_f64, bsc_lgamma_f64 (and their conventions off x > 0)
 
 constexpr int BSC_PROF_SLOTS = 3;
 constexpr int BSC_EXCHANGE_SLOTS = 16;
@@ -90,45 +91,6 @@ struct bsc_ctx {
 };
 
 // Records an event pair around one launch when ctx->profile is on.
-#if defined(__HIPCC__)
-// digamma in float64: recurrence up to x >= 8, then the asymptotic series
-//   ln x - 1/2x - 1/12x^2 + 1/120x^4 - 1/252x^6 + 1/240x^8 - 5/660x^10 + 691/32760x^12
-// (absolute error < 1e-15 there).  Shared by the Dirichlet / Normal-Gamma
-// expectations and the element-wise digamma of the executor.
-__device__ inline double bsc_digamma_f64(double x) {
-#pragma clang fp contract(off)
-    // shift x up to >= 8: psi(x) = psi(x + n) - sum_{i<n} 1/(x + i).  The sum is P'(x)/P(x) for
-    // P = prod (x + i), built with multiplies and adds, so it costs ONE division instead of n
-    // (float64 division is ~10x a multiply; this halves bsc_dirichlet_expectation)
-    double P = 1.0, dP = 0.0;
-    while (x < 8.0) {
-        dP = dP * x + P;
-        P *= x;
-        x += 1.0;
-    }
-    const double acc = -dP / P;
-    const double inv = 1.0 / x, inv2 = inv * inv;
-    const double series = inv2 * (1.0 / 12.0 - inv2 * (1.0 / 120.0 - inv2 * (1.0 / 252.0 - inv2 *
-                          (1.0 / 240.0 - inv2 * (5.0 / 660.0 - inv2 * (691.0 / 32760.0))))));
-    return acc + log(x) - 0.5 * inv - series;
-}
-
-// lnGamma in float64 by the same route: lnGamma(x) = lnGamma(x + n) - log prod_{i<n} (x + i), x + n >= 8,
-// Stirling's series there (next term 1 / (156 y^13) < 2e-14 at y = 8).  x > 0.
-__device__ inline double bsc_lgamma_f64(double x) {
-#pragma clang fp contract(off)
-    double P = 1.0;
-    while (x < 8.0) {
-        P *= x;
-        x += 1.0;
-    }
-    const double inv = 1.0 / x, inv2 = inv * inv;
-    const double series = inv * (1.0 / 12.0 - inv2 * (1.0 / 360.0 - inv2 * (1.0 / 1260.0 - inv2 *
-                          (1.0 / 1680.0 - inv2 * (1.0 / 1188.0 - inv2 * (691.0 / 360360.0))))));
-    return (x - 0.5) * log(x) - x + 0.91893853320467274178032973640562 + series - log(P);
-}
-#endif
-
 struct bsc_prof_scope {
     bsc_ctx* ctx;
     int slot;

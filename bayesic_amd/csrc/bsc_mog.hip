@@ -594,7 +594,7 @@ struct PsiLg {
 __device__ __forceinline__ PsiLg psi_lgamma_f64(double x) {
 #pragma clang fp contract(off)
     double P = 1.0, dP = 0.0;
-    while (x < 8.0) {
+    for (int k = 0; k < 8 && x < 8.0; ++k) {    // (x > 0: at most 8 steps; any other input ends as well)
         dP = dP * x + P;
         P *= x;
         x += 1.0;

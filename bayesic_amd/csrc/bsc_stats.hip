@@ -147,7 +147,7 @@ __global__ __launch_bounds__(1024) void row_sum_kernel(const float* __restrict__
 __device__ __forceinline__ double exp_digamma_minus(double x, double c) {
 #pragma clang fp contract(off)
     double P = 1.0, dP = 0.0;
-    while (x < 8.0) {
+    for (int k = 0; k < 8 && x < 8.0; ++k) {    // (x > 0: at most 8 steps; any other input ends as well)
         dP = dP * x + P;
         P *= x;
         x += 1.0;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void dirichlet_expect_bound_kernel(const float
         const int64_t r = i / cols, c = i - r * cols;
         const double x0 = (double)lam[r * ld + c];
         double x = x0, P = 1.0, dP = 0.0;
-        while (x < 8.0) {
+        for (int k = 0; k < 8 && x < 8.0; ++k) {    // (x > 0: at most 8 steps; any other input ends as well)
             dP = dP * x + P;
             P *= x;
             x += 1.0;

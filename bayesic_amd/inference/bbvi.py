@@ -203,14 +203,14 @@ class ScoreFunctionVI(object):
         return self._eps_dev.cpu().numpy()
 
     def log_joint_values(self, z):
-        """log p(data, z_s) for the rows of z [S, P]; the latents go to the device as float32."""
+        """log p(data, z_s) for the rows of z [S, P]; the latents go to the device in their declared dtypes."""
         inputs = dict(self._data)
         offset = 0
         if self._graph and self._z_dev is None:
-            self._z_dev = {v.name: self.backend.from_host(np.zeros((self.S, n), np.float32), *self._types[v.name])
-                           for v, n in self.latents}
+            self._z_dev = {v.name: self.backend.from_host(np.zeros((self.S, n), self._types[v.name][0]),
+                                                          *self._types[v.name]) for v, n in self.latents}
         for v, n in self.latents:
-            block = np.ascontiguousarray(z[:, offset:offset + n], dtype=np.float32)
+            block = np.ascontiguousarray(z[:, offset:offset + n], dtype=self._types[v.name][0])
             if self._graph:
                 import torch
                 self._z_dev[v.name].copy_(torch.from_numpy(block))

@@ -194,7 +194,10 @@ class ReparamVI(object):
               "m1": torch.zeros(2 * P, **f64), "m2": torch.zeros(2 * P, **f64),
               "eps": torch.zeros((S, P), **f64), "elbo": None, "gmu": None, "grho": None}
         if len(self.latents) > 1:
-            st["g"] = torch.zeros((S, P), dtype=torch.float32, device=dev)
+            # the latents' gradients side by side: float64 as soon as one latent is declared float64 (a float32 buffer
+            # rounded its gradient)
+            wide = any(str(np.dtype(self._types[v.name][0])) == "float64" for v, _ in self.latents)
+            st["g"] = torch.zeros((S, P), dtype=torch.float64 if wide else torch.float32, device=dev)
         EPS, MU, RHO, G, F = A.var("eps", 2), A.var("mu", 1), A.var("rho", 1), A.var("g", 2), A.var("f", 1)
         sigma = A.dimshuffle(A.exp(RHO), "x", 0)
         st["z_fn"] = (A.dimshuffle(MU, "x", 0) + sigma * EPS).compile(b).device_fn
@@ -206,6 +209,11 @@ class ReparamVI(object):
             # d Q_s / d w_s = -2 G_s joins the executor's gradient of the parameter-sized surrogate (all float64, [S, D])
             GW, C, GS = A.var("gw", 2), A.var("c", 1), A.var("G", 2)
             st["gw_fn"] = (GW + A.dimshuffle(C, 0, "x") * GS * (-2.0)).compile(b).device_fn
+            if str(np.dtype(self._types[self._pass_plan.W][0])) != "float32":
+                # the pass reads float32 W [S, D]: a fixed buffer for a float32 copy of a W declared wider (the
+                # surrogate keeps the declared dtype)
+                D = next(n for v, n in self.latents if v.name == self._pass_plan.W)
+                st["w32"] = torch.zeros((S, D), dtype=torch.float32, device=dev)
             self.route += ", state resident on the device"
         else:
             self.route = "general, state resident on the device"
@@ -244,7 +252,12 @@ class ReparamVI(object):
                 # the data term by ONE fused pass over X, y; the executor differentiates the parameter-sized surrogate
                 plan = self._pass_plan
                 X, y = self._data[plan.X], self._data[plan.y]
-                ctx.call("bsc_blr_data_pass_sweep", X, X.stride(0), y, X.shape[0], X.shape[1], inputs[plan.W], S,
+                W = inputs[plan.W]
+                if "w32" in st:         # (a recordable C-ABI call: replay and graph re-issue it with the pass)
+                    ctx.call("bsc_convert", _DT[W.dtype], _DT[torch.float32], 2, _i64(W.shape), W, _i64(W.stride()),
+                             st["w32"], _i64(st["w32"].stride()))
+                    W = st["w32"]
+                ctx.call("bsc_blr_data_pass_sweep", X, X.stride(0), y, X.shape[0], X.shape[1], W, S,
                          self._pass_Q, self._pass_G, 0)
                 small = {name: inputs[name] for name in names}
                 small[plan.Q_NAME] = b._convert(self._pass_Q, torch.float32)
