@@ -57,18 +57,14 @@ const bsc_option OPTIONS[] = {
     {"blr_waves_per_simd", &bsc_ctx::blr_waves_per_simd, 0, 8, nullptr, false},
     {"blr_nt", &bsc_ctx::blr_nt_loads, 0, 1, nullptr, false},
     {"blr_finish_block", &bsc_ctx::blr_finish_block, 256, 1024, "256,512,1024", false},
-    {"blr_pk", &bsc_ctx::blr_pk, 0, 1, nullptr, false},
     {"blr_keep", &bsc_ctx::blr_keep, -1, 1 << 20, nullptr, false},
-    {"blr_mx", &bsc_ctx::blr_mx, 0, 4, "0,1,2,4", false},           // 4 is a deletion build: checked apart
     {"blr_wide", &bsc_ctx::blr_wide, 0, 1, nullptr, false},
-    {"blr_rot", &bsc_ctx::blr_rot, 0, 15, nullptr, false},
-    {"blr_dma", &bsc_ctx::blr_dma, 0, 1, nullptr, false},
-    {"blr_q", &bsc_ctx::blr_q, 0, 1, nullptr, false},
+    // blr_q and blr_mx accept one value each: bench.py reads them to name the kernel it timed, and an unknown key is an error
+    {"blr_q", &bsc_ctx::blr_q, 1, 1, nullptr, false},
+    {"blr_mx", &bsc_ctx::blr_mx, 0, 0, nullptr, false},
     {"blr_q_dbg", &bsc_ctx::blr_q_dbg, 0, 3, nullptr, true},
     {"blr_q_bias", &bsc_ctx::blr_q_bias, 0, 400, nullptr, false},
     {"blr_q_prio", &bsc_ctx::blr_q_prio, 0, 2, nullptr, false},
-    {"blr_fold", &bsc_ctx::blr_fold, 0, 1, nullptr, false},
-    {"blr_steal", &bsc_ctx::blr_steal, 0, 500, nullptr, false},
     {"blr_stamps", &bsc_ctx::blr_stamps, 0, 1, nullptr, false},
     {"fused_map_blocks_per_cu", &bsc_ctx::fused_map_blocks_per_cu, 1, 64, nullptr, false},
     {"fused_map_flat", &bsc_ctx::fused_map_flat, 0, 1, nullptr, false},
@@ -142,21 +138,6 @@ int bsc_ctx_create(int device, void* stream, bsc_ctx** out) {
     ctx->device = device;
     ctx->stream = (hipStream_t)stream;
     ctx->cu_count = prop.multiProcessorCount;
-    // the arrival counters of the folded finish (csrc/bsc_blr.hip FoldArgs): allocated here, not on first use, so that
-    // a graph capture never meets an allocation
-    // ... and behind them the tile queues of blr_pass_q_kernel's stealing tail (StealArgs: 64 heads 256 bytes apart + one counter)
-    constexpr size_t COUNTER_BYTES = 256 + (64 * 64 + 64) * sizeof(unsigned);
-    if (hipMalloc((void**)&ctx->fold_counters, COUNTER_BYTES) == hipSuccess) {
-        if (hipMemset(ctx->fold_counters, 0, COUNTER_BYTES) != hipSuccess) {
-            (void)hipFree(ctx->fold_counters);
-            ctx->fold_counters = nullptr;
-        } else {
-            ctx->steal_heads = ctx->fold_counters + 64;
-        }
-    } else {
-        ctx->fold_counters = nullptr;
-        (void)hipGetLastError();
-    }
     *out = ctx;
     return BSC_OK;
 }
@@ -167,7 +148,6 @@ int bsc_ctx_destroy(bsc_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->workspace) (void)hipFree(ctx->workspace);
     if (ctx->stamps) (void)hipFree(ctx->stamps);
-    if (ctx->fold_counters) (void)hipFree(ctx->fold_counters);
     (void)bsc_comm_destroy(ctx);
     for (auto* v : {&ctx->prof_events[0], &ctx->prof_events[1], &ctx->prof_events[2], &ctx->prof_pool})
         for (auto& ev : *v) {
@@ -196,7 +176,7 @@ int bsc_ctx_set_option(bsc_ctx* ctx, const char* key, int64_t value) {
     BSC_REQUIRE(o != nullptr, "bsc_ctx_set_option: unknown option '%s'", key ? key : "(null)");
     BSC_REQUIRE(value_allowed(*o, value), "bsc_ctx_set_option: %s=%lld is not accepted (%s%s, range [%d, %d])", key,
                 (long long)value, o->allowed ? "one of " : "", o->allowed ? o->allowed : "any integer", o->lo, o->hi);
-    const bool wrong = (o->dbg && value != 0) || (o->field == &bsc_ctx::blr_mx && value == 4);
+    const bool wrong = o->dbg && value != 0;
     if (wrong && !ctx->profiling_builds)
         return bsc_fail(BSC_ERR_INVALID,
                         "bsc_ctx_set_option: %s=%lld selects a profiling-only kernel that computes WRONG results; set the "

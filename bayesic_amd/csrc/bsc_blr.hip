@@ -119,17 +119,6 @@ __device__ __forceinline__ void axpy4(float4& acc, float c, const float4& x) {
     acc.w = fmaf(c, x.w, acc.w);
 }
 
-// The same four FMAs as two packed ones (v_pk_fma_f32, the scalar broadcast through op_sel):
-// a packed FMA costs the MFMA pipe of the other wave what ONE scalar FMA does
-// (profiles/r01_ubench_mfma_valu_mix.txt), and the results are the same bits.
-typedef float pass_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void axpy4_pk(float4& acc, float c, const float4& x) {
-    const pass_f32x2 c2 = {c, c};
-    const pass_f32x2 lo = __builtin_elementwise_fma(c2, pass_f32x2{x.x, x.y}, pass_f32x2{acc.x, acc.y});
-    const pass_f32x2 hi = __builtin_elementwise_fma(c2, pass_f32x2{x.z, x.w}, pass_f32x2{acc.z, acc.w});
-    acc.x = lo[0]; acc.y = lo[1]; acc.z = hi[0]; acc.w = hi[1];
-}
-
 // Forward + backward for one tile; `wl` is this wave's LDS region.
 template <int ROWS>
 __device__ __forceinline__ void compute_tile(const Tile<ROWS>& t, const float4 (&w)[SG],
@@ -264,24 +253,14 @@ __global__ __launch_bounds__(PASS_BLOCK, Geo<ROWS>::OCC) void blr_pass_kernel(
     }
 }
 
-// ---- variant with the forward pass on the MFMA pipe (D == 256) -------------------
+// ---- 16-row tiles for the kernels that contract on the MFMA pipe (D == 256) -----------------
 //
 // The kernel above keeps ~83 % of the VALU issue slots busy behind the HBM stream,
 // so it slows down on boxes whose sustained shader clock is lower (measured: pure-read
 // ceiling equal or higher, pass 10-20 % slower).  fp32 MFMA has the same peak as fp32
-// VALU on this part, but it is a SEPARATE pipe: putting the forward x.w products there
-// halves the VALU work and removes the transpose-reduce altogether.
-//
-// A wave owns 16-row tiles.  The tile is written to the wave's LDS region row-major
-// (stride 260 floats) and read back twice:
-//   forward   A operand of v_mfma_f32_16x16x4_f32: lane (i = l&15, kq = l>>4) reads
-//             X[row i][16 j + 4 kq .. +3] (one ds_read_b128 feeds 4 MFMAs); B operand
-//             = W[sample l&15][same columns], 64 registers loaded once; the result
-//             D[row 4 kq + reg][sample l&15] is the 16 x 8 block of dot products
-//             (columns 8..15 of the MFMA are idle).
-//   backward  lane l reads X[row][4l..4l+3] again (conflict-free) and the residuals by
-//             LDS broadcast: acc[s] += resid(row, s) * x, as above.
-// Only the prefetched NEXT tile lives in registers (64 VGPRs); 2 waves per SIMD.
+// VALU on this part, but it is a SEPARATE pipe: the kernels below put both contractions
+// there.  A wave owns 16-row tiles, held row-major in the wave's LDS region (stride 260
+// floats).
 constexpr int MT_ROWS = 16;
 constexpr int MT_RS = GCOLS + 4;                         // LDS row stride (floats)
 constexpr int MT_WAVE_LDS = MT_ROWS * MT_RS + MT_ROWS * SG;   // tile + residual buffer
@@ -321,166 +300,11 @@ __device__ __forceinline__ void load_mtile_policy(MTile& t, const float* __restr
                        __uint_as_float(v[3]));
 }
 
-// One iteration of a wave: the tile in `t` goes to LDS and `t` takes the tile at next_row0 with
-// the cache policy STREAM (non-temporal) or not (allocating); then forward, residuals, backward.
-template <int AUX, bool PK>
-__device__ __forceinline__ void mfma_tile_step(MTile& t, float* __restrict__ tl, float* __restrict__ rb,
-                                               const float (&wreg)[GCOLS / 4], float4 (&acc)[SG],
-                                               float& qacc, const float* __restrict__ X, int64_t ldx,
-                                               const float* __restrict__ y, int64_t next_row0,
-                                               int64_t B, int lane) {
-    const int i16 = lane & 15, kq = lane >> 4;
-    const bool live = i16 < SG;                 // lanes whose MFMA column is a sample
-    // the tile to LDS, then its registers take the next tile (unconditional prefetch:
-    // tiles outside the mini-batch read zeros without touching memory)
-#pragma unroll
-    for (int r = 0; r < MT_ROWS; ++r)
-        *reinterpret_cast<float4*>(tl + r * MT_RS + 4 * lane) = t.x[r];
-    const float4 yv = t.yv;
-    load_mtile_policy<AUX>(t, X, ldx, y, next_row0, B, lane);
-    wave_lds_sync();
-
-    // forward on the MFMA pipe; two accumulators so that no MFMA waits on its predecessor
-    mfma_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
-    const float* arow = tl + i16 * MT_RS + 64 * kq;
-#pragma unroll
-    for (int j = 0; j < GCOLS / 16; j += 2) {
-        const float4 a0 = *reinterpret_cast<const float4*>(arow + 4 * j);
-        const float4 a1 = *reinterpret_cast<const float4*>(arow + 4 * j + 4);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, wreg[4 * j + 0], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, wreg[4 * j + 4], d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, wreg[4 * j + 1], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, wreg[4 * j + 5], d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, wreg[4 * j + 2], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, wreg[4 * j + 6], d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, wreg[4 * j + 3], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, wreg[4 * j + 7], d1, 0, 0, 0);
-    }
-    // result register reg of lane (i16, kq) = dot(row 4 kq + reg, sample i16)
-    if (live) {
-        const float r0 = yv.x - (d0[0] + d1[0]), r1 = yv.y - (d0[1] + d1[1]);
-        const float r2 = yv.z - (d0[2] + d1[2]), r3 = yv.w - (d0[3] + d1[3]);
-        qacc = fmaf(r0, r0, qacc); qacc = fmaf(r1, r1, qacc);
-        qacc = fmaf(r2, r2, qacc); qacc = fmaf(r3, r3, qacc);
-        float* dst = rb + (4 * kq) * SG + i16;
-        dst[0] = r0; dst[SG] = r1; dst[2 * SG] = r2; dst[3 * SG] = r3;
-    }
-    wave_lds_sync();
-
-    // backward on the VALU: rows from LDS (row-major again), residuals by broadcast
-#pragma unroll
-    for (int r = 0; r < MT_ROWS; ++r) {
-        if ((r & 3) == 0 && r) asm volatile("" ::: "memory");   // four rows of reads in flight
-        const float4 x4 = *reinterpret_cast<const float4*>(tl + r * MT_RS + 4 * lane);
-        const float4 c0 = *reinterpret_cast<const float4*>(rb + r * SG);
-        const float4 c1 = *reinterpret_cast<const float4*>(rb + r * SG + 4);
-        if (PK) {
-            axpy4_pk(acc[0], c0.x, x4); axpy4_pk(acc[1], c0.y, x4);
-            axpy4_pk(acc[2], c0.z, x4); axpy4_pk(acc[3], c0.w, x4);
-            axpy4_pk(acc[4], c1.x, x4); axpy4_pk(acc[5], c1.y, x4);
-            axpy4_pk(acc[6], c1.z, x4); axpy4_pk(acc[7], c1.w, x4);
-        } else {
-            axpy4(acc[0], c0.x, x4); axpy4(acc[1], c0.y, x4);
-            axpy4(acc[2], c0.z, x4); axpy4(acc[3], c0.w, x4);
-            axpy4(acc[4], c1.x, x4); axpy4(acc[5], c1.y, x4);
-            axpy4(acc[6], c1.z, x4); axpy4(acc[7], c1.w, x4);
-        }
-    }
-    wave_lds_sync();   // the next iteration overwrites the tile
-}
-
-// Sweep order.  Iteration k of every wave reads one contiguous WINDOW of gridDim.x * 4 tiles (33 MB at
-// 1M x 256 on 505 workgroups); `rev` walks the windows from the end of the mini-batch to its start.
-// The last `keep` windows of a sweep are read with the allocating cache policy, everything before them
-// non-temporal: they are then still in the 256 MiB Infinity Cache when the NEXT sweep over the same
-// mini-batch -- run in the other direction -- starts with exactly those windows.  The policy changes
-// once per sweep, so the loop is split in two straight-line bodies rather than branching per tile
-// (a per-tile branch around the loads cost 6 us of the 164).
-template <bool NT, bool PK>
-__global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_mfma_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, int64_t B,
-    const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter, int rev, int keep) {
-    constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > SLAB_STRIDE ? MT_WAVE_LDS : SLAB_STRIDE);
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i16 = lane & 15, kq = lane >> 4;
-    float* tl = lds + wave * MT_WAVE_LDS;      // this wave's tile
-    float* rb = tl + MT_ROWS * MT_RS;          // residuals [row][sample]
-
-    // B operand: W[sample i16][64 kq + 4 j + c]; samples >= S (and MFMA columns 8..15) are zero.
-    // Lane group kq contracts columns 64 kq .. 64 kq + 63, so the four 16-byte A reads of a row
-    // lie 256 B apart on the same banks and each ds_read_b128 lane group (all 16 rows once,
-    // two different kq) is conflict-free; interleaved columns (16 j + 4 kq) gave every lane
-    // group a 2-way conflict (SQ_LDS_BANK_CONFLICT 18 % of the LDS cycles).
-    float wreg[GCOLS / 4];
-#pragma unroll
-    for (int j = 0; j < GCOLS / 16; ++j) {
-        float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i16 < S) w4 = *reinterpret_cast<const float4*>(W + (int64_t)i16 * GCOLS + 64 * kq + 4 * j);
-        wreg[4 * j + 0] = w4.x; wreg[4 * j + 1] = w4.y;
-        wreg[4 * j + 2] = w4.z; wreg[4 * j + 3] = w4.w;
-    }
-    float4 acc[SG];
-#pragma unroll
-    for (int s = 0; s < SG; ++s) acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-    float qacc = 0.f;
-    const bool live = i16 < SG;
-
-    const int64_t stride0 = (int64_t)gridDim.x * PASS_WAVES;
-    const int64_t stride = rev ? -stride0 : stride0;
-    int64_t tile = (int64_t)blockIdx.x * PASS_WAVES + wave + (rev ? (int64_t)(n_iter - 1) * stride0 : 0);
-    if (!NT) keep = n_iter;                    // every load allocating
-    const int n_stream = n_iter - keep > 0 ? n_iter - keep : 0;   // windows read non-temporal
-    MTile t;
-    if (n_stream > 0) load_mtile_policy<2>(t, X, ldx, y, n_iter > 0 ? tile * MT_ROWS : B, B, lane);
-    else load_mtile_policy<0>(t, X, ldx, y, n_iter > 0 ? tile * MT_ROWS : B, B, lane);
-    int k = 0;
-    for (; k + 1 < n_stream; ++k) {            // this window and the next one streamed
-        tile += stride;
-        mfma_tile_step<2, PK>(t, tl, rb, wreg, acc, qacc, X, ldx, y, tile * MT_ROWS, B, lane);
-    }
-    for (; k < n_iter; ++k) {                  // the next window is kept (or is the empty one after the last)
-        tile += stride;
-        mfma_tile_step<0, PK>(t, tl, rb, wreg, acc, qacc, X, ldx, y,
-                                  k + 1 < n_iter ? tile * MT_ROWS : B, B, lane);
-    }
-
-    // block reduction through LDS, fixed order over waves (same slab layout as above)
-    __syncthreads();
-    float* ep = lds + wave * SLAB_STRIDE;
-#pragma unroll
-    for (int s = 0; s < SG; ++s)
-        *reinterpret_cast<float4*>(ep + s * GCOLS + 4 * lane) = acc[s];
-    float qv = live ? qacc : 0.f;          // lane (i16 < 8, kq): rows 4 kq .. of sample i16
-    qv += __shfl_xor(qv, 16);
-    qv += __shfl_xor(qv, 32);
-    if (lane < SG) ep[SLAB_G + lane] = qv;
-    __syncthreads();
-    float* out = slab + (int64_t)blockIdx.x * SLAB_STRIDE;
-    for (int i = tid; i < SLAB_STRIDE; i += PASS_BLOCK) {
-        const int src = i < SLAB_G ? (i & 7) * GCOLS + (i >> 3) : i;
-        float v = lds[src];
-#pragma unroll
-        for (int k = 1; k < PASS_WAVES; ++k) v += lds[k * SLAB_STRIDE + src];
-        out[i] = v;
-    }
-}
-
-// ---- the same pass with the tile brought by LDS-DMA: the default since the end of round 3 (BSC_BLR_DMA=0: the kernel
-// above).  166 -> 161 us per 1M x 256 pass in alternating runs on one box (tools/ab_blr_dma.sh) -----------------------
-// buffer_load ... lds writes a row's 1 KiB straight into the wave's LDS tile: no 64 staging registers, no sixteen
-// ds_write_b128 a tile, and on this part a pure read by LDS-DMA reaches 6.9 TB/s where loads into registers reach 6.4
-// (bsc_hbm_read_probe).  One tile buffer per wave as before: the backward reads ALL sixteen rows into registers first
-// (the registers the prefetched tile used to occupy), which frees the buffer, issues the next tile's sixteen DMAs, and
-// only then does its rank-1 updates from the registers -- so the DMAs have the whole backward and the other wave's turn
-// to land, and no LDS read of the tile follows a DMA in flight (the compiler answers such a read with vmcnt(0): the
-// residuals, which ARE read during the backward, come by inline asm with their own lgkmcnt waits).
-// VROW: the row's offset rides in the VECTOR offset (sixteen loop-invariant registers) instead of the scalar one -- for
-// the stealing loop of blr_pass_q_kernel, where the compiler otherwise parks the fifteen scalar products in vector
-// registers and wraps every DMA in a waterfall loop.
-template <int AUX, bool VROW = false>
+// The tile by LDS-DMA: buffer_load ... lds writes a row's 1 KiB straight into the wave's LDS tile: no 64 staging
+// registers, no sixteen ds_write_b128 a tile, and on this part a pure read by LDS-DMA reaches 6.9 TB/s where loads into
+// registers reach 6.4 (bsc_hbm_read_probe).  No LDS read of the tile may follow a DMA in flight: the compiler answers
+// such a read with vmcnt(0) (q_tile_step orders its reads accordingly).
+template <int AUX>
 __device__ __forceinline__ void dma_mtile(float* __restrict__ tl, const float* __restrict__ X, int64_t ldx,
                                           const float* __restrict__ y, int64_t row0, int64_t B, int lane, float4& yv) {
     const int64_t rem = row0 < 0 ? 0 : B - row0;
@@ -496,210 +320,16 @@ __device__ __forceinline__ void dma_mtile(float* __restrict__ tl, const float* _
     auto ys = __builtin_amdgcn_make_buffer_rsrc((void*)(y + safe0), 0, yrec, 0x00020000);
     const int row_bytes = (int)(ldx * 4);
 #pragma unroll
-    for (int r = 0; r < MT_ROWS; ++r) {
-        if (VROW) __builtin_amdgcn_raw_ptr_buffer_load_lds(xs, (bsc_lds_ptr)(tl + r * MT_RS), 16, 16 * lane + r * row_bytes, 0, 0, AUX);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(xs, (bsc_lds_ptr)(tl + r * MT_RS), 16, 16 * lane, r * row_bytes, 0, AUX);
-    }
+    for (int r = 0; r < MT_ROWS; ++r)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xs, (bsc_lds_ptr)(tl + r * MT_RS), 16, 16 * lane, r * row_bytes, 0, AUX);
     auto v = __builtin_amdgcn_raw_buffer_load_b128(ys, 16 * (lane >> 4), 0, 0);
     yv = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
 }
 
-template <int AUX>
-__device__ __forceinline__ void dma_tile_step(float4& yv_cur, float* __restrict__ tl, float* __restrict__ rb,
-                                              const float (&wreg)[GCOLS / 4], float4 (&acc)[SG], float& qacc,
-                                              const float* __restrict__ X, int64_t ldx, const float* __restrict__ y,
-                                              int64_t next_row0, int64_t B, int lane) {
-    const int i16 = lane & 15, kq = lane >> 4;
-    const bool live = i16 < SG;
-    // the tile's DMAs (issued a step ago) and its y have landed
-    __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
-    asm volatile("" ::: "memory");
-    const float4 yv = yv_cur;
-    mfma_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
-    const float* arow = tl + i16 * MT_RS + 64 * kq;
-#pragma unroll
-    for (int j = 0; j < GCOLS / 16; j += 2) {
-        const float4 a0 = *reinterpret_cast<const float4*>(arow + 4 * j);
-        const float4 a1 = *reinterpret_cast<const float4*>(arow + 4 * j + 4);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, wreg[4 * j + 0], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, wreg[4 * j + 4], d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, wreg[4 * j + 1], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, wreg[4 * j + 5], d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, wreg[4 * j + 2], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, wreg[4 * j + 6], d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, wreg[4 * j + 3], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, wreg[4 * j + 7], d1, 0, 0, 0);
-    }
-    if (live) {
-        const float r0 = yv.x - (d0[0] + d1[0]), r1 = yv.y - (d0[1] + d1[1]);
-        const float r2 = yv.z - (d0[2] + d1[2]), r3 = yv.w - (d0[3] + d1[3]);
-        qacc = fmaf(r0, r0, qacc); qacc = fmaf(r1, r1, qacc);
-        qacc = fmaf(r2, r2, qacc); qacc = fmaf(r3, r3, qacc);
-        float* dst = rb + (4 * kq) * SG + i16;
-        dst[0] = r0; dst[SG] = r1; dst[2 * SG] = r2; dst[3 * SG] = r3;
-    }
-    // every row into registers, then the buffer belongs to the next tile
-    float4 x4[MT_ROWS];
-#pragma unroll
-    for (int r = 0; r < MT_ROWS; ++r) x4[r] = *reinterpret_cast<const float4*>(tl + r * MT_RS + 4 * lane);
-    wave_lds_sync();            // (the residual writes before the asm reads below; the row reads before the DMAs)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    dma_mtile<AUX>(tl, X, ldx, y, next_row0, B, lane, yv_cur);
-    // backward from the registers; residuals by LDS broadcast, read by asm (see the header)
-    const unsigned rb_addr = (unsigned)(uintptr_t)(bsc_lds_ptr)rb;
-#define BSC_BLR_GROUP(G4)                                                                                          \
-    {                                                                                                             \
-        mfma_f32x4 c0[4], c1[4];                                                                                  \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c0[0]) : "v"(rb_addr), "n"((4 * G4 + 0) * 32) : "memory");      \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c1[0]) : "v"(rb_addr), "n"((4 * G4 + 0) * 32 + 16) : "memory"); \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c0[1]) : "v"(rb_addr), "n"((4 * G4 + 1) * 32) : "memory");      \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c1[1]) : "v"(rb_addr), "n"((4 * G4 + 1) * 32 + 16) : "memory"); \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c0[2]) : "v"(rb_addr), "n"((4 * G4 + 2) * 32) : "memory");      \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c1[2]) : "v"(rb_addr), "n"((4 * G4 + 2) * 32 + 16) : "memory"); \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c0[3]) : "v"(rb_addr), "n"((4 * G4 + 3) * 32) : "memory");      \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(c1[3]) : "v"(rb_addr), "n"((4 * G4 + 3) * 32 + 16) : "memory"); \
-        asm volatile("s_waitcnt lgkmcnt(0)"                                                                       \
-                     : "+v"(c0[0]), "+v"(c1[0]), "+v"(c0[1]), "+v"(c1[1]), "+v"(c0[2]), "+v"(c1[2]), "+v"(c0[3]), "+v"(c1[3])); \
-        _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                           \
-            const float4 xr = x4[4 * G4 + k];                                                                     \
-            axpy4_pk(acc[0], c0[k][0], xr); axpy4_pk(acc[1], c0[k][1], xr);                                       \
-            axpy4_pk(acc[2], c0[k][2], xr); axpy4_pk(acc[3], c0[k][3], xr);                                       \
-            axpy4_pk(acc[4], c1[k][0], xr); axpy4_pk(acc[5], c1[k][1], xr);                                       \
-            axpy4_pk(acc[6], c1[k][2], xr); axpy4_pk(acc[7], c1[k][3], xr);                                       \
-        }                                                                                                         \
-    }
-    BSC_BLR_GROUP(0) BSC_BLR_GROUP(1) BSC_BLR_GROUP(2) BSC_BLR_GROUP(3)
-#undef BSC_BLR_GROUP
-    // (the asm reads of the residuals are done: the next step's forward may overwrite rb after its own barrier)
-    wave_lds_sync();
-}
-
-template <bool NT>
-__global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_dma_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, int64_t B,
-    const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter, int rev, int keep) {
-    constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > SLAB_STRIDE ? MT_WAVE_LDS : SLAB_STRIDE);
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i16 = lane & 15, kq = lane >> 4;
-    float* tl = lds + wave * MT_WAVE_LDS;
-    float* rb = tl + MT_ROWS * MT_RS;
-    float wreg[GCOLS / 4];
-#pragma unroll
-    for (int j = 0; j < GCOLS / 16; ++j) {
-        float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i16 < S) w4 = *reinterpret_cast<const float4*>(W + (int64_t)i16 * GCOLS + 64 * kq + 4 * j);
-        wreg[4 * j + 0] = w4.x; wreg[4 * j + 1] = w4.y;
-        wreg[4 * j + 2] = w4.z; wreg[4 * j + 3] = w4.w;
-    }
-    float4 acc[SG];
-#pragma unroll
-    for (int s = 0; s < SG; ++s) acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-    float qacc = 0.f;
-    const bool live = i16 < SG;
-    const int64_t stride0 = (int64_t)gridDim.x * PASS_WAVES;
-    const int64_t stride = rev ? -stride0 : stride0;
-    int64_t tile = (int64_t)blockIdx.x * PASS_WAVES + wave + (rev ? (int64_t)(n_iter - 1) * stride0 : 0);
-    if (!NT) keep = n_iter;
-    const int n_stream = n_iter - keep > 0 ? n_iter - keep : 0;
-    float4 yv;
-    if (n_stream > 0) dma_mtile<2>(tl, X, ldx, y, n_iter > 0 ? tile * MT_ROWS : B, B, lane, yv);
-    else dma_mtile<0>(tl, X, ldx, y, n_iter > 0 ? tile * MT_ROWS : B, B, lane, yv);
-    int k = 0;
-    for (; k + 1 < n_stream; ++k) {
-        tile += stride;
-        dma_tile_step<2>(yv, tl, rb, wreg, acc, qacc, X, ldx, y, tile * MT_ROWS, B, lane);
-    }
-    for (; k < n_iter; ++k) {
-        tile += stride;
-        dma_tile_step<0>(yv, tl, rb, wreg, acc, qacc, X, ldx, y, k + 1 < n_iter ? tile * MT_ROWS : B, B, lane);
-    }
-    // no LDS-DMA of this wave may still be in flight when the tile region is reused for the block reduction
-    __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
-    __syncthreads();
-    float* ep = lds + wave * SLAB_STRIDE;
-#pragma unroll
-    for (int s = 0; s < SG; ++s)
-        *reinterpret_cast<float4*>(ep + s * GCOLS + 4 * lane) = acc[s];
-    float qv = live ? qacc : 0.f;
-    qv += __shfl_xor(qv, 16);
-    qv += __shfl_xor(qv, 32);
-    if (lane < SG) ep[SLAB_G + lane] = qv;
-    __syncthreads();
-    float* out = slab + (int64_t)blockIdx.x * SLAB_STRIDE;
-    for (int i = tid; i < SLAB_STRIDE; i += PASS_BLOCK) {
-        const int src = i < SLAB_G ? (i & 7) * GCOLS + (i >> 3) : i;
-        float v = lds[src];
-#pragma unroll
-        for (int kk = 1; kk < PASS_WAVES; ++kk) v += lds[kk * SLAB_STRIDE + src];
-        out[i] = v;
-    }
-}
-
-// The finish kernel's arguments (blr_fused_update_kernel further down; defined here because the round-4 pass kernel can
-// carry them: FoldArgs).
-struct FusedArgs {
-    const float* slab;     // block partials of the pass kernel, or nullptr
-    int n_slab;            // slab rows
-    const double* stats;   // [Q (S) | G (S*D)] when slab == nullptr
-    const double* lam_in;
-    double* lam_out;
-    double* m1;
-    double* m2;
-    const double* eps;
-    const float* W;
-    const double* xi;
-    double* eps_next;      // nullptr: no next draw
-    int eps_next_ready;    // 1: eps_next already holds the noise of next_step (bsc_blr_noise)
-    float* W_next;
-    double* xi_next;
-    double* elbo;
-    double* grad;
-    int D, S;
-    // the log-joint per draw as a member of the family (bsc_blr_fused_update_general):
-    //   f(w, xi; Q) = c0 + c_xi xi + e^{-xi} (-s_q Q / 2 - k_w |w|^2 / 2 - beta)
-    double c0, c_xi, s_q, k_w, beta;
-    double lr, beta1, beta2, adam_eps, corr1, corr2;
-    uint64_t seed;
-    uint32_t next_step;
-};
-
-// ---- the finish folded into the pass's tail (round 4, option blr_fold) ---------------------------------------------------
-// VERDICT r2 #6 / r3 #2(b).  After its slab row a workgroup takes an arrival ticket; the LAST `n_roles` arrivals do
-// what the finish kernel's workgroups do (mode 1: role r = that kernel's block r -- slab -> float64 -> ELBO, gradient,
-// Adam, next draws; mode 2: the float64 statistics [Q | G] for the all-reduce of the N > 1 structure), once every row
-// has arrived.  One launch per update instead of two: the pass -> finish boundary (~1.7 us) and the finish kernel's
-// own launch and small-operand round trips leave the critical path.
-//
-// Visibility across CUs and XCDs (MI355X_MICROARCH.md, "inter-workgroup visibility"): the slab row is stored
-// write-through (sc1: relaxed agent-scope atomic stores), every storing wave drains (s_waitcnt vmcnt(0)), the
-// workgroup's barrier, then ONE lane adds to the arrival counter (agent scope).  A role workgroup polls that counter
-// with sc1 loads (one lane, s_sleep, bounded), barrier, and reads the slab with sc1 loads only (L1 bypassed; no XCD's L2
-// can hold a slab line of this launch before the rows are complete: nothing reads the slab earlier, and L1 / L2 start
-// a launch invalidated).  The arithmetic of a role is fixed, whichever workgroup performs it: reproducible.  The last
-// role to finish zeroes the counters for the next launch.  The role workgroups spin only for workgroups that are
-// resident (the grid never exceeds two workgroups per CU).
-struct FoldArgs {
-    FusedArgs a;           // mode 1
-    unsigned* counters;    // [0] arrivals, [1] roles done (zero between launches)
-    double* Q;             // mode 2: Q[s_base + s], G[(s_base + s) * D + d]
-    double* G;
-    int mode;              // 0 = no fold (the slab is the kernel's result)
-    int s_base, S_total;
-};
-// `wait()` is called by every thread of the workgroup right before the first access to the slab: the folded finish
-// waits there for the last partial (everything a role can do without the slab happens before it).
-template <int BLOCK, bool COH, typename Wait>
-__device__ void fused_update_role(const FusedArgs& a, int role, Wait wait);
-template <int BLOCK, bool COH, typename Wait>
-__device__ void slab_stats_role(const float* __restrict__ slab, int n_blocks, int D, int S, int s_base,
-                                double* __restrict__ Q, double* __restrict__ G, int role, Wait wait);
-
 // ---- round 4: BOTH contractions on v_mfma_f32_4x4x1_16B_f32, the tile by LDS-DMA (D == 256, S <= 8) -----------------
 //
-// The counters of blr_pass_dma_kernel (profiles/r03_pmc_blr_pass_dma.txt) say what holds it at 0.80 of the peak: a
+// The counters of round 3's pass (forward on v_mfma_f32_16x16x4, backward on packed VALU FMAs, the tile by LDS-DMA;
+// profiles/r03_pmc_blr_pass_dma.txt) say what held it at 0.80 of the peak: a
 // 16-row tile costs a SIMD 64 v_mfma_f32_16x16x4 of 32 cycles (half of each idle: eight draws in sixteen columns) plus
 // ~310 vector instructions at ~4.6 matrix-pipe cycles apiece (fp32 MFMA and VALU do not overlap on a SIMD:
 // profiles/r01_ubench_mfma_valu_mix.txt) -- ~3 500 issue cycles a tile, ~0.75 of the time HBM takes to deliver it.
@@ -717,19 +347,20 @@ __device__ void slab_stats_role(const float* __restrict__ slab, int n_blocks, in
 //   backward  as blr_pass_mx_kernel: A = r[n][4 sb + lane % 4] (LDS broadcast), B = x[n][4 lane + q], register i of
 //             accumulator (sb, q) is G[4 sb + i][4 lane + q].  128 MFMAs of 8 cycles.
 //
-// ~2 050 matrix-pipe cycles and ~45 vector instructions a tile.  The feed is blr_pass_dma_kernel's: one 16-row buffer
+// ~2 050 matrix-pipe cycles and ~45 vector instructions a tile.  The feed (dma_mtile): one 16-row buffer
 // per wave; every operand of the backward (sixteen rows, the residuals) goes to registers before the next tile's
 // sixteen DMAs are issued, so those have the backward and the other wave's turn to land.
 constexpr int QW = 32;   // forward B operand: registers per lane
 
 // DBG (profiling only, WRONG results; BSC_BLR_Q_DBG + BSC_PROFILING_BUILDS): 1 = no arithmetic at all (the feed's own
 // ceiling: DMAs, waits, LDS reads), 2 = forward only, 3 = backward only
-// `next_row0()` is called once, right before the next tile's DMAs are issued, `after_dma()` right behind them.
-template <int AUX, int DBG, int PRIO, bool VROW = false, typename NextRow, typename AfterDma>
+// `next_row0()` is called once, right before the next tile's DMAs are issued: evaluated earlier, its result would be
+// live across the forward (4 VGPRs more).
+template <int AUX, int DBG, int PRIO, typename NextRow>
 __device__ __forceinline__ void q_tile_step(float4& yv_cur, float* __restrict__ tl, float* __restrict__ rb,
                                             const float (&wreg)[QW], mfma_f32x4 (&acc)[2][4], float& qacc,
                                             const float* __restrict__ X, int64_t ldx, const float* __restrict__ y,
-                                            NextRow next_row0, AfterDma after_dma, int64_t B, int lane) {
+                                            NextRow next_row0, int64_t B, int lane) {
     const int kq = lane >> 4;
     // the tile's DMAs (issued a step ago) and its y have landed
     __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
@@ -789,8 +420,7 @@ __device__ __forceinline__ void q_tile_step(float4& yv_cur, float* __restrict__ 
             ra[sb][g] = *reinterpret_cast<const float4*>(rb + (4 * sb + (lane & 3)) * MT_ROWS + 4 * g);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     wave_lds_sync();
-    dma_mtile<AUX, VROW>(tl, X, ldx, y, next_row0(), B, lane, yv_cur);
-    after_dma();
+    dma_mtile<AUX>(tl, X, ldx, y, next_row0(), B, lane, yv_cur);
     if (PRIO == 1) __builtin_amdgcn_s_setprio(0);
     if (PRIO == 2) __builtin_amdgcn_s_setprio(1);
     if (DBG == 0 || DBG == 3) {
@@ -816,54 +446,6 @@ __device__ __forceinline__ void q_tile_step(float4& yv_cur, float* __restrict__ 
     }
 }
 
-// ---- the queued tail of blr_pass_q_kernel (option blr_steal) ---------------------------------------------------------
-//
-// The static schedule below ends when the slowest workgroup does, and the workgroups do not run at one speed: the
-// mean end of a workgroup differs by 8-9 us of ~145 between the XCDs of one part (and WHICH XCDs are slow differs from
-// part to part: tools/stamps_structure.py), with another ~5 us of launch-to-launch noise on top.  So every wave takes
-// only (1000 - blr_steal) per mille of an even share statically and draws the remaining tiles, one at a time, from
-// one of up to 64 queues.  Queue q holds a contiguous run of `per_q` tiles and serves the workgroups with
-// (blockIdx / 8) % nq = q -- workgroups are dealt to the XCDs round-robin, so a queue is shared by one workgroup of
-// every XCD (twice over at 512 workgroups) and the fast XCDs take the tiles the slow ones do not get to.  A wave leaves
-// when its queue is empty; nothing moves between queues.
-//   * The request goes out BEFORE the wait for the current tile's DMAs and is looked at only when the next tile's DMAs
-//     are issued, so its latency is behind a wait the wave has anyway.
-//   * A cache line serves one returning atomic per ~15 ns whatever the address in it (tools/ubench_atomic_queue.hip):
-//     hence 64 heads 256 bytes apart, not one counter -- and no device-wide "who is last" counter either: the
-//     workgroups of a queue count themselves out on the queue's own line and the last one zeroes it.
-//   * (Measured and dropped: waves of an empty queue moving on to other queues.  Finding one takes a look at all 64 heads;
-//     2 048 waves doing that within microseconds of each other, and then falling on the few queues with a tile left,
-//     cost 20-40 us a launch: profiles/r04_ab_pass_q_steal.txt.)
-// Which wave adds which tile into its partial sums now depends on timing: the LAST BITS of the f32 sums differ from
-// launch to launch (blr_steal = 0 keeps the reproducible static schedule).
-constexpr int STEAL_Q = 64, STEAL_STRIDE = 64;      // queues; words between their heads (word 1 of a line: workgroups done)
-struct StealArgs {
-    unsigned* heads;          // nullptr: static schedule only
-    int per_q;                // tiles per queue (the last non-empty one may hold fewer)
-    int nq;                   // queues in use: min(64, whole groups of 8 workgroups)
-    long long t0, n_dyn;      // first queued tile, queued tiles
-};
-__device__ __forceinline__ int steal_len(const StealArgs& s, int q) {
-    const long long r = s.n_dyn - (long long)q * s.per_q;
-    return r <= 0 ? 0 : r < s.per_q ? (int)r : s.per_q;
-}
-// (inline asm: the compiler's atomic optimizer rewrites a one-lane __hip_atomic_fetch_add and waits for the result -- vmcnt(0),
-// so for every DMA in flight as well -- right behind it.  The result is valid after the caller's next vmcnt(0).)
-__device__ __forceinline__ unsigned steal_request(const StealArgs& s, int q, int lane) {
-    unsigned t = 1u;
-    const unsigned off = (unsigned)q * (STEAL_STRIDE * 4u);
-    if (lane == 0) asm volatile("global_atomic_add %0, %1, %0, %2 sc0" : "+v"(t) : "v"(off), "s"(s.heads) : "memory");
-    return t;
-}
-// row0 of the tile the request `pend` on queue q drew, or B: the queue is empty
-__device__ __forceinline__ int64_t steal_resolve(const StealArgs& s, unsigned pend, int q, int64_t B) {
-    // (the value is looked at HERE, not where the request was made; wave-uniform, and said so: or every DMA built on
-    // it sits in a waterfall loop)
-    asm volatile("" : "+v"(pend));
-    const unsigned t = __builtin_amdgcn_readfirstlane(pend);
-    return (long long)t < (long long)steal_len(s, q) ? (s.t0 + (int64_t)q * s.per_q + (int64_t)t) * MT_ROWS : B;
-}
-
 // Which tiles a wave of blr_pass_q_kernel reads.
 //
 // STATIC (reproducible: a wave's tiles and their order are a function of the launch geometry alone).  Window w < n_all
@@ -876,7 +458,8 @@ __device__ __forceinline__ int64_t steal_resolve(const StealArgs& s, unsigned pe
 //
 // (Measured and dropped: tiles popped from eight atomic queues, one per XCD, with stealing -- every workgroup then ends
 // within 0.2 us of every other, but 62 500 returning atomics on eight words take 226 us where the static schedule takes
-// 160, profiles/r04_ab_pass_q_schedules.txt; and the sums would no longer be reproducible in the last bits.)
+// 160, profiles/r04_ab_pass_q_schedules.txt; and the sums would no longer be reproducible in the last bits.  Likewise a
+// queued tail behind a static share: 0.5-1.5 us of 157 gained, the last bits lost, profiles/r04_ab_pass_q_steal.txt.)
 struct QSched {
     int n_all, n_mine, rev, keep;
     int64_t w_all, w_a, slot, slot_a, B;
@@ -889,11 +472,11 @@ struct QSched {
     }
 };
 
-template <bool NT, int DBG, int PRIO, bool STEAL = false>
+template <bool NT, int DBG, int PRIO>
 __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_q_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, int64_t B,
     const float* __restrict__ W, int S, float* __restrict__ slab, int n_all, int n_a, int rev, int keep,
-    unsigned long long* __restrict__ stamps, FoldArgs fold, StealArgs steal) {
+    unsigned long long* __restrict__ stamps) {
     constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > SLAB_STRIDE ? MT_WAVE_LDS : SLAB_STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
@@ -938,45 +521,14 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_q_kernel(
         else dma_mtile<0>(tl, X, ldx, y, sc.row0(0), B, lane, yv);
         load_w();
         int k = 0;
-        if constexpr (STEAL) {
-            // static share (the host: n_mine >= 1 for every wave, keep = 0), then one queued tile per step until none is left
-            for (; k + 1 < n_mine; ++k)
-                q_tile_step<2, DBG, PRIO, true>(yv, tl, rb, wreg, acc, qacc, X, ldx, y, [&] { return sc.row0(k + 1); }, [] {}, B, lane);
-            const int q = (blockIdx.x >> 3) % steal.nq;
-            if (stamps && tid == 0) stamps[8 * (int64_t)blockIdx.x + 4] = __builtin_amdgcn_s_memrealtime();     // wave 0: static share read
-            unsigned long long taken = 0;
-            for (;;) {
-                const unsigned pend = steal_request(steal, q, lane);
-                int64_t next = 0;
-                q_tile_step<2, DBG, PRIO, true>(yv, tl, rb, wreg, acc, qacc, X, ldx, y,
-                                                [&] { next = steal_resolve(steal, pend, q, B); return next; }, [] {}, B, lane);
-                if (next >= B) break;
-                ++taken;
-            }
-            if (stamps && tid == 0) {
-                stamps[8 * (int64_t)blockIdx.x + 5] = __builtin_amdgcn_s_memrealtime();     // wave 0: left the queue
-                stamps[8 * (int64_t)blockIdx.x + 6] = taken;                                // ... with this many queued tiles
-            }
-        } else {
-            for (; k + 1 < n_stream; ++k)
-                q_tile_step<2, DBG, PRIO>(yv, tl, rb, wreg, acc, qacc, X, ldx, y, [&] { return sc.row0(k + 1); }, [] {}, B, lane);
-            for (; k < n_mine; ++k)
-                q_tile_step<0, DBG, PRIO>(yv, tl, rb, wreg, acc, qacc, X, ldx, y, [&] { return sc.row0(k + 1); }, [] {}, B, lane);
-        }
+        for (; k + 1 < n_stream; ++k)
+            q_tile_step<2, DBG, PRIO>(yv, tl, rb, wreg, acc, qacc, X, ldx, y, [&] { return sc.row0(k + 1); }, B, lane);
+        for (; k < n_mine; ++k)
+            q_tile_step<0, DBG, PRIO>(yv, tl, rb, wreg, acc, qacc, X, ldx, y, [&] { return sc.row0(k + 1); }, B, lane);
     }
     // no LDS-DMA of this wave may still be in flight when the tile region is reused for the block reduction
     __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
     __syncthreads();
-    __shared__ unsigned steal_last_s;
-    if (STEAL && tid == 0) {
-        // every wave of this workgroup has left its queue: count the workgroup out on the queue's line; the last of the
-        // queue's workgroups (groups of 8 with group % nq = q; the last group of the grid may be short) zeroes the line
-        const int q = (blockIdx.x >> 3) % steal.nq;
-        int homes = 0;
-        for (int j = q; 8 * j < (int)gridDim.x; j += steal.nq) homes += (int)gridDim.x - 8 * j < 8 ? (int)gridDim.x - 8 * j : 8;
-        steal_last_s = __hip_atomic_fetch_add(steal.heads + q * STEAL_STRIDE + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                       (unsigned)homes - 1u;
-    }
     float* ep = lds + wave * SLAB_STRIDE;
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb)
@@ -989,62 +541,17 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_q_kernel(
     qv += __shfl_xor(qv, 32);
     if (lane < SG) ep[SLAB_G + lane] = qv;
     __syncthreads();
-    if (STEAL && steal_last_s && tid < 2)      // the queue's last workgroup: head and count back to zero
-        __hip_atomic_store(steal.heads + ((blockIdx.x >> 3) % steal.nq) * STEAL_STRIDE + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     float* out = slab + (int64_t)blockIdx.x * SLAB_STRIDE;
     for (int i = tid; i < SLAB_STRIDE; i += PASS_BLOCK) {
         const int src = i < SLAB_G ? (i & 7) * GCOLS + (i >> 3) : i;
         float v = lds[src];
 #pragma unroll
         for (int kk = 1; kk < PASS_WAVES; ++kk) v += lds[kk * SLAB_STRIDE + src];
-        // (folded finish: write-through, so that a workgroup on another XCD reads the row from memory)
-        if (!STEAL && fold.mode) __hip_atomic_store(out + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else out[i] = v;
-    }
-    if (!STEAL && fold.mode) {
-        // ---- the finish in the pass's tail (FoldArgs) ----
-        __shared__ unsigned ticket_s;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's slab stores have been written through
-        __syncthreads();                                        // ... and every other wave's of the workgroup
-        if (tid == 0) {
-            if (stamps) stamps[8 * (int64_t)blockIdx.x + 4] = __builtin_amdgcn_s_memrealtime();     // slab row written through
-            ticket_s = __hip_atomic_fetch_add(fold.counters, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (stamps) { stamps[8 * (int64_t)blockIdx.x + 5] = __builtin_amdgcn_s_memrealtime(); stamps[8 * (int64_t)blockIdx.x + 7] = ticket_s; }
-        }
-        __syncthreads();
-        const int n_roles = fold.mode == 1 ? (fold.a.D + 7) / 8 + 1 : (SLAB_STRIDE + BSC_WAVE - 1) / BSC_WAVE;
-        // the LAST arrival takes role 0, the earliest of the last n_roles the highest role (mode 1: the scalar role,
-        // which has the most to do before it needs the slab -- and the longest wait for the last partial)
-        const int role = (int)gridDim.x - 1 - (int)ticket_s;
-        if (role < n_roles) {                                   // one of the last n_roles arrivals
-            auto all_arrived = [&] {
-                if (tid == 0) {
-                    // every row has arrived?  (sc1 poll by one lane; the rows still missing belong to workgroups that
-                    // are computing on resident slots.  Bounded: ~2 s of the 100 MHz clock, then carry on.)
-                    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-                    while (__hip_atomic_load(fold.counters, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x) {
-                        __builtin_amdgcn_s_sleep(4);
-                        if (__builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) break;
-                    }
-                    if (stamps) stamps[8 * (int64_t)blockIdx.x + 6] = __builtin_amdgcn_s_memrealtime();
-                }
-                __syncthreads();
-            };
-            if (fold.mode == 1) fused_update_role<PASS_BLOCK, true>(fold.a, role, all_arrived);
-            else slab_stats_role<PASS_BLOCK, true>(slab, (int)gridDim.x, GCOLS, fold.S_total, fold.s_base, fold.Q, fold.G, role, all_arrived);
-            __syncthreads();
-            if (tid == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const unsigned done = __hip_atomic_fetch_add(fold.counters + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (done == (unsigned)n_roles - 1u) {           // the last role: zero the counters for the next launch
-                    __hip_atomic_store(fold.counters, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(fold.counters + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
+        out[i] = v;
     }
     if (stamps) {
         // measurement aid (option blr_stamps): when did this workgroup start and end, and on which XCD did it run
+        // (words 4-7 of a row are unused)
         __syncthreads();
         if (tid == 0) {
             unsigned long long* st = stamps + 8 * (int64_t)blockIdx.x;
@@ -1056,39 +563,34 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_q_kernel(
     }
 }
 
-// ---- both contractions on the MFMA pipe (D == 256) ------------------------------------------
+// ---- sixteen draws per pass (D == 256, 9 <= S <= 16: bsc_blr_data_pass with S > 8) -------------
 //
-// With every load served from the caches blr_pass_mfma_kernel still takes ~150 us per 1M x 256
-// pass (tools/ab_pass.py floor): 64 v_mfma_f32_16x16x4 (half of each idle: S = 8 of 16 columns)
-// plus 256 v_pk_fma_f32 per 16-row tile keep a SIMD busy about as long as HBM takes to deliver the
-// tile, so a faster memory schedule alone cannot show.  Here the backward rank-1 updates
-// G[s, :] += r[n, s] x[n, :] run on v_mfma_f32_4x4x1_16B_f32 -- sixteen independent 4 x 4 outer
-// products per instruction, no idle half: block b = lane / 4 owns columns 16 b .. 16 b + 15, the A
-// operand is the residual r[n][4 sb + lane % 4] (the same in every block), the B operand component
-// q of the row as the lane holds it (column 4 lane + q), and the result register i of accumulator
-// (sb, q) is G[4 sb + i][4 lane + q] -- the accumulators the VALU variant keeps, so the epilogue and
-// the slab are unchanged.  128 MFMAs of 8 cycles replace 256 packed FMAs of 8 cycles and leave the
-// VALU with the sixteen residuals.
+// One pass over X for 16 draws instead of two.  The tile comes through registers (the prefetched
+// NEXT tile: 64 VGPRs), is written to the wave's LDS region row-major and read back twice:
+//   forward   A operand of v_mfma_f32_16x16x4_f32: lane (i = l&15, kq = l>>4) reads
+//             X[row i][64 kq + 4 j .. +3] (one ds_read_b128 feeds 4 MFMAs); B operand
+//             = W[draw l&15][same columns], 64 registers loaded once; result register reg of the
+//             lane is dot(row 4 kq + reg, draw l&15): all sixteen MFMA columns carry a draw.
+//   backward  the rank-1 updates G[s, :] += r[n, s] x[n, :] on v_mfma_f32_4x4x1_16B_f32 -- sixteen
+//             independent 4 x 4 outer products per instruction: block b = lane / 4 owns columns
+//             16 b .. 16 b + 15, the A operand is the residual r[n][4 sb + lane % 4] (the same in
+//             every block), the B operand component q of the row as the lane holds it (column
+//             4 lane + q), and the result register i of accumulator (sb, q) is
+//             G[4 sb + i][4 lane + q] -- the accumulators the VALU kernel keeps, so the epilogue and
+//             the slab layout are unchanged.
 //
-// Schedule (`Sched`): the windows (one per iteration: gridDim.x * 4 tiles) are walked forward,
-// backward, or ROTATED: workgroup group g = blockIdx >> rot_shift starts at window g % n_iter and
-// wraps around.  Windows [0, keep) -- the head of the mini-batch -- are read with the allocating
-// policy and stay in the 256 MiB Infinity Cache from pass to pass, all others non-temporal; with the
-// rotation a fraction keep / n_iter of the workgroups is in the cached zone at any moment, so cache
-// hits and HBM reads overlap for the whole pass instead of taking turns.
+// Schedule (`Sched`).  Iteration k of every wave reads one contiguous WINDOW of gridDim.x * 4 tiles
+// (33 MB at 1M x 256 on 505 workgroups); `rev` walks the windows from the end of the mini-batch to
+// its start.  The last `keep` windows of a sweep are read with the allocating cache policy,
+// everything before them non-temporal: they are then still in the 256 MiB Infinity Cache when the
+// NEXT sweep over the same mini-batch -- run in the other direction -- starts with exactly those
+// windows.
 struct Sched {
-    int n_iter, mode, keep, phi;
+    int n_iter, rev, keep;
     int64_t stride0, slot, B;
-    __device__ __forceinline__ int window(int p) const {
-        if (mode == 2) { const int w = p + phi; return w >= n_iter ? w - n_iter : w; }
-        if (mode == 4) return 0;          // measurement only: every position re-reads window 0
-        return mode == 1 ? n_iter - 1 - p : p;
-    }
+    __device__ __forceinline__ int window(int p) const { return rev ? n_iter - 1 - p : p; }
     // allocating policy for the window at position p?  (p = n_iter: the empty prefetch after the last)
-    __device__ __forceinline__ bool kept(int p) const {
-        if (p >= n_iter) return true;
-        return mode == 2 ? window(p) < keep : p >= n_iter - keep;
-    }
+    __device__ __forceinline__ bool kept(int p) const { return p >= n_iter - keep; }
     __device__ __forceinline__ int64_t row0(int p) const {
         return p < n_iter ? ((int64_t)window(p) * stride0 + slot) * MT_ROWS : B;
     }
@@ -1096,15 +598,13 @@ struct Sched {
 
 constexpr int MX_WAVE_LDS = MT_ROWS * MT_RS + MT_ROWS * 16;   // tile + residuals of up to 16 draws
 
-// NSB = sample groups of four per pass: 2 (S <= 8) or 4 (S <= 16: the forward MFMA's sixteen columns
-// all carry a draw -- the second eight cost the forward nothing --, the backward doubles; one pass
-// over X for 16 draws instead of two, bsc_blr_data_pass with S > 8).  The block partials of draws
-// 8 .. 15 go to a second slab behind the first (slab + gridDim.x rows).
+// NSB = draw groups of four per pass: 4 is the only instantiation (the forward is the same for any
+// NSB <= 4, the backward's cost is proportional to it).  The block partials of draws 8 .. 15 go to a
+// second slab behind the first (slab + gridDim.x rows).
 template <bool NT, int NSB>
 __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_mx_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, int64_t B,
-    const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter, int mode, int keep,
-    int rot_shift) {
+    const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter, int rev, int keep) {
     constexpr int NS = 4 * NSB;                 // draws per pass
     constexpr int NH = NSB / 2;                 // slabs (one per eight draws)
     constexpr int LDS_FLOATS = PASS_WAVES * (MX_WAVE_LDS > NH * SLAB_STRIDE ? MX_WAVE_LDS : NH * SLAB_STRIDE);
@@ -1116,7 +616,11 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_mx_kernel(
     float* tl = lds + wave * MX_WAVE_LDS;      // this wave's tile
     float* rb = tl + MT_ROWS * MT_RS;          // residuals [sample][row]
 
-    float wreg[GCOLS / 4];                     // forward B operand, as in blr_pass_mfma_kernel
+    // forward B operand: W[draw i16][64 kq + 4 j + c]; draws >= S are zero.  Lane group kq contracts
+    // columns 64 kq .. 64 kq + 63, so the four 16-byte A reads of a row lie 256 B apart on the same
+    // banks and each ds_read_b128 lane group (all 16 rows once, two different kq) is conflict-free;
+    // interleaved columns (16 j + 4 kq) gave every lane group a 2-way conflict.
+    float wreg[GCOLS / 4];
 #pragma unroll
     for (int j = 0; j < GCOLS / 16; ++j) {
         float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1133,11 +637,10 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_mx_kernel(
     const bool live = i16 < NS;                // lanes whose forward MFMA column is a sample
 
     Sched sc;
-    sc.n_iter = n_iter; sc.mode = mode; sc.keep = NT ? keep : n_iter;
+    sc.n_iter = n_iter; sc.rev = rev; sc.keep = NT ? keep : n_iter;
     sc.stride0 = (int64_t)gridDim.x * PASS_WAVES;
     sc.slot = (int64_t)blockIdx.x * PASS_WAVES + wave;
     sc.B = B;
-    sc.phi = (mode == 2 && n_iter > 0) ? (int)((blockIdx.x >> rot_shift) % (unsigned)n_iter) : 0;
 
     MTile t;
     if (sc.kept(0)) load_mtile_policy<0>(t, X, ldx, y, sc.row0(0), B, lane);
@@ -1181,7 +684,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_mx_kernel(
         }
         wave_lds_sync();
 
-        // backward on v_mfma_f32_4x4x1_16B_f32: per row 2 sample groups x 4 column components
+        // backward on v_mfma_f32_4x4x1_16B_f32: per row NSB draw groups x 4 column components
 #pragma unroll
         for (int g = 0; g < MT_ROWS / 4; ++g) {
             if (g) asm volatile("" ::: "memory");   // four rows of reads in flight
@@ -1235,8 +738,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_mx_kernel(
 // Loads are issued in batches of 16 before any add: the partials were written by
 // another kernel, so every load is a MALL/HBM round trip (~0.4 us) and a
 // load-add-load-add chain would serialise them.
-// COH: the rows were written by other workgroups of THIS launch (the folded finish): sc1 loads.
-template <int BATCH = 16, bool COH = false>
+template <int BATCH = 16>
 __device__ __forceinline__ double slab_column_sum(const float* __restrict__ p, int first,
                                                   int step, int n_rows) {
     double sum = 0.0;
@@ -1245,8 +747,7 @@ __device__ __forceinline__ double slab_column_sum(const float* __restrict__ p, i
 #pragma unroll
         for (int j = 0; j < BATCH; ++j) {
             const int b = b0 + j * step;
-            if (COH) v[j] = b < n_rows ? __hip_atomic_load(p + (int64_t)b * SLAB_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-            else v[j] = b < n_rows ? p[(int64_t)b * SLAB_STRIDE] : 0.f;
+            v[j] = b < n_rows ? p[(int64_t)b * SLAB_STRIDE] : 0.f;
         }
 #pragma unroll
         for (int j = 0; j < BATCH; ++j) sum += (double)v[j];
@@ -1265,8 +766,7 @@ __device__ __forceinline__ double slab_column_sum(const float* __restrict__ p, i
 // guarded scalar loads this replaces (1.5 KB of code) cost 10 us before the first load had
 // even been issued (cycle counters, round 1).
 // JJ: loads in flight per lane and trip (8: the finish kernels' 16 waves cover 512 rows in one trip; 32: four waves do).
-// AUX: cache policy of the loads (16 = sc1, for rows written by other workgroups of this launch).
-template <int N_WAVES, int JJ = 8, int AUX = 0, typename F>
+template <int N_WAVES, int JJ = 8, typename F>
 __device__ __forceinline__ void slab_run_sum(const float* __restrict__ slab, int n_slab, int col0,
                                              int wave, int lane, double (&s4)[4], F between) {
     const uint64_t slab_bytes = (uint64_t)n_slab * SLAB_STRIDE * 4u;
@@ -1281,7 +781,7 @@ __device__ __forceinline__ void slab_run_sum(const float* __restrict__ slab, int
 #pragma unroll
         for (int jj = 0; jj < JJ; ++jj) {
             auto v = __builtin_amdgcn_raw_buffer_load_b128(
-                rs, voff, base * (SLAB_STRIDE * 4) + jj * BATCH_BYTES, AUX);
+                rs, voff, base * (SLAB_STRIDE * 4) + jj * BATCH_BYTES, 0);
             v8[jj] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
                                  __uint_as_float(v[3]));
         }
@@ -1305,18 +805,16 @@ __device__ __forceinline__ void slab_run_sum(const float* __restrict__ slab, int
 constexpr int RED_BLOCK = 1024;
 constexpr int RED_WAVES = RED_BLOCK / BSC_WAVE;
 
-template <int BLOCK, bool COH, typename Wait>
-__device__ void slab_stats_role(const float* __restrict__ slab, int n_blocks, int D, int S, int s_base,
-                                double* __restrict__ Q, double* __restrict__ G, int role, Wait wait) {
-    constexpr int WAVES = BLOCK / BSC_WAVE;
-    __shared__ double part[WAVES][BSC_WAVE];
+__global__ __launch_bounds__(RED_BLOCK) void blr_slab_reduce_kernel(
+    const float* __restrict__ slab, int n_blocks, int D, int S, int s_base,
+    double* __restrict__ Q, double* __restrict__ G) {
+    __shared__ double part[RED_WAVES][BSC_WAVE];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int i = role * BSC_WAVE + lane;
+    const int i = blockIdx.x * BSC_WAVE + lane;
     double s4[4];
-    wait();
-    slab_run_sum<WAVES, (WAVES >= 16 ? 8 : 32), (COH ? 16 : 0)>(slab, n_blocks, role * BSC_WAVE, wave, lane, s4, [] {});
-    if (lane < 16) {   // (columns past SLAB_STRIDE in the last role are read but never written out)
+    slab_run_sum<RED_WAVES>(slab, n_blocks, blockIdx.x * BSC_WAVE, wave, lane, s4, [] {});
+    if (lane < 16) {   // (columns past SLAB_STRIDE in the last workgroup are read but never written out)
 #pragma unroll
         for (int k = 0; k < 4; ++k) part[wave][4 * lane + k] = s4[k];
     }
@@ -1324,7 +822,7 @@ __device__ void slab_stats_role(const float* __restrict__ slab, int n_blocks, in
     if (wave == 0 && i < SLAB_STRIDE) {
         double tot = part[0][lane];
 #pragma unroll
-        for (int k = 1; k < WAVES; ++k) tot += part[k][lane];
+        for (int k = 1; k < RED_WAVES; ++k) tot += part[k][lane];
         if (i < SLAB_G) {
             int s = i & 7, d = i >> 3;
             if (s_base + s < S && d < D) G[(int64_t)(s_base + s) * D + d] = tot;
@@ -1333,12 +831,6 @@ __device__ void slab_stats_role(const float* __restrict__ slab, int n_blocks, in
             if (s_base + s < S) Q[s_base + s] = tot;
         }
     }
-}
-
-__global__ __launch_bounds__(RED_BLOCK) void blr_slab_reduce_kernel(
-    const float* __restrict__ slab, int n_blocks, int D, int S, int s_base,
-    double* __restrict__ Q, double* __restrict__ G) {
-    slab_stats_role<RED_BLOCK, false>(slab, n_blocks, D, S, s_base, Q, G, (int)blockIdx.x, [] {});
 }
 
 // ---- sampler and ELBO/gradient finish (tiny, float64) ----------------------
@@ -1545,6 +1037,32 @@ __global__ __launch_bounds__(FIN_BLOCK) void blr_elbo_grad_kernel(
 // double-buffered by the caller (lam_in/lam_out, cur/next draws) so no
 // workgroup reads what another one writes.
 
+struct FusedArgs {
+    const float* slab;     // block partials of the pass kernel, or nullptr
+    int n_slab;            // slab rows
+    const double* stats;   // [Q (S) | G (S*D)] when slab == nullptr
+    const double* lam_in;
+    double* lam_out;
+    double* m1;
+    double* m2;
+    const double* eps;
+    const float* W;
+    const double* xi;
+    double* eps_next;      // nullptr: no next draw
+    int eps_next_ready;    // 1: eps_next already holds the noise of next_step (bsc_blr_noise)
+    float* W_next;
+    double* xi_next;
+    double* elbo;
+    double* grad;
+    int D, S;
+    // the log-joint per draw as a member of the family (bsc_blr_fused_update_general):
+    //   f(w, xi; Q) = c0 + c_xi xi + e^{-xi} (-s_q Q / 2 - k_w |w|^2 / 2 - beta)
+    double c0, c_xi, s_q, k_w, beta;
+    double lr, beta1, beta2, adam_eps, corr1, corr2;
+    uint64_t seed;
+    uint32_t next_step;
+};
+
 __device__ __forceinline__ double adam_ascent_one(double lam, double g, double& m1, double& m2,
                                                   const FusedArgs& a) {
     const double na = a.beta1 * m1 + (1.0 - a.beta1) * g;
@@ -1558,19 +1076,20 @@ __device__ __forceinline__ double adam_ascent_one(double lam, double g, double& 
 
 // BLOCK threads per workgroup (1024 = 16 waves: 32 slab rows per wave at 512 partials; fewer waves
 // launch sooner -- BSC_BLR_FINISH_BLOCK, A/B in tools/ab_pass.py)
-template <int FUSED_BLOCK, bool COH, typename Wait>
-__device__ void fused_update_role(const FusedArgs& a, int role, Wait wait) {
+template <int FUSED_BLOCK>
+__global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs a) {
     constexpr int FUSED_WAVES = FUSED_BLOCK / BSC_WAVE;
     __shared__ double red[FUSED_WAVES][BSC_WAVE];
     __shared__ double sh[2 * FIN_MAX_S + 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = a.D, S = a.S;
     const int n_chunks = (D + 7) / 8;
+    const int chunk = (int)blockIdx.x;   // == n_chunks: the scalar workgroup
     const double inv_S = 1.0 / (double)S;
 
-    if (role < n_chunks) {
+    if (chunk < n_chunks) {
         // ---------------- column workgroup: columns d0 .. d0+7 ----------------
-        const int d0 = 8 * role;
+        const int d0 = 8 * chunk;
         const int dl = lane >> 3, sl = lane & 7;  // slab order within the run is [d][s]
         const int d = d0 + dl;
         double gm = 0.0, gr = 0.0;
@@ -1599,15 +1118,7 @@ __device__ void fused_update_role(const FusedArgs& a, int role, Wait wait) {
             // float64 exponentials that do not depend on it run while it is in flight
             double s4[4];
             double e_mxs = 0.0;
-            if (COH) {              // (the operands above are on their way; the exponentials do not need the slab either)
-                if (wave == 0) {
-                    e_mxs = exp(-xs);
-                    e_rho = exp(p_rho);
-                }
-                wait();
-            }
-            slab_run_sum<FUSED_WAVES, (FUSED_WAVES >= 16 ? 8 : 32), (COH ? 16 : 0)>(a.slab, a.n_slab, 64 * role, wave, lane, s4, [&] {
-                if (COH) return;
+            slab_run_sum<FUSED_WAVES, (FUSED_WAVES >= 16 ? 8 : 32)>(a.slab, a.n_slab, 64 * chunk, wave, lane, s4, [&] {
                 if (wave == 0) {
                     e_mxs = exp(-xs);
                     e_rho = exp(p_rho);
@@ -1677,7 +1188,7 @@ __device__ void fused_update_role(const FusedArgs& a, int role, Wait wait) {
         } else if (a.eps_next) {
             // two Philox blocks per sample cover the 8 columns
             for (int i = lane; i < 2 * S; i += BSC_WAVE) {
-                const int s = i >> 1, pb = 2 * role + (i & 1);
+                const int s = i >> 1, pb = 2 * chunk + (i & 1);
                 if (4 * pb < D)
                     blr_draw_block(new_m - d0, new_rho - d0, D, s, pb, a.seed, a.next_step,
                                    a.eps_next, a.W_next);
@@ -1716,45 +1227,9 @@ __device__ void fused_update_role(const FusedArgs& a, int role, Wait wait) {
             if (d < D) wpre[j] = a.W[(int64_t)wave * D + d];
         }
     }
-    // folded finish: everything that does not need the slab first -- this role belongs to the EARLIEST of the role
-    // workgroups, which has the longest wait for the last partial (a second draw per wave prefetched too: four
-    // waves here, sixteen in the finish kernel)
-    float wpre2[4] = {0.f, 0.f, 0.f, 0.f};
-    bool sums_done = false;
-    if (COH) {
-        if (FUSED_WAVES < FIN_MAX_S && wave + FUSED_WAVES < S) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int d = lane + BSC_WAVE * j;
-                if (d < D) wpre2[j] = a.W[(int64_t)(wave + FUSED_WAVES) * D + d];
-            }
-        }
-        for (int s = wave; s < S; s += FUSED_WAVES) {
-            double part = 0.0;
-            int d = lane;
-            if (s == wave || s == wave + FUSED_WAVES) {   // the prefetched columns, same ascending order as the loop below
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float wj = s == wave ? wpre[j] : wpre2[j];
-                    if (d < D) part += (double)wj * (double)wj;
-                    d += BSC_WAVE;
-                }
-            }
-            for (; d < D; d += BSC_WAVE) {
-                const double wv = (double)a.W[(int64_t)s * D + d];
-                part += wv * wv;
-            }
-            part = wave_allsum_f64(part);
-            if (lane == 0) wsq[s] = part;
-        }
-        rho_part = wave_allsum_f64(rho_part);
-        if (lane == 0) red[wave][32] = rho_part;
-        sums_done = true;
-        wait();
-    }
     if (a.slab) {  // S <= 8: thread -> (sample tid&7, slab-row group tid>>3)
-        double part = slab_column_sum<(FUSED_BLOCK >= 1024 ? 8 : 16), COH>(a.slab + SLAB_G + (tid & 7), tid >> 3, FUSED_BLOCK / 8,
-                                         a.n_slab);
+        double part = slab_column_sum<(FUSED_BLOCK >= 1024 ? 8 : 16)>(a.slab + SLAB_G + (tid & 7), tid >> 3, FUSED_BLOCK / 8,
+                                                                       a.n_slab);
         // fold the 8 row groups of this wave (lane bits 3-5), then the 16 waves
         part += __shfl_xor(part, 8);
         part += __shfl_xor(part, 16);
@@ -1763,7 +1238,7 @@ __device__ void fused_update_role(const FusedArgs& a, int role, Wait wait) {
     } else {
         for (int s = tid; s < S; s += FUSED_BLOCK) Qs[s] = a.stats[s];
     }
-    for (int s = wave; s < S && !sums_done; s += FUSED_WAVES) {
+    for (int s = wave; s < S; s += FUSED_WAVES) {
         double part = 0.0;
         int d = lane;
         if (s == wave) {  // the prefetched columns, same ascending order as the loop below
@@ -1780,10 +1255,8 @@ __device__ void fused_update_role(const FusedArgs& a, int role, Wait wait) {
         part = wave_allsum_f64(part);
         if (lane == 0) wsq[s] = part;
     }
-    if (!sums_done) {
-        rho_part = wave_allsum_f64(rho_part);
-        if (lane == 0) red[wave][32] = rho_part;  // column 32: clear of the Q staging columns
-    }
+    rho_part = wave_allsum_f64(rho_part);
+    if (lane == 0) red[wave][32] = rho_part;  // column 32: clear of the Q staging columns
     __syncthreads();
     if (a.slab && tid < 8) {
         double t = 0.0;
@@ -1835,11 +1308,6 @@ __device__ void fused_update_role(const FusedArgs& a, int role, Wait wait) {
         for (int s = tid; s < S; s += FUSED_BLOCK)
             blr_draw_scale(misc[1], misc[2], D, s, a.seed, a.next_step, a.eps_next, a.xi_next);
     }
-}
-
-template <int FUSED_BLOCK>
-__global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs a) {
-    fused_update_role<FUSED_BLOCK, false>(a, (int)blockIdx.x, [] {});
 }
 
 // Grid and per-wave trip count: fill the resident wave slots, then balance so
@@ -1916,99 +1384,48 @@ int keep_windows(const bsc_ctx* ctx, int64_t ldx, PassGrid g) {
 // sweep: BSC_SWEEP_STREAM (0) forward, every load non-temporal; BSC_SWEEP_FORWARD_KEEP (1) forward,
 // BSC_SWEEP_BACKWARD_KEEP (2) backward, the windows read last left in the Infinity Cache.  The 4-
 // and 8-row kernels (D != 256) always stream forward.
-// Can this pass carry its finish (FoldArgs)?  Only blr_pass_q_kernel does, and only when the grid leaves the role
-// workgroups something to wait for.
-bool pass_can_fold(const bsc_ctx* ctx, int D, const float* y, int sg, PassGrid g) {
-    return ctx->blr_fold && ctx->fold_counters && pass_rows(ctx, D, y) == 16 && ctx->blr_q && !ctx->blr_mx &&
-           !ctx->blr_q_dbg && ctx->blr_nt_loads && sg <= SG && g.n_iter > 0 && g.n_blocks >= 2 * ((SLAB_STRIDE + 63) / 64);
-}
-
 void launch_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, int64_t B, int D,
-                 const float* W, int sg, PassGrid g, float* slab, int sweep, bool wide = false,
-                 const FoldArgs* fold_in = nullptr) {
+                 const float* W, int sg, PassGrid g, float* slab, int sweep, bool wide = false) {
     const bool nt = ctx->blr_nt_loads != 0;
     const int rows = pass_rows(ctx, D, y);
     bsc_prof_scope prof(ctx);  // times the pass kernel alone
-    if (rows == 16) {
-        const int rev = sweep == BSC_SWEEP_BACKWARD_KEEP ? 1 : 0;
-        const int keep = sweep == BSC_SWEEP_STREAM ? 0 : keep_windows(ctx, ldx, g);
-#define BSC_PASS_MFMA(NT_, PK_)                                                                    \
-    hipLaunchKernelGGL((blr_pass_mfma_kernel<NT_, PK_>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0,   \
-                       ctx->stream, X, ldx, y, B, W, sg, slab, g.n_iter, rev, keep)
-        if (ctx->blr_mx || wide) {
-            // both contractions on the MFMA pipe; BSC_BLR_MX = 1 turns a keeping sweep into the rotated
-            // cached-zone schedule, 4 re-reads window 0 at every position (the compute floor)
-            int mode = rev, rot = 0;
-            if (sweep != BSC_SWEEP_STREAM && ctx->blr_mx == 1) { mode = 2; rot = ctx->blr_rot; }
-            if (ctx->blr_mx == 4) mode = 4;
-#define BSC_PASS_MX(NT_, NSB_)                                                                     \
-    hipLaunchKernelGGL((blr_pass_mx_kernel<NT_, NSB_>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0,    \
-                       ctx->stream, X, ldx, y, B, W, sg, slab, g.n_iter, mode, keep, rot)
-            if (wide && nt) BSC_PASS_MX(true, 4);
-            else if (wide) BSC_PASS_MX(false, 4);
-            else if (nt) BSC_PASS_MX(true, 2);
-            else BSC_PASS_MX(false, 2);
-#undef BSC_PASS_MX
-        } else if (ctx->blr_q) {
-            // both contractions on v_mfma_f32_4x4x1, the tile by LDS-DMA (round 4; option blr_q = 0: the kernels below)
-            unsigned long long* stamps = nullptr;
-            if (ctx->blr_stamps && !ctx->capturing) {
-                if (!ctx->stamps && hipMalloc(&ctx->stamps, (size_t)MAX_SLAB_ROWS * 64) != hipSuccess) ctx->stamps = nullptr;
-                stamps = (unsigned long long*)ctx->stamps;
-                ctx->stamp_rows = g.n_blocks <= MAX_SLAB_ROWS ? g.n_blocks : 0;
-                if (!ctx->stamp_rows) stamps = nullptr;
-            }
-            // windows of every workgroup / of the even ones (QSched): `blr_q_bias` per mille more for the even ones
-            const int64_t n_tiles = (B + MT_ROWS - 1) / MT_ROWS;
-            const int64_t w_all = (int64_t)g.n_blocks * PASS_WAVES, w_a = (int64_t)((g.n_blocks + 1) / 2) * PASS_WAVES;
-            int extra = (int)((int64_t)g.n_iter * ctx->blr_q_bias + 500) / 1000;
-            if (g.n_blocks < 2 || sweep != BSC_SWEEP_STREAM) extra = 0;
-            int64_t rest = n_tiles - (int64_t)extra * w_a;
-            if (rest < 0) { rest = n_tiles; extra = 0; }
-            const int n_all = extra ? (int)((rest + w_all - 1) / w_all) : g.n_iter;
-            const int n_a = n_all + extra;
-            FoldArgs fold{};
-            if (fold_in) fold = *fold_in;
-            // the stealing tail (StealArgs): every wave `n_st` tiles of its own, the rest in the queues
-            StealArgs steal{};
-            int n_st = (int)((n_tiles * (1000 - ctx->blr_steal)) / (1000 * w_all));
-            if (ctx->blr_steal > 0 && ctx->steal_heads && nt && sweep == BSC_SWEEP_STREAM && n_st >= 1 && !ctx->blr_q_dbg && !fold.mode) {
-                steal.heads = ctx->steal_heads;
-                steal.t0 = (long long)n_st * w_all;
-                steal.n_dyn = n_tiles - steal.t0;
-                // whole groups of 8 workgroups only: a short last group joins queue (groups - 1) % nq -- a queue of its own
-                // would hold a full share of tiles for an eighth of the waves
-                steal.nq = g.n_blocks / 8 < 1 ? 1 : g.n_blocks / 8 < STEAL_Q ? g.n_blocks / 8 : STEAL_Q;
-                steal.per_q = (int)((steal.n_dyn + steal.nq - 1) / steal.nq);
-            }
-            const int q_all = steal.heads ? n_st : n_all, q_a = steal.heads ? n_st : n_a;
+    const int rev = sweep == BSC_SWEEP_BACKWARD_KEEP ? 1 : 0;
+    const int keep = sweep == BSC_SWEEP_STREAM ? 0 : keep_windows(ctx, ldx, g);   // (the 16-row kernels only)
+    if (rows == 16 && wide) {
+        // sixteen draws per pass
+        if (nt) hipLaunchKernelGGL((blr_pass_mx_kernel<true, 4>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y,
+                                   B, W, sg, slab, g.n_iter, rev, keep);
+        else hipLaunchKernelGGL((blr_pass_mx_kernel<false, 4>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y,
+                                B, W, sg, slab, g.n_iter, rev, keep);
+    } else if (rows == 16) {
+        // both contractions on v_mfma_f32_4x4x1, the tile by LDS-DMA
+        unsigned long long* stamps = nullptr;
+        if (ctx->blr_stamps && !ctx->capturing) {
+            if (!ctx->stamps && hipMalloc(&ctx->stamps, (size_t)MAX_SLAB_ROWS * 64) != hipSuccess) ctx->stamps = nullptr;
+            stamps = (unsigned long long*)ctx->stamps;
+            ctx->stamp_rows = g.n_blocks <= MAX_SLAB_ROWS ? g.n_blocks : 0;
+            if (!ctx->stamp_rows) stamps = nullptr;
+        }
+        // windows of every workgroup / of the even ones (QSched): `blr_q_bias` per mille more for the even ones
+        const int64_t n_tiles = (B + MT_ROWS - 1) / MT_ROWS;
+        const int64_t w_all = (int64_t)g.n_blocks * PASS_WAVES, w_a = (int64_t)((g.n_blocks + 1) / 2) * PASS_WAVES;
+        int extra = (int)((int64_t)g.n_iter * ctx->blr_q_bias + 500) / 1000;
+        if (g.n_blocks < 2 || sweep != BSC_SWEEP_STREAM) extra = 0;
+        int64_t rest = n_tiles - (int64_t)extra * w_a;
+        if (rest < 0) { rest = n_tiles; extra = 0; }
+        const int n_all = extra ? (int)((rest + w_all - 1) / w_all) : g.n_iter;
+        const int n_a = n_all + extra;
 #define BSC_PASS_Q(NT_, DBG_, PRIO_)                                                               \
     hipLaunchKernelGGL((blr_pass_q_kernel<NT_, DBG_, PRIO_>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0, \
-                       ctx->stream, X, ldx, y, B, W, sg, slab, q_all, q_a, rev, keep, stamps, fold, steal)
-            if (ctx->blr_q_dbg == 1) BSC_PASS_Q(true, 1, 0);
-            else if (ctx->blr_q_dbg == 2) BSC_PASS_Q(true, 2, 0);
-            else if (ctx->blr_q_dbg == 3) BSC_PASS_Q(true, 3, 0);
-            else if (steal.heads && ctx->blr_q_prio == 1)
-                hipLaunchKernelGGL((blr_pass_q_kernel<true, 0, 1, true>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y,
-                                   B, W, sg, slab, q_all, q_a, rev, keep, stamps, fold, steal);
-            else if (steal.heads)
-                hipLaunchKernelGGL((blr_pass_q_kernel<true, 0, 0, true>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y,
-                                   B, W, sg, slab, q_all, q_a, rev, keep, stamps, fold, steal);
-            else if (nt && ctx->blr_q_prio == 1) BSC_PASS_Q(true, 0, 1);
-            else if (nt && ctx->blr_q_prio == 2) BSC_PASS_Q(true, 0, 2);
-            else if (nt) BSC_PASS_Q(true, 0, 0);
-            else BSC_PASS_Q(false, 0, 0);
+                       ctx->stream, X, ldx, y, B, W, sg, slab, n_all, n_a, rev, keep, stamps)
+        if (ctx->blr_q_dbg == 1) BSC_PASS_Q(true, 1, 0);
+        else if (ctx->blr_q_dbg == 2) BSC_PASS_Q(true, 2, 0);
+        else if (ctx->blr_q_dbg == 3) BSC_PASS_Q(true, 3, 0);
+        else if (nt && ctx->blr_q_prio == 1) BSC_PASS_Q(true, 0, 1);
+        else if (nt && ctx->blr_q_prio == 2) BSC_PASS_Q(true, 0, 2);
+        else if (nt) BSC_PASS_Q(true, 0, 0);
+        else BSC_PASS_Q(false, 0, 0);
 #undef BSC_PASS_Q
-        } else if (ctx->blr_dma && ctx->blr_pk) {
-            if (nt) hipLaunchKernelGGL((blr_pass_dma_kernel<true>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx,
-                                       y, B, W, sg, slab, g.n_iter, rev, keep);
-            else hipLaunchKernelGGL((blr_pass_dma_kernel<false>), dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx,
-                                    y, B, W, sg, slab, g.n_iter, rev, keep);
-        } else if (nt && ctx->blr_pk) BSC_PASS_MFMA(true, true);
-        else if (nt) BSC_PASS_MFMA(true, false);
-        else if (ctx->blr_pk) BSC_PASS_MFMA(false, true);
-        else BSC_PASS_MFMA(false, false);
-#undef BSC_PASS_MFMA
     } else if (rows == 8) {
         if (nt) launch_pass_rows<8, true>(ctx, X, ldx, y, B, D, W, sg, g, slab);
         else launch_pass_rows<8, false>(ctx, X, ldx, y, B, D, W, sg, g, slab);
@@ -2037,16 +1454,6 @@ int data_pass_impl(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, in
         const bool wide = wide_ok && S - s0 > SG;
         const int cap = wide ? 2 * SG : SG;
         const int sg = (S - s0 < cap) ? (S - s0) : cap;
-        if (!wide && pass_can_fold(ctx, (int)D, y, sg, g)) {
-            // the float64 statistics come out of the pass's own tail (FoldArgs mode 2): no reduce launch
-            FoldArgs fold{};
-            fold.mode = 2; fold.counters = ctx->fold_counters; fold.Q = Q; fold.G = G; fold.s_base = s0; fold.S_total = (int)S;
-            launch_pass(ctx, X, ldx, y, B, (int)D, W + (int64_t)s0 * D, sg, g, slab, sweep, false, &fold);
-            BSC_LAUNCH_CHECK();
-            s0 += sg;
-            if (sweep != BSC_SWEEP_STREAM) sweep = 3 - sweep;
-            continue;
-        }
         launch_pass(ctx, X, ldx, y, B, (int)D, W + (int64_t)s0 * D, sg, g, slab, sweep, wide);
         BSC_LAUNCH_CHECK();
         hipLaunchKernelGGL(blr_slab_reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, slab,
@@ -2186,7 +1593,7 @@ int fused_update_impl(bsc_ctx* ctx, const char* who, const double* stats, const 
                       int32_t S, double c0, double c_xi, double s_q, double k_w, double beta, int64_t t, double lr,
                       double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
                       double* eps_next, int32_t eps_next_ready, float* W_next, double* xi_next, double* elbo,
-                      double* grad, FusedArgs* out_args = nullptr) {
+                      double* grad) {
     BSC_CHECK_CTX(ctx);
     BSC_REQUIRE(lam_in && lam_out && m1 && m2 && eps && W && xi && elbo && grad, "%s: null pointer", who);
     BSC_REQUIRE(lam_in != lam_out, "%s: lam_in and lam_out must differ", who);
@@ -2200,7 +1607,7 @@ int fused_update_impl(bsc_ctx* ctx, const char* who, const double* stats, const 
     a.stats = stats;
     a.slab = nullptr;
     a.n_slab = 0;
-    if (!stats && !out_args) {
+    if (!stats) {
         BSC_REQUIRE(ctx->slab_rows > 0 && ctx->workspace,
                     "%s: stats is null and no bsc_blr_data_pass_partial slab is pending", who);
         BSC_REQUIRE(S <= SG && D <= GCOLS, "%s: slab input needs S<=8, D<=256", who);
@@ -2219,10 +1626,6 @@ int fused_update_impl(bsc_ctx* ctx, const char* who, const double* stats, const 
     a.corr2 = 1.0 - pow(beta2, (double)t);
     a.seed = seed;
     a.next_step = next_step;
-    if (out_args) {             // bsc_blr_pass_update: the pass launches with these (FoldArgs mode 1)
-        *out_args = a;
-        return BSC_OK;
-    }
     {
         bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish kernel, timed apart from the pass
         const dim3 fgrid((D + 7) / 8 + 1);
@@ -2256,9 +1659,7 @@ int bsc_blr_fused_update(bsc_ctx* ctx, const double* stats, const double* lam_in
 }
 
 namespace {
-// One update = the pass with its finish folded into its tail when the shape allows it (blr_pass_q_kernel: D = 256,
-// S <= 8, a grid of at least 66 workgroups, option blr_fold), else the two launches bsc_blr_data_pass_partial_sweep +
-// bsc_blr_fused_update[_general] make.  Same results either way up to the order of the float64 slab sum.
+// One update = the two launches bsc_blr_data_pass_partial_sweep + bsc_blr_fused_update[_general] (stats = NULL) make.
 int pass_update_impl(bsc_ctx* ctx, const char* who, const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
                      int32_t sweep, const double* lam_in, double* lam_out, double* m1, double* m2, const double* eps,
                      const float* W, const double* xi, int32_t S, double c0, double c_xi, double s_q, double k_w,
@@ -2269,30 +1670,11 @@ int pass_update_impl(bsc_ctx* ctx, const char* who, const float* X, int64_t ldx,
     int rc = check_pass_args(X, ldx, y, B, D, W, S, SG);
     if (rc != BSC_OK) return rc;
     BSC_REQUIRE(sweep >= 0 && sweep <= 2, "%s: sweep=%d (0, 1 or 2)", who, sweep);
-    const PassGrid g = pass_grid(ctx, B, pass_rows(ctx, D, y));
-    if (!pass_can_fold(ctx, (int)D, y, (int)S, g)) {
-        rc = data_pass_partial_impl(ctx, X, ldx, y, B, D, W, S, sweep);
-        if (rc != BSC_OK) return rc;
-        return fused_update_impl(ctx, who, nullptr, lam_in, lam_out, m1, m2, eps, W, xi, D, S, c0, c_xi, s_q, k_w, beta, t,
-                                 lr, beta1, beta2, adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, xi_next,
-                                 elbo, grad);
-    }
-    FoldArgs fold{};
-    rc = fused_update_impl(ctx, who, nullptr, lam_in, lam_out, m1, m2, eps, W, xi, D, S, c0, c_xi, s_q, k_w, beta, t, lr,
-                           beta1, beta2, adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, xi_next, elbo, grad,
-                           &fold.a);
+    rc = data_pass_partial_impl(ctx, X, ldx, y, B, D, W, S, sweep);
     if (rc != BSC_OK) return rc;
-    void* ws = nullptr;
-    rc = bsc_workspace(ctx, (size_t)2 * g.n_blocks * SLAB_STRIDE * sizeof(float), &ws);
-    if (rc != BSC_OK) return rc;
-    fold.a.slab = (const float*)ws;
-    fold.a.n_slab = g.n_blocks;
-    fold.mode = 1;
-    fold.counters = ctx->fold_counters;
-    launch_pass(ctx, X, ldx, y, B, (int)D, W, (int)S, g, (float*)ws, sweep, false, &fold);
-    BSC_LAUNCH_CHECK();
-    ctx->slab_rows = 0;      // consumed inside the launch
-    return BSC_OK;
+    return fused_update_impl(ctx, who, nullptr, lam_in, lam_out, m1, m2, eps, W, xi, D, S, c0, c_xi, s_q, k_w, beta, t,
+                             lr, beta1, beta2, adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, xi_next,
+                             elbo, grad);
 }
 }  // namespace
 

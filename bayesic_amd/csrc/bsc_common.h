@@ -50,26 +50,19 @@ struct bsc_ctx {
     int mog_nt = 0;              // bsc_mog_estep: 1 = non-temporal loads of X (BSC_MOG_NT).  Default 0: both half-waves read the same rows and the L2 keeps a row for the second one -- 1.01 x the algorithmic bytes instead of 1.19 x, same time (profiles/r03_pmc_kernels.txt)
     int wo_wg_per_cu = 2;        // bsc_weighted_outer: resident workgroups per CU the grid is sized for
     int fused_waves_per_cu = 16; // bsc_map_reduce: reduce splits target this many waves per CU
-    int blr_dma = 1;             // blr_pass_dma_kernel (the tile by LDS-DMA: 166 -> 161 us at 1M x 256) -- BSC_BLR_DMA=0: blr_pass_mfma_kernel (tile through registers), for A/B
-    int blr_q = 1;               // blr_pass_q_kernel (both contractions on v_mfma_f32_4x4x1, the tile by LDS-DMA; round 4) -- BSC_BLR_Q=0: blr_pass_dma_kernel, for A/B
+    int blr_q = 1;               // pinned: blr_pass_q_kernel (both contractions on v_mfma_f32_4x4x1, the tile by LDS-DMA) is the D = 256, S <= 8 pass
     int blr_q_dbg = 0;           // deletion builds of blr_pass_q_kernel (BSC_BLR_Q_DBG + BSC_PROFILING_BUILDS): WRONG results
     int blr_q_bias = 70;         // blr_pass_q_kernel, static schedule: per mille of further windows for the workgroups with an even blockIdx (QSched)
     int blr_q_prio = 1;          // blr_pass_q_kernel: s_setprio 1 from a tile's landing to the next tile's DMAs (1), or during the backward (2)
-    int blr_fold = 0;            // 1: blr_pass_q_kernel carries its finish (or the float64 statistics of the N > 1 structure) in its tail -- one launch per update (FoldArgs).  Built and measured in round 4: break-even (162.9-163.1 vs 162.5-162.9 us per 1M-row update, 36.4 vs 35.3-36.4 at 125k rows, profiles/r04_fold_*.txt), so off by default
-    unsigned* fold_counters = nullptr;   // [arrivals, roles done] of the folded finish: zero between launches
-    int blr_steal = 0;           // blr_pass_q_kernel, streaming sweep: per mille of the tiles left to the queues (StealArgs) the waves draw on after their static share.  Built and measured in round 4 (profiles/r04_ab_pass_q_steal.txt): every workgroup then ends within ~4 us of every other, but the launch gains 0.5-1.5 us of 157 at 1M rows, 2-2.7 of 85 at 500k, loses 0.5 of 28.7 at 125k -- the static schedule's early finishers leave their bandwidth to the late ones, so little was lost -- and the last bits of the sums are no longer reproducible: off by default
-    unsigned* steal_heads = nullptr;     // 64 queue heads 256 bytes apart + the workgroups-done counter (inside fold_counters' allocation): zero between launches
     int blr_stamps = 0;          // blr_pass_q_kernel: every workgroup leaves start / end s_memrealtime stamps and its XCD (bsc_blr_read_stamps)
-    void* stamps = nullptr;      // 32 bytes per workgroup, allocated when blr_stamps is first used
+    void* stamps = nullptr;      // 64 bytes per workgroup (words 0-3 used), allocated when blr_stamps is first used
     int stamp_rows = 0;          // workgroups of the last stamped launch
     int profiling_builds = 0;    // 1: the deletion builds (options marked dbg) may be selected -- WRONG results, timing only
-    int blr_pk = 1;              // MFMA pass: backward rank-1 updates as packed FMAs (BSC_BLR_PK=0: scalar; +0.4 % in-process A/B, same bits)
     int blr_finish_block = 1024; // threads per workgroup of blr_fused_update_kernel (BSC_BLR_FINISH_BLOCK = 256 | 512 | 1024)
     int blr_nt_loads = 1;        // non-temporal loads of X (read once per pass): +9% measured
     int blr_keep = -1;           // windows a keeping sweep leaves in the Infinity Cache (BSC_BLR_KEEP; -1 = what fits 256 MiB)
-    int blr_mx = 0;              // BSC_BLR_MX: 1 = blr_pass_mx_kernel (backward on 4x4x1 MFMA) with the rotated cached-zone schedule, 2 = that kernel with the plain sweep orders
+    int blr_mx = 0;              // pinned: blr_pass_mx_kernel runs for S > 8 only (blr_wide)
     int blr_wide = 1;            // BSC_BLR_WIDE: S > 8 runs sixteen draws per pass (blr_pass_mx_kernel<., 4>); 0 = eight per pass
-    int blr_rot = 2;             // BSC_BLR_ROT: workgroups per rotation group = 2^rot
     int slab_rows = 0;  // block partials left in `workspace` by bsc_blr_data_pass_partial
     int capturing = 0;  // between bsc_capture_begin and bsc_capture_end: launches are recorded, not run
     // optional per-kernel timing of the dominant kernel (bsc_ctx_profile)

@@ -138,9 +138,8 @@ class Context:
         return int(out.value)
 
     def read_stamps(self):
-        """Option blr_stamps: (rows, 8) uint64 array {start tick, end tick, XCD, HW_ID, and -- folded finish -- partial
-        written, ticket taken, every row arrived, ticket} per workgroup of the last D = 256, S <= 8 pass (100 MHz
-        ticks); syncs."""
+        """Option blr_stamps: (rows, 8) uint64 array {start tick, end tick, XCD, HW_ID, four unused words} per workgroup
+        of the last D = 256, S <= 8 pass (100 MHz ticks); syncs."""
         import numpy as np
         buf = np.zeros((2048, 8), np.uint64)
         n = ctypes.c_int32()

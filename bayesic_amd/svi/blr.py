@@ -94,8 +94,8 @@ class BLRReparamSVI:
         self.batch_rows = self.exchange.global_count(self.B, dev)
         self.n_total = float(n_total) if n_total is not None else self.batch_rows
         self.fused = bool(fused)
-        # one launch per update (bsc_blr_pass_update: the finish in the pass's tail) where the library offers the entry
-        # point; a test double without it, or one_launch = False, takes the two launches
+        # one call per update (bsc_blr_pass_update: the pass, then the finish from its slab) where the library offers the
+        # entry point; a test double without it, or one_launch = False, makes the two calls itself
         self.one_launch = hasattr(getattr(self.ctx, "lib", None), "bsc_blr_pass_update")
         self.reproducible = bool(reproducible)
         if sweep not in ("alternate", "stream"):
@@ -368,7 +368,7 @@ class BLRReparamSVI:
         if self.fused and self.world == 1 and not self.exchange.rccl and self.S <= 8 and not self.reproducible \
                 and self.covariance_kind == "diag":
             if self.one_launch:
-                self._pass_update()         # the pass with the finish in its tail: one launch (falls back inside the library)
+                self._pass_update()         # the pass and the finish in one call
             else:
                 self.ctx.call("bsc_blr_data_pass_partial_sweep", self._Xarg, self._ldx,
                               self._yarg, self.B, self.D, self.W, self.S, self._take_sweep())

@@ -18,15 +18,12 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # kernel-name substring -> (max VGPRs, max scratch bytes per lane)
 LIMITS = {
     "bsc_blr.hip": {
-        "blr_pass_mfma_kernelILb1E": (232, 0),          # 2 waves/SIMD needs <= 256
-        "blr_pass_dma_kernelILb1E": (232, 0),           # round 3's pass (option blr_q = 0): the tile by LDS-DMA
-        "blr_pass_q_kernelILb1ELi0ELi0E": (224, 0),         # the default pass since round 4: both contractions on v_mfma_f32_4x4x1 (2 waves/SIMD)
-        "blr_pass_mx_kernelILb1ELi2E": (232, 0),
+        "blr_pass_q_kernelILb1ELi0ELi1E": (224, 0),     # the default pass: both contractions on v_mfma_f32_4x4x1 (2 waves/SIMD needs <= 256)
         "blr_pass_mx_kernelILb1ELi4E": (256, 0),        # sixteen draws per pass: 64 accumulator registers
         "blr_pass_kernelILb1ELi8ELb1E": (256, 0),
         "blr_fused_update_kernelILi1024E": (128, 0),    # the default: sixteen waves = four per SIMD
         "blr_fused_update_kernelILi512E": (192, 0),     # (A/B variants: eight / four waves, the slab in one trip of
-        "blr_fused_update_kernelILi256E": (192, 0),     #  32 loads per lane, as the folded finish's roles read it)
+        "blr_fused_update_kernelILi256E": (192, 0),     #  32 loads per lane)
     },
     "bsc_rowsoftmax.hip": {
         "gemm_softmax_rows_kernelILi20E": (256, 0),     # K = 40 (the derived mixture): 2 waves/SIMD, no scratch

@@ -28,12 +28,8 @@ def main():
     y = torch.randn(B, generator=g, device=dev)
     W = torch.randn((S, D), generator=g, device=dev) / 16
     ctxs = {}
-    # (tile rows, waves/SIMD cap, non-temporal loads); append "pk" on the command line to
-    # compare the MFMA pass with scalar vs packed backward FMAs instead
+    # (tile rows, waves/SIMD cap, non-temporal loads)
     variants = [(8, 0, 1), (16, 0, 1)]
-    pk_mode = "pk" in sys.argv
-    if pk_mode:
-        variants = [(16, 0, 1), (16, 1000, 1)]      # second entry: BSC_BLR_PK=1 (cap field reused as a tag)
     if "wide" in sys.argv:
         # S > 8: sixteen draws per pass (BSC_BLR_WIDE=1, default) against eight per pass
         res = {}
@@ -68,32 +64,22 @@ def main():
         # `keep` trailing windows left in the Infinity Cache (-1 = the library's own choice) against
         # the plain streaming pass
         ctxs = {}
-        # alt >= 10: fixed cached zone of `keep` windows + rotated schedule, rotation unit 2^(alt-10) workgroups
-        # (alt, keep): alt 0 = streaming pass, 1 = alternating keeping sweeps; + 10 * BSC_BLR_MX
-        # (10/11: blr_pass_mx_kernel with the rotated cached zone; 20/21: that kernel, plain sweeps);
-        # + 100 * BSC_BLR_ROT
-        # BSC_BLR_MX = 4: every position re-reads window 0 (cache hits only: the kernel's compute floor)
-        for alt, keep in [(0, 0), (1, -1), (20, 0), (21, -1), (211, 7), (40, 0), (41, 33)]:
+        # (alt, keep): alt 0 = streaming pass, 1 = alternating keeping sweeps
+        for alt, keep in [(0, 0), (1, -1), (1, 4), (1, 7), (1, 10)]:
             os.environ["BSC_BLR_KEEP"] = str(keep)
-            os.environ["BSC_BLR_MX"] = str((alt % 100) // 10)
-            os.environ["BSC_PROFILING_BUILDS"] = "1"      # (BSC_BLR_MX=4 is a deletion build: wrong results, timing only)
-            os.environ["BSC_BLR_ROT"] = str(alt // 100)
             os.environ["BSC_BLR_TILE_ROWS"] = "16"
             ctxs[(alt, keep)] = Context(0)
             ctxs[(alt, keep)].reserve(16 << 20)
         variants = []
     for rows, wps, nt in variants:
-        os.environ["BSC_BLR_PK"] = "1" if (pk_mode and wps == 1000) else "0"
-        if pk_mode:
-            wps = 0 if wps != 1000 else 1000
         os.environ["BSC_BLR_TILE_ROWS"] = str(rows)
-        os.environ["BSC_BLR_WAVES_PER_SIMD"] = str(0 if wps == 1000 else wps)
+        os.environ["BSC_BLR_WAVES_PER_SIMD"] = str(wps)
         os.environ["BSC_BLR_NT"] = str(nt)
         ctxs[(rows, wps, nt)] = Context(0)
         ctxs[(rows, wps, nt)].reserve(16 << 20)
     res = {k: [] for k in ctxs}
     def launch(key, c, i):
-        if sweep_mode and key[0] % 10:
+        if sweep_mode and key[0]:
             c.call("bsc_blr_data_pass_partial_sweep", ptr(X), D, ptr(y), B, D, ptr(W), S, 1 + (i & 1))
         else:
             c.call("bsc_blr_data_pass_partial", ptr(X), D, ptr(y), B, D, ptr(W), S)

@@ -1,6 +1,5 @@
-"""Interleaved A/B of the config-2 pass kernels in ONE process (round 4): blr_pass_dma_kernel (BSC_BLR_Q=0) against
-blr_pass_q_kernel (both contractions on v_mfma_f32_4x4x1) and its deletion builds, at the metric's mini-batch and at
-its 2/4/8-GPU shares.  Every launch reads a DIFFERENT resident mini-batch (a 1M x 256 buffer x 3 cut into pieces of the
+"""Interleaved A/B of blr_pass_q_kernel (the config-2 pass: both contractions on v_mfma_f32_4x4x1) in ONE process: its
+schedule and priority options and its deletion builds, at the metric's mini-batch and at its 2/4/8-GPU shares.  Every launch reads a DIFFERENT resident mini-batch (a 1M x 256 buffer x 3 cut into pieces of the
 row count under test), so nothing is served from the Infinity Cache.
 
     python tools/ab_q.py [rounds] [launches_per_round] [rows,rows,...]  [variants=...]
@@ -19,25 +18,16 @@ from bayesic_amd.device import Context
 
 VARIANTS = {
     # name: options of the context (bsc_ctx_set_option)
-    "dma": dict(blr_q=0),
-    "q": dict(blr_q=1),
-    "q-prio1": dict(blr_q=1, blr_q_prio=1),
-    "q-prio2": dict(blr_q=1, blr_q_prio=2),
-    "q-bias40": dict(blr_q=1, blr_q_bias=40),
-    "q-bias100p1": dict(blr_q=1, blr_q_bias=100, blr_q_prio=1),
-    "q-bias0": dict(blr_q=1, blr_q_bias=0),
-    "q-bias100": dict(blr_q=1, blr_q_bias=100),
-    "q-bias130": dict(blr_q=1, blr_q_bias=130),
-    "q-steal1": dict(blr_q=1, blr_steal=1),
-    "q-steal60": dict(blr_q=1, blr_steal=60),
-    "q-steal100": dict(blr_q=1, blr_steal=100),
-    "q-steal150": dict(blr_q=1, blr_steal=150),
-    "q-steal200": dict(blr_q=1, blr_steal=200),
-    "q-steal350": dict(blr_q=1, blr_steal=350),
-    "q-steal250": dict(blr_q=1, blr_steal=250),
-    "q-nocompute": dict(profiling_builds=1, blr_q=1, blr_q_dbg=1),
-    "q-fwdonly": dict(profiling_builds=1, blr_q=1, blr_q_dbg=2),
-    "q-bwdonly": dict(profiling_builds=1, blr_q=1, blr_q_dbg=3),
+    "q": dict(),
+    "q-prio0": dict(blr_q_prio=0),
+    "q-prio2": dict(blr_q_prio=2),
+    "q-bias40": dict(blr_q_bias=40),
+    "q-bias0": dict(blr_q_bias=0),
+    "q-bias100": dict(blr_q_bias=100),
+    "q-bias130": dict(blr_q_bias=130),
+    "q-nocompute": dict(profiling_builds=1, blr_q_dbg=1),
+    "q-fwdonly": dict(profiling_builds=1, blr_q_dbg=2),
+    "q-bwdonly": dict(profiling_builds=1, blr_q_dbg=3),
 }
 
 
@@ -69,14 +59,6 @@ def stamp_report(c, name):
     print("    %-12s per CU (end of its last workgroup): even XCDs mean %.1f max %.1f | odd XCDs mean %.1f max %.1f; all: p10 %.1f p50 %.1f p90 %.1f"
           % (name, cu_end[cu_par == 0].mean(), cu_end[cu_par == 0].max(), cu_end[cu_par == 1].mean(), cu_end[cu_par == 1].max(),
              np.percentile(cu_end, 10), np.percentile(cu_end, 50), np.percentile(cu_end, 90)))
-    if VARIANTS[name].get("blr_steal"):
-        a = (st[:, 4] - t0).astype(np.float64) / 100.0
-        b = (st[:, 5] - t0).astype(np.float64) / 100.0
-        print("    %-12s wave 0 of a workgroup: static share read at p10 %.1f p50 %.1f p90 %.1f us; left the queue at p10 %.1f p50 %.1f p90 %.1f max %.1f;"
-              " queued tiles taken mean %.2f min %d max %d; end - left p50 %.1f max %.1f"
-              % (name, *np.percentile(a, [10, 50, 90]), *np.percentile(b, [10, 50, 90, 100]), st[:, 6].mean(), st[:, 6].min(), st[:, 6].max(),
-                 np.median(end - b), (end - b).max()))
-        print("    %-12s queued tiles taken by wave 0, mean per XCD:" % name, " ".join("[%d] %.2f" % (x, st[xcd == x, 6].mean()) for x in range(8) if (xcd == x).any()))
     pairs = [v for v in per_cu.values() if len(v) == 2]
     if pairs:
         d = np.array([abs(a - b) for a, b in pairs])
@@ -130,12 +112,11 @@ def main():
         bytes_ = 4.0 * B * D + 4.0 * B
         if "stamps" in sys.argv:
             for n, c in ctxs.items():
-                if VARIANTS[n].get("blr_q", 1):
-                    c.set_option("blr_stamps", 1)
-                    for _ in range(4):
-                        launch(c)
-                    stamp_report(c, n)
-                    c.set_option("blr_stamps", 0)
+                c.set_option("blr_stamps", 1)
+                for _ in range(4):
+                    launch(c)
+                stamp_report(c, n)
+                c.set_option("blr_stamps", 0)
         for n in names:
             a = np.array(res[n])
             print("rows=%8d  %-12s per-launch us: median %7.2f  min %7.2f  max %7.2f  -> %5.0f GB/s = %.3f of 8 TB/s"
