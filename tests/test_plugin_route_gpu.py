@@ -142,13 +142,20 @@ def test_shapes_the_pass_refuses_fall_back_to_the_general_route_with_the_reason(
     npt.assert_allclose(eng.elbo, host.elbo, rtol=1e-5)
     assert np.abs(eng.grad - host.grad).max() <= 2e-4 * np.abs(host.grad).max()
     # a column-sliced view of a wider matrix: D = 8 is fine, the view is not the pass's layout either way it is run
-    Xw = ctx.to_device(np.ascontiguousarray(np.random.RandomState(0).standard_normal((B, 13)).astype(np.float32)))
+    Xw_host = np.ascontiguousarray(np.random.RandomState(0).standard_normal((B, 13)).astype(np.float32))
+    Xw = ctx.to_device(Xw_host)
     view = Xw[:, 1:9]                                    # stride 13, offset 4 bytes: neither % 4 nor 16-byte aligned
-    eng2 = ReparamVI(lj, [(v["W"], 8), (v["xi"], 1)], dict(X=view, y=ctx.to_device(y)), n_samples=S, seed=11,
-                     backend=DeviceBackend(ctx))
+    latents2 = [(v["W"], 8), (v["xi"], 1)]
+    eng2 = ReparamVI(lj, latents2, dict(X=view, y=ctx.to_device(y)), n_samples=S, seed=11, backend=DeviceBackend(ctx))
     assert eng2.route == "general" and "envelope" in eng2.route_reason
+    # the general route must be RIGHT on the view, not merely finite: the host twin on the same draws and values
+    eps2 = eng2.draw(0)
+    host2 = ReparamVI(lj, latents2, dict(X=Xw_host[:, 1:9], y=y), n_samples=S, seed=11,
+                      backend=NumpyBackend(np.float64), noise=lambda step: eps2)
     eng2.step()
-    assert np.isfinite(eng2.elbo)
+    host2.step()
+    npt.assert_allclose(eng2.elbo, host2.elbo, rtol=1e-5)
+    assert np.abs(eng2.grad - host2.grad).max() <= 2e-4 * np.abs(host2.grad).max()
 
 
 def test_set_data_with_another_row_count_is_refused_on_the_pass_route_too(ctx):
