@@ -27,3 +27,34 @@ def linear_regression_log_joint(n_total_over_batch=1.0, alpha0=1.0, beta0=1.0, d
     prior_w = A.sum(Normal().log_likelihood(W, mean=0.0, variance=s2_rows), axis=1)
     prior_xi = InverseGamma().log_likelihood(s2, shape=float(alpha0), scale=float(beta0)) + x
     return likelihood + prior_w + prior_xi, dict(X=X, y=y, W=W, xi=xi)
+
+
+def _glm_log_joint(link, n_total_over_batch, prior_precision, dtype):
+    import math
+    X, y, W = A.var("X", 2, dtype), A.var("y", 1, dtype), A.var("W", 2, dtype)
+    logits = A.dot(W, X.T)                                  # [S, N]
+    log_partition = A.log(1.0 + A.exp(logits)) if link == "logistic" else A.exp(logits)
+    likelihood = A.sum(A.dimshuffle(y, "x", 0) * logits - log_partition, axis=1) * float(n_total_over_batch)
+    tau = float(prior_precision)
+    prior_w = A.sum(W * W, axis=1) * (-0.5 * tau) + A.shape(W, 1) * (0.5 * math.log(tau / (2.0 * math.pi)))
+    return likelihood + prior_w, dict(X=X, y=y, W=W)
+
+
+def logistic_regression_log_joint(n_total_over_batch=1.0, prior_precision=1.0, dtype="float32"):
+    """Bernoulli-logit regression: y_n ~ Bernoulli(sigmoid(x_n . w)), w ~ N(0, I / prior_precision), with a leading
+    Monte-Carlo sample axis on the latent ``W`` [S, D]:
+
+        log p(y, w) = scale * sum_n [y_n l_n - log(1 + exp(l_n))] + sum_d log N(w_d | 0, 1 / prior_precision),   l = X w
+
+    (an intercept is a column of ones in X).  Returns (log-joint [S], the vars ``X`` [N, D], ``y`` [N], ``W``)."""
+    return _glm_log_joint("logistic", n_total_over_batch, prior_precision, dtype)
+
+
+def poisson_regression_log_joint(n_total_over_batch=1.0, prior_precision=1.0, dtype="float32"):
+    """Poisson regression with the log link: y_n ~ Poisson(exp(x_n . w)), w ~ N(0, I / prior_precision):
+
+        log p(y, w) = scale * sum_n [y_n l_n - exp(l_n)] + sum_d log N(w_d | 0, 1 / prior_precision),   l = X w
+
+    without the term -scale * sum_n lnGamma(y_n + 1), which depends on no latent.  Same return as
+    ``logistic_regression_log_joint``."""
+    return _glm_log_joint("poisson", n_total_over_batch, prior_precision, dtype)

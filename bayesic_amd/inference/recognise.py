@@ -21,6 +21,8 @@ probe points and checking the fit at random others, in host float64 (``_param_ba
 testing by evaluation, which does not care in which of many equivalent ways the model was written
 (``exp(-xi)``, ``1 / exp(xi)``, ``pow(var, -1)`` ...).
 """
+import math
+
 import numpy as np
 
 from .. import algebra as A
@@ -492,3 +494,95 @@ def logistic_hierarchy(log_joint, latents, data_shapes, n_samples, why=None):
                     reason = "%s while evaluating the log-joint on a seven-row instance: %s" % (type(e).__name__, e)
                     continue
     return _say(why, reason)
+
+
+# ---- canonical-link GLMs with an isotropic Gaussian prior (svi/glm.py) ---------------------------------------------
+
+class GLMLinear(object):
+    """What ``glm_linear`` found: log p(data, w_s) = scale * sum_n [y_n l_ns - A(l_ns)] - tau / 2 |w_s|^2 + (terms
+    free of w), l_ns = x_n . w_s, with A = softplus (``link`` "logistic") or A = exp ("poisson") -- the model
+    csrc/bsc_glm.hip's pass and finish compute.  X, y, W: the names of the design matrix [N, D], the targets [N]
+    and the latent weights [S, D]."""
+
+    def __init__(self, link, X, y, W, scale, tau):
+        self.link, self.X, self.y, self.W, self.scale, self.tau = link, X, y, W, scale, tau
+
+
+_GLM_LINKS = (("logistic", lambda L: np.logaddexp(0.0, L), lambda rng, n: (rng.uniform(size=n) < 0.5).astype(np.float64)),
+              ("poisson", np.exp, lambda rng, n: rng.randint(5, size=n).astype(np.float64)))
+
+
+def glm_linear(log_joint, latents, data_shapes, n_samples, why=None):
+    """Is ``log_joint`` (ndim 1, one value per draw) the closed form above for SOME scale > 0 and tau > 0, whatever
+    way it was written (softplus as ``log(1 + exp(l))``, constants kept or dropped, the scale inside or outside the
+    sum over the rows)?  Identity testing by evaluation on a seven-row instance in host float64 (``_param_backend``),
+    as ``logistic_hierarchy`` does it: scale and tau are fitted from differences in w on one instance -- terms free of
+    w, such as the Poisson density's -sum_n lnGamma(y_n + 1), cancel -- and the fit is then checked at random other
+    instances and weights.  Returns a ``GLMLinear`` or None; ``why`` (a list, optional) receives the reason.  More
+    latents than the weights, another prior, or another likelihood are declined."""
+    try:
+        return _glm_linear(log_joint, latents, data_shapes, n_samples, why)
+    except NOT_THIS_MODEL as e:
+        return _say(why, "%s while reading the log-joint: %s" % (type(e).__name__, e))
+
+
+def _glm_linear(log_joint, latents, data_shapes, n_samples, why):
+    types = log_joint.input_types
+    if len(latents) != 1:
+        return _say(why, "the fused GLM update has one latent block, the weights under w ~ N(0, I / tau); got %d "
+                         "(a hierarchical or scale latent is outside it)" % len(latents))
+    Wv, D = latents[0]
+    shapes = dict(data_shapes)
+    shapes[Wv.name] = (n_samples, D)
+    log_joint = _without_shapes(log_joint, shapes)      # explicit extents keep the REAL data's value
+    used = sorted(n for n in types if n != Wv.name)
+    two_d = [n for n in used if types[n][1] == 2 and n in data_shapes and data_shapes[n][1] == D]
+    one_d = [n for n in used if types[n][1] == 1 and n in data_shapes]
+    if len(used) != 2 or len(two_d) != 1 or len(one_d) != 1 or data_shapes[two_d[0]][0] != data_shapes[one_d[0]][0]:
+        return _say(why, "the data inputs are not one design matrix [N, %d] and one target vector [N] (got %s)"
+                    % (D, ", ".join(used) or "none"))
+    Xn, yn = two_d[0], one_d[0]
+    rng = np.random.RandomState(53)
+    n, S = 7, 3
+    reasons = []
+    for link, A_fn, draw_y in _GLM_LINKS:
+        def instance():
+            return rng.standard_normal((n, D)) / math.sqrt(D), draw_y(rng, n)
+
+        def F(data, w):
+            return np.asarray(_PROBE.evaluate(log_joint, {Xn: data[0], yn: data[1], Wv.name: w}), np.float64).reshape(-1)
+
+        def ell(data, w):
+            L = data[0] @ w.T
+            return (data[1][:, None] * L - A_fn(L)).sum(axis=0)
+
+        def delta(data, w):
+            """(F, ell, -|w|^2 / 2) at w minus the same at w = 0, per draw."""
+            zero = np.zeros_like(w)
+            return F(data, w) - F(data, zero), ell(data, w) - ell(data, zero), -0.5 * (w * w).sum(axis=1)
+
+        d0 = instance()
+        f, a, b = delta(d0, rng.standard_normal((2, D)) * np.array([[1.0], [2.0]]))
+        det = a[0] * b[1] - a[1] * b[0]
+        if not np.isfinite(det) or abs(det) <= 1e-12 * (abs(a[0] * b[1]) + abs(a[1] * b[0])):
+            reasons.append("%s: the probe points do not separate the data term from the prior" % link)
+            continue
+        scale = float((f[0] * b[1] - f[1] * b[0]) / det)
+        tau = float((a[0] * f[1] - a[1] * f[0]) / det)
+        ok = np.isfinite(scale) and np.isfinite(tau)
+        for _ in range(3):
+            if not ok:
+                break
+            f, a, b = delta(instance(), rng.standard_normal((S, D)) * 1.5)
+            want = scale * a + tau * b
+            ok = bool(np.all(np.abs(f - want) <= 1e-9 * (np.abs(scale * a) + np.abs(tau * b) + 1e-300)))
+        if not ok:
+            reasons.append("%s: log p is not scale * sum_n [y_n l_ns - A(l_ns)] - tau / 2 |w_s|^2 + const with "
+                           "l = dot(W, X.T) (checked at random points)" % link)
+            continue
+        if not scale > 0.0:
+            return _say(why, "the %s data term enters with the scale %g: it must be positive" % (link, scale))
+        if not tau > 0.0:
+            return _say(why, "the prior on the weights is not a proper N(0, I / tau): fitted tau = %g" % tau)
+        return GLMLinear(link, Xn, yn, Wv.name, scale, tau)
+    return _say(why, "; ".join(reasons))

@@ -39,6 +39,11 @@ written with ``Normal`` / ``InverseGamma`` nodes is such a model: 0.17 ms per up
 ``route="auto"`` (default) takes the fused route when the model qualifies, ``"general"`` never does,
 ``"fused"`` insists (ValueError otherwise).
 
+**The fused GLM route.**  A log-joint whose data enter only as ``c * sum_n [y_n l_ns - A(l_ns)]``, ``l = dot(W, X.T)``,
+with A = softplus or A = exp, over ONE latent block under an isotropic Gaussian prior (``recognise.glm_linear``:
+Bernoulli-logit and Poisson-log regression, ``inference/models.py``) is stepped by ``svi/glm.py``: one pass over X
+(csrc/bsc_glm.hip) and its fused finish, mean-field guide only.  The draws are ``bsc_blr_noise``'s stream 0.
+
 **The pass route.**  When the data term is recognised but the parameter-sized remainder is NOT of that family
 (a known noise variance, another prior, more latents), the step still needs the data only through
 Q_s = sum_n (y_n - x_n . w_s)^2 and G_s = sum_n (y_n - x_n . w_s) x_n: ONE ``bsc_blr_data_pass_sweep`` gives
@@ -324,6 +329,9 @@ class ReparamVI(object):
         said = []
         plan = recognise.gaussian_linear(self.log_joint, self.latents, shapes, self.S, why=said)
         if plan is None:
+            glm = recognise.glm_linear(self.log_joint, self.latents, shapes, self.S) if self.guide == "diag" else None
+            if glm is not None:
+                return self._route_glm(glm)
             return ("the data do not enter the log-joint as coefficient_s * sum_n (y_n - x_n . w_s)^2: %s"
                     % (said[-1] if said else "no reason recorded"))
         self.plan = plan
@@ -366,6 +374,29 @@ class ReparamVI(object):
         self.route = "fused: bsc_blr_data_pass + bsc_blr_fused_update_general"
         return None
 
+    def _route_glm(self, plan):
+        """The svi/glm.py driver behind this engine for a recognised Bernoulli-logit / Poisson-log regression with an
+        isotropic Gaussian prior (``recognise.glm_linear``); returns None, or the reason the pass would refuse the data."""
+        import torch
+        from ..svi.glm import GLMReparamSVI
+        X, y = self._data[plan.X], self._data[plan.y]
+        D = int(X.shape[1])
+        if not (isinstance(X, torch.Tensor) and X.dtype == torch.float32 and y.dtype == torch.float32):
+            return "the fused pass streams float32 data"
+        why = _outside_pass_envelope(X, y, D, self.S)
+        if why is not None:
+            return why
+        self.plan = plan
+        self._planned_shape = (int(X.shape[0]), D)
+        # lam = [mu (D) | rho (D)] is the driver's own layout
+        self._fused = GLMReparamSVI(X, y, link=plan.link, n_total=plan.scale * int(X.shape[0]), n_samples=self.S,
+                                    seed=self.seed, lr=self.lr, prior_precision=plan.tau, ctx=self.backend.ctx,
+                                    lam0=self._lam)
+        self._fused_D = D
+        self._fused_glm = True
+        self.route = "fused: bsc_glm_data_pass + bsc_glm_update (%s link)" % plan.link
+        return None
+
     def _to_blr_layout(self, lam):
         """[mu (P) | rho (P)] in the order of ``latents`` -> svi/blr.py's [m (D) | rho (D) | a | b]."""
         P, D = self.P, self.P - 1
@@ -384,7 +415,7 @@ class ReparamVI(object):
 
     def _from_fused(self, v):
         v = v.cpu().numpy()
-        return v if self.guide == "full" else self._from_blr_layout(v)
+        return v if self.guide == "full" or getattr(self, "_fused_glm", False) else self._from_blr_layout(v)
 
     @property
     def lam(self):

@@ -356,6 +356,50 @@ int bsc_blr_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam
                             double* eps_next, int32_t eps_next_ready, float* W_next, double* xi_next, double* elbo,
                             double* grad);
 
+/* ---- reparameterised SVI for canonical-link GLMs (csrc/bsc_glm.hip; ABSENT in the reference: README.md:51,
+ *      69-79 on the likelihood split of bayesic/distribution/base.py:47-69) ----------------------------------
+ *
+ * One streaming pass over X[B,D] (row-major, leading dimension ldx floats) and y[B], for S draws W[S,D]:
+ *      l[n,s]  = sum_d X[n,d] W[s,d]
+ *      ell[s]  = sum_n ( y[n] l[n,s] - A(l[n,s]) )          (float64 out)
+ *      G[s,d]  = sum_n ( y[n] - A'(l[n,s]) ) X[n,d]         (float64 out, [S,D])
+ * link = BSC_GLM_LOGISTIC: A = softplus, max(l, 0) + log1p(exp(-|l|)), A' = sigmoid from the same exponential
+ * (finite for every finite l); y in {0, 1}.  link = BSC_GLM_POISSON: A = A' = exp(l), NOT clamped -- a clamp
+ * would change the gradient silently -- so the results are finite for l <= 88 only; ell leaves the constant
+ * -sum_n lnGamma(y[n] + 1) of the Poisson log-density out.
+ * The envelope is bsc_blr_data_pass's: D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 (eight draws per launch), X and W
+ * 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26, contiguous y; B = 0 gives zeros.  Deterministic: fixed
+ * partition, float32 block partials, fixed-order float64 finish, no float atomics. */
+#define BSC_GLM_LOGISTIC 0
+#define BSC_GLM_POISSON 1
+int bsc_glm_data_pass(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
+                      const float* W, int32_t S, double* ell, double* G);
+
+/* Finish of one update for q(w) = N(m, diag e^{2 rho}), lam = [m (D) | rho (D)], under the prior
+ * w ~ N(0, I / prior_precision), in one launch: (float64 reduction of the pending pass partials when
+ * stats == NULL -- S <= 8 --, else stats = [ell (S) | G (S*D)] as the pass and the all-reduce leave them) ->
+ *     elbo   = mean_s [scale ell_s - tau/2 |w_s|^2] + D/2 log(tau / 2 pi) + sum rho + D/2 (1 + log 2 pi)
+ *     g_s    = scale G_s - tau w_s          (w_s: the float32 draw the pass read),   scale = n_total / batch_rows
+ *     d/d m  = mean_s g_s,     d/d rho_d = mean_s g_sd eps_sd e^{rho_d} + 1
+ * -> Adam ascent step t (bsc_blr_fused_update's form and bias correction; lam_in is not modified, m1 and m2 are
+ * updated in place) -> when the *_next buffers are set, W_next = m' + e^{rho'} eps_next rounded to float32.
+ * eps and eps_next are in bsc_blr_noise's [S, D+1] layout (Philox stream 0 in columns 0 .. D-1; column D is not
+ * read); eps_next_ready = 0: the noise of next_step is drawn into eps_next first (one bsc_blr_noise launch).
+ * For the Poisson link elbo leaves -scale sum_n lnGamma(y_n + 1) out (it does not depend on lam).
+ * The caller double-buffers lam and the draws: *_next must not alias eps / W. */
+int bsc_glm_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1, double* m2,
+                   const double* eps, const float* W, int32_t D, int32_t S, double scale, double prior_precision,
+                   int64_t t, double lr, double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
+                   double* eps_next, int32_t eps_next_ready, float* W_next, double* elbo, double* grad);
+
+/* One call per update: the pass (S <= 8, its partials left in the workspace) followed by the finish with
+ * stats = NULL -- two launches. */
+int bsc_glm_pass_update(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
+                        const double* lam_in, double* lam_out, double* m1, double* m2, const double* eps, const float* W,
+                        int32_t S, double scale, double prior_precision, int64_t t, double lr, double beta1, double beta2,
+                        double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
+                        float* W_next, double* elbo, double* grad);
+
 /* ---- parameter updates --------------------------------------------------- */
 
 /* Adam ascent on a flat float64 vector; t is the 1-based step count. */
