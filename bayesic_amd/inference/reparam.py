@@ -625,6 +625,14 @@ class ReparamVI(object):
         grad = np.concatenate([g.mean(axis=0), (g * eps).mean(axis=0) * sigma + 1.0])
         return elbo, grad
 
+    def predict(self, X, y=None, n_samples=64, seed=None, draws=None):
+        """Posterior predictive for new rows (svi/predict.py): on a fused regression route the driver's own
+        ``predict``; every other route has no likelihood the engine could name, and refuses."""
+        if self._fused is None or not self.route.startswith(("fused: bsc_blr", "fused: bsc_glm")):
+            raise NotImplementedError("predict needs a fused regression route (fused: bsc_blr... / bsc_glm...); this "
+                                      "engine runs on route %r" % (self.route,))
+        return self._fused.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
+
     def step(self):
         if self._fused is not None:
             self._fused.step()          # asynchronous: pass + fused finish on the context's stream

@@ -190,6 +190,16 @@ class GLMReparamSVI:
             self.all_reduce()
             self._finish(self.stats)
 
+    # -- posterior predictive (svi/predict.py: one bsc_predict_pass over X for all draws) --------
+    def predict(self, X, y=None, n_samples=64, seed=None, draws=None):
+        from .predict import predict
+        return predict(self, X, y, n_samples=n_samples, seed=seed, draws=draws)
+
+    def heldout_lpd(self, X, y, n_samples=64, seed=None, draws=None):
+        """Mean log predictive density per held-out row (a host float)."""
+        from .predict import heldout_lpd
+        return heldout_lpd(self, X, y, n_samples=n_samples, seed=seed, draws=draws)
+
     # -- host views -----------------------------------------------------------
     def params(self):
         lam = self.lam.cpu().numpy()

@@ -1,0 +1,123 @@
+"""Posterior predictive and held-out log density of the fitted regression models, on one fused pass.
+
+Host-side driver of csrc/bsc_predict.hip (include/bayesic_hip.h: bsc_predict_pass).  For S draws of the model's
+CURRENT q the pass reads X once and returns, per row, the predictive mean, the predictive variance (law of total
+variance over the draws) and, given y, the log predictive density lpd_n = log 1/S sum_s p(y_n | w_s), whose
+float64 sum is the held-out score.
+
+Draws (``posterior_draws``): standard normals from bsc_philox_normal on Philox stream 2, step 0, counter and key
+as oracle/philox.py lays them out (its streams 0 and 1 belong to the training entry points: 0 = the weights and
+every draw of bsc_blr_noise, 1 = the scale latent of bsc_blr_sample), so predicting never repeats training noise.
+The transform is parameter-sized and runs once per call: float64 on the host, rounded to float32, as
+GLMReparamSVI.sample() does.
+    GLMReparamSVI                     eps [S, D]:      w = m + e^rho eps
+    BLRReparamSVI(covariance="diag")  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  xi = a + e^b eps[:, D]
+    BLRReparamSVI(covariance="full")  eps [S, D + 1]:  z = mu + L eps over z = [w | xi]
+xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass).
+"""
+import numpy as np
+import torch
+
+# include/bayesic_hip.h: BSC_PREDICT_*
+FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
+PREDICT_STREAM = 2     # Philox stream of the predictive draws
+MAX_SAMPLES = 64       # draws per bsc_predict_pass call
+
+__all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_STREAM", "MAX_SAMPLES"]
+
+
+def family_of(model):
+    """The likelihood family of a driver: its GLM link, or "gaussian" for BLRReparamSVI."""
+    link = getattr(model, "link", None)
+    if link is not None:
+        return link
+    if getattr(model, "family", None) is not None:
+        raise NotImplementedError(
+            "predict: this BLRReparamSVI was built with family=(c0, c_xi, s_q, k_w, beta); the five coefficients of "
+            "the log-joint do not identify the likelihood precision (s_q and k_w mix it with the prior's), so the "
+            "predictive distribution is not defined by them")
+    return "gaussian"
+
+
+def _check_samples(n_samples):
+    S = int(n_samples)
+    if S > MAX_SAMPLES:
+        raise ValueError("n_samples=%d: one predictive pass takes at most %d draws" % (S, MAX_SAMPLES))
+    if S < 1:
+        raise ValueError("n_samples must be at least 1")
+    return S
+
+
+def posterior_draws(model, n_samples=64, seed=None):
+    """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q."""
+    S = _check_samples(n_samples)
+    family = family_of(model)
+    ctx, D = model.ctx, model.D
+    seed = model.seed if seed is None else int(seed)
+    P = D + 1 if family == "gaussian" else D
+    eps_d = torch.zeros((S, P), dtype=torch.float64, device=ctx.device)
+    ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P, eps_d)
+    eps = eps_d.cpu().numpy()
+    lam = model.lam.cpu().numpy()
+    logvar = None
+    if family != "gaussian":
+        W = lam[None, :D] + np.exp(lam[D:2 * D])[None, :] * eps
+    elif model.covariance_kind == "full":
+        mu, L = model._unpack_full(lam)
+        z = mu[None, :] + eps @ L.T
+        W, logvar = z[:, :D], z[:, D]
+    else:
+        W = lam[None, :D] + np.exp(lam[D:2 * D])[None, :] * eps[:, :D]
+        logvar = lam[2 * D] + np.exp(lam[2 * D + 1]) * eps[:, D]
+    Wd = ctx.to_device(np.ascontiguousarray(W, np.float32))
+    lvd = None if logvar is None else ctx.to_device(np.ascontiguousarray(logvar, np.float32))
+    return Wd, lvd
+
+
+def _data(model, X, y):
+    """The drivers' own checks and messages for a batch (GLMReparamSVI.__init__)."""
+    ctx = model.ctx
+    X = X if isinstance(X, torch.Tensor) else ctx.to_device(X, torch.float32)
+    if y is not None:
+        y = y if isinstance(y, torch.Tensor) else ctx.to_device(y, torch.float32)
+    if X.dtype != torch.float32 or (y is not None and y.dtype != torch.float32):
+        raise TypeError("X and y must be float32")
+    if X.dim() != 2 or (y is not None and (y.dim() != 1 or X.shape[0] != y.shape[0])):
+        raise ValueError("X must be [B, D] and y [B]")
+    if X.stride(1) != 1:
+        raise ValueError("X must be row-major (unit stride along columns)")
+    if X.shape[1] != model.D:
+        raise ValueError("X has %d columns; the model was fitted at D = %d" % (X.shape[1], model.D))
+    if y is not None and y.numel() > 1 and y.stride(0) != 1:
+        raise ValueError("y must be contiguous")
+    return X, y
+
+
+def predict(model, X, y=None, n_samples=64, seed=None, draws=None):
+    """Posterior predictive of ``model`` for the rows of X: a dict of device tensors ``mean`` and ``var`` (float32
+    [B]) and, with y, ``lpd`` (float32 [B]) and ``lpd_sum`` (float64 [1]).  ``draws`` = (W, logvar) reuses draws of
+    ``posterior_draws``; otherwise n_samples (at most 64) are drawn with ``seed`` (default: the model's)."""
+    family = family_of(model)
+    if draws is None:
+        draws = posterior_draws(model, n_samples, seed)
+    W, logvar = draws
+    S = _check_samples(W.shape[0])
+    X, y = _data(model, X, y)
+    ctx = model.ctx
+    B = int(X.shape[0])
+    ldx = int(X.stride(0)) if B > 1 else max(int(X.stride(0)), model.D)
+    dev = ctx.device
+    out = {"mean": torch.empty(B, dtype=torch.float32, device=dev),
+           "var": torch.empty(B, dtype=torch.float32, device=dev)}
+    if y is not None:
+        out["lpd"] = torch.empty(B, dtype=torch.float32, device=dev)
+        out["lpd_sum"] = torch.zeros(1, dtype=torch.float64, device=dev)
+    ctx.call("bsc_predict_pass", FAMILIES[family], X, ldx, y, B, model.D, W, logvar, S, out["mean"], out["var"],
+             out.get("lpd"), out.get("lpd_sum"))
+    return out
+
+
+def heldout_lpd(model, X, y, n_samples=64, seed=None, draws=None):
+    """Mean log predictive density per row of the held-out (X, y): lpd_sum / B, a host float (synchronises)."""
+    out = predict(model, X, y, n_samples=n_samples, seed=seed, draws=draws)
+    return float(out["lpd_sum"].item()) / max(int(out["lpd"].shape[0]), 1)
