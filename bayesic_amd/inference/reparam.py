@@ -21,7 +21,8 @@ lam = [mu (P) | L packed row-major, lower triangle incl. the diagonal (P(P+1)/2)
 
 On the general route the draws and the gradient are host float64 numpy; on the fused route the finish is
 ``bsc_blr_fullrank_update`` (svi/blr.py, ``covariance="full"``; it orders z as [w | xi], so the latents must list the
-weights first).  The state kept on the device (``resident``) is mean-field only: a full guide steps on the host.
+weights first) or, for a recognised GLM, ``bsc_glm_fullrank_update``.  The state kept on the device (``resident``) is
+mean-field only: a full guide steps on the host.
 
 Noise is Philox4x32-10 keyed as in ``ScoreFunctionVI`` (and bsc_blr_noise's stream layout is
 NOT assumed: this engine shares draws with ScoreFunctionVI, so the two estimators can be compared
@@ -42,7 +43,9 @@ written with ``Normal`` / ``InverseGamma`` nodes is such a model: 0.17 ms per up
 **The fused GLM route.**  A log-joint whose data enter only as ``c * sum_n [y_n l_ns - A(l_ns)]``, ``l = dot(W, X.T)``,
 with A = softplus or A = exp, over ONE latent block under an isotropic Gaussian prior (``recognise.glm_linear``:
 Bernoulli-logit and Poisson-log regression, ``inference/models.py``) is stepped by ``svi/glm.py``: one pass over X
-(csrc/bsc_glm.hip) and its fused finish, mean-field guide only.  The draws are ``bsc_blr_noise``'s stream 0.
+(csrc/bsc_glm.hip) and its fused finish: ``bsc_glm_update`` for the mean-field guide, ``bsc_glm_fullrank_update``
+(csrc/bsc_glm_full.hip; ``svi/glm.py``, ``covariance="full"``) for ``guide="full"`` -- over one latent block the engine's
+full layout is the driver's.  The draws are ``bsc_blr_noise``'s stream 0.
 
 **The pass route.**  When the data term is recognised but the parameter-sized remainder is NOT of that family
 (a known noise variance, another prior, more latents), the step still needs the data only through
@@ -329,7 +332,7 @@ class ReparamVI(object):
         said = []
         plan = recognise.gaussian_linear(self.log_joint, self.latents, shapes, self.S, why=said)
         if plan is None:
-            glm = recognise.glm_linear(self.log_joint, self.latents, shapes, self.S) if self.guide == "diag" else None
+            glm = recognise.glm_linear(self.log_joint, self.latents, shapes, self.S)
             if glm is not None:
                 return self._route_glm(glm)
             return ("the data do not enter the log-joint as coefficient_s * sum_n (y_n - x_n . w_s)^2: %s"
@@ -388,13 +391,14 @@ class ReparamVI(object):
             return why
         self.plan = plan
         self._planned_shape = (int(X.shape[0]), D)
-        # lam = [mu (D) | rho (D)] is the driver's own layout
+        # lam = [mu (D) | rho (D)], or [mu (D) | packed L] over the one latent block, is the driver's own layout
         self._fused = GLMReparamSVI(X, y, link=plan.link, n_total=plan.scale * int(X.shape[0]), n_samples=self.S,
                                     seed=self.seed, lr=self.lr, prior_precision=plan.tau, ctx=self.backend.ctx,
-                                    lam0=self._lam)
+                                    lam0=self._lam, covariance=self.guide)
         self._fused_D = D
         self._fused_glm = True
-        self.route = "fused: bsc_glm_data_pass + bsc_glm_update (%s link)" % plan.link
+        finish = "bsc_glm_fullrank_update" if self.guide == "full" else "bsc_glm_update"
+        self.route = "fused: bsc_glm_data_pass + %s (%s link)" % (finish, plan.link)
         return None
 
     def _to_blr_layout(self, lam):

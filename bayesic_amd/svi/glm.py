@@ -15,9 +15,16 @@ noise drawn a block ahead by bsc_blr_noise (Philox stream 0, as oracle.svi.blr_s
 belongs to BLR's scalar latent and is not read).  An intercept is a column of ones in X.  The ELBO of the Poisson
 model leaves the constant -scale sum_n lnGamma(y_n + 1) out.
 
+``covariance="full"``: q(w) = N(mu, L L^T), L lower-triangular with L_ii = e^{rho_i}; lam = [mu (D) | L packed
+row-major, lower triangle incl. the diagonal (D(D+1)/2), rho_i in the diagonal slots] (include/bayesic_hip.h,
+bsc_glm_fullrank_update: svi/blr.py's full layout with P = D).  The data pass is the same; the finish is
+bsc_glm_fullrank_update, always behind data_pass() -> all_reduce(), so S up to 64 works and the exchange is the
+mean-field driver's.  A mean-field guide cannot represent the posterior correlation of w that correlated features
+induce and shrinks its marginal variances; the full guide can.
+
 Data parallelism is wired as in svi/blr.py: each rank holds a block of mini-batch rows, and the one exchange per
 update is an all-reduce(sum) of the float64 vector [ell (S) | G (S*D)] between the pass and the finish.  That branch
-has been exercised at world size 1 only.
+(the one every update of the full guide takes) has been exercised at world size 1 only.
 """
 import math
 
@@ -34,7 +41,12 @@ class GLMReparamSVI:
     NOISE_BLOCK = 32
 
     def __init__(self, X, y, link="logistic", n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0,
-                 ctx=None, group=None, lam0=None):
+                 ctx=None, group=None, lam0=None, covariance="diag"):
+        """``covariance``: "diag" (the mean-field guide, default) or "full" (module docstring; ``lam0`` then in the
+        full layout, default: the mean-field default's mu and rho with zero off-diagonal entries)."""
+        if covariance not in ("diag", "full"):
+            raise ValueError("covariance must be 'diag' or 'full', got %r" % (covariance,))
+        self.covariance_kind = covariance
         if link not in LINKS:
             raise ValueError("link must be 'logistic' or 'poisson', got %r" % (link,))
         self.link, self._link = link, LINKS[link]
@@ -65,19 +77,27 @@ class GLMReparamSVI:
         D, S = self.D, self.S
         f64 = torch.float64
         # double-buffered state: index t & 1 is current at the start of step t + 1
-        self._lam = torch.zeros((2, 2 * D), dtype=f64, device=dev)
+        n_lam = D + D * (D + 1) // 2 if covariance == "full" else 2 * D
+        self._lam = torch.zeros((2, n_lam), dtype=f64, device=dev)
         if lam0 is None:
-            self._lam[0, D:] = math.log(0.1)
+            if covariance == "full":
+                diag = torch.arange(D, device=dev)
+                self._lam[0, D + diag * (diag + 1) // 2 + diag] = math.log(0.1)
+            else:
+                self._lam[0, D:] = math.log(0.1)
         else:
-            self._lam[0].copy_(torch.as_tensor(lam0, dtype=f64))
+            lam0 = torch.as_tensor(lam0, dtype=f64)
+            if covariance == "full" and lam0.numel() != n_lam:
+                raise ValueError("lam0 has %d entries; covariance='full' at D = %d needs %d" % (lam0.numel(), D, n_lam))
+            self._lam[0].copy_(lam0)
         # noise ring: NOISE_BLOCK steps are drawn per launch, two blocks resident
         self._ring = 2 * self.NOISE_BLOCK
         self._eps = torch.zeros((self._ring, S * (D + 1)), dtype=f64, device=dev)
         self._noise_upto = 0   # noise of Philox steps [0, _noise_upto) has been requested
         self._W = torch.zeros((2, S * D), dtype=torch.float32, device=dev)
-        self.m1 = torch.zeros(2 * D, dtype=f64, device=dev)
-        self.m2 = torch.zeros(2 * D, dtype=f64, device=dev)
-        self.grad = torch.zeros(2 * D, dtype=f64, device=dev)
+        self.m1 = torch.zeros(n_lam, dtype=f64, device=dev)
+        self.m2 = torch.zeros(n_lam, dtype=f64, device=dev)
+        self.grad = torch.zeros(n_lam, dtype=f64, device=dev)
         self.elbo = torch.zeros(1, dtype=f64, device=dev)
         self.stats = torch.zeros(S * (D + 1), dtype=f64, device=dev)  # [ell | G]
         self.ell = self.stats[:S]
@@ -143,9 +163,24 @@ class GLMReparamSVI:
         self._ensure_noise(step)
         eps = self._eps[step % self._ring].cpu().numpy().reshape(S, D + 1)[:, :D]
         lam = self._lam[c].cpu().numpy()
-        W = (lam[None, :D] + np.exp(lam[None, D:]) * eps).astype(np.float32)
+        if self.covariance_kind == "full":      # w_s = mu + L eps_s
+            mu, L = self._unpack_full(lam)
+            W = (mu[None, :] + eps @ L.T).astype(np.float32)
+        else:
+            W = (lam[None, :D] + np.exp(lam[None, D:]) * eps).astype(np.float32)
         self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(W).reshape(-1)))
         self._drawn = True
+
+    def _unpack_full(self, lam):
+        """[mu | packed L] -> (mu [D], dense L [D, D]) with L_ii = e^{rho_i}."""
+        import numpy as np
+        D = self.D
+        rows, cols = np.tril_indices(D)            # row-major lower triangle: the packed order
+        L = np.zeros((D, D))
+        L[rows, cols] = lam[D:]
+        d = np.arange(D)
+        L[d, d] = np.exp(L[d, d])
+        return np.array(lam[:D], np.float64), L
 
     def data_pass(self):
         self.ctx.call("bsc_glm_data_pass", self._link, self._Xarg, self._ldx, self._yarg, self.B, self.D, self.W,
@@ -165,7 +200,8 @@ class GLMReparamSVI:
         c, n = self.cur, 1 - self.cur
         t = self.t + 1
         self._ensure_noise(t)
-        self.ctx.call("bsc_glm_update", stats, self._lam[c], self._lam[n], self.m1, self.m2,
+        name = "bsc_glm_fullrank_update" if self.covariance_kind == "full" else "bsc_glm_update"
+        self.ctx.call(name, stats, self._lam[c], self._lam[n], self.m1, self.m2,
                       self._eps[self.t % self._ring], self._W[c], self.D, self.S, *self._tail(t))
         self.t = t
 
@@ -183,7 +219,7 @@ class GLMReparamSVI:
         """One ELBO-gradient update; asynchronous on the context stream."""
         if not self._drawn:
             self.sample(self.t)  # Philox step index == number of completed updates
-        if self.world == 1 and not self.exchange.rccl and self.S <= 8:
+        if self.world == 1 and not self.exchange.rccl and self.S <= 8 and self.covariance_kind == "diag":
             self._pass_update()
         else:
             self.data_pass()
@@ -202,5 +238,19 @@ class GLMReparamSVI:
 
     # -- host views -----------------------------------------------------------
     def params(self):
+        """diag: m, rho.  full: m = mu [D], the dense lower-triangular L [D, D] and rho = log diag L."""
+        import numpy as np
         lam = self.lam.cpu().numpy()
+        if self.covariance_kind == "full":
+            m, L = self._unpack_full(lam)
+            d = np.arange(self.D)
+            return dict(m=m, L=L, rho=np.array(lam[self.D + d * (d + 1) // 2 + d]))
         return dict(m=lam[:self.D], rho=lam[self.D:])
+
+    def covariance(self):
+        """Cov_q(w) (D x D, host float64): L L^T of the full guide, diag(e^{2 rho}) of the mean-field one."""
+        import numpy as np
+        if self.covariance_kind == "full":
+            _, L = self._unpack_full(self.lam.cpu().numpy())
+            return L @ L.T
+        return np.diag(np.exp(2.0 * self.params()["rho"]))

@@ -10,7 +10,8 @@ as oracle/philox.py lays them out (its streams 0 and 1 belong to the training en
 every draw of bsc_blr_noise, 1 = the scale latent of bsc_blr_sample), so predicting never repeats training noise.
 The transform is parameter-sized and runs once per call: float64 on the host, rounded to float32, as
 GLMReparamSVI.sample() does.
-    GLMReparamSVI                     eps [S, D]:      w = m + e^rho eps
+    GLMReparamSVI(covariance="diag")  eps [S, D]:      w = m + e^rho eps
+    GLMReparamSVI(covariance="full")  eps [S, D]:      w = mu + L eps
     BLRReparamSVI(covariance="diag")  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  xi = a + e^b eps[:, D]
     BLRReparamSVI(covariance="full")  eps [S, D + 1]:  z = mu + L eps over z = [w | xi]
 xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass).
@@ -60,7 +61,10 @@ def posterior_draws(model, n_samples=64, seed=None):
     eps = eps_d.cpu().numpy()
     lam = model.lam.cpu().numpy()
     logvar = None
-    if family != "gaussian":
+    if family != "gaussian" and getattr(model, "covariance_kind", "diag") == "full":
+        mu, L = model._unpack_full(lam)
+        W = mu[None, :] + eps @ L.T
+    elif family != "gaussian":
         W = lam[None, :D] + np.exp(lam[D:2 * D])[None, :] * eps
     elif model.covariance_kind == "full":
         mu, L = model._unpack_full(lam)

@@ -400,6 +400,32 @@ int bsc_glm_pass_update(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx,
                         double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
                         float* W_next, double* elbo, double* grad);
 
+/* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
+ * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
+ *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
+ * row i of L starts at lam[D + i(i+1)/2] and its diagonal slot holds rho_i (33 152 doubles at D = 256): the layout of
+ * bsc_blr_fullrank_update with P = D; m1, m2 and grad have lam's layout.  Same model, scale and prior_precision (tau)
+ * as bsc_glm_update; per update, with eps_s in bsc_blr_noise's [S, D+1] layout (column D is not read) and W_s the
+ * float32-rounded draws the pass read:
+ *     g_s  = scale G_s - tau W_s
+ *     ELBO = mean_s [scale ell_s - tau/2 |w_s|^2] + D/2 log(tau / 2 pi) + sum_i rho_i + D/2 (1 + log 2 pi)
+ *     d / d mu = mean_s g_s,   d / d L_ij = mean_s g_si eps_sj (j < i),   d / d rho_i = mean_s g_si eps_si e^{rho_i} + 1
+ * then Adam ascent on every entry (bsc_glm_update's hyper-parameters and bias correction; lam_in is not modified) and,
+ * when the *_next buffers are set, the next draw w'_s = mu' + L' eps'_s rounded to float32 into W_next [S, D].
+ * eps_next_ready = 0: the noise of next_step is drawn into eps_next first (one bsc_blr_noise launch).  With every
+ * off-diagonal entry zero the ELBO, the mu / rho gradients and their Adam step equal bsc_glm_update's on the same
+ * stats and noise.
+ * stats = [ell (S) | G (S*D)] as bsc_glm_data_pass and the all-reduce leave them (NULL is refused: pending pass
+ * partials are not read).  One launch of D / 2 workgroups, workgroup k owning rows k and D - 1 - k of L; fixed-order
+ * sums, no atomics: reproducible bit for bit.  The caller double-buffers lam and the draws: lam_in != lam_out, and
+ * *_next (both set or both NULL) must not alias eps / W.
+ * Requires D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64, t >= 1, prior_precision > 0, scale > 0. */
+int bsc_glm_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                            double* m2, const double* eps, const float* W, int32_t D, int32_t S, double scale,
+                            double prior_precision, int64_t t, double lr, double beta1, double beta2, double adam_eps,
+                            uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready, float* W_next,
+                            double* elbo, double* grad);
+
 /* ---- posterior predictive and held-out log density (csrc/bsc_predict.hip; ABSENT in the reference) ---------
  *
  * One streaming pass over X[B,D] (row-major, leading dimension ldx floats) for S draws W[S,D] of a fitted q.  With

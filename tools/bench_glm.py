@@ -6,6 +6,9 @@ events; a line reports the median block and the min-max spread:
   (a) bsc_blr_data_pass on the default route        (the HBM-bound yardstick: the same bytes per row)
   (b) bsc_glm_data_pass, logistic and Poisson        ((b) / (a) is the figure of merit)
   (c) a GLMReparamSVI update, both links             (pass + fused finish)
+  (e) a GLMReparamSVI(covariance="full") update, both links (pass + slab reduce + bsc_glm_fullrank_update), with
+      the finish kernel's own time (bsc_ctx_profile slot 2) -- next to (c), and next to
+  (f) ReparamVI(guide="full", route="general") on the logistic log-joint: the same guide stepped on the host
   (d) ReparamVI(route="general") on the logistic log-joint: what the same model cost before the fused route
 
     python tools/bench_glm.py [--rows N] [--json]
@@ -94,6 +97,31 @@ def main():
     from bayesic_amd.inference import ReparamVI
     from bayesic_amd.inference.models import logistic_regression_log_joint
     lj, v = logistic_regression_log_joint(10.0, 1.0)
+
+    t_e = {}
+    for link, y in (("logistic", y_bern), ("poisson", y_pois)):
+        model = GLMReparamSVI(X, y, link=link, n_total=10.0 * N, n_samples=S, seed=1, lr=1e-3, ctx=ctx,
+                              covariance="full")
+        t_e[link] = timed(ctx, model.step)
+        report("(e) GLMReparamSVI(covariance='full').step %s" % link, t_e[link])
+        ctx.profile(1)                      # the finish kernel alone: event pairs around its launch (slot 2)
+        ctx.profile_read(2)
+        for _ in range(50):
+            model.step()
+        ms, cnt = ctx.profile_read(2)
+        ctx.profile(0)
+        line = {"case": "(e) glm_fullrank_update_kernel %s D=%d S=%d" % (link, D, S),
+                "us_mean": round(ms / max(cnt, 1) * 1e3, 2), "launches": cnt,
+                "beside": "blr_fullrank_update_kernel: 8.4 us mean (profiles/fullrank_kernel_stats.csv)"}
+        results.append(line)
+        print(json.dumps(line), flush=True)
+        del model
+    full_general = ReparamVI(lj, [(v["W"], D)], dict(X=X, y=y_bern), n_samples=S, seed=1, lr=1e-3,
+                             backend=DeviceBackend(ctx), route="general", guide="full")
+    assert full_general.route.startswith("general"), full_general.route
+    t_f = timed(ctx, full_general.step, reps=3, warm_ms=10.0)
+    report("(f) ReparamVI(guide='full', route='general').step logistic", t_f, passes=0)
+    del full_general
     eng = ReparamVI(lj, [(v["W"], D)], dict(X=X, y=y_bern), n_samples=S, seed=1, lr=1e-3, backend=DeviceBackend(ctx),
                     route="general", resident=True)
     assert eng.route.startswith("general"), eng.route
@@ -109,6 +137,8 @@ def main():
                "b_over_a": {k: round(t_b[k][0] / t_a[0], 3) for k in t_b},
                "spread_of_a": round(spread_a, 3),
                "c_over_d": {k: round(t_c[k][0] / t_d[0], 3) for k in t_c},
+               "e_over_c": {k: round(t_e[k][0] / t_c[k][0], 3) for k in t_e},
+               "e_over_f": {k: round(t_e[k][0] / t_f[0], 3) for k in t_e},
                "c_faster_than_d": all(t_c[k][0] < t_d[0] for k in t_c)}
     print(json.dumps(summary), flush=True)
     if not summary["c_faster_than_d"]:
