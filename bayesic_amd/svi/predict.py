@@ -14,6 +14,8 @@ GLMReparamSVI.sample() does.
     GLMReparamSVI(covariance="full")  eps [S, D]:      w = mu + L eps
     BLRReparamSVI(covariance="diag")  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  xi = a + e^b eps[:, D]
     BLRReparamSVI(covariance="full")  eps [S, D + 1]:  z = mu + L eps over z = [w | xi]
+    SoftmaxReparamSVI                 eps [S, K D]:    the two GLM transforms at width K D, W returned [S, K, D]
+                                      (predict() below hands over to its predict(): bsc_softmax_predict_pass)
 xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass).
 """
 import numpy as np
@@ -28,7 +30,10 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 
 
 def family_of(model):
-    """The likelihood family of a driver: its GLM link, or "gaussian" for BLRReparamSVI."""
+    """The likelihood family of a driver: its GLM link, "softmax" for SoftmaxReparamSVI, or "gaussian" for
+    BLRReparamSVI."""
+    if getattr(model, "n_classes", None) is not None:
+        return "softmax"
     link = getattr(model, "link", None)
     if link is not None:
         return link
@@ -50,10 +55,13 @@ def _check_samples(n_samples):
 
 
 def posterior_draws(model, n_samples=64, seed=None):
-    """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q."""
+    """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q; W is [S, K, D] for
+    SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d)."""
     S = _check_samples(n_samples)
     family = family_of(model)
     ctx, D = model.ctx, model.D
+    if family == "softmax":
+        D = model.n_classes * model.D          # the guide's width; the transforms below are the GLM ones
     seed = model.seed if seed is None else int(seed)
     P = D + 1 if family == "gaussian" else D
     eps_d = torch.zeros((S, P), dtype=torch.float64, device=ctx.device)
@@ -73,6 +81,8 @@ def posterior_draws(model, n_samples=64, seed=None):
     else:
         W = lam[None, :D] + np.exp(lam[D:2 * D])[None, :] * eps[:, :D]
         logvar = lam[2 * D] + np.exp(lam[2 * D + 1]) * eps[:, D]
+    if family == "softmax":
+        W = W.reshape(S, model.n_classes, model.D)
     Wd = ctx.to_device(np.ascontiguousarray(W, np.float32))
     lvd = None if logvar is None else ctx.to_device(np.ascontiguousarray(logvar, np.float32))
     return Wd, lvd
@@ -102,6 +112,8 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None):
     [B]) and, with y, ``lpd`` (float32 [B]) and ``lpd_sum`` (float64 [1]).  ``draws`` = (W, logvar) reuses draws of
     ``posterior_draws``; otherwise n_samples (at most 64) are drawn with ``seed`` (default: the model's)."""
     family = family_of(model)
+    if family == "softmax":      # its own pass and outputs (prob [B, K] instead of mean and var)
+        return model.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
     if draws is None:
         draws = posterior_draws(model, n_samples, seed)
     W, logvar = draws

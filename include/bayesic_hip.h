@@ -455,6 +455,37 @@ int bsc_predict_pass(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, 
                      const float* W, const float* logvar, int32_t S, float* mean, float* var, float* lpd,
                      double* lpd_sum);
 
+/* ---- multi-class softmax regression (csrc/bsc_softmax.hip; ABSENT in the reference) ------------------------
+ *
+ * Labels y[n] in {0 .. K-1} (int32), weights W[S,K,D] (S draws of a K x D matrix, flattened parameter p = k D + d)
+ * under w ~ N(0, I / prior_precision) on all K D entries.  One streaming pass over X[B,D] (row-major, leading
+ * dimension ldx floats) and y[B] per group of floor(16 / K) draws:
+ *      l[n,s,k]  = sum_d X[n,d] W[s,k,d],      lse[n,s] = logsumexp_k l[n,s,k]      (maximum subtracted)
+ *      ell[s]    = sum_n ( l[n,s,y[n]] - lse[n,s] )                           (float64 out, [S])
+ *      G[s,k,d]  = sum_n ( 1[y[n] = k] - softmax_k(l[n,s,:]) ) X[n,d]          (float64 out, [S,K,D])
+ * A row whose label is outside [0, K) is skipped entirely (nothing in ell, nothing in G); the label is only compared
+ * with class indices, never used as an address, so any int32 value is memory-safe.  [ell | G] is the stats vector of
+ * bsc_glm_update / bsc_glm_fullrank_update called with D := K D.
+ * Envelope (BSC_ERR_INVALID with a message naming the quantity, outputs untouched): 2 <= K <= 16, D % 4 == 0,
+ * 4 <= D <= 256, 1 <= S <= 64, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26, non-NULL ell and G.
+ * y is contiguous with any 4-byte alignment.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block
+ * partials in the workspace (pending pass partials of bsc_blr_data_pass_partial are dropped), fixed-order float64
+ * reduction, no float atomics. */
+int bsc_softmax_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const int32_t* y, int64_t B, int32_t D, int32_t K,
+                          const float* W, int32_t S, double* ell, double* G);
+
+/* Posterior predictive of the softmax model for S draws W[S,K,D] of a fitted q; X is read once for every S.  Per row
+ * (each output may be NULL)
+ *      prob[n,k] = 1/S sum_s softmax_k(l[n,s,:])                                          (float32 [B,K])
+ *      lpd[n]    = logsumexp_s ( l[n,s,y[n]] - lse[n,s] ) - log S                         (float32 [B]; needs y)
+ *      lpd_sum   = sum_n lpd[n]                                                           (float64 [1]; needs y)
+ * A row whose label is outside [0, K) gets lpd[n] = 0 and adds nothing to lpd_sum; prob is written for every row.
+ * Argument errors (BSC_ERR_INVALID, outputs untouched): the envelope of bsc_softmax_data_pass, no output requested,
+ * lpd or lpd_sum without y.  B = 0 writes lpd_sum = 0 and nothing else.  Deterministic: float64 block partials of
+ * lpd in the workspace (pending pass partials are dropped), fixed-order finish, no float atomics. */
+int bsc_softmax_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const int32_t* y, int64_t B, int32_t D,
+                             int32_t K, const float* W, int32_t S, float* prob, float* lpd, double* lpd_sum);
+
 /* ---- parameter updates --------------------------------------------------- */
 
 /* Adam ascent on a flat float64 vector; t is the 1-based step count. */
