@@ -94,7 +94,9 @@ def test_pass_matches_the_reference(ctx, B, D, K):
 
 @pytest.mark.parametrize("K", KS)
 def test_pass_with_more_than_one_tile_per_wave(ctx, K):
-    """B = 33 000 > 2 048 resident waves x 16 rows: every wave runs a second tile."""
+    """B = 33 000 > 2 048 resident waves x 16 rows: every wave runs a second tile.  The row count assumes 256 CUs (an
+    MI355X); on a larger device this is one tile per wave again.  tests/test_regression_multi_tile_gpu.py sizes its
+    batches from the device's CU count and goes on to three tiles per wave."""
     S = 16 // K + 1
     X, y, W = _inputs(33000, 256, K, S, seed=K)
     ell, G = _pass(ctx, X, y, W)
