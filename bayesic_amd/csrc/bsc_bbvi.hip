@@ -1067,7 +1067,6 @@ __global__ __launch_bounds__(BB_BLOCK) void bbvi_f_kernel(
     __shared__ double red[BB_WAVES];
     const int P = D + G + 1;
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double LOG_2PI = 1.8378770664093454835606594728112;
     const double zeta = lam[P - 1] + exp(lam[2 * P - 1]) * eps[(int64_t)s * P + P - 1];
     const double tau = exp(zeta);
     double part = 0.0;
@@ -1075,10 +1074,10 @@ __global__ __launch_bounds__(BB_BLOCK) void bbvi_f_kernel(
         const double e = eps[(int64_t)s * P + i], rho = lam[P + i];
         const double z = lam[i] + exp(rho) * e;
         double lp;
-        if (i < D) lp = -0.5 * LOG_2PI - 0.5 * z * z;
-        else if (i < D + G) lp = -0.5 * LOG_2PI + 0.5 * zeta - 0.5 * tau * z * z;
+        if (i < D) lp = -0.5 * BSC_LOG_2PI - 0.5 * z * z;
+        else if (i < D + G) lp = -0.5 * BSC_LOG_2PI + 0.5 * zeta - 0.5 * tau * z * z;
         else lp = log_prior_const + a0 * zeta - b0 * tau;
-        const double lq = -0.5 * LOG_2PI - rho - 0.5 * e * e;
+        const double lq = -0.5 * BSC_LOG_2PI - rho - 0.5 * e * e;
         part += lp - lq;
     }
     part = wave_allsum_f64(part);

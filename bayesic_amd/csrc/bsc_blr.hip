@@ -19,44 +19,12 @@
 // FMA 1.55x a plain FMA) are why the cross-lane work rides the LDS pipe and
 // every FMA is all-VGPR.  Block partials go to a slab; they are summed in
 // float64 in a fixed order (bitwise reproducible, no float atomics).
-#include "bsc_common.h"
+#include "bsc_regress.h"
 
 namespace {
 
-constexpr int SG = 8;  // samples per pass
-constexpr int PASS_BLOCK = 256;
-constexpr int PASS_WAVES = PASS_BLOCK / BSC_WAVE;
-constexpr int GCOLS = 256;                    // column capacity of the lane layout
-constexpr int SLAB_G = SG * GCOLS;            // slab[b][d*8 + s], then Q at [SLAB_G + s]
-constexpr int SLAB_STRIDE = SLAB_G + SG;      // floats per block partial
-
-// Geometry of one wave's tile, for ROWS = 8 (2 waves/SIMD) or 4 (3 waves/SIMD).
-// A lane writes its ROWS*8 partial dots as one LDS row of PSTR floats; PSTR = 4 mod 32
-// keeps the 16-byte writes conflict-free, and the row blocks read by the four (eight)
-// lane groups start a multiple of 32 (64) floats apart, so the 16-byte column reads are
-// conflict-free as well.
-template <int ROWS>
-struct Geo {
-    static constexpr int NVAL = ROWS * SG;        // values per lane: 64 or 32
-    static constexpr int PSTR = NVAL + 4;         // 68 or 36 floats
-    static constexpr int NGRP = NVAL / 4;         // lanes per value group set: 16 or 8
-    static constexpr int NQ = BSC_WAVE / NGRP;    // row subsets: 4 or 8
-    static constexpr int RPQ = BSC_WAVE / NQ;     // lane-rows per subset: 16 or 8
-    static constexpr int WAVE_LDS = BSC_WAVE * PSTR + NVAL;  // + residual broadcast buffer
-    static constexpr int OCC = ROWS == 8 ? 2 : 3;  // waves per SIMD (VGPR budget 256 / 168)
-};
-
-template <int ROWS>
-struct Tile {
-    float4 x[ROWS];
-    float yv;
-};
-
-// After the transposing reduction lane k holds value v(k) = row*8 + sample.
-template <int ROWS>
-__device__ __forceinline__ int lane_value(int lane) {
-    return 4 * (lane & (Geo<ROWS>::NGRP - 1)) + 2 * ((lane >> 5) & 1) + ((lane >> 4) & 1);
-}
+constexpr int SLAB_G = REG_SLAB_G;            // slab[b][d*8 + s], then Q at [SLAB_G + s]
+constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
 
 // One tile = ROWS rows starting at row0, through buffer loads: the descriptor
 // (SGPRs) covers exactly the rows [row0, B), so rows past the end -- and whole
@@ -64,7 +32,7 @@ __device__ __forceinline__ int lane_value(int lane) {
 // code path and a trip count that is the same for every wave.  Everything but
 // the 16*lane byte offset is wave-uniform.
 template <int ROWS, bool FULL, bool NT>
-__device__ __forceinline__ void load_tile(Tile<ROWS>& t, const float* __restrict__ X,
+__device__ __forceinline__ void load_tile(RowTile<ROWS>& t, const float* __restrict__ X,
                                           int64_t ldx, const float* __restrict__ y,
                                           int64_t row0, int64_t B, int D, int lane) {
     const int64_t rem = B - row0;  // rows left; <= 0 for a tile past the end
@@ -93,35 +61,9 @@ __device__ __forceinline__ void load_tile(Tile<ROWS>& t, const float* __restrict
         __builtin_amdgcn_raw_buffer_load_b32(ys, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
 }
 
-__device__ __forceinline__ float swap_add32(float a, float b) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false,
-                                              false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-__device__ __forceinline__ float swap_add16(float a, float b) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false,
-                                              false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-    float v = a.x * b.x;
-    v = fmaf(a.y, b.y, v);
-    v = fmaf(a.z, b.z, v);
-    return fmaf(a.w, b.w, v);
-}
-
-__device__ __forceinline__ void axpy4(float4& acc, float c, const float4& x) {
-    acc.x = fmaf(c, x.x, acc.x);
-    acc.y = fmaf(c, x.y, acc.y);
-    acc.z = fmaf(c, x.z, acc.z);
-    acc.w = fmaf(c, x.w, acc.w);
-}
-
 // Forward + backward for one tile; `wl` is this wave's LDS region.
 template <int ROWS>
-__device__ __forceinline__ void compute_tile(const Tile<ROWS>& t, const float4 (&w)[SG],
+__device__ __forceinline__ void compute_tile(const RowTile<ROWS>& t, const float4 (&w)[SG],
                                              float4 (&acc)[SG], float& qacc, float* wl,
                                              int lane) {
     using G = Geo<ROWS>;
@@ -216,7 +158,7 @@ __global__ __launch_bounds__(PASS_BLOCK, Geo<ROWS>::OCC) void blr_pass_kernel(
     // vmcnt(0), i.e. no prefetch at all -- and out-of-range tiles cost no traffic.
     const int64_t stride = (int64_t)gridDim.x * PASS_WAVES;
     int64_t tile = (int64_t)blockIdx.x * PASS_WAVES + wave;
-    Tile<ROWS> ta, tb;
+    RowTile<ROWS> ta, tb;
     load_tile<ROWS, FULL, NT>(ta, X, ldx, y, tile * ROWS, B, D, lane);
     for (int k = 0; k + 1 < n_iter; k += 2) {
         load_tile<ROWS, FULL, NT>(tb, X, ldx, y, (tile + stride) * ROWS, B, D, lane);
@@ -734,103 +676,10 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_mx_kernel(
     }
 }
 
-// float64 sum of p[b * SLAB_STRIDE] over slab rows b = first, first+step, ...
-// Loads are issued in batches of 16 before any add: the partials were written by
-// another kernel, so every load is a MALL/HBM round trip (~0.4 us) and a
-// load-add-load-add chain would serialise them.
-template <int BATCH = 16>
-__device__ __forceinline__ double slab_column_sum(const float* __restrict__ p, int first,
-                                                  int step, int n_rows) {
-    double sum = 0.0;
-    for (int b0 = first; b0 < n_rows; b0 += step * BATCH) {
-        float v[BATCH];
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) {
-            const int b = b0 + j * step;
-            v[j] = b < n_rows ? p[(int64_t)b * SLAB_STRIDE] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) sum += (double)v[j];
-    }
-    return sum;
-}
-
-// Float64 sums of a 64-column run of the slab (columns col0 .. col0+63) over the rows
-// wave + n_waves * k that this wave owns: 16-byte buffer loads covering four rows apiece
-// (lane = (row group lane>>4, column chunk lane&15)); rows past n_slab read as zero through
-// the descriptor.  On return lanes 0-15 hold, in s4[0..3], the sums of columns
-// col0 + 4*lane .. +3.  `between` runs after the first batch of loads has been issued and
-// before it is consumed (work that does not depend on the slab).
-// Kept deliberately compact: these finishing kernels start instruction-cache cold behind the
-// 165-us data pass, and straight-line code is fetched at ~0.5 us per 64 bytes -- the 32
-// guarded scalar loads this replaces (1.5 KB of code) cost 10 us before the first load had
-// even been issued (cycle counters, round 1).
-// JJ: loads in flight per lane and trip (8: the finish kernels' 16 waves cover 512 rows in one trip; 32: four waves do).
-template <int N_WAVES, int JJ = 8, typename F>
-__device__ __forceinline__ void slab_run_sum(const float* __restrict__ slab, int n_slab, int col0,
-                                             int wave, int lane, double (&s4)[4], F between) {
-    const uint64_t slab_bytes = (uint64_t)n_slab * SLAB_STRIDE * 4u;
-    auto rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)slab, 0, slab_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)slab_bytes, 0x00020000);
-    const int q4 = lane >> 4, c16 = lane & 15;
-    const int voff = ((wave + N_WAVES * q4) * SLAB_STRIDE + col0 + 4 * c16) * 4;
-    constexpr int BATCH_BYTES = 4 * N_WAVES * SLAB_STRIDE * 4;      // 4 * N_WAVES rows per load
-    s4[0] = s4[1] = s4[2] = s4[3] = 0.0;
-    for (int base = 0; base < n_slab; base += 4 * JJ * N_WAVES) {   // one trip up to 4 JJ N_WAVES partials
-        float4 v8[JJ];
-#pragma unroll
-        for (int jj = 0; jj < JJ; ++jj) {
-            auto v = __builtin_amdgcn_raw_buffer_load_b128(
-                rs, voff, base * (SLAB_STRIDE * 4) + jj * BATCH_BYTES, 0);
-            v8[jj] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
-                                 __uint_as_float(v[3]));
-        }
-        if (base == 0) between();
-#pragma unroll
-        for (int jj = 0; jj < JJ; ++jj) {
-            s4[0] += (double)v8[jj].x; s4[1] += (double)v8[jj].y;
-            s4[2] += (double)v8[jj].z; s4[3] += (double)v8[jj].w;
-        }
-    }
-    // fold the four row groups (lane bits 4, 5)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        s4[i] += __shfl_xor(s4[i], 16);
-        s4[i] += __shfl_xor(s4[i], 32);
-    }
-}
-
-// Sum block partials in float64, fixed order.  One output per lane; the 16
-// waves of a block split the slab rows, then combine through LDS in wave order.
-constexpr int RED_BLOCK = 1024;
-constexpr int RED_WAVES = RED_BLOCK / BSC_WAVE;
-
 __global__ __launch_bounds__(RED_BLOCK) void blr_slab_reduce_kernel(
     const float* __restrict__ slab, int n_blocks, int D, int S, int s_base,
     double* __restrict__ Q, double* __restrict__ G) {
-    __shared__ double part[RED_WAVES][BSC_WAVE];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int i = blockIdx.x * BSC_WAVE + lane;
-    double s4[4];
-    slab_run_sum<RED_WAVES>(slab, n_blocks, blockIdx.x * BSC_WAVE, wave, lane, s4, [] {});
-    if (lane < 16) {   // (columns past SLAB_STRIDE in the last workgroup are read but never written out)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) part[wave][4 * lane + k] = s4[k];
-    }
-    __syncthreads();
-    if (wave == 0 && i < SLAB_STRIDE) {
-        double tot = part[0][lane];
-#pragma unroll
-        for (int k = 1; k < RED_WAVES; ++k) tot += part[k][lane];
-        if (i < SLAB_G) {
-            int s = i & 7, d = i >> 3;
-            if (s_base + s < S && d < D) G[(int64_t)(s_base + s) * D + d] = tot;
-        } else {
-            int s = i - SLAB_G;
-            if (s_base + s < S) Q[s_base + s] = tot;
-        }
-    }
+    regress_slab_reduce(slab, n_blocks, D, S, s_base, Q, G);
 }
 
 // ---- sampler and ELBO/gradient finish (tiny, float64) ----------------------
@@ -960,7 +809,6 @@ __global__ void blr_sample_kernel(const double* __restrict__ lam, int D, int S, 
 constexpr int FIN_BLOCK = 256;
 constexpr int FIN_WAVES = FIN_BLOCK / BSC_WAVE;
 constexpr int FIN_MAX_S = 64;
-constexpr double LOG_2PI = 1.8378770664093454835606594728112;
 
 __global__ __launch_bounds__(FIN_BLOCK) void blr_elbo_grad_kernel(
     const double* __restrict__ lam, const double* __restrict__ eps,
@@ -1018,14 +866,14 @@ __global__ __launch_bounds__(FIN_BLOCK) void blr_elbo_grad_kernel(
                          e * (0.5 * scale * Q[s] + 0.5 * wsq[s] + beta0);
             fa += dxi;
             fb += dxi * eps[(int64_t)s * (D + 1) + D];
-            double loglik = scale * (-0.5 * batch_rows * (LOG_2PI + x) - 0.5 * e * Q[s]);
-            double logpw = -0.5 * (double)D * (LOG_2PI + x) - 0.5 * e * wsq[s];
+            double loglik = scale * (-0.5 * batch_rows * (BSC_LOG_2PI + x) - 0.5 * e * Q[s]);
+            double logpw = -0.5 * (double)D * (BSC_LOG_2PI + x) - 0.5 * e * wsq[s];
             double logpxi = alpha0 * log(beta0) - lgamma(alpha0) - alpha0 * x - beta0 * e;
             fsum += loglik + logpw + logpxi;
         }
         grad[2 * D] = fa * inv_S;
         grad[2 * D + 1] = fb * inv_S * exp(b) + 1.0;
-        elbo[0] = fsum * inv_S + sum_rho + b + 0.5 * (double)(D + 1) * (1.0 + LOG_2PI);
+        elbo[0] = fsum * inv_S + sum_rho + b + 0.5 * (double)(D + 1) * (1.0 + BSC_LOG_2PI);
     }
 }
 
@@ -1058,21 +906,10 @@ struct FusedArgs {
     // the log-joint per draw as a member of the family (bsc_blr_fused_update_general):
     //   f(w, xi; Q) = c0 + c_xi xi + e^{-xi} (-s_q Q / 2 - k_w |w|^2 / 2 - beta)
     double c0, c_xi, s_q, k_w, beta;
-    double lr, beta1, beta2, adam_eps, corr1, corr2;
+    bsc_adam adam;
     uint64_t seed;
     uint32_t next_step;
 };
-
-__device__ __forceinline__ double adam_ascent_one(double lam, double g, double& m1, double& m2,
-                                                  const FusedArgs& a) {
-    const double na = a.beta1 * m1 + (1.0 - a.beta1) * g;
-    const double nb = a.beta2 * m2 + (1.0 - a.beta2) * g * g;
-    m1 = na;
-    m2 = nb;
-    const double mhat = na / a.corr1;
-    const double vhat = nb / a.corr2;
-    return lam + a.lr * mhat / (sqrt(vhat) + a.adam_eps);
-}
 
 // BLOCK threads per workgroup (1024 = 16 waves: 32 slab rows per wave at 512 partials; fewer waves
 // launch sooner -- BSC_BLR_FINISH_BLOCK, A/B in tools/ab_pass.py)
@@ -1118,7 +955,7 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
             // float64 exponentials that do not depend on it run while it is in flight
             double s4[4];
             double e_mxs = 0.0;
-            slab_run_sum<FUSED_WAVES, (FUSED_WAVES >= 16 ? 8 : 32)>(a.slab, a.n_slab, 64 * chunk, wave, lane, s4, [&] {
+            slab_run_sum<SLAB_STRIDE, FUSED_WAVES, (FUSED_WAVES >= 16 ? 8 : 32)>(a.slab, a.n_slab, 64 * chunk, wave, lane, s4, [&] {
                 if (wave == 0) {
                     e_mxs = exp(-xs);
                     e_rho = exp(p_rho);
@@ -1166,10 +1003,10 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
             a.grad[d] = g_m;
             a.grad[D + d] = g_r;
             double m1 = p_m1, m2 = p_m2;
-            const double nm = adam_ascent_one(p_m, g_m, m1, m2, a);
+            const double nm = bsc_adam_ascent(p_m, g_m, m1, m2, a.adam);
             a.m1[d] = m1; a.m2[d] = m2;
             double r1 = p_r1, r2 = p_r2;
-            const double nr = adam_ascent_one(rho, g_r, r1, r2, a);
+            const double nr = bsc_adam_ascent(rho, g_r, r1, r2, a.adam);
             a.m1[D + d] = r1; a.m2[D + d] = r2;
             a.lam_out[d] = nm;
             a.lam_out[D + d] = nr;
@@ -1228,7 +1065,7 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
         }
     }
     if (a.slab) {  // S <= 8: thread -> (sample tid&7, slab-row group tid>>3)
-        double part = slab_column_sum<(FUSED_BLOCK >= 1024 ? 8 : 16)>(a.slab + SLAB_G + (tid & 7), tid >> 3, FUSED_BLOCK / 8,
+        double part = slab_column_sum<SLAB_STRIDE, (FUSED_BLOCK >= 1024 ? 8 : 16)>(a.slab + SLAB_G + (tid & 7), tid >> 3, FUSED_BLOCK / 8,
                                                                        a.n_slab);
         // fold the 8 row groups of this wave (lane bits 3-5), then the 16 waves
         part += __shfl_xor(part, 8);
@@ -1291,10 +1128,10 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
         const double g_b = fb * inv_S * exp(bv) + 1.0;
         a.grad[2 * D] = g_a;
         a.grad[2 * D + 1] = g_b;
-        a.elbo[0] = fsum * inv_S + sum_rho + bv + 0.5 * (double)(D + 1) * (1.0 + LOG_2PI);
-        const double na = adam_ascent_one(av, g_a, am1, am2, a);
+        a.elbo[0] = fsum * inv_S + sum_rho + bv + 0.5 * (double)(D + 1) * (1.0 + BSC_LOG_2PI);
+        const double na = bsc_adam_ascent(av, g_a, am1, am2, a.adam);
         a.m1[2 * D] = am1; a.m2[2 * D] = am2;
-        const double nb = adam_ascent_one(bv, g_b, bm1, bm2, a);
+        const double nb = bsc_adam_ascent(bv, g_b, bm1, bm2, a.adam);
         a.m1[2 * D + 1] = bm1; a.m2[2 * D + 1] = bm2;
         a.lam_out[2 * D] = na;
         a.lam_out[2 * D + 1] = nb;
@@ -1310,13 +1147,6 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
     }
 }
 
-// Grid and per-wave trip count: fill the resident wave slots, then balance so
-// that every wave runs the same number of (almost all real) tiles.
-struct PassGrid {
-    int n_blocks;
-    int n_iter;
-};
-
 // Tile height of the variant that will run: 16 = forward on the MFMA pipe (needs the full
 // 256-column layout and 16-byte aligned y), else the VALU kernel with 8- or 4-row tiles.
 int pass_rows(const bsc_ctx* ctx, int D, const float* y) {
@@ -1325,38 +1155,20 @@ int pass_rows(const bsc_ctx* ctx, int D, const float* y) {
     return ctx->blr_tile_rows;
 }
 
-PassGrid pass_grid(bsc_ctx* ctx, int64_t B, int rows) {
-    const int64_t n_tiles = (B + rows - 1) / rows;
+// The grid for tiles of `rows` rows at the occupancy of the kernel that runs them (capped by blr_waves_per_simd).
+PassGrid blr_pass_grid(const bsc_ctx* ctx, int64_t B, int rows) {
     int occ = rows == 4 ? Geo<4>::OCC : 2;
     if (ctx->blr_waves_per_simd > 0 && ctx->blr_waves_per_simd < occ) occ = ctx->blr_waves_per_simd;
-    const int64_t max_waves = (int64_t)occ * 4 * ctx->cu_count;
-    PassGrid g;
-    if (n_tiles <= 0) {
-        g.n_blocks = 1;
-        g.n_iter = 0;
-        return g;
-    }
-    const int64_t n_iter = (n_tiles + max_waves - 1) / max_waves;
-    const int64_t waves = (n_tiles + n_iter - 1) / n_iter;
-    g.n_blocks = (int)((waves + PASS_WAVES - 1) / PASS_WAVES);
-    g.n_iter = (int)n_iter;
-    return g;
+    return pass_grid(ctx, B, rows, occ);
 }
 
 constexpr int MAX_SLAB_ROWS = 4 * 256 + 64;  // workspace sizing hint for callers
 
+// Every pass entry point reports under the name of bsc_blr_data_pass.
 int check_pass_args(const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
                     const float* W, int32_t S, int max_s) {
-    BSC_REQUIRE(B >= 0, "bsc_blr_data_pass: B=%lld", (long long)B);
-    BSC_REQUIRE(((X && y) || B == 0) && W, "bsc_blr_data_pass: null pointer");
-    BSC_REQUIRE(D > 0 && D <= GCOLS && D % 4 == 0,
-                "bsc_blr_data_pass: D=%d must be a multiple of 4 in [4,%d]", D, GCOLS);
-    BSC_REQUIRE(S >= 1 && S <= max_s, "bsc_blr_data_pass: S=%d must be in [1,%d]", S, max_s);
-    BSC_REQUIRE(ldx >= D && ldx % 4 == 0 && ldx < ((int64_t)1 << 26),
-                "bsc_blr_data_pass: ldx=%lld must be >= D, %% 4 == 0 and < 2^26", (long long)ldx);
-    BSC_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0,
-                "bsc_blr_data_pass: X and W must be 16-byte aligned");
-    return BSC_OK;
+    BSC_REQUIRE(y || B <= 0, "bsc_blr_data_pass: null pointer");
+    return check_regress_args("bsc_blr_data_pass", X, ldx, B, D, W, S, max_s);
 }
 
 template <int ROWS, bool NT>
@@ -1441,7 +1253,7 @@ int data_pass_impl(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, in
     if (rc != BSC_OK) return rc;
     BSC_REQUIRE(Q && G, "bsc_blr_data_pass: null output");
     BSC_REQUIRE(sweep >= 0 && sweep <= 2, "bsc_blr_data_pass: sweep=%d (0, 1 or 2)", sweep);
-    const PassGrid g = pass_grid(ctx, B, pass_rows(ctx, D, y));
+    const PassGrid g = blr_pass_grid(ctx, B, pass_rows(ctx, D, y));
     void* ws = nullptr;
     rc = bsc_workspace(ctx, (size_t)2 * g.n_blocks * SLAB_STRIDE * sizeof(float), &ws);
     if (rc != BSC_OK) return rc;
@@ -1476,7 +1288,7 @@ int data_pass_partial_impl(bsc_ctx* ctx, const float* X, int64_t ldx, const floa
     int rc = check_pass_args(X, ldx, y, B, D, W, S, SG);
     if (rc != BSC_OK) return rc;
     BSC_REQUIRE(sweep >= 0 && sweep <= 2, "bsc_blr_data_pass_partial: sweep=%d (0, 1 or 2)", sweep);
-    const PassGrid g = pass_grid(ctx, B, pass_rows(ctx, D, y));
+    const PassGrid g = blr_pass_grid(ctx, B, pass_rows(ctx, D, y));
     void* ws = nullptr;
     rc = bsc_workspace(ctx, (size_t)2 * g.n_blocks * SLAB_STRIDE * sizeof(float), &ws);
     if (rc != BSC_OK) return rc;
@@ -1621,9 +1433,7 @@ int fused_update_impl(bsc_ctx* ctx, const char* who, const double* stats, const 
     a.elbo = elbo; a.grad = grad;
     a.D = D; a.S = S;
     a.c0 = c0; a.c_xi = c_xi; a.s_q = s_q; a.k_w = k_w; a.beta = beta;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps;
-    a.corr1 = 1.0 - pow(beta1, (double)t);
-    a.corr2 = 1.0 - pow(beta2, (double)t);
+    a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
     a.seed = seed;
     a.next_step = next_step;
     {
@@ -1653,7 +1463,7 @@ int bsc_blr_fused_update(bsc_ctx* ctx, const double* stats, const double* lam_in
     //   scale [-B/2 (log 2 pi + xi) - e Q / 2] - D/2 (log 2 pi + xi) - e |w|^2 / 2 + alpha0 log beta0 - lnGamma(alpha0) - alpha0 xi - beta0 e
     const double half = 0.5 * (scale * batch_rows + (double)D);
     return fused_update_impl(ctx, "bsc_blr_fused_update", stats, lam_in, lam_out, m1, m2, eps, W, xi, D, S,
-                             -half * LOG_2PI + alpha0 * log(beta0) - lgamma(alpha0), -half - alpha0, scale, 1.0, beta0,
+                             -half * BSC_LOG_2PI + alpha0 * log(beta0) - lgamma(alpha0), -half - alpha0, scale, 1.0, beta0,
                              t, lr, beta1, beta2, adam_eps, seed, next_step, eps_next, eps_next_ready, W_next,
                              xi_next, elbo, grad);
 }
@@ -1687,7 +1497,7 @@ int bsc_blr_pass_update(bsc_ctx* ctx, const float* X, int64_t ldx, const float* 
     BSC_REQUIRE(alpha0 > 0 && beta0 > 0, "bsc_blr_pass_update: bad hyper-parameters");
     const double half = 0.5 * (scale * batch_rows + (double)D);       // (config 2 as a member of the family: bsc_blr_fused_update)
     return pass_update_impl(ctx, "bsc_blr_pass_update", X, ldx, y, B, D, sweep, lam_in, lam_out, m1, m2, eps, W, xi, S,
-                            -half * LOG_2PI + alpha0 * log(beta0) - lgamma(alpha0), -half - alpha0, scale, 1.0, beta0, t, lr,
+                            -half * BSC_LOG_2PI + alpha0 * log(beta0) - lgamma(alpha0), -half - alpha0, scale, 1.0, beta0, t, lr,
                             beta1, beta2, adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, xi_next, elbo, grad);
 }
 

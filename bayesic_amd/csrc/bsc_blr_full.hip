@@ -9,7 +9,7 @@
 //     d / d L_ij  = mean_s g_si eps_sj                   (j < i)
 //     d / d rho_i = mean_s g_si eps_si e^{rho_i} + 1
 //     ELBO        = mean_s f_s + sum_i rho_i + P/2 (1 + log 2 pi)
-// then Adam ascent on every entry (adam_ascent_one's arithmetic) and the next draw z'_s = mu' + L' eps'_s.
+// then Adam ascent on every entry (bsc_adam_ascent) and the next draw z'_s = mu' + L' eps'_s.
 //
 // Rows of L are independent once the per-sample scalars e^{-xi_s} (and, for the xi row, |w_s|^2 and Q_s) are known, so
 // workgroup k owns rows k and P-1-k (i + 1 and P - i entries: P + 1 together; P = D + 1 is odd, so the middle row
@@ -17,7 +17,7 @@
 // the ELBO.  Each workgroup forms its rows of the next draw from its own rows of L'.  Every sum runs in a fixed order,
 // no atomics, no inter-workgroup communication: the result is the same bytes run to run.  The caller double-buffers
 // lam and the draws.  Small and latency-bound: a handful of dependent memory round trips per workgroup.
-#include "bsc_common.h"
+#include "bsc_fullrank.h"
 
 // as the mean-field finish (csrc/bsc_blr.hip): no contraction into FMAs, so that with a diagonal L the two finishes do
 // the same arithmetic
@@ -25,11 +25,7 @@
 
 namespace {
 
-constexpr int FR_BLOCK = 256;
-constexpr int FR_WAVES = FR_BLOCK / BSC_WAVE;
-constexpr int FR_MAX_S = 64;
 constexpr int FR_MAX_P = 257;
-constexpr double FR_LOG_2PI = 1.8378770664093454835606594728112;
 
 struct FullArgs {
     const double* stats;   // [Q (S) | G (S*D)]
@@ -47,19 +43,8 @@ struct FullArgs {
     double* grad;          // lam's layout
     int D, S;
     double c0, c_xi, s_q, k_w, beta;
-    double lr, beta1, beta2, adam_eps, corr1, corr2;
+    bsc_adam adam;
 };
-
-// adam_ascent_one (csrc/bsc_blr.hip), the same arithmetic
-__device__ __forceinline__ double fr_adam(double lam, double g, double& m1, double& m2, const FullArgs& a) {
-    const double na = a.beta1 * m1 + (1.0 - a.beta1) * g;
-    const double nb = a.beta2 * m2 + (1.0 - a.beta2) * g * g;
-    m1 = na;
-    m2 = nb;
-    const double mhat = na / a.corr1;
-    const double vhat = nb / a.corr2;
-    return lam + a.lr * mhat / (sqrt(vhat) + a.adam_eps);
-}
 
 __global__ __launch_bounds__(FR_BLOCK) void blr_fullrank_update_kernel(FullArgs a) {
     __shared__ double e_inv[FR_MAX_S];
@@ -71,10 +56,8 @@ __global__ __launch_bounds__(FR_BLOCK) void blr_fullrank_update_kernel(FullArgs 
     __shared__ double rho_sum;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = a.D, S = a.S, P = D + 1;
-    const int k = blockIdx.x;
-    const int row0 = k, row1 = P - 1 - k;  // row1 >= row0
-    const int n_rows = row0 == row1 ? 1 : 2;
-    const bool xi_wg = k == 0;             // owns row P-1 (xi) and the ELBO
+    const fr_rows rp = fr_row_pair(blockIdx.x, P);
+    const bool xi_wg = blockIdx.x == 0;    // owns row P-1 (xi) and the ELBO
     const double inv_S = 1.0 / (double)S;
 
     // ---- per-sample scalars (and, in workgroup 0, |w_s|^2 and sum rho) ----
@@ -99,8 +82,8 @@ __global__ __launch_bounds__(FR_BLOCK) void blr_fullrank_update_kernel(FullArgs 
     __syncthreads();
 
     // ---- g_{s,i} for the rows of this workgroup ----
-    for (int idx = tid; idx < n_rows * S; idx += FR_BLOCK) {
-        const int r = idx / S, s = idx - r * S, i = r ? row1 : row0;
+    for (int idx = tid; idx < rp.n_rows * S; idx += FR_BLOCK) {
+        const int r = idx / S, s = idx - r * S, i = r ? rp.row1 : rp.row0;
         const double e = e_inv[s];
         if (i < D) {
             const double wv = (double)a.W[(int64_t)s * D + i];
@@ -114,62 +97,19 @@ __global__ __launch_bounds__(FR_BLOCK) void blr_fullrank_update_kernel(FullArgs 
     }
     __syncthreads();
 
-    // ---- gradient + Adam: one entry per thread; item j = -1 is mu_i, j = 0..i the row's entries of L ----
-    const int n0 = row0 + 2;
-    const int n_items = n0 + (n_rows == 2 ? row1 + 2 : 0);
-    for (int it = tid; it < n_items; it += FR_BLOCK) {
-        const int r = it < n0 ? 0 : 1;
-        const int i = r ? row1 : row0;
-        const int j = (r == 0 ? it : it - n0) - 1;
-        const int64_t off = j < 0 ? (int64_t)i : (int64_t)P + (int64_t)i * (i + 1) / 2 + j;
-        const double p = a.lam_in[off];
-        double m1 = a.m1[off], m2 = a.m2[off];
-        double acc = 0.0;
-        if (j < 0) {
-            for (int s = 0; s < S; ++s) acc += gs[r][s];
-        } else {
-            for (int s = 0; s < S; ++s) acc += gs[r][s] * a.eps[(int64_t)s * P + j];
-        }
-        double g;
-        if (j < 0) g = acc * inv_S;
-        else if (j == i) g = acc * inv_S * exp(p) + 1.0;
-        else g = acc * inv_S;
-        a.grad[off] = g;
-        const double np = fr_adam(p, g, m1, m2, a);
-        a.m1[off] = m1;
-        a.m2[off] = m2;
-        a.lam_out[off] = np;
-        if (j < 0) mu_new[r] = np;
-        else Lnew[r][j] = j == i ? exp(np) : np;
-    }
+    fr_grad_adam(rp, P, P, S, gs, a.lam_in, a.lam_out, a.m1, a.m2, a.grad, a.eps, a.adam, Lnew, mu_new);
     if (xi_wg && tid == 0) {
         double fsum = 0.0;
         for (int s = 0; s < S; ++s) fsum += ft[s];
-        a.elbo[0] = fsum * inv_S + rho_sum + 0.5 * (double)P * (1.0 + FR_LOG_2PI);
+        a.elbo[0] = fsum * inv_S + rho_sum + 0.5 * (double)P * (1.0 + BSC_LOG_2PI);
     }
     if (!a.eps_next) return;
     __syncthreads();
 
-    // ---- next draw of these rows: z'_{s,i} = mu'_i + sum_{j<=i} L'_ij eps'_sj (a wave per sample, both rows at once) ----
-    for (int s = wave; s < S; s += FR_WAVES) {
-        const double* e = a.eps_next + (int64_t)s * P;
-        double z0 = 0.0, z1 = 0.0;
-        for (int j = lane; j <= row1; j += BSC_WAVE) {
-            const double ev = e[j];
-            if (j <= row0) z0 += Lnew[0][j] * ev;
-            z1 += Lnew[n_rows - 1][j] * ev;
-        }
-        z0 = wave_allsum_f64(z0);
-        z1 = wave_allsum_f64(z1);
-        if (lane == 0) {
-            for (int r = 0; r < n_rows; ++r) {
-                const int i = r ? row1 : row0;
-                const double z = mu_new[r] + (r == 0 ? z0 : z1);
-                if (i < D) a.W_next[(int64_t)s * D + i] = (float)z;
-                else a.xi_next[s] = z;
-            }
-        }
-    }
+    fr_next_draw(rp, P, S, a.eps_next, Lnew, mu_new, [&](int s, int i, double z) {
+        if (i < D) a.W_next[(int64_t)s * D + i] = (float)z;
+        else a.xi_next[s] = z;
+    });
 }
 
 }  // namespace
@@ -184,22 +124,13 @@ int bsc_blr_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam
                             double* grad) {
     const char* who = "bsc_blr_fullrank_update";
     BSC_CHECK_CTX(ctx);
-    BSC_REQUIRE(stats, "%s: stats must be the [Q | G] of the data pass (pending partials are not read)", who);
-    BSC_REQUIRE(lam_in && lam_out && m1 && m2 && eps && W && xi && elbo && grad, "%s: null pointer", who);
-    BSC_REQUIRE(lam_in != lam_out, "%s: lam_in and lam_out must differ", who);
-    BSC_REQUIRE(D >= 4 && D <= FR_MAX_P - 1 && D % 4 == 0, "%s: D=%d must be a multiple of 4 in [4,%d]", who, D,
-                FR_MAX_P - 1);
-    BSC_REQUIRE(S >= 1 && S <= FR_MAX_S, "%s: S=%d must be in [1,%d]", who, S, FR_MAX_S);
-    BSC_REQUIRE(t >= 1, "%s: the Adam step count starts at 1", who);
+    int rc = fr_check_state(who, "Q | G", stats, lam_in && lam_out && m1 && m2 && eps && W && xi && elbo && grad, lam_in,
+                            lam_out, D, FR_MAX_P - 1, S, t);
+    if (rc != BSC_OK) return rc;
     BSC_REQUIRE(s_q >= 0.0 && k_w >= 0.0, "%s: s_q=%g k_w=%g must not be negative", who, s_q, k_w);
-    BSC_REQUIRE((eps_next && W_next && xi_next) || (!eps_next && !W_next && !xi_next),
-                "%s: next-draw buffers must be all set or all null", who);
-    BSC_REQUIRE(!eps_next || (eps_next != eps && W_next != W && xi_next != xi),
-                "%s: next-draw buffers must not alias the current draws", who);
-    if (eps_next && !eps_next_ready) {   // the next step's noise first (bsc_blr_noise's layout), then the finish
-        const int rc = bsc_blr_noise(ctx, D, S, seed, next_step, 1, eps_next);
-        if (rc != BSC_OK) return rc;
-    }
+    rc = fr_next_noise(ctx, who, /*has_xi=*/true, eps, W, xi, eps_next, W_next, xi_next, D, S, seed, next_step,
+                       eps_next_ready);
+    if (rc != BSC_OK) return rc;
     FullArgs a;
     a.stats = stats;
     a.lam_in = lam_in; a.lam_out = lam_out; a.m1 = m1; a.m2 = m2;
@@ -208,9 +139,7 @@ int bsc_blr_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam
     a.elbo = elbo; a.grad = grad;
     a.D = D; a.S = S;
     a.c0 = c0; a.c_xi = c_xi; a.s_q = s_q; a.k_w = k_w; a.beta = beta;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps;
-    a.corr1 = 1.0 - pow(beta1, (double)t);
-    a.corr2 = 1.0 - pow(beta2, (double)t);
+    a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
     {
         bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish kernel, timed apart from the pass
         hipLaunchKernelGGL(blr_fullrank_update_kernel, dim3((D + 2) / 2), dim3(FR_BLOCK), 0, ctx->stream, a);

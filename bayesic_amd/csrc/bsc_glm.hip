@@ -23,16 +23,12 @@
 //
 // Rows past the end of the mini-batch read as zeros through the buffer descriptor (no ragged-tail path); their
 // logit is 0, so they add nothing to G (x = 0) and are masked out of ell (A(0) != 0).
-#include "bsc_common.h"
+#include "bsc_regress.h"
 
 namespace {
 
-constexpr int SG = 8;                         // draws per pass
-constexpr int PASS_BLOCK = 256;
-constexpr int PASS_WAVES = PASS_BLOCK / BSC_WAVE;
-constexpr int GCOLS = 256;                    // column capacity of the lane layout
-constexpr int SLAB_G = SG * GCOLS;            // slab[b][d*8 + s], then ell at [SLAB_G + s]
-constexpr int SLAB_STRIDE = SLAB_G + SG;      // floats per block partial
+constexpr int SLAB_G = REG_SLAB_G;            // slab[b][d*8 + s], then ell at [SLAB_G + s]
+constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
 constexpr int MAX_S = 64;
 
 // ---- the link: ell += y l - A(l) for a real row, resid = y - A'(l) ------------------------------------------
@@ -61,23 +57,10 @@ __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, floa
     return yv - da;
 }
 
-// ---- 8-row tiles on the VALU (any D % 4 == 0 up to 256): blr_pass_kernel<., 8, .>'s geometry -----------------
+// ---- 8-row tiles on the VALU (any D % 4 == 0 up to 256): blr_pass_kernel<., 8, .>'s tile (csrc/bsc_regress.h) ----
 constexpr int ROWS = 8;
-constexpr int NVAL = ROWS * SG;               // values per lane: 64
-constexpr int PSTR = NVAL + 4;                // 68 floats: 16-byte writes and column reads conflict-free
-constexpr int NGRP = NVAL / 4;                // 16
-constexpr int RPQ = 16;                       // lane-rows per subset
-constexpr int WAVE_LDS = BSC_WAVE * PSTR + NVAL;
-
-struct Tile {
-    float4 x[ROWS];
-    float yv;
-};
-
-// After the transposing reduction lane k holds value v(k) = row*8 + draw.
-__device__ __forceinline__ int lane_value(int lane) {
-    return 4 * (lane & (NGRP - 1)) + 2 * ((lane >> 5) & 1) + ((lane >> 4) & 1);
-}
+using G8 = Geo<ROWS>;
+using Tile = RowTile<ROWS>;
 
 // One tile = ROWS rows from row0 on, through descriptors that cover exactly the rows [row0, B).
 template <bool FULL>
@@ -95,31 +78,7 @@ __device__ __forceinline__ void load_tile(Tile& t, const float* __restrict__ X, 
         if (!FULL && 4 * lane >= D) f = make_float4(0.f, 0.f, 0.f, 0.f);  // the next row's bytes
         t.x[r] = f;
     }
-    t.yv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ys, 4 * (lane_value(lane) >> 3), 0, 0));
-}
-
-__device__ __forceinline__ float swap_add32(float a, float b) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-__device__ __forceinline__ float swap_add16(float a, float b) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-    float v = a.x * b.x;
-    v = fmaf(a.y, b.y, v);
-    v = fmaf(a.z, b.z, v);
-    return fmaf(a.w, b.w, v);
-}
-
-__device__ __forceinline__ void axpy4(float4& acc, float c, const float4& x) {
-    acc.x = fmaf(c, x.x, acc.x);
-    acc.y = fmaf(c, x.y, acc.y);
-    acc.z = fmaf(c, x.z, acc.z);
-    acc.w = fmaf(c, x.w, acc.w);
+    t.yv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ys, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
 }
 
 // Forward + link + backward for one tile; `wl` is this wave's LDS region, `rows_left` = B - row0.
@@ -127,7 +86,7 @@ template <int LINK>
 __device__ __forceinline__ void compute_tile(const Tile& t, const float4 (&w)[SG], float4 (&acc)[SG], float& ell,
                                              float* wl, int lane, int64_t rows_left) {
     // 1. per-lane partial dots, row by row, into this lane's row of the buffer
-    float* mine = wl + lane * PSTR;
+    float* mine = wl + lane * G8::PSTR;
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
         float4 lo, hi;
@@ -140,14 +99,14 @@ __device__ __forceinline__ void compute_tile(const Tile& t, const float4 (&w)[SG
     }
     wave_lds_sync();
     // 2. lane k sums values 4g..4g+3 (g = k % 16) over the lane-rows 16 q .. 16 q + 15
-    const int g = lane & (NGRP - 1), q = lane / NGRP;
-    const float* col = wl + q * RPQ * PSTR + 4 * g;
+    const int g = lane & (G8::NGRP - 1), q = lane / G8::NGRP;
+    const float* col = wl + q * G8::RPQ * G8::PSTR + 4 * g;
     float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int part = 0; part < RPQ / 8; ++part) {
+    for (int part = 0; part < G8::RPQ / 8; ++part) {
         float4 v[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const float4*>(col + (8 * part + i) * PSTR);
+        for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const float4*>(col + (8 * part + i) * G8::PSTR);
 #pragma unroll
         for (int h = 4; h >= 1; h >>= 1) {
 #pragma unroll
@@ -162,9 +121,9 @@ __device__ __forceinline__ void compute_tile(const Tile& t, const float4 (&w)[SG
     const float t0 = swap_add32(s4.x, s4.z);
     const float t1 = swap_add32(s4.y, s4.w);
     const float logit = swap_add16(t0, t1);
-    const int val = lane_value(lane);
+    const int val = lane_value<ROWS>(lane);
     const float resid = glm_link<LINK>(logit, t.yv, (int64_t)(val >> 3) < rows_left, ell);
-    float* rb = wl + BSC_WAVE * PSTR;
+    float* rb = wl + BSC_WAVE * G8::PSTR;
     rb[val] = resid;
     wave_lds_sync();
     // 4. backward: acc[s] += resid(r, s) * x[r]; residuals arrive by LDS broadcast
@@ -197,12 +156,12 @@ template <int LINK, bool FULL>
 __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_pass_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, int64_t B, int D,
     const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter) {
-    constexpr int LDS_FLOATS = PASS_WAVES * (WAVE_LDS > SLAB_STRIDE ? WAVE_LDS : SLAB_STRIDE);
+    constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > SLAB_STRIDE ? G8::WAVE_LDS : SLAB_STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* wl = lds + wave * WAVE_LDS;
+    float* wl = lds + wave * G8::WAVE_LDS;
 
     float4 w[SG], acc[SG];
 #pragma unroll
@@ -236,7 +195,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_pass_kernel(
     ev += __shfl_xor(ev, 2);
     ev += __shfl_xor(ev, 4);
     ev += __shfl_xor(ev, 8);
-    if ((lane & 14) == 0) ep[SLAB_G + (lane_value(lane) & 7)] = ev;
+    if ((lane & 14) == 0) ep[SLAB_G + (lane_value<ROWS>(lane) & 7)] = ev;
     __syncthreads();
     write_block_partial(lds, slab, tid);
 }
@@ -383,90 +342,11 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_pass_mfma_kernel(
     write_block_partial(lds, slab, tid);
 }
 
-// ---- float64 reduction of the slab (csrc/bsc_blr.hip's, restated: that file keeps it internal) ---------------
-
-// float64 sum of p[b * SLAB_STRIDE] over slab rows b = first, first + step, ...; loads in batches before any add
-template <int BATCH>
-__device__ __forceinline__ double slab_column_sum(const float* __restrict__ p, int first, int step, int n_rows) {
-    double sum = 0.0;
-    for (int b0 = first; b0 < n_rows; b0 += step * BATCH) {
-        float v[BATCH];
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) {
-            const int b = b0 + j * step;
-            v[j] = b < n_rows ? p[(int64_t)b * SLAB_STRIDE] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) sum += (double)v[j];
-    }
-    return sum;
-}
-
-// Float64 sums of a 64-column run of the slab (columns col0 .. col0 + 63) over the rows wave + N_WAVES * k:
-// 16-byte buffer loads covering four rows apiece (lane = (row group lane >> 4, column chunk lane & 15)); rows past
-// n_slab read as zero.  On return lanes 0-15 hold, in s4[0..3], the sums of columns col0 + 4 lane .. + 3.
-// Compact on purpose: the finish starts instruction-cache cold behind the pass (NOTES section 4).
-template <int N_WAVES, int JJ = 8>
-__device__ __forceinline__ void slab_run_sum(const float* __restrict__ slab, int n_slab, int col0, int wave, int lane,
-                                             double (&s4)[4]) {
-    const uint64_t slab_bytes = (uint64_t)n_slab * SLAB_STRIDE * 4u;
-    auto rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)slab, 0, slab_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)slab_bytes, 0x00020000);
-    const int q4 = lane >> 4, c16 = lane & 15;
-    const int voff = ((wave + N_WAVES * q4) * SLAB_STRIDE + col0 + 4 * c16) * 4;
-    constexpr int BATCH_BYTES = 4 * N_WAVES * SLAB_STRIDE * 4;      // 4 * N_WAVES rows per load
-    s4[0] = s4[1] = s4[2] = s4[3] = 0.0;
-    for (int base = 0; base < n_slab; base += 4 * JJ * N_WAVES) {
-        float4 v8[JJ];
-#pragma unroll
-        for (int jj = 0; jj < JJ; ++jj) {
-            auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, base * (SLAB_STRIDE * 4) + jj * BATCH_BYTES, 0);
-            v8[jj] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
-                                 __uint_as_float(v[3]));
-        }
-#pragma unroll
-        for (int jj = 0; jj < JJ; ++jj) {
-            s4[0] += (double)v8[jj].x; s4[1] += (double)v8[jj].y;
-            s4[2] += (double)v8[jj].z; s4[3] += (double)v8[jj].w;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {       // fold the four row groups (lane bits 4, 5)
-        s4[i] += __shfl_xor(s4[i], 16);
-        s4[i] += __shfl_xor(s4[i], 32);
-    }
-}
-
-constexpr int RED_BLOCK = 1024;
-constexpr int RED_WAVES = RED_BLOCK / BSC_WAVE;
-
-// One output per lane; the 16 waves of a block split the slab rows, then combine through LDS in wave order.
+// ---- float64 reduction of the slab: blr_slab_reduce_kernel's body, ell where that one writes Q -------------------
 __global__ __launch_bounds__(RED_BLOCK) void glm_slab_reduce_kernel(const float* __restrict__ slab, int n_blocks, int D,
                                                                     int S, int s_base, double* __restrict__ ell,
                                                                     double* __restrict__ G) {
-    __shared__ double part[RED_WAVES][BSC_WAVE];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int i = blockIdx.x * BSC_WAVE + lane;
-    double s4[4];
-    slab_run_sum<RED_WAVES>(slab, n_blocks, blockIdx.x * BSC_WAVE, wave, lane, s4);
-    if (lane < 16) {   // (columns past SLAB_STRIDE in the last workgroup are read as zeros and never written out)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) part[wave][4 * lane + k] = s4[k];
-    }
-    __syncthreads();
-    if (wave == 0 && i < SLAB_STRIDE) {
-        double tot = part[0][lane];
-#pragma unroll
-        for (int k = 1; k < RED_WAVES; ++k) tot += part[k][lane];
-        if (i < SLAB_G) {
-            const int s = i & 7, d = i >> 3;
-            if (s_base + s < S && d < D) G[(int64_t)(s_base + s) * D + d] = tot;
-        } else {
-            const int s = i - SLAB_G;
-            if (s_base + s < S) ell[s_base + s] = tot;
-        }
-    }
+    regress_slab_reduce(slab, n_blocks, D, S, s_base, ell, G);
 }
 
 // ---- the finish: slab reduce + ELBO + pathwise gradient + Adam + next draw, one launch ----------------------
@@ -494,16 +374,8 @@ struct GlmArgs {
     double* grad;
     int D, S;
     double scale, tau, c0;   // c0 = D/2 log(tau / 2 pi) + D/2 (1 + log 2 pi)
-    double lr, beta1, beta2, adam_eps, corr1, corr2;
+    bsc_adam adam;
 };
-
-__device__ __forceinline__ double adam_ascent_one(double lam, double g, double& m1, double& m2, const GlmArgs& a) {
-    const double na = a.beta1 * m1 + (1.0 - a.beta1) * g;
-    const double nb = a.beta2 * m2 + (1.0 - a.beta2) * g * g;
-    m1 = na;
-    m2 = nb;
-    return lam + a.lr * (na / a.corr1) / (sqrt(nb / a.corr2) + a.adam_eps);
-}
 
 __global__ __launch_bounds__(FIN_BLOCK) void glm_update_kernel(GlmArgs a) {
     __shared__ double red[FIN_WAVES][BSC_WAVE];
@@ -538,7 +410,7 @@ __global__ __launch_bounds__(FIN_BLOCK) void glm_update_kernel(GlmArgs a) {
                 ev = a.eps[(int64_t)sl * (D + 1) + d];
             }
             double s4[4];
-            slab_run_sum<FIN_WAVES>(a.slab, a.n_slab, 64 * chunk, wave, lane, s4);
+            slab_run_sum<SLAB_STRIDE, FIN_WAVES>(a.slab, a.n_slab, 64 * chunk, wave, lane, s4, [] {});
             if (lane < 16) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) red[wave][4 * lane + i] = s4[i];
@@ -576,9 +448,9 @@ __global__ __launch_bounds__(FIN_BLOCK) void glm_update_kernel(GlmArgs a) {
             const double g_r = gr * inv_S * exp(p_rho) + 1.0;
             a.grad[d] = g_m;
             a.grad[D + d] = g_r;
-            const double nm = adam_ascent_one(p_m, g_m, p_m1, p_m2, a);
+            const double nm = bsc_adam_ascent<true>(p_m, g_m, p_m1, p_m2, a.adam);
             a.m1[d] = p_m1; a.m2[d] = p_m2;
-            const double nr = adam_ascent_one(p_rho, g_r, p_r1, p_r2, a);
+            const double nr = bsc_adam_ascent<true>(p_rho, g_r, p_r1, p_r2, a.adam);
             a.m1[D + d] = p_r1; a.m2[D + d] = p_r2;
             a.lam_out[d] = nm;
             a.lam_out[D + d] = nr;
@@ -601,7 +473,7 @@ __global__ __launch_bounds__(FIN_BLOCK) void glm_update_kernel(GlmArgs a) {
     double rho_part = 0.0;
     for (int d = tid; d < D; d += FIN_BLOCK) rho_part += a.lam_in[D + d];
     if (a.slab) {  // S <= 8: thread -> (draw tid & 7, slab-row group tid >> 3)
-        double part = slab_column_sum<8>(a.slab + SLAB_G + (tid & 7), tid >> 3, FIN_BLOCK / 8, a.n_slab);
+        double part = slab_column_sum<SLAB_STRIDE, 8>(a.slab + SLAB_G + (tid & 7), tid >> 3, FIN_BLOCK / 8, a.n_slab);
         part += __shfl_xor(part, 8);
         part += __shfl_xor(part, 16);
         part += __shfl_xor(part, 32);
@@ -639,44 +511,16 @@ __global__ __launch_bounds__(FIN_BLOCK) void glm_update_kernel(GlmArgs a) {
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
-struct PassGrid {
-    int n_blocks;
-    int n_iter;
-};
-
 // 16 = the MFMA kernel (needs the full 256-column layout and a 16-byte aligned y), else 8-row tiles.
 int pass_rows(int D, const float* y) { return (D == GCOLS && (((uintptr_t)y) & 15) == 0) ? MT_ROWS : ROWS; }
 
-// Fill the resident wave slots (two waves per SIMD), then balance: every wave runs the same number of tiles.
-PassGrid pass_grid(const bsc_ctx* ctx, int64_t B, int rows) {
-    const int64_t n_tiles = (B + rows - 1) / rows;
-    const int64_t max_waves = (int64_t)2 * 4 * ctx->cu_count;
-    PassGrid g;
-    if (n_tiles <= 0) {
-        g.n_blocks = 1;
-        g.n_iter = 0;
-        return g;
-    }
-    const int64_t n_iter = (n_tiles + max_waves - 1) / max_waves;
-    const int64_t waves = (n_tiles + n_iter - 1) / n_iter;
-    g.n_blocks = (int)((waves + PASS_WAVES - 1) / PASS_WAVES);
-    g.n_iter = (int)n_iter;
-    return g;
-}
-
-// check_pass_args's envelope (csrc/bsc_blr.hip), every message naming the quantity
+// the link, then the envelope of every regression pass
 int check_glm_args(const char* who, int32_t link, const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
                    const float* W, int32_t S, int max_s) {
     BSC_REQUIRE(link == BSC_GLM_LOGISTIC || link == BSC_GLM_POISSON,
                 "%s: link=%d must be BSC_GLM_LOGISTIC (0) or BSC_GLM_POISSON (1)", who, link);
-    BSC_REQUIRE(B >= 0, "%s: B=%lld", who, (long long)B);
-    BSC_REQUIRE(((X && y) || B == 0) && W, "%s: null pointer", who);
-    BSC_REQUIRE(D > 0 && D <= GCOLS && D % 4 == 0, "%s: D=%d must be a multiple of 4 in [4,%d]", who, D, GCOLS);
-    BSC_REQUIRE(S >= 1 && S <= max_s, "%s: S=%d must be in [1,%d]", who, S, max_s);
-    BSC_REQUIRE(ldx >= D && ldx % 4 == 0 && ldx < ((int64_t)1 << 26),
-                "%s: ldx=%lld must be >= D, %% 4 == 0 and < 2^26", who, (long long)ldx);
-    BSC_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: X and W must be 16-byte aligned", who);
-    return BSC_OK;
+    BSC_REQUIRE(y || B <= 0, "%s: null pointer", who);
+    return check_regress_args(who, X, ldx, B, D, W, S, max_s);
 }
 
 template <int LINK>
@@ -749,16 +593,13 @@ int update_impl(bsc_ctx* ctx, const char* who, const double* stats, const double
         const int rc = bsc_blr_noise(ctx, D, S, seed, next_step, 1, eps_next);
         if (rc != BSC_OK) return rc;
     }
-    const double log_2pi = 1.8378770664093454835606594728112;
     a.lam_in = lam_in; a.lam_out = lam_out; a.m1 = m1; a.m2 = m2;
     a.eps = eps; a.W = W; a.eps_next = eps_next; a.W_next = W_next;
     a.elbo = elbo; a.grad = grad;
     a.D = D; a.S = S;
     a.scale = scale; a.tau = tau;
-    a.c0 = 0.5 * (double)D * (log(tau) - log_2pi) + 0.5 * (double)D * (1.0 + log_2pi);
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps;
-    a.corr1 = 1.0 - pow(beta1, (double)t);
-    a.corr2 = 1.0 - pow(beta2, (double)t);
+    a.c0 = 0.5 * (double)D * (log(tau) - BSC_LOG_2PI) + 0.5 * (double)D * (1.0 + BSC_LOG_2PI);
+    a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
     {
         bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish kernel, timed apart from the pass
         hipLaunchKernelGGL(glm_update_kernel, dim3((D + 7) / 8 + 1), dim3(FIN_BLOCK), 0, ctx->stream, a);

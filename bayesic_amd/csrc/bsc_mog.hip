@@ -626,7 +626,6 @@ __global__ __launch_bounds__(1024) void mog_expected_params_kernel(const double*
     __shared__ double alpha_sum;
     __shared__ double comp_bound[1024], comp_A[1024];
     const int dl = threadIdx.x & 15;
-    const double LOG_2PI = 1.8378770664093454835606594728112;
     const bool with_bound = eta0 != nullptr;
     if (threadIdx.x < 64) {   // one wave: the Dirichlet's total, fixed order
         double a = 0.0;
@@ -669,10 +668,10 @@ __global__ __launch_bounds__(1024) void mog_expected_params_kernel(const double*
             if (dl == 1 && d0 == 0) lg_sum = r_al.lg;
             const double elog_tau = r_a.psi - log_b;
             if (cell) {
-                c += 0.5 * elog_tau - 0.5 * LOG_2PI - 0.5 * T * m * m - 0.5 / kappa;
+                c += 0.5 * elog_tau - 0.5 * BSC_LOG_2PI - 0.5 * T * m * m - 0.5 / kappa;
                 Wmat[(int64_t)k * 2 * D + d] = (float)(T * m);
                 Wmat[(int64_t)k * 2 * D + D + d] = (float)(-0.5 * T);
-                ga += r_a.lg - a * log_b - 0.5 * log_k + 0.5 * LOG_2PI;
+                ga += r_a.lg - a * log_b - 0.5 * log_k + 0.5 * BSC_LOG_2PI;
                 if (with_bound) {
                     const double p1 = eta0[K + i], kappa0 = eta0[K + KD + i], p3 = eta0[K + 2 * KD + i],
                                  p4 = eta0[K + 3 * KD + i];

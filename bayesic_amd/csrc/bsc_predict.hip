@@ -24,7 +24,7 @@
 // Rows past the end read as zeros through the buffer descriptors and are not stored.
 // lpd_sum: float64 lane sums in tile order -> wave -> block partial in wave order -> one fixed-order finish.  No
 // float atomics: bitwise reproducible.
-#include "bsc_common.h"
+#include "bsc_regress.h"
 
 namespace {
 
@@ -95,7 +95,7 @@ __device__ __forceinline__ void predict_link(float l, float yv, float lv, float 
         const float r = yv - l;
         mu = l;
         v = ev;
-        lp = fmaf(-0.5f * iv * r, r, -0.5f * (lv + 1.8378770664093453f));
+        lp = fmaf(-0.5f * iv * r, r, -0.5f * (lv + (float)BSC_LOG_2PI));
     } else if (FAM == BSC_PREDICT_LOGISTIC) {
         const float e = expf(-fabsf(l));
         const float t = 1.0f + e;
@@ -109,18 +109,6 @@ __device__ __forceinline__ void predict_link(float l, float yv, float lv, float 
         v = mu;
         lp = fmaf(yv, l, -mu);
     }
-}
-
-__device__ __forceinline__ float fold4_sum(float v) {   // over the four lanes of a row (lane bits 4, 5)
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    return v;
-}
-
-__device__ __forceinline__ float fold4_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16));
-    v = fmaxf(v, __shfl_xor(v, 32));
-    return v;
 }
 
 // FULL: D == 256 (two strips, 32 columns per lane group, everything unrolled).
@@ -302,13 +290,10 @@ __global__ __launch_bounds__(P_BLOCK, 2) void predict_kernel(PredictArgs a) {
     }
 }
 
-// lpd_sum = the block partials in block order: lane k takes blocks k, k + 64, ..., then one butterfly.
+// lpd_sum = the block partials in block order
 __global__ __launch_bounds__(BSC_WAVE) void predict_sum_kernel(const double* __restrict__ partial, int n,
                                                                double* __restrict__ out) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < n; b += BSC_WAVE) s += partial[b];
-    s = wave_allsum_f64(s);
-    if (threadIdx.x == 0) out[0] = s;
+    block_partial_sum(partial, n, out);
 }
 
 template <int FAM, int NC>

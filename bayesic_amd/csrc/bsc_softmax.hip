@@ -29,7 +29,7 @@
 // class probabilities and the running log-mean-exp of its (row, slot) pairs, the four slots of a row are folded by two
 // butterflies, lanes 0 .. 15 store one row each.  lpd_sum: float64 lane sums -> wave -> block partial -> one
 // fixed-order finish.
-#include "bsc_common.h"
+#include "bsc_regress.h"
 
 namespace {
 
@@ -37,9 +37,6 @@ constexpr int NCOL = 16;                      // (draw, class) columns per launc
 constexpr int MAX_K = 16;
 constexpr int MAX_S = 64;
 constexpr int MAX_G = 8;                      // draws per launch at K = 2
-constexpr int PASS_BLOCK = 256;
-constexpr int PASS_WAVES = PASS_BLOCK / BSC_WAVE;
-constexpr int GCOLS = 256;                    // column capacity of the lane layout
 constexpr int T_ROWS = 16;                    // rows per tile
 constexpr int T_RS = GCOLS + 4;               // LDS row stride of the tile (floats)
 constexpr int LG_RS = NCOL + 1;               // logits lg[row][c]: odd stride, the K-loop of 64 lanes spreads over banks
@@ -259,9 +256,6 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void softmax_pass_kernel(
 
 // ---- float64 reduction of the slab: one output per lane, the 16 waves of a block split the slab rows and combine
 //      through LDS in wave order ------------------------------------------------------------------------------------
-constexpr int RED_BLOCK = 1024;
-constexpr int RED_WAVES = RED_BLOCK / BSC_WAVE;
-
 __global__ __launch_bounds__(RED_BLOCK) void softmax_slab_reduce_kernel(const float* __restrict__ slab, int n_blocks,
                                                                         int D, int K, int s0, int sg,
                                                                         double* __restrict__ ell,
@@ -303,12 +297,6 @@ struct PredictArgs {
     int n_iter;              // tiles per wave
     int do_lp;               // y is set and lpd or lpd_sum is wanted
 };
-
-__device__ __forceinline__ float fold4_sum(float v) {   // over the four slots of a row (lane bits 4, 5)
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    return v;
-}
 
 __global__ __launch_bounds__(PASS_BLOCK, 2) void softmax_predict_kernel(PredictArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[PASS_WAVES * P_WAVE_LDS];
@@ -412,50 +400,22 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void softmax_predict_kernel(PredictA
     }
 }
 
-// lpd_sum = the block partials in block order: lane k takes blocks k, k + 64, ..., then one butterfly.
+// lpd_sum = the block partials in block order
 __global__ __launch_bounds__(BSC_WAVE) void softmax_predict_sum_kernel(const double* __restrict__ partial, int n,
                                                                        double* __restrict__ out) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < n; b += BSC_WAVE) s += partial[b];
-    s = wave_allsum_f64(s);
-    if (threadIdx.x == 0) out[0] = s;
+    block_partial_sum(partial, n, out);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
-struct PassGrid {
-    int n_blocks;
-    int n_iter;
-};
-
-// Fill the resident wave slots (two waves per SIMD), then balance: every wave runs the same number of tiles.
-PassGrid pass_grid(const bsc_ctx* ctx, int64_t B) {
-    const int64_t n_tiles = (B + T_ROWS - 1) / T_ROWS;
-    const int64_t max_waves = (int64_t)2 * 4 * ctx->cu_count;
-    PassGrid g;
-    if (n_tiles <= 0) {
-        g.n_blocks = 1;
-        g.n_iter = 0;
-        return g;
-    }
-    const int64_t n_iter = (n_tiles + max_waves - 1) / max_waves;
-    const int64_t waves = (n_tiles + n_iter - 1) / n_iter;
-    g.n_blocks = (int)((waves + PASS_WAVES - 1) / PASS_WAVES);
-    g.n_iter = (int)n_iter;
-    return g;
-}
-
-// bsc_glm_data_pass's envelope plus 2 <= K <= 16, every message naming the quantity
+// the envelope of every regression pass, with 2 <= K <= 16 where it has always been checked
 int check_softmax_args(const char* who, const float* X, int64_t ldx, int64_t B, int32_t D, int32_t K, const float* W,
                        int32_t S) {
-    BSC_REQUIRE(B >= 0, "%s: B=%lld", who, (long long)B);
-    BSC_REQUIRE((X || B == 0) && W, "%s: null pointer", who);
+    int rc = check_regress_batch(who, X, B, W);
+    if (rc != BSC_OK) return rc;
     BSC_REQUIRE(K >= 2 && K <= MAX_K, "%s: K=%d must be in [2,%d]", who, K, MAX_K);
-    BSC_REQUIRE(D > 0 && D <= GCOLS && D % 4 == 0, "%s: D=%d must be a multiple of 4 in [4,%d]", who, D, GCOLS);
-    BSC_REQUIRE(S >= 1 && S <= MAX_S, "%s: S=%d must be in [1,%d]", who, S, MAX_S);
-    BSC_REQUIRE(ldx >= D && ldx % 4 == 0 && ldx < ((int64_t)1 << 26),
-                "%s: ldx=%lld must be >= D, %% 4 == 0 and < 2^26", who, (long long)ldx);
-    BSC_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: X and W must be 16-byte aligned", who);
+    rc = check_regress_shape(who, X, ldx, D, W, S, MAX_S);
+    if (rc != BSC_OK) return rc;
     BSC_REQUIRE((B + T_ROWS - 1) / T_ROWS < ((int64_t)1 << 40), "%s: B=%lld is too large", who, (long long)B);
     return BSC_OK;
 }
@@ -472,7 +432,7 @@ int bsc_softmax_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const int32
     if (rc != BSC_OK) return rc;
     BSC_REQUIRE(y || B == 0, "%s: y is null", who);
     BSC_REQUIRE(ell && G, "%s: null output (ell, G)", who);
-    const PassGrid g = pass_grid(ctx, B);
+    const PassGrid g = pass_grid(ctx, B, T_ROWS);
     void* ws = nullptr;
     rc = bsc_workspace(ctx, (size_t)g.n_blocks * SLAB_STRIDE * sizeof(float), &ws);
     if (rc != BSC_OK) return rc;
@@ -507,7 +467,7 @@ int bsc_softmax_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const in
         if (lpd_sum) BSC_HIP(hipMemsetAsync(lpd_sum, 0, sizeof(double), ctx->stream));
         return BSC_OK;
     }
-    const PassGrid g = pass_grid(ctx, B);
+    const PassGrid g = pass_grid(ctx, B, T_ROWS);
     PredictArgs a;
     a.X = X; a.ldx = ldx; a.y = y; a.B = B; a.W = W;
     a.prob = prob; a.lpd = lpd; a.partial = nullptr;

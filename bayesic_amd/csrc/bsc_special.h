@@ -25,6 +25,7 @@
 
 constexpr double BSC_PI = 3.14159265358979323846264338327950288;
 constexpr double BSC_LOG_PI = 1.14472988584940017414342735135305871;
+constexpr double BSC_LOG_2PI = 1.8378770664093454835606594728112;
 
 // digamma: recurrence up to x >= 8, then the asymptotic series
 //   ln x - 1/2x - 1/12x^2 + 1/120x^4 - 1/252x^6 + 1/240x^8 - 5/660x^10 + 691/32760x^12 - 1/12x^14

@@ -44,15 +44,14 @@ import math
 import torch
 
 from ..device import default_context
+from ._reparam_base import ReparamDriver, default_lam0, unpack_full
 from .exchange import Exchange
 
 # include/bayesic_hip.h: BSC_SWEEP_*
 SWEEP_STREAM, SWEEP_FORWARD_KEEP, SWEEP_BACKWARD_KEEP = 0, 1, 2
 
 
-class BLRReparamSVI:
-    NOISE_BLOCK = 32
-
+class BLRReparamSVI(ReparamDriver):
     VIRTUAL_SHARDS = 8
 
     def __init__(self, X, y, n_total=None, n_samples=8, seed=1234, lr=1e-2, alpha0=1.0,
@@ -70,16 +69,7 @@ class BLRReparamSVI:
         self.covariance_kind = covariance
         self.ctx = ctx or default_context()
         dev = self.ctx.device
-        self.X = X if isinstance(X, torch.Tensor) else self.ctx.to_device(X, torch.float32)
-        self.y = y if isinstance(y, torch.Tensor) else self.ctx.to_device(y, torch.float32)
-        if self.X.dtype != torch.float32 or self.y.dtype != torch.float32:
-            raise TypeError("X and y must be float32")
-        if self.X.dim() != 2 or self.y.dim() != 1 or self.X.shape[0] != self.y.shape[0]:
-            raise ValueError("X must be [B, D] and y [B]")
-        if self.X.stride(1) != 1:
-            raise ValueError("X must be row-major (unit stride along columns)")
-        self.B, self.D = self.X.shape
-        self._Xarg, self._yarg, self._ldx = self.X, self.y, self.X.stride(0)
+        self._float_batch(X, y)
         self.S = int(n_samples)
         self.seed = int(seed)
         self.lr = float(lr)
@@ -128,8 +118,7 @@ class BLRReparamSVI:
         self._lam = torch.zeros((2, n_lam), dtype=f64, device=dev)
         if lam0 is None:
             if covariance == "full":
-                diag = torch.arange(P, device=dev)
-                self._lam[0, P + diag * (diag + 1) // 2 + diag] = math.log(0.1)
+                self._lam[0].copy_(torch.as_tensor(default_lam0(P, "full"), dtype=f64))
             else:
                 self._lam[0, D:2 * D] = math.log(0.1)
                 self._lam[0, 2 * D + 1] = math.log(0.1)
@@ -138,10 +127,8 @@ class BLRReparamSVI:
             if covariance == "full" and lam0.numel() != n_lam:
                 raise ValueError("lam0 has %d entries; covariance='full' at D = %d needs %d" % (lam0.numel(), D, n_lam))
             self._lam[0].copy_(lam0)
-        # noise ring: NOISE_BLOCK steps are drawn per launch, two blocks resident
-        self._ring = 2 * self.NOISE_BLOCK
-        self._eps = torch.zeros((self._ring, S * (D + 1)), dtype=f64, device=dev)
-        self._noise_upto = 0   # noise of Philox steps [0, _noise_upto) has been requested
+        self._noise_dim, self._guide_dim = D, D + 1
+        self._alloc_noise(dev)
         self._W = torch.zeros((2, S * D), dtype=torch.float32, device=dev)
         self._xi = torch.zeros((2, S), dtype=f64, device=dev)
         self.m1 = torch.zeros(n_lam, dtype=f64, device=dev)
@@ -159,24 +146,8 @@ class BLRReparamSVI:
         self.ctx.reserve((4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 8) * 4)
 
     def set_batch(self, X, y, rows=None, ldx=None):
-        """Point the next update at another device-resident mini-batch of the same width:
-        torch tensors, or raw device pointers with `rows` (and `ldx`, default D) -- what
-        MiniBatchLoader.acquire() returns.  The mini-batch scaling n_total / batch_rows
-        keeps the batch size the model was built with."""
-        if isinstance(X, torch.Tensor):
-            if X.dtype != torch.float32 or y.dtype != torch.float32 or X.dim() != 2 or \
-                    X.shape[1] != self.D or X.stride(1) != 1 or y.shape[0] != X.shape[0]:
-                raise ValueError("batch must be float32 X [rows, %d] row-major and y [rows]" % self.D)
-            self.X, self.y = X, y
-            self._Xarg, self._yarg, self._ldx, self.B = X, y, X.stride(0), X.shape[0]
-            self._fresh_batch = True
-        else:
-            if rows is None:
-                raise ValueError("raw device pointers need `rows`")
-            self.X = self.y = None
-            self._Xarg, self._yarg = int(X), int(y)
-            self._ldx, self.B = int(ldx if ldx is not None else self.D), int(rows)
-            self._fresh_batch = True
+        super().set_batch(X, y, rows, ldx)
+        self._fresh_batch = True
 
     def _take_sweep(self):
         """Sweep order of the pass about to be issued (and book-keeping for the one after)."""
@@ -209,33 +180,7 @@ class BLRReparamSVI:
                 self._pass_count = (key, (self.S + 7) // 8)
         return self._pass_count[1]
 
-    # -- current views ---------------------------------------------------------
-    @property
-    def cur(self):
-        return self.t & 1
-
-    @property
-    def lam(self):
-        return self._lam[self.cur]
-
-    @property
-    def W(self):
-        return self._W[self.cur]
-
-    @property
-    def eps(self):
-        return self._eps[self.t % self._ring]
-
-    def _ensure_noise(self, step):
-        """Noise of Philox step `step` is in ring row step % ring (drawn a block ahead)."""
-        nb = self.NOISE_BLOCK
-        while self._noise_upto <= step:
-            start = self._noise_upto
-            r0 = start % self._ring
-            self.ctx.call("bsc_blr_noise", self.D, self.S, self.seed, start, nb,
-                          self._eps[r0:r0 + nb])
-            self._noise_upto = start + nb
-
+    # -- current views (cur, lam, W, eps: ReparamDriver) ----------------------------
     @property
     def xi(self):
         return self._xi[self.cur]
@@ -257,22 +202,11 @@ class BLRReparamSVI:
         c, D, S = self.cur, self.D, self.S
         self._ensure_noise(step)
         eps = self._eps[step % self._ring].cpu().numpy().reshape(S, D + 1)
-        m, L = self._unpack_full(self._lam[c].cpu().numpy())
+        m, L = unpack_full(self._lam[c].cpu().numpy(), D + 1)
         z = m[None, :] + eps @ L.T
         self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :D], np.float32).reshape(-1)))
         self._xi[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, D])))
         self._drawn = True
-
-    def _unpack_full(self, lam):
-        """[mu | packed L] -> (mu [P], dense L [P, P]) with L_ii = e^{rho_i}."""
-        import numpy as np
-        P = self.D + 1
-        rows, cols = np.tril_indices(P)            # row-major lower triangle: the packed order
-        L = np.zeros((P, P))
-        L[rows, cols] = lam[P:]
-        d = np.arange(P)
-        L[d, d] = np.exp(L[d, d])
-        return np.array(lam[:P], np.float64), L
 
     def data_pass(self):
         if self.reproducible:
@@ -394,7 +328,7 @@ class BLRReparamSVI:
         lam = self.lam.cpu().numpy()
         D = self.D
         if self.covariance_kind == "full":
-            m, L = self._unpack_full(lam)
+            m, L = unpack_full(lam, D + 1)
             return dict(m=m, L=L)
         return dict(m=lam[:D], rho=lam[D:2 * D], a=lam[2 * D], b=lam[2 * D + 1])
 
@@ -403,7 +337,7 @@ class BLRReparamSVI:
         e^{2 rho}, e^{2 b} of the mean-field one."""
         import numpy as np
         if self.covariance_kind == "full":
-            _, L = self._unpack_full(self.lam.cpu().numpy())
+            _, L = unpack_full(self.lam.cpu().numpy(), self.D + 1)
             return L @ L.T
         p = self.params()
         return np.diag(np.exp(2.0 * np.concatenate([p["rho"], [p["b"]]])))

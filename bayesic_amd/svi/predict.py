@@ -21,6 +21,8 @@ xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pa
 import numpy as np
 import torch
 
+from ._reparam_base import unpack_full
+
 # include/bayesic_hip.h: BSC_PREDICT_*
 FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
 PREDICT_STREAM = 2     # Philox stream of the predictive draws
@@ -70,12 +72,12 @@ def posterior_draws(model, n_samples=64, seed=None):
     lam = model.lam.cpu().numpy()
     logvar = None
     if family != "gaussian" and getattr(model, "covariance_kind", "diag") == "full":
-        mu, L = model._unpack_full(lam)
+        mu, L = unpack_full(lam, P)
         W = mu[None, :] + eps @ L.T
     elif family != "gaussian":
         W = lam[None, :D] + np.exp(lam[D:2 * D])[None, :] * eps
     elif model.covariance_kind == "full":
-        mu, L = model._unpack_full(lam)
+        mu, L = unpack_full(lam, P)
         z = mu[None, :] + eps @ L.T
         W, logvar = z[:, :D], z[:, D]
     else:

@@ -28,13 +28,11 @@ Data parallelism is wired as in svi/glm.py: each rank holds a block of mini-batc
 update is an all-reduce(sum) of the float64 stats vector between the pass and the finish.  That branch has been
 exercised at world size 1 only.
 """
-import math
-
 import numpy as np
 import torch
 
 from ..device import default_context
-from .exchange import Exchange
+from ._reparam_base import ReparamRegressionBase, full_size
 
 MAX_CLASSES = 16          # csrc/bsc_softmax.hip: the sixteen (draw, class) columns of one launch
 FULL_MAX_PARAMS = 256     # bsc_glm_fullrank_update's envelope
@@ -59,8 +57,7 @@ def _check_labels(y, K, what="y"):
         raise ValueError("%s has labels in [%d, %d]; n_classes = %d needs them in [0, %d)" % (what, lo, hi, K, K))
 
 
-class SoftmaxReparamSVI:
-    NOISE_BLOCK = 32
+class SoftmaxReparamSVI(ReparamRegressionBase):
     link = None               # svi/predict.py: not a GLM link
 
     def __init__(self, X, y, n_classes, n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0,
@@ -87,8 +84,11 @@ class SoftmaxReparamSVI:
         if covariance == "full" and (P > FULL_MAX_PARAMS or P % 4 != 0):
             raise ValueError("covariance='full' needs n_classes * D <= %d and a multiple of 4 "
                              "(bsc_glm_fullrank_update); got %d * %d = %d" % (FULL_MAX_PARAMS, K, D, P))
+        n_lam = full_size(P) if covariance == "full" else 2 * P
+        if lam0 is not None and torch.as_tensor(lam0).numel() != n_lam:
+            raise ValueError("lam0 has %d entries; covariance=%r at K * D = %d needs %d"
+                             % (torch.as_tensor(lam0).numel(), covariance, P, n_lam))
         self.ctx = ctx or default_context()
-        dev = self.ctx.device
         self.X = X if isinstance(X, torch.Tensor) else self.ctx.to_device(X, torch.float32)
         self.y = y if isinstance(y, torch.Tensor) else self.ctx.to_device(y, torch.int32)
         if self.X.dtype != torch.float32:
@@ -97,50 +97,11 @@ class SoftmaxReparamSVI:
             raise ValueError("X must be row-major (unit stride along columns)")
         if self.y.numel() > 1 and self.y.stride(0) != 1:
             raise ValueError("y must be contiguous")
-        self.B, self.D, self.P = int(self.X.shape[0]), D, P
+        self.B, self.D = int(self.X.shape[0]), D
         self._Xarg, self._yarg, self._ldx = self.X, self.y, self.X.stride(0)
-        self.S = int(n_samples)
-        self.seed = int(seed)
-        self.lr = float(lr)
-        self.group = group
-        self.exchange = Exchange(self.ctx, group)   # RCCL behind the C ABI when ctx has a communicator
-        self.world = self.exchange.world
-        # global mini-batch rows (all ranks); ranks may hold unequal blocks
-        self.batch_rows = self.exchange.global_count(self.B, dev)
-        self.n_total = float(n_total) if n_total is not None else self.batch_rows
-        S = self.S
-        f64 = torch.float64
-        # double-buffered state: index t & 1 is current at the start of step t + 1
-        n_lam = P + P * (P + 1) // 2 if covariance == "full" else 2 * P
-        self._lam = torch.zeros((2, n_lam), dtype=f64, device=dev)
-        if lam0 is None:
-            if covariance == "full":
-                diag = torch.arange(P, device=dev)
-                self._lam[0, P + diag * (diag + 1) // 2 + diag] = math.log(0.1)
-            else:
-                self._lam[0, P:] = math.log(0.1)
-        else:
-            lam0 = torch.as_tensor(lam0, dtype=f64)
-            if lam0.numel() != n_lam:
-                raise ValueError("lam0 has %d entries; covariance=%r at K * D = %d needs %d"
-                                 % (lam0.numel(), covariance, P, n_lam))
-            self._lam[0].copy_(lam0)
-        # noise ring: NOISE_BLOCK steps are drawn per launch, two blocks resident
-        self._ring = 2 * self.NOISE_BLOCK
-        self._eps = torch.zeros((self._ring, S * (P + 1)), dtype=f64, device=dev)
-        self._noise_upto = 0   # noise of Philox steps [0, _noise_upto) has been requested
-        self._W = torch.zeros((2, S * P), dtype=torch.float32, device=dev)
-        self.m1 = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.m2 = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.grad = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.elbo = torch.zeros(1, dtype=f64, device=dev)
-        self.stats = torch.zeros(S * (P + 1), dtype=f64, device=dev)  # [ell | G]
-        self.ell = self.stats[:S]
-        self.G = self.stats[S:]
-        self.t = 0
-        self._drawn = False
-        # size the slab once so step() never allocates: two workgroups per CU at most
-        self.ctx.reserve((2 * self.ctx.info()["cu_count"] + 8) * SLAB_FLOATS * 4)
+        # the slab is sized for two workgroups per CU at most
+        self._init_state(P, n_total, n_samples, seed, lr, group, lam0,
+                         slab_bytes=(2 * self.ctx.info()["cu_count"] + 8) * SLAB_FLOATS * 4)
 
     def set_batch(self, X, y, rows=None, ldx=None):
         """Point the next update at another device-resident mini-batch of the same width: torch tensors (the labels
@@ -157,85 +118,11 @@ class SoftmaxReparamSVI:
             self.X, self.y = X, y
             self._Xarg, self._yarg, self._ldx, self.B = X, y, X.stride(0), X.shape[0]
         else:
-            if rows is None:
-                raise ValueError("raw device pointers need `rows`")
-            self.X = self.y = None
-            self._Xarg, self._yarg = int(X), int(y)
-            self._ldx, self.B = int(ldx if ldx is not None else self.D), int(rows)
-
-    # -- current views ---------------------------------------------------------
-    @property
-    def cur(self):
-        return self.t & 1
-
-    @property
-    def lam(self):
-        return self._lam[self.cur]
-
-    @property
-    def W(self):
-        return self._W[self.cur]
-
-    @property
-    def eps(self):
-        return self._eps[self.t % self._ring]
-
-    @property
-    def scale(self):
-        return self.n_total / self.batch_rows
-
-    def _ensure_noise(self, step):
-        """Noise of Philox step `step` is in ring row step % ring (drawn a block ahead)."""
-        nb = self.NOISE_BLOCK
-        while self._noise_upto <= step:
-            start = self._noise_upto
-            r0 = start % self._ring
-            self.ctx.call("bsc_blr_noise", self.P, self.S, self.seed, start, nb, self._eps[r0:r0 + nb])
-            self._noise_upto = start + nb
-
-    # -- phases ------------------------------------------------------------------
-    def sample(self, step):
-        """The first draw w_s = m + e^rho eps_s (every later one comes out of the finish): once per model, in
-        float64 on the host from bsc_blr_noise's draws, rounded to float32 as the finish rounds."""
-        c, P, S = self.cur, self.P, self.S
-        self._ensure_noise(step)
-        eps = self._eps[step % self._ring].cpu().numpy().reshape(S, P + 1)[:, :P]
-        lam = self._lam[c].cpu().numpy()
-        if self.covariance_kind == "full":      # w_s = mu + L eps_s
-            mu, L = self._unpack_full(lam)
-            W = (mu[None, :] + eps @ L.T).astype(np.float32)
-        else:
-            W = (lam[None, :P] + np.exp(lam[None, P:]) * eps).astype(np.float32)
-        self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(W).reshape(-1)))
-        self._drawn = True
-
-    def _unpack_full(self, lam):
-        """[mu | packed L] -> (mu [K D], dense L [K D, K D]) with L_ii = e^{rho_i}."""
-        P = self.P
-        rows, cols = np.tril_indices(P)            # row-major lower triangle: the packed order
-        L = np.zeros((P, P))
-        L[rows, cols] = lam[P:]
-        d = np.arange(P)
-        L[d, d] = np.exp(L[d, d])
-        return np.array(lam[:P], np.float64), L
+            self._set_raw_batch(X, y, rows, ldx)
 
     def data_pass(self):
         self.ctx.call("bsc_softmax_data_pass", self._Xarg, self._ldx, self._yarg, self.B, self.D, self.K, self.W,
                       self.S, self.ell, self.G)
-
-    def all_reduce(self):
-        self.exchange.all_reduce(self.stats)
-
-    def _finish(self, stats):
-        """Gradient + Adam + next draw from all-reduced statistics; flips the double buffer."""
-        c, n = self.cur, 1 - self.cur
-        t = self.t + 1                 # Adam step count = Philox step of the NEXT draw
-        self._ensure_noise(t)
-        name = "bsc_glm_fullrank_update" if self.covariance_kind == "full" else "bsc_glm_update"
-        self.ctx.call(name, stats, self._lam[c], self._lam[n], self.m1, self.m2, self._eps[self.t % self._ring],
-                      self._W[c], self.P, self.S, self.scale, self.prior_precision, t, self.lr, 0.9, 0.999, 1e-8,
-                      self.seed, t, self._eps[t % self._ring], 1, self._W[n], self.elbo, self.grad)
-        self.t = t
 
     def step(self):
         """One ELBO-gradient update; asynchronous on the context stream."""
@@ -295,17 +182,6 @@ class SoftmaxReparamSVI:
     def params(self):
         """diag: m, rho, each [K, D].  full: m [K, D], the dense lower-triangular L [K D, K D] and rho = log diag L
         [K, D]."""
-        K, D, P = self.K, self.D, self.P
-        lam = self.lam.cpu().numpy()
-        if self.covariance_kind == "full":
-            m, L = self._unpack_full(lam)
-            d = np.arange(P)
-            return dict(m=m.reshape(K, D), L=L, rho=np.array(lam[P + d * (d + 1) // 2 + d]).reshape(K, D))
-        return dict(m=lam[:P].reshape(K, D), rho=lam[P:].reshape(K, D))
-
-    def covariance(self):
-        """Cov_q(vec W) (K D x K D, host float64): L L^T of the full guide, diag(e^{2 rho}) of the mean-field one."""
-        if self.covariance_kind == "full":
-            _, L = self._unpack_full(self.lam.cpu().numpy())
-            return L @ L.T
-        return np.diag(np.exp(2.0 * self.params()["rho"].reshape(-1)))
+        p = self._flat_params()
+        p["m"], p["rho"] = p["m"].reshape(self.K, self.D), p["rho"].reshape(self.K, self.D)
+        return p
