@@ -78,7 +78,6 @@ const bsc_option OPTIONS[] = {
     {"gemm_dbg", &bsc_ctx::gemm_dbg, 0, 15, nullptr, true},
     {"gemm_nt_c", &bsc_ctx::gemm_nt_c, 0, 1, nullptr, false},
     {"gemm_sym", &bsc_ctx::gemm_sym, 0, 1, nullptr, false},
-    {"gram_pp", &bsc_ctx::gram_pp, 0, 1, nullptr, false},
     {"gram_dbg", &bsc_ctx::gram_dbg, 0, 7, nullptr, true},
     {"rows_dbg", &bsc_ctx::rows_dbg, 0, 15, nullptr, true},
     {"rows_wg", &bsc_ctx::rows_wg_per_cu, 0, 64, nullptr, false},
@@ -86,8 +85,7 @@ const bsc_option OPTIONS[] = {
     {"skinny_nt_wg", &bsc_ctx::skinny_nt_wg_per_cu, 1, 2, nullptr, false},
     {"lda_stream", &bsc_ctx::lda_stream, 0, 1, nullptr, false},
     {"lda_dbg", &bsc_ctx::lda_dbg, 0, 15, nullptr, true},
-    {"bbvi_waves", &bsc_ctx::bbvi_waves, 4, 8, "4,8", false},
-    {"bbvi_kernel", &bsc_ctx::bbvi_kernel, 0, 2, nullptr, false},
+    {"bbvi_kernel", &bsc_ctx::bbvi_kernel, 1, 2, nullptr, false},
     {"bbvi_dbg", &bsc_ctx::bbvi_dbg, 0, 15, nullptr, true},
     {"csc_fast", &bsc_ctx::csc_fast, 0, 1, nullptr, false},
     {"mog_nt", &bsc_ctx::mog_nt, 0, 1, nullptr, false},

@@ -5,255 +5,45 @@
 // README.md:69-79 for mini-batching; in bayesic.algebra terms the data-sized
 // contraction is dot(W, X.T) (cfg 5).
 //
-// logreg_loglik_kernel: ONE read of X[N,D], y[N], g[N] gives, for S = 64 Monte
+// bsc_logreg_bbvi_loglik: ONE read of X[N,D], y[N], g[N] gives, for S <= 128 Monte
 // Carlo draws of (w, b) at once,
 //     l_ns  = x_n . Wz[s] + Bz[g_n, s]
 //     ell_s = sum_n ( y_n l_ns - softplus(l_ns) )
-// 32 flop/B: close to the HBM/FP32 ridge, so the contraction runs on
-// v_mfma_f32_16x16x4_f32 (exact f32) and everything else is cheap.  A workgroup
-// (4 waves) owns 32-row tiles staged in LDS by coalesced 1-KiB row loads; wave w
-// owns samples 16w..16w+15 and keeps its slice of Wz in 64 registers as the MFMA
-// B operand for the whole kernel.  The k order inside a contraction is free, so
-// k-step s of lane group k reads column 16(s/4) + 4k + (s%4): one ds_read_b128
-// feeds four MFMAs.  LDS row stride 264 floats makes those reads conflict-free.
-#include "bsc_common.h"
-#include "bsc_bf16split.h"
-
-namespace {
-
-constexpr int LS = 64;            // samples
-constexpr int LD = 256;           // column capacity
-constexpr int LT = 32;            // rows per tile
-constexpr int LSTR = LD + 4;      // LDS row stride (floats): row r starts on bank 4 r, so 16 rows x 16 B cover the 64 banks once
-constexpr int LR_BLOCK = 256;
-constexpr int TILE_FLOATS = LT * LSTR + LT;   // rows + y
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int RW>
-struct Stage {   // one wave's share of a tile in registers: RW rows x 16 B per lane
-    float4 x[RW];
-    float yv;
-};
-
-template <bool FULL, int RW>
-__device__ __forceinline__ void stage_load(Stage<RW>& st, const float* __restrict__ X, int64_t ldx,
-                                           const float* __restrict__ y, const int* __restrict__ g,
-                                           int64_t row0, int64_t N, int D, int wave, int lane) {
-    const int64_t rem = N - row0;
-    uint64_t xb = 0, yb = 0;
-    if (rem > 0) {
-        xb = ((uint64_t)(rem - 1) * (uint64_t)ldx + (uint64_t)D) * 4u;
-        yb = (uint64_t)rem * 4u;
-    }
-    const unsigned xrec = xb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)xb;
-    const unsigned yrec = yb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)yb;
-    const int64_t safe0 = rem > 0 ? row0 : 0;
-    auto xs = __builtin_amdgcn_make_buffer_rsrc((void*)(X + safe0 * ldx), 0, xrec, 0x00020000);
-    auto ys = __builtin_amdgcn_make_buffer_rsrc((void*)(y + safe0), 0, yrec, 0x00020000);
-    const int row_bytes = (int)(ldx * 4);
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        auto v = __builtin_amdgcn_raw_buffer_load_b128(xs, 16 * lane, (RW * wave + r) * row_bytes, 2);  // nt
-        float4 f = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
-                               __uint_as_float(v[3]));
-        if (!FULL && 4 * lane >= D) f = make_float4(0.f, 0.f, 0.f, 0.f);
-        st.x[r] = f;
-    }
-    // wave 0 also brings the tile's y
-    st.yv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ys, 4 * (lane & 31), 0, 0));
-}
-
-// Byte offsets (group id * 256) into Bz of the rows whose logits this lane ends up holding
-// (MFMA result rows 16 (rb0 + rb) + 4 kq + r).  No clamping: the gather below is a buffer
-// load, so an id outside [0, n_groups) reads an intercept of 0 instead of faulting, and rows
-// past N read id 0 (their result is masked).
-template <int RB>
-__device__ __forceinline__ void load_groups(int (&gi)[4 * RB], const int* __restrict__ g, int64_t row0,
-                                            int64_t N, int kq, int rb0) {
-    const int64_t rem = N - row0;
-    const uint64_t gb = rem > 0 ? (uint64_t)rem * 4u : 0;
-    const unsigned grec = gb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)gb;
-    auto gs = __builtin_amdgcn_make_buffer_rsrc((void*)(g + (rem > 0 ? row0 : 0)), 0, grec, 0x00020000);
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        auto v = __builtin_amdgcn_raw_buffer_load_b128(gs, 4 * (16 * (rb0 + rb) + 4 * kq), 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) gi[4 * rb + r] = (int)v[r] * (LS * 4);
-    }
-}
-
-template <int RW>
-__device__ __forceinline__ void stage_store(const Stage<RW>& st, float* tile, int wave, int lane) {
-#pragma unroll
-    for (int r = 0; r < RW; ++r)
-        *reinterpret_cast<float4*>(tile + (RW * wave + r) * LSTR + 4 * lane) = st.x[r];
-    if (wave == 0 && lane < 32) tile[LT * LSTR + lane] = st.yv;
-}
-
-// NW = 4: a wave owns 16 samples for both 16-row blocks of the tile (two accumulators).
-// NW = 8: a wave owns 16 samples for ONE row block -- twice the waves per SIMD to cover the
-// softplus epilogue, the LDS stores and the barrier of the others.
-template <bool FULL, int NW>   // FULL: D == 256, no column masking
-__global__ __launch_bounds__(64 * NW, 2) void logreg_loglik_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y,
-    const int* __restrict__ g, int64_t N, int D, const float* __restrict__ Wz,
-    const float* __restrict__ Bz, int n_groups, float* __restrict__ slab, int n_iter) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * TILE_FLOATS];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i16 = lane & 15, kq = lane >> 4;
-    constexpr int RB = 8 / NW;          // row blocks per wave
-    constexpr int RW = LT / NW;         // rows a wave stages per tile
-    const int sb = wave & 3;            // sample block
-    const int rb0 = NW == 8 ? (wave >> 2) : 0;
-
-    // B operand: Wz[sample 16*sb + i16][column of (k-step s, lane group kq)]
-    float wreg[LD / 4];
-#pragma unroll
-    for (int s = 0; s < LD / 4; ++s) {
-        // lane group kq contracts columns [64 kq, 64 kq + 64): the four 16-byte A reads of a
-        // row then sit 256 B apart, on the same banks, and every ds_read_b128 lane group
-        // (each holds all 16 rows once, with two different kq) is conflict-free; with the
-        // columns interleaved (4 kq + 16 q) each lane group had one 2-way conflict
-        const int col = 64 * kq + s;
-        wreg[s] = col < D ? Wz[(int64_t)(16 * sb + i16) * D + col] : 0.f;
-    }
-    double acc_ll = 0.0;   // per-tile float32 sums enter a float64 accumulator: no drift over the 60 tiles
-
-    int64_t tile = blockIdx.x;
-    const int64_t stride = gridDim.x;
-    Stage<RW> st;
-    stage_load<FULL>(st, X, ldx, y, g, tile * LT, N, D, wave, lane);
-    stage_store(st, lds, wave, lane);
-    // The intercept b[g_n, s] is a gather that depends on the row's group id: requested
-    // when it is needed it costs a full memory round trip per tile with the MFMA pipe idle.
-    // So group ids run two tiles ahead and intercepts one tile ahead, in registers.
-    // Bz[g, s] gathered through a buffer descriptor: 32-bit offsets, out-of-range ids read 0
-    const auto bz_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Bz, 0, (unsigned)n_groups * (LS * 4u), 0x00020000);
-    const int bz_off = 4 * (16 * sb + i16);
-    auto bz_load = [&](int goff) {
-        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bz_rsrc, goff + bz_off, 0, 0));
-    };
-    int gi[4 * RB];
-    float bz_a[4 * RB], bz_b[4 * RB];
-    load_groups<RB>(gi, g, tile * LT, N, kq, rb0);
-#pragma unroll
-    for (int e = 0; e < 4 * RB; ++e) bz_a[e] = bz_load(gi[e]);
-    load_groups<RB>(gi, g, (tile + stride) * LT, N, kq, rb0);
-    __syncthreads();
-    int cur = 0;
-    // One tile.  bz_cur holds this tile's intercepts (requested a tile ago), bz_next
-    // receives the next tile's; the caller alternates the two register sets so that no
-    // copy (which would wait for the loads straight away) is needed.
-    auto one_tile = [&](const float (&bz_cur)[4 * RB], float (&bz_next)[4 * RB]) {
-        stage_load<FULL>(st, X, ldx, y, g, (tile + stride) * LT, N, D, wave, lane);   // prefetch
-        const float* t = lds + cur * TILE_FLOATS;
-        f32x4 acc[RB];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // A operands one k-group ahead in registers: the MFMAs of group q cover the LDS
-        // latency of group q+1.  (A single dependent accumulator chain runs at the full
-        // 32-cycle rate -- tools/ubench_mfma_mix.hip -- so the row blocks need not alternate
-        // for the pipe's sake; they do because one A read then feeds four MFMAs.)
-        const float* ta = t + (16 * rb0 + i16) * LSTR + 64 * kq;
-        float4 an[RB];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) an[rb] = *reinterpret_cast<const float4*>(ta + 16 * rb * LSTR);
-        __builtin_amdgcn_sched_group_barrier(0x100, RB, 0);       // the reads of group 0
-#pragma unroll
-        for (int q = 0; q < LD / 16; ++q) {
-            float4 a[RB];
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) a[rb] = an[rb];
-            if (q + 1 < LD / 16) {
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb)
-                    an[rb] = *reinterpret_cast<const float4*>(ta + 16 * rb * LSTR + 4 * (q + 1));
-            }
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb].x, wreg[4 * q + 0], acc[rb], 0, 0, 0);
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb].y, wreg[4 * q + 1], acc[rb], 0, 0, 0);
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb].z, wreg[4 * q + 2], acc[rb], 0, 0, 0);
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb].w, wreg[4 * q + 3], acc[rb], 0, 0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, RB, 0);       // LDS reads of group q+1 ...
-            __builtin_amdgcn_sched_group_barrier(0x008, 4 * RB, 0);   // ... then the MFMAs of group q
-        }
-        // next tile's intercepts (its group ids arrived during the MFMAs), then the ids
-        // of the tile after
-#pragma unroll
-        for (int e = 0; e < 4 * RB; ++e) bz_next[e] = bz_load(gi[e]);
-        load_groups<RB>(gi, g, (tile + 2 * stride) * LT, N, kq, rb0);
-        // C/D map of 16x16x4: col = lane & 15 (sample), row = 4 * (lane >> 4) + reg
-        const int64_t row0 = tile * LT;
-        float tile_ll = 0.f;
-        // y l - softplus(l),  softplus(l) = max(l,0) + ln2 log2(1 + 2^(-|l| log2e)) on the raw
-        // v_exp_f32 / v_log_f32 (the log's argument is in (1, 2], the exponent's <= 0: no
-        // denormal handling needed, ~1e-7 ABSOLUTE error, far inside the stated tolerance).
-        // Instruction count matters here: VALU work delays the MFMAs of the other waves.
-        constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-        const bool whole = row0 + LT <= N;      // uniform: only the last tile masks rows
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * (rb0 + rb) + 4 * kq + r;
-                const float yv = t[LT * LSTR + row];
-                const float l = acc[rb][r] + bz_cur[4 * rb + r];
-                const float g2 = __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(-fabsf(l) * LOG2E));
-                float v = __builtin_fmaf(yv, l, -fmaxf(l, 0.f));
-                v = __builtin_fmaf(-LN2, g2, v);
-                if (!whole && row0 + row >= N) v = 0.f;
-                tile_ll += v;
-            }
-        acc_ll += (double)tile_ll;
-        stage_store(st, lds + (cur ^ 1) * TILE_FLOATS, wave, lane);
-        __syncthreads();
-        cur ^= 1;
-        tile += stride;
-    };
-    for (int it = 0; it < n_iter; it += 2) {   // n_iter is even (host)
-        one_tile(bz_a, bz_b);
-        one_tile(bz_b, bz_a);
-    }
-    // lanes with the same sample (lane & 15) hold different rows: fold bits 4,5
-    acc_ll += __shfl_xor(acc_ll, 16);
-    acc_ll += __shfl_xor(acc_ll, 32);
-    if (lane < 16)
-        slab[((int64_t)blockIdx.x * (NW / 4) + (wave >> 2)) * LS + 16 * sb + lane] = (float)acc_ll;
-}
-
-// ---- second generation: a wave owns rows, the draws live in LDS -----------------------------
-// The kernel above stages X tiles in LDS (a store, a workgroup barrier and an A-operand read per
-// tile) and keeps the draws in registers.  What its time is made of was measured this round:
+// 32 flop/B at S = 64: close to the HBM/FP32 ridge, so the contraction runs on
+// v_mfma_f32_16x16x4_f32 (exact f32) and everything else has to be cheap.  What the time of such
+// a pass is made of was measured:
 //   * fp32 MFMA and VALU share the SIMD's issue: every VALU instruction between MFMAs costs the
 //     matrix pipe ~4.6 cycles (profiles/r01_ubench_mfma_valu_mix.txt);
 //   * a vector load that RETURNS TO REGISTERS costs the issuing SIMD ~115 cycles of MFMA time,
 //     whatever its width (a dword gather as much as a 1-KiB dwordx4), an LDS-DMA
-//     (buffer_load ... lds) ~45 (tools/ubench_mfma_vmem.hip, profiles/r02_ubench_mfma_vmem.txt);
-//     the 32-row tile of the first kernel took 8 + 8 such loads per wave and 128 MFMAs.
-// Both kernels below give a wave 16-row tiles of X for ALL sample blocks:
+//     (buffer_load ... lds) ~45 (tools/ubench_mfma_vmem.hip, profiles/r02_ubench_mfma_vmem.txt).
+// (A first kernel staged 32-row X tiles in LDS -- a store, a workgroup barrier and an A-operand
+// read per tile, 8 + 8 register-returning loads per wave for 128 MFMAs -- and kept the draws in
+// registers; it last existed in commit d12f6c7.)
+// The kernels below give a wave 16-row tiles of X for ALL sample blocks:
 //   * the S <= 128 draws Wz (static for the whole launch) are written ONCE to LDS in exactly the
 //     order the MFMA B operand is read: block (sb, j) = 1 KiB, lane l's 16 bytes at l*16 --
 //     every ds_read_b128 is conflict-free, no padding, no per-tile stores, no barrier per tile;
 //   * lane i16 owns the NSB consecutive samples NSB i16 .. NSB i16 + NSB - 1, so the intercepts
-//     b[g_n, s] of a row are ONE 4 NSB-byte gather per lane (the first kernel: one dword gather
-//     per row and sample block), and they enter as the MFMA's C input (the C layout is the
-//     result layout): l = x.w + b costs no add;
+//     b[g_n, s] of a row are ONE 4 NSB-byte gather per lane, and they enter as the MFMA's C input
+//     (the C layout is the result layout): l = x.w + b costs no add;
 //   * epilogue on packed f32 math with two transcendentals per element:
 //       y l - softplus(l) = y l - (l + |l|)/2 - ln2 log2(1 + 2^(-|l| log2 e)),
 //     the four rows a lane holds per sample share ONE v_log_f32 (log2 of the product of their
 //     (1 + t) in (1, 16]); sums of y l, l, |l| run on v_pk_fma/add_f32;
 //   * waves never synchronise; a wave leaves the loop as soon as its tiles are done.
+// X reaches the A operand by LDS-DMA (logreg_loglik_dma_kernel, the default up to S = 64, and its
+// split-bf16 twin logreg_loglik_dma_bx_kernel) or through VGPRs (logreg_loglik_xreg_kernel: any
+// S <= 128, and the A/B partner of the DMA kernel).
+#include "bsc_common.h"
+#include "bsc_bf16split.h"
+
+namespace {
+
+constexpr int LD = 256;       // column capacity
 constexpr int XT = 16;        // rows per wave tile
 constexpr int XW = 8;         // waves per workgroup (2 per SIMD, one workgroup per CU)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef bsc_lds_ptr lds_ptr;
 constexpr int vmcnt_only(int n) { return bsc_vmcnt_only(n); }
@@ -338,9 +128,7 @@ __device__ __forceinline__ void loglik_finish(const double (&acc_ll)[NSB], doubl
 // X[row i][16 j + 4 kq .. +3] for j = 0..15 (sixteen 16-byte buffer loads; the four kq lanes of a
 // row read 64 contiguous bytes).  Register set j is refilled for the NEXT tile as soon as its last
 // MFMA has issued, so 64 VGPRs hold the tile and the prefetch.
-// DBG != 0: deletion builds for profiling only (results wrong): bit 0 drops the X refill loads,
-// bit 1 the epilogue, bit 2 the LDS operand reads, bit 3 the intercept / y / id loads.
-template <bool FULL, int NSB, int DBG = 0>   // FULL: D == 256; NSB: 16-sample blocks (S <= 16 NSB)
+template <bool FULL, int NSB>   // FULL: D == 256; NSB: 16-sample blocks (S <= 16 NSB)
 __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y,
     const int* __restrict__ g, int64_t N, int D, const float* __restrict__ Wz,
@@ -431,10 +219,8 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
         // next tile's y and intercepts (its ids arrived a tile ago) and the ids of the tile after,
         // requested FIRST: they are then older than the 16 refill loads below, so the next tile's
         // first MFMA (which takes the intercepts as its C input) waits for nothing recent
-        if (!(DBG & 8)) {
-            side_load(nxt, (tile + n_waves) * XT);
-            g_load((tile + 2 * n_waves) * XT);
-        }
+        side_load(nxt, (tile + n_waves) * XT);
+        g_load((tile + 2 * n_waves) * XT);
         // The draws in LDS never change, so the compiler would hoist all 16 NSB operand reads out
         // of the tile loop (and spill them): the address is made opaque once per tile.  B operands
         // run one k-group ahead of the MFMAs that consume them.
@@ -450,7 +236,7 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
             f32x4 b[NSB];
 #pragma unroll
             for (int sb = 0; sb < NSB; ++sb) b[sb] = bn[sb];
-            if (j + 1 < 16 && !(DBG & 4)) {
+            if (j + 1 < 16) {
 #pragma unroll
                 for (int sb = 0; sb < NSB; ++sb) bn[sb] = wp[(sb * 16 + j + 1) * 64];
             }
@@ -460,17 +246,12 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
 #pragma unroll
                 for (int sb = 0; sb < NSB; ++sb)
                     acc[sb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], b[sb][r], acc[sb], 0, 0, 0);
-            if (!(DBG & 1)) A[j] = x_load(rs_next, j);                   // refill for the next tile
-            if (j + 1 < 16 && !(DBG & 4)) __builtin_amdgcn_sched_group_barrier(0x100, NSB, 0);   // LDS reads of group j+1 ...
+            A[j] = x_load(rs_next, j);                                   // refill for the next tile
+            if (j + 1 < 16) __builtin_amdgcn_sched_group_barrier(0x100, NSB, 0);   // LDS reads of group j+1 ...
             __builtin_amdgcn_sched_group_barrier(0x008, 4 * NSB, 0);               // ... the MFMAs of group j ...
-            if (!(DBG & 1)) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);     // ... the refill load
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                     // ... the refill load
         }
-        if (DBG & 2) {
-#pragma unroll
-            for (int sb = 0; sb < NSB; ++sb) acc_ll[sb] += (double)(acc[sb][0] + acc[sb][1] + acc[sb][2] + acc[sb][3]);
-        } else {
-            loglik_epilogue<NSB>(acc, cur.yv, row0 + XT <= N, row0, N, kq, acc_ll);
-        }
+        loglik_epilogue<NSB>(acc, cur.yv, row0 + XT <= N, row0, N, kq, acc_ll);
         tile += n_waves;
     };
     for (int it = 0; it < n_iter; it += 2) {   // n_iter is even (host)
@@ -497,6 +278,8 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
 // lgkmcnt(0) a k-group later, and (2) strip waits are counted by hand (see DMA_WAIT).  With four
 // sample blocks the draws of block 0 stay in 64 registers, so that W (48 KiB) + 8 waves x 13 KiB
 // fit the CU's 160 KiB; it also saves one of the four B-operand reads per k-group.
+// DBG != 0: deletion builds for profiling only (option bbvi_dbg; results wrong): bit 0 drops the X
+// refill DMAs, bit 1 the epilogue, bit 2 the LDS operand reads, bit 3 the intercept / y / id DMAs.
 constexpr int XR = 8;         // ring slots per wave (divides 16: the slot of strip j is j % XR)
 constexpr int DMA_SIDE = 6;   // vector-memory operations a tile issues before its first strip wait
 constexpr int DMA_WAVE_BYTES = XR * 1024 + 4096 + 4 * 256;   // ring | intercepts | y[2] | ids[2]
@@ -678,10 +461,7 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
             // DMAs and this tile's j strips = XR - 2 + DMA_SIDE; one issued in this tile by XR - 2.
             // (pieces: strip j + 1 of an even j lies in the block that strip j was read from; behind an odd j = 2 c + 1
             // block c + 1 is followed by XR / 2 - 2 blocks of two pieces = XR - 4)
-            if (DBG & 16) {
-                // profiling only: no strip wait at all (reads race the DMAs; the time shows what the
-                // waits cost)
-            } else if (j & 1) {
+            if (j & 1) {
                 if ((j + 1) / 2 < XR / 2) __builtin_amdgcn_s_waitcnt(vmcnt_only(XR - 4 + ((DBG & 8) ? 0 : DMA_SIDE)));
                 else __builtin_amdgcn_s_waitcnt(vmcnt_only(XR - 4));
             }
@@ -737,7 +517,7 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y,
     const int* __restrict__ g, int64_t N, int D, const float* __restrict__ Wz,
     const float* __restrict__ Bz, int n_groups, int S, double* __restrict__ slab, int n_iter) {
-    constexpr int NSB = 4, WREG = 1, NL = NSB - WREG, DBG = 0, SPLIT = 2;
+    constexpr int NSB = 4, WREG = 1, NL = NSB - WREG, SPLIT = 2;
     // the draws as two bf16 terms, in B-operand order: [sb - WREG][k-step jj][term][lane] -> the eight columns
     // 32 jj + 4 kq .. + 3 and 32 jj + 16 + 4 kq .. + 3 of sample NSB i16 + sb (the A operand takes the same eight from
     // strips 2 jj and 2 jj + 1)
@@ -879,11 +659,9 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
         }
         // side DMAs of the tiles ahead, FIRST (DMA_SIDE = 6 of them): older than this tile's strips,
         // so the last strip wait of this tile also covers them
-        if (!(DBG & 8)) {
-            row_dma(y, (tile + n_waves) * XT, Y_OFF + (par ^ 1) * 256);
-            row_dma(g, (tile + 2 * n_waves) * XT, G_OFF + par * 256);
-            bz_dma(ids_next);
-        }
+        row_dma(y, (tile + n_waves) * XT, Y_OFF + (par ^ 1) * 256);
+        row_dma(g, (tile + 2 * n_waves) * XT, G_OFF + par * 256);
+        bz_dma(ids_next);
         int wo = lane;          // opaque once per tile: keeps the static B-operand reads inside the loop
         asm volatile("" : "+v"(wo));
         const bsc_u32x4* wp = wl + wo;
@@ -953,14 +731,9 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
         }
         // the next tile's side data: its DMAs were this tile's first, and the last strip wait
         // (vmcnt <= XR - 2) has covered them; the epilogue below covers the LDS latency
-        if (!(DBG & 8)) side_read(par ^ 1);
+        side_read(par ^ 1);
         __builtin_amdgcn_sched_barrier(0);
-        if (DBG & 2) {
-#pragma unroll
-            for (int sb = 0; sb < NSB; ++sb) acc_ll[sb] += (double)(acc[sb][0] + acc[sb][1] + acc[sb][2] + acc[sb][3]);
-        } else {
-            loglik_epilogue<NSB>(acc, yv, row0 + XT <= N, row0, N, kq, acc_ll);
-        }
+        loglik_epilogue<NSB>(acc, yv, row0 + XT <= N, row0, N, kq, acc_ll);
         tile += n_waves;
     };
     for (int it = 0; it < n_iter; it += 2) {   // n_iter is even (host)
@@ -976,20 +749,9 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
 #undef BSC_LDS_B128
 }
 
-// ell[s] = sum over the block partials, float64, fixed order.  One wave per sample (a single
+// ell[s] = sum over the workgroups' float64 partials, fixed order.  One wave per sample (a single
 // 1024-thread workgroup walking all 64 columns took 10 us, mostly latency: a third of what the
 // whole parameter side of an update costs).
-__global__ __launch_bounds__(256) void loglik_reduce_kernel(const float* __restrict__ slab,
-                                                            int n_rows, double* __restrict__ ell) {
-    const int lane = threadIdx.x & 63;
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    double sum = 0.0;
-    for (int b = lane; b < n_rows; b += 64) sum += (double)slab[(int64_t)b * LS + s];
-    sum = wave_allsum_f64(sum);
-    if (lane == 0) ell[s] = sum;
-}
-
-// The same for the float64 workgroup partials of logreg_loglik_xreg_kernel and any S.
 __global__ __launch_bounds__(256) void loglik_reduce_f64_kernel(const double* __restrict__ slab,
                                                                 int n_rows, int S,
                                                                 double* __restrict__ ell) {
@@ -1330,40 +1092,7 @@ int bsc_logreg_bbvi_loglik(bsc_ctx* ctx, const float* X, int64_t ldx, const floa
     BSC_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)Wz & 15) == 0 && (N == 0 || ((uintptr_t)y & 15) == 0) &&
                     (N == 0 || ((uintptr_t)g & 15) == 0),
                 "bsc_logreg_bbvi_loglik: X, y, g and Wz must be 16-byte aligned");
-    if (ctx->bbvi_kernel == 0 && S == LS) {
-        // first-generation kernel (X tiles staged in LDS, draws in registers): kept for in-process A/B
-        const int64_t n_tiles = (N + LT - 1) / LT;
-        const int64_t max_blocks = 2 * (int64_t)ctx->cu_count;
-        int n_iter = 0, n_blocks = 1;
-        if (n_tiles > 0) {
-            const int64_t it = (n_tiles + max_blocks - 1) / max_blocks;
-            n_iter = (int)(it + (it & 1));   // even: the kernel alternates two register sets per tile pair
-            n_blocks = (int)((n_tiles + it - 1) / it);
-        }
-        void* ws = nullptr;
-        const int nw = ctx->bbvi_waves == 8 ? 8 : 4;   // 8 measured 1 % slower (346 vs 342 us): kept as a knob
-        int rc = bsc_workspace(ctx, (size_t)n_blocks * (nw / 4) * LS * sizeof(float), &ws);
-        if (rc != BSC_OK) return rc;
-        ctx->slab_rows = 0;
-        {
-            bsc_prof_scope prof(ctx);
-#define BSC_LL(FULL, NW)                                                                         \
-    hipLaunchKernelGGL((logreg_loglik_kernel<FULL, NW>), dim3(n_blocks), dim3(64 * NW), 0,        \
-                       ctx->stream, X, ldx, y, (const int*)g, N, (int)D, Wz, Bz, (int)n_groups,  \
-                       (float*)ws, n_iter)
-            if (D == LD && nw == 8) BSC_LL(true, 8);
-            else if (D == LD) BSC_LL(true, 4);
-            else if (nw == 8) BSC_LL(false, 8);
-            else BSC_LL(false, 4);
-#undef BSC_LL
-        }
-        BSC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(loglik_reduce_kernel, dim3(LS / 4), dim3(256), 0, ctx->stream, (const float*)ws,
-                           n_blocks * (nw / 4), ell);
-        BSC_LAUNCH_CHECK();
-        return BSC_OK;
-    }
-    // X in registers, draws in LDS: one 512-thread workgroup per CU, waves take 16-row tiles
+    // draws in LDS: one 512-thread workgroup per CU, waves take 16-row tiles
     const int64_t n_tiles = (N + XT - 1) / XT;
     int n_blocks = (int)((n_tiles + XW - 1) / XW);
     if (n_blocks > ctx->cu_count) n_blocks = ctx->cu_count;
@@ -1375,7 +1104,10 @@ int bsc_logreg_bbvi_loglik(bsc_ctx* ctx, const float* X, int64_t ldx, const floa
     int rc = bsc_workspace(ctx, (size_t)n_blocks * S * sizeof(double), &ws);
     if (rc != BSC_OK) return rc;
     ctx->slab_rows = 0;
+    // X by LDS-DMA when the intercept gathers are 16-byte aligned four-sample runs (S in 36..64,
+    // S % 4 == 0: config 5's S = 64) and option bbvi_kernel does not say 2; X through VGPRs otherwise
     const int nsb = S <= 16 ? 1 : S <= 32 ? 2 : S <= 64 ? 4 : 8;
+    const bool dma_ok = nsb == 4 && S % 4 == 0 && ((uintptr_t)Bz & 15) == 0 && ctx->bbvi_kernel != 2;
     {
         bsc_prof_scope prof(ctx);
 #define BSC_LL_ARGS                                                                                   \
@@ -1386,11 +1118,8 @@ int bsc_logreg_bbvi_loglik(bsc_ctx* ctx, const float* X, int64_t ldx, const floa
         if (D == LD) hipLaunchKernelGGL((logreg_loglik_xreg_kernel<true, NSB>), BSC_LL_ARGS);         \
         else hipLaunchKernelGGL((logreg_loglik_xreg_kernel<false, NSB>), BSC_LL_ARGS);                \
     } while (0)
-        // X by LDS-DMA when the intercept gathers are 16-byte aligned four-sample runs (S in 36..64,
-        // S % 4 == 0: config 5's S = 64); X through VGPRs otherwise
-        const bool dma_ok = nsb == 4 && S % 4 == 0 && ((uintptr_t)Bz & 15) == 0 && ctx->bbvi_kernel != 2;
         if (dma_ok && ctx->bbvi_dbg && D == LD) {
-            // profiling-only deletion builds (BSC_BBVI_DBG): wrong results by construction
+            // profiling-only deletion builds (option bbvi_dbg): wrong results by construction
             switch (ctx->bbvi_dbg) {
                 case 1: hipLaunchKernelGGL((logreg_loglik_dma_kernel<true, 4, 1>), BSC_LL_ARGS); break;
                 case 2: hipLaunchKernelGGL((logreg_loglik_dma_kernel<true, 4, 2>), BSC_LL_ARGS); break;
@@ -1398,7 +1127,6 @@ int bsc_logreg_bbvi_loglik(bsc_ctx* ctx, const float* X, int64_t ldx, const floa
                 case 7: hipLaunchKernelGGL((logreg_loglik_dma_kernel<true, 4, 7>), BSC_LL_ARGS); break;
                 case 11: hipLaunchKernelGGL((logreg_loglik_dma_kernel<true, 4, 11>), BSC_LL_ARGS); break;
                 case 15: hipLaunchKernelGGL((logreg_loglik_dma_kernel<true, 4, 15>), BSC_LL_ARGS); break;
-                case 16: hipLaunchKernelGGL((logreg_loglik_dma_kernel<true, 4, 16>), BSC_LL_ARGS); break;
                 default: hipLaunchKernelGGL((logreg_loglik_dma_kernel<true, 4>), BSC_LL_ARGS); break;
             }
         } else if (dma_ok && ctx->mfma_split == 2) {

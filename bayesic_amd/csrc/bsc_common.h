@@ -24,7 +24,6 @@ struct bsc_ctx {
     int blr_tile_rows = 16;      // 16: forward on the MFMA pipe when D == 256 (else 8-row VALU tiles); 8 | 4: VALU variants
     int blr_waves_per_simd = 0;  // tuning: cap resident waves per SIMD (0 = kernel's own limit)
     int fused_map_blocks_per_cu = 8;  // bsc_map_reduce, pure map: grid cap (256-thread blocks)
-    int gram_pp = 0;                  // 1: gram256_pp_kernel (the two waves of a SIMD take turns on the matrix pipe: two half-steps, two barriers a step) instead of gram256_bx_kernel -- measured no faster (267 vs 261 us), off
     int gram_dbg = 0;                 // deletion builds of gram256_bx_kernel (BSC_GRAM_DBG + BSC_PROFILING_BUILDS): WRONG results
     int rows_dbg = 0;                 // deletion builds of map_reduce_rows_f32_kernel (BSC_ROWS_DBG + BSC_PROFILING_BUILDS): WRONG results
     int rows_wg_per_cu = 64;          // map_reduce_rows_f32_kernel: workgroups per CU in the grid, eight of them resident (BSC_ROWS_WG; 0 = one step per wave)
@@ -41,10 +40,9 @@ struct bsc_ctx {
     int gemm_dbg = 0;                 // profiling only (BSC_GEMM_DBG): 1 = the stream kernel drops its whole-tile stores
     int gemm_pipe = 1;                // GEMM: LDS operand reads one k-pair ahead of the MFMAs
     int fused_nt_store = 1;           // dense map: non-temporal stores of the result
-    int bbvi_waves = 4;          // bsc_logreg_bbvi_loglik: waves per workgroup (4: one wave per 16 samples, 8: per (16 samples, 16 rows))
-    int bbvi_kernel = 1;         // bsc_logreg_bbvi_loglik: 1 = draws in LDS, X by LDS-DMA strips (S <= 64; S <= 128 X through VGPRs), 2 = X through VGPRs, 0 = first-generation LDS-staged tiles (S == 64)
+    int bbvi_kernel = 1;         // bsc_logreg_bbvi_loglik (draws in LDS): 1 = X by LDS-DMA strips where eligible (S in 36..64, S % 4 == 0; X through VGPRs otherwise), 2 = X through VGPRs always
     int lda_dbg = 0;             // BSC_LDA_DBG: profiling-only deletion builds of the split-operand LDA kernel (1: no DMAs after the first two steps; 2: no arithmetic) -- wrong results
-    int bbvi_dbg = 0;            // BSC_BBVI_DBG: profiling-only deletion builds of the xreg kernel (wrong results)
+    int bbvi_dbg = 0;            // BSC_BBVI_DBG: profiling-only deletion builds of logreg_loglik_dma_kernel (wrong results)
     int csc_fast = 1;            // bsc_lda_sstats_csc: buffer-descriptor gathers (BSC_CSC_FAST=0 turns them off)
     int mfma_split = 0;          // 0: f32 MFMA (exact f32 products; the default and the dtype of every reported line); 2 / 3: f32 operands as sums of two / three bf16 terms on the bf16 MFMA, 3 / 6 products (csrc/bsc_bf16split.h; BSC_MFMA_SPLIT, bsc_set_mfma_split) where a kernel offers it
     int mog_nt = 0;              // bsc_mog_estep: 1 = non-temporal loads of X (BSC_MOG_NT).  Default 0: both half-waves read the same rows and the L2 keeps a row for the second one -- 1.01 x the algorithmic bytes instead of 1.19 x, same time (profiles/r03_pmc_kernels.txt)

@@ -137,23 +137,49 @@ def test_loglik_any_sample_count(ctx, S, N, D, G):
     assert (np.abs(ell - want) <= 2e-5 * bound + 1e-9).all(), np.abs((ell - want) / bound).max()
 
 
-def test_first_generation_kernel_still_agrees(ctx):
-    """option bbvi_kernel = 0 keeps the LDS-staged kernel for in-process A/B runs; same oracle."""
-    import os
+@pytest.mark.parametrize("D", [256, 64])
+def test_vgpr_and_dma_routes_agree_with_the_oracle(ctx, D):
+    """At S = 64 the default context brings X by LDS-DMA; option bbvi_kernel = 2 sends it through VGPRs (the kernel
+    that otherwise runs only for the other sample counts).  Same oracle, same tolerance, for D = 256 and for the
+    column-masking instantiation (D = 64).  The draws are scaled by 1 / sqrt(D) (1/16 at D = 256), so the logits
+    have the same spread at both widths: a float32 evaluation of ell on the CPU (float32 terms, float64 sum, as
+    the kernels add them) is within 9.6e-9 (D = 256) and 5.8e-9 (D = 64) of the float64 oracle for these inputs."""
     from bayesic_amd.device import Context
-    old = Context(0, options=dict(bbvi_kernel=0))
+    xreg = Context(0, options=dict(bbvi_kernel=2))
     rs = np.random.RandomState(5)
-    N, D, G = 3001, 256, 19
+    N, G = 3001, 19
     X = rs.standard_normal((N, D)).astype(np.float32)
     g = rs.randint(G, size=N).astype(np.int32)
     y = (rs.uniform(size=N) < 0.4).astype(np.float32)
-    Wz = (rs.standard_normal((64, D)) / 16).astype(np.float32)
+    Wz = (rs.standard_normal((64, D)) / math.sqrt(D)).astype(np.float32)
     Bz = rs.standard_normal((G, 64)).astype(np.float32)
-    a, b = _loglik(old, X, y, g, Wz, Bz), _loglik(ctx, X, y, g, Wz, Bz)
+    a, b = _loglik(xreg, X, y, g, Wz, Bz), _loglik(ctx, X, y, g, Wz, Bz)
     want = svi.logreg_loglik(X, y, g, Wz, Bz)
     npt.assert_allclose(a, want, rtol=2e-6)
     npt.assert_allclose(b, want, rtol=2e-6)
-    old.close()
+    xreg.close()
+
+
+def test_removed_kernel_options_are_refused():
+    """The LDS-staged first kernel (bbvi_kernel = 0, bbvi_waves) and the Gram ping-pong loop (gram_pp) are gone: asking
+    for them is an error, not a silent default, and the context stays usable."""
+    from bayesic_amd._ffi import BayesicHipError
+    from bayesic_amd.device import Context
+    c = Context(0)
+    for name, value in (("bbvi_kernel", 0), ("bbvi_waves", 8), ("gram_pp", 1)):
+        with pytest.raises(BayesicHipError):
+            c.set_option(name, value)
+        with pytest.raises(BayesicHipError):
+            Context(0, options={name: value})
+    rs = np.random.RandomState(50)
+    N, D, G = 50, 256, 3
+    X = rs.standard_normal((N, D)).astype(np.float32)
+    g = rs.randint(G, size=N).astype(np.int32)
+    y = (rs.uniform(size=N) < 0.4).astype(np.float32)
+    Wz = (rs.standard_normal((64, D)) / math.sqrt(D)).astype(np.float32)
+    Bz = rs.standard_normal((G, 64)).astype(np.float32)
+    npt.assert_allclose(_loglik(c, X, y, g, Wz, Bz), svi.logreg_loglik(X, y, g, Wz, Bz), rtol=2e-6)
+    c.close()
 
 
 @pytest.mark.parametrize("D,G,S", [(24, 9, 64), (256, 1000, 64), (4, 1, 7), (60, 130, 33)])

@@ -53,7 +53,6 @@ LIMITS = {
     },
     "bsc_gram.hip": {
         "gram256_bx_kernel": (256, 0),                  # eight waves a CU = two per SIMD
-        "gram256_pp_kernel": (256, 0),                  # (option gram_pp: the same budget)
     },
     "bsc_gemm.hip": {
         "gemm_f32_mfma_kernelILb1ELb1ELb1E": (256, 0),
@@ -73,7 +72,7 @@ LIMITS = {
         "mog_estep_bx_kernel": (256, 8),                # (one register parked before the tile loop and fetched after it)
     },
     "bsc_bbvi.hip": {
-        "logreg_loglik_kernel": (256, 0),
+        "logreg_loglik_xreg_kernelILb1ELi4E": (160, 0), # X through VGPRs at S = 64 (option bbvi_kernel = 2): three waves/SIMD
         "logreg_loglik_dma_kernelILb1ELi4ELi0E": (192, 0),
         "logreg_loglik_dma_bx_kernel": (200, 0),
         "bbvi_update_kernel": (96, 0),

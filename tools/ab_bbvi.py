@@ -32,14 +32,11 @@ def main():
     pos = [a for a in sys.argv[1:] if not a.startswith("--")]
     rounds = int(pos[0]) if pos else 6
     S = int(pos[1]) if len(pos) > 1 else 64
-    variants = {"lds-staged (r1)": make_ctx({"BSC_BBVI_KERNEL": "0"}),
-                "X through VGPRs (r2a)": make_ctx({"BSC_BBVI_KERNEL": "2"}),
+    variants = {"X through VGPRs (r2a)": make_ctx({"BSC_BBVI_KERNEL": "2"}),
                 "X by LDS-DMA (r2b, default)": make_ctx({"BSC_BBVI_KERNEL": "1"})}
-    if S != 64:
-        variants.pop("lds-staged (r1)")
     if "--deletion" in sys.argv:
-        # profiling-only builds of the r2 kernel with parts removed (results wrong, time matters)
-        for dbg, what in ((16, "no strip waits (reads race the DMAs)"), (1, "no X refill loads"), (2, "no epilogue"), (3, "no X loads, no epilogue"),
+        # profiling-only builds of the r2b kernel with parts removed (results wrong, time matters)
+        for dbg, what in ((1, "no X refill loads"), (2, "no epilogue"), (3, "no X loads, no epilogue"),
                           (11, "no X loads, epilogue, side loads"), (7, "MFMA + side loads only"),
                           (15, "MFMA only")):
             variants["r2b dbg=%d %s" % (dbg, what)] = make_ctx({"BSC_BBVI_KERNEL": "1", "BSC_BBVI_DBG": str(dbg), "BSC_PROFILING_BUILDS": "1"})
