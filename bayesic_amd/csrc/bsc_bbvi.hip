@@ -43,15 +43,20 @@ namespace {
 constexpr int LD = 256;       // column capacity
 constexpr int XT = 16;        // rows per wave tile
 constexpr int XW = 8;         // waves per workgroup (2 per SIMD, one workgroup per CU)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef bsc_lds_ptr lds_ptr;
-constexpr int vmcnt_only(int n) { return bsc_vmcnt_only(n); }
-__device__ __forceinline__ auto x_tile_rsrc(const float* X, int64_t ldx, int D, int64_t N, int64_t row0) {
-    return bsc_rows_rsrc(X, ldx, D, N, row0);       // rows past N read as zero
-}
-__device__ __forceinline__ auto row_vec_rsrc(const void* base, int64_t N, int64_t row0) {   // y or g: 4 B per row
-    return bsc_vec_rsrc(base, N, row0);
+
+// The draws Wz[S, D] into LDS in the order the MFMA B operand is read, for sample blocks WREG .. NSB - 1 (the
+// first WREG stay in registers): wl[sb - WREG][j][lane] = the four columns 16 j + 4 kq .. + 3 of sample
+// NSB i16 + sb; samples past S and columns past D are zeros.  The caller's __syncthreads() follows.
+template <int NSB, int WREG>
+__device__ __forceinline__ void fill_draws(f32x4* wl, const float* Wz, int S, int D, int tid) {
+    for (int idx = tid; idx < (NSB - WREG) * 16 * 64; idx += 64 * XW) {
+        const int ln = idx & 63, j = (idx >> 6) & 15, sb = (idx >> 10) + WREG;
+        const int sample = NSB * (ln & 15) + sb, col = 16 * j + 4 * (ln >> 4);
+        f32x4 w = {0.f, 0.f, 0.f, 0.f};
+        if (sample < S && col < D) w = *reinterpret_cast<const f32x4*>(Wz + (int64_t)sample * D + col);
+        wl[idx] = w;
+    }
 }
 
 // One tile's epilogue: acc[sb][r] = logit of row 4 kq + r, sample NSB i16 + sb; yv = y of those rows.
@@ -139,19 +144,13 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i16 = lane & 15, kq = lane >> 4;
 
-    for (int idx = tid; idx < NSB * 16 * 64; idx += 64 * XW) {
-        const int ln = idx & 63, j = (idx >> 6) & 15, sb = idx >> 10;
-        const int sample = NSB * (ln & 15) + sb, col = 16 * j + 4 * (ln >> 4);
-        f32x4 w = {0.f, 0.f, 0.f, 0.f};
-        if (sample < S && col < D) w = *reinterpret_cast<const f32x4*>(Wz + (int64_t)sample * D + col);
-        wl[idx] = w;
-    }
+    fill_draws<NSB, 0>(wl, Wz, S, D, tid);
     __syncthreads();
 
     const int64_t n_waves = (int64_t)gridDim.x * XW;
     int64_t tile = (int64_t)blockIdx.x * XW + wave;
     const int x_voff = i16 * (int)(ldx * 4) + 16 * kq;
-    auto x_load = [&](decltype(x_tile_rsrc(X, ldx, D, N, 0)) rs, int j) {
+    auto x_load = [&](bsc_rsrc_t rs, int j) {
         auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, x_voff, 64 * j, 2);   // nt: X is read once
         f32x4 f = {__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
         if (!FULL && 16 * j + 4 * kq >= D) f = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -167,12 +166,12 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
     };
     int gi[4];             // group-id byte offsets of the tile after next
     auto g_load = [&](int64_t row0) {
-        auto v = __builtin_amdgcn_raw_buffer_load_b128(row_vec_rsrc(g, N, row0), 16 * kq, 0, 0);
+        auto v = __builtin_amdgcn_raw_buffer_load_b128(bsc_vec_rsrc(g, N, row0), 16 * kq, 0, 0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) gi[r] = (int)v[r] * row_b;
     };
     auto side_load = [&](Side& sd, int64_t row0) {      // uses gi = ids of this tile
-        auto v = __builtin_amdgcn_raw_buffer_load_b128(row_vec_rsrc(y, N, row0), 16 * kq, 0, 0);
+        auto v = __builtin_amdgcn_raw_buffer_load_b128(bsc_vec_rsrc(y, N, row0), 16 * kq, 0, 0);
         sd.yv = f32x4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
         // (padded samples >= S read the neighbouring bytes or 0; their W is 0 and they are never stored)
         const int soff = 4 * NSB * i16;
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
 
     f32x4 A[16];
     {
-        const auto rs = x_tile_rsrc(X, ldx, D, N, tile * XT);
+        const auto rs = bsc_rows_rsrc(X, ldx, D, N, tile * XT);
 #pragma unroll
         for (int j = 0; j < 16; ++j) A[j] = x_load(rs, j);
     }
@@ -212,7 +211,7 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
 
     auto one_tile = [&](const Side& cur, Side& nxt) {
         const int64_t row0 = tile * XT;
-        const auto rs_next = x_tile_rsrc(X, ldx, D, N, (tile + n_waves) * XT);
+        const auto rs_next = bsc_rows_rsrc(X, ldx, D, N, (tile + n_waves) * XT);
         f32x4 acc[NSB];
 #pragma unroll
         for (int sb = 0; sb < NSB; ++sb) acc[sb] = cur.bz[sb];          // C input = intercepts
@@ -265,10 +264,9 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
 
 // ---- X by LDS-DMA (NSB <= 4: the default up to S = 64) ------------------------------------------
 // Nothing a tile needs passes through a VGPR-returning load.  Each wave owns in LDS
-//   * a ring of XR 1-KiB slots: the tile arrives in pieces of 8 rows x 128 bytes (whole lines: pieces
-//     shaped like one strip of A operands, 16 rows x 64 bytes, read 23 % slower -- tools/ab_skinny_nt.py),
-//     two per block of 32 columns, DMA'd XR pieces ahead of their use into an XOR-permuted image from
-//     which strip j of a tile (the A-operand block of k-group j) is one conflict-free ds_read_b128;
+//   * a ring of XR 1-KiB slots (bsc_line_ring, csrc/bsc_common.h: the piece shape and the XOR image): the tile
+//     arrives in whole-line pieces, two per block of 32 columns, DMA'd XR pieces ahead of their use, and strip j
+//     of a tile (the A-operand block of k-group j) is one conflict-free ds_read_b128;
 //   * y and the group ids of the next tiles (a 256-B dword DMA each: lane l <- row0 + l);
 //   * the 4-KiB block of intercepts b[g_row, NSB i16 ..] of the next tile, gathered by four
 //     dwordx4 DMAs whose per-lane offsets come from the ids, read back as the MFMA's C input.
@@ -283,6 +281,89 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_xreg_kernel(
 constexpr int XR = 8;         // ring slots per wave (divides 16: the slot of strip j is j % XR)
 constexpr int DMA_SIDE = 6;   // vector-memory operations a tile issues before its first strip wait
 constexpr int DMA_WAVE_BYTES = XR * 1024 + 4096 + 4 * 256;   // ring | intercepts | y[2] | ids[2]
+constexpr int BZ_OFF = XR * 1024, Y_OFF = BZ_OFF + 4096, G_OFF = Y_OFF + 512;
+
+// A wave's DMA region in the two kernels below (ring | intercepts | y[2] | ids[2]): addresses, offsets,
+// descriptors and the side data read back from it.  Operands, accumulators and tile registers stay locals of the
+// kernels: captured prefetch registers have gone to scratch before with every parity test green
+// (tests/test_kernel_resources.py).
+template <int NSB>
+struct DmaRegion {
+    const bsc_line_ring ring;       // X in whole 128-byte lines: the piece shape and the XOR image are bsc_line_ring's
+    int64_t N;
+    int lane;
+    bsc_rsrc_t bz_rsrc;             // Bz[g, s]: 32-bit offsets, ids outside [0, n_groups) read 0
+    int row_b, soff;
+    unsigned addr_lane, addr_kq;    // lane l's 16 bytes of a 1-KiB block; the 4 rows 4 kq .. 4 kq + 3 of a row vector
+    // LDS -> registers (side_read): a tile's intercepts q[r] (lane l's 16 bytes = samples NSB i16 .., the first NSB
+    // count), its y, and the ids of the tile after it
+    f32x4 q[4], yv_n, ids_n;
+
+    __device__ __forceinline__ DmaRegion(char* my, int lane_, int i16, int kq, int64_t ldx, int64_t N_, const float* Bz,
+                                         int n_groups, int S)
+        : ring(my, lane_, i16, kq, (int)(ldx * 4)), N(N_), lane(lane_) {
+        const unsigned my_addr = (unsigned)(uintptr_t)(bsc_lds_ptr)my;
+        addr_lane = my_addr + 16u * lane;
+        addr_kq = my_addr + 16u * kq;
+        bz_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Bz, 0, (unsigned)n_groups * (unsigned)S * 4u, 0x00020000);
+        row_b = S * 4;
+        soff = 4 * NSB * i16;
+    }
+    // ---- the DMAs (every one counts in vmcnt, in this order) ----
+    // piece s -> slot s % XR
+    __device__ __forceinline__ void x_dma(bsc_rsrc_t rs, int s) const { ring.dma(rs, s, s % XR); }
+    // lane l <- 4 bytes of row0 + l
+    __device__ __forceinline__ void row_dma(const void* base, int64_t row0, int lds_off) const {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(bsc_vec_rsrc(base, N, row0), (bsc_lds_ptr)(ring.base + lds_off), 4,
+                                                 4 * lane, 0, 0, 0);
+    }
+    // ids (as int bits) of rows 4 kq .. +3 -> intercepts [r][lane][NSB]
+    __device__ __forceinline__ void bz_dma(const f32x4 ids) const {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(bz_rsrc, (bsc_lds_ptr)(ring.base + BZ_OFF + r * 1024), 16,
+                                                     __float_as_int(ids[r]) * row_b + soff, 0, 0, 0);
+    }
+    // ---- reads of DMA'd bytes: inline asm (see the header), valid after the next lgkmcnt(0) ----
+    // strip j = 2 c + t: both of its pieces sit in slots (2 c) % XR, + 1
+    __device__ __forceinline__ f32x4 a_read(int j) const {
+        f32x4 f;
+        if (j & 1) BSC_LDS_B128(f, ring.addr1, ((j & ~1) % XR) * 1024);
+        else BSC_LDS_B128(f, ring.addr0, ((j & ~1) % XR) * 1024);
+        return f;
+    }
+    __device__ __forceinline__ void side_read(int par) {     // for the tile of parity `par`
+        BSC_LDS_B128(q[0], addr_lane, BZ_OFF);
+        BSC_LDS_B128(q[1], addr_lane, BZ_OFF + 1024);
+        BSC_LDS_B128(q[2], addr_lane, BZ_OFF + 2048);
+        BSC_LDS_B128(q[3], addr_lane, BZ_OFF + 3072);
+        if (par) {
+            BSC_LDS_B128(yv_n, addr_kq, Y_OFF + 256);
+            BSC_LDS_B128(ids_n, addr_kq, G_OFF);
+        } else {
+            BSC_LDS_B128(yv_n, addr_kq, Y_OFF);
+            BSC_LDS_B128(ids_n, addr_kq, G_OFF + 256);
+        }
+    }
+    // strips 0 .. XR-1 (descriptor rs), y, ids and intercepts of the first tile, ids of the second
+    __device__ __forceinline__ void prologue(bsc_rsrc_t rs, const float* y, const int* g, int64_t tile,
+                                             int64_t n_waves) const {
+#pragma unroll
+        for (int j = 0; j < XR; ++j) x_dma(rs, j);
+        row_dma(y, tile * XT, Y_OFF);
+        row_dma(g, tile * XT, G_OFF);
+        row_dma(g, (tile + n_waves) * XT, G_OFF + 256);
+        __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
+        asm volatile("" ::: "memory");
+        f32x4 ids;
+        BSC_LDS_B128(ids, addr_kq, G_OFF);
+        __builtin_amdgcn_s_waitcnt(BSC_LGKMCNT0);
+        __builtin_amdgcn_sched_barrier(0);
+        bz_dma(ids);
+        __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
+        asm volatile("" ::: "memory");
+    }
+};
 
 template <bool FULL, int NSB, int DBG = 0>
 __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
@@ -299,13 +380,7 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i16 = lane & 15, kq = lane >> 4;
 
-    for (int idx = tid; idx < NL * 16 * 64; idx += 64 * XW) {
-        const int ln = idx & 63, j = (idx >> 6) & 15, sb = (idx >> 10) + WREG;
-        const int sample = NSB * (ln & 15) + sb, col = 16 * j + 4 * (ln >> 4);
-        f32x4 w = {0.f, 0.f, 0.f, 0.f};
-        if (sample < S && col < D) w = *reinterpret_cast<const f32x4*>(Wz + (int64_t)sample * D + col);
-        wl[idx] = w;
-    }
+    fill_draws<NSB, WREG>(wl, Wz, S, D, tid);
     f32x4 wreg[WREG ? 16 : 1];      // draws of sample NSB i16 + 0: [j] -> columns 16 j + 4 kq .. +3
     if constexpr (WREG) {
 #pragma unroll
@@ -319,114 +394,37 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
 
     const int64_t n_waves = (int64_t)gridDim.x * XW;
     int64_t tile = (int64_t)blockIdx.x * XW + wave;
-    // X arrives in WHOLE 128-byte lines (pieces of 16 rows x 64 bytes read 23 % slower: tools/ab_skinny_nt.py, and see
-    // csrc/bsc_skinny.hip): piece s = 2 c + sp is rows 8 sp .. + 7 x columns 32 c .. + 31, DMA lane l = (row l >> 3,
-    // 16-byte position l & 7); the chunk fetched into position p of row a is p ^ f, f = (a >> 1) | (sp << 2), which
-    // keeps the operand read (lane (i16, kq) <- row i16, chunk kq + 4 t of block c = strip 2 c + t) conflict-free
-    const int x_row_bytes = (int)(ldx * 4);
-    const int x_voff0 = (lane >> 3) * x_row_bytes + 16 * ((lane & 7) ^ (lane >> 4));
-    const int x_voff1 = (lane >> 3) * x_row_bytes + 16 * ((lane & 7) ^ ((lane >> 4) | 4));
-    char* const my = dma + wave * DMA_WAVE_BYTES;                       // this wave's DMA region
-    const unsigned my_addr = (unsigned)(uintptr_t)(lds_ptr)my;
-    const unsigned addr_x0 = my_addr + 1024u * (i16 >> 3) + 128u * (i16 & 7) + 16u * (kq ^ (((i16 & 7) >> 1) | ((i16 >> 3) << 2)));
-    const unsigned addr_x1 = addr_x0 ^ 64u;
-    constexpr int BZ_OFF = XR * 1024, Y_OFF = BZ_OFF + 4096, G_OFF = Y_OFF + 512;
-
-    // ---- the DMAs (every one counts in vmcnt, in this order) ----
-    auto x_dma = [&](decltype(x_tile_rsrc(X, ldx, D, N, 0)) rs, int s) {            // piece s -> slot s % XR
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(my + (s % XR) * 1024), 16, (s & 1) ? x_voff1 : x_voff0,
-                                                 (s & 1) * 8 * x_row_bytes + 128 * (s >> 1), 0, 2);
-    };
-    auto row_dma = [&](const void* base, int64_t row0, int lds_off) {              // lane l <- 4 bytes of row0 + l
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(row_vec_rsrc(base, N, row0), (lds_ptr)(my + lds_off), 4, 4 * lane, 0, 0, 0);
-    };
-    const auto bz_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Bz, 0, (unsigned)n_groups * (unsigned)S * 4u,
-                                                           0x00020000);
-    const int row_b = S * 4, soff = 4 * NSB * i16;
-    auto bz_dma = [&](const f32x4 ids) {    // ids (as int bits) of rows 4 kq .. +3 -> intercepts [r][lane][NSB]
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(bz_rsrc, (lds_ptr)(my + BZ_OFF + r * 1024), 16,
-                                                     __float_as_int(ids[r]) * row_b + soff, 0, 0, 0);
-    };
-    // ---- reads of DMA'd bytes: inline asm (see the header), valid after lds_ready() ----
-    const unsigned addr_lane = my_addr + 16u * lane;     // lane l's 16 bytes of a 1-KiB block
-    const unsigned addr_kq = my_addr + 16u * kq;         // the 4 rows 4 kq .. 4 kq + 3 of a row vector
-#define BSC_LDS_B128(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
-    auto a_read = [&](int j) {          // strip j = 2 c + t: both of its pieces sit in slots (2 c) % XR, + 1
-        f32x4 f;
-        if (j & 1) BSC_LDS_B128(f, addr_x1, ((j & ~1) % XR) * 1024);
-        else BSC_LDS_B128(f, addr_x0, ((j & ~1) % XR) * 1024);
-        return f;
-    };
-
-    // ---- prologue: strips 0 .. XR-1, y, ids and intercepts of the first tile, ids of the second ----
-    {
-        const auto rs = x_tile_rsrc(X, ldx, D, N, tile * XT);
-#pragma unroll
-        for (int j = 0; j < XR; ++j) x_dma(rs, j);
-    }
-    row_dma(y, tile * XT, Y_OFF);
-    row_dma(g, tile * XT, G_OFF);
-    row_dma(g, (tile + n_waves) * XT, G_OFF + 256);
-    __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
-    asm volatile("" ::: "memory");
-    {
-        f32x4 ids;
-        BSC_LDS_B128(ids, addr_kq, G_OFF);
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_sched_barrier(0);
-        bz_dma(ids);
-    }
-    __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
-    asm volatile("" ::: "memory");
-    f32x4 an = a_read(0);           // the A operand of the next k-group, read one group ahead
+    DmaRegion<NSB> w(dma + wave * DMA_WAVE_BYTES, lane, i16, kq, ldx, N, Bz, n_groups, S);
+    w.prologue(bsc_rows_rsrc(X, ldx, D, N, tile * XT), y, g, tile, n_waves);
+    f32x4 an = w.a_read(0);           // the A operand of the next k-group, read one group ahead
 
     double acc_ll[NSB];
 #pragma unroll
     for (int sb = 0; sb < NSB; ++sb) acc_ll[sb] = 0.0;
-
-    // LDS -> registers for the tile of parity `par`: its intercepts q[r] (lane l's 16 bytes = samples
-    // NSB i16 .., the first NSB count), its y, and the ids of the tile after it.  Valid after the
-    // next lgkmcnt(0).
-    f32x4 q[4], yv_n, ids_n;
-    auto side_read = [&](int par) {
-        BSC_LDS_B128(q[0], addr_lane, BZ_OFF);
-        BSC_LDS_B128(q[1], addr_lane, BZ_OFF + 1024);
-        BSC_LDS_B128(q[2], addr_lane, BZ_OFF + 2048);
-        BSC_LDS_B128(q[3], addr_lane, BZ_OFF + 3072);
-        if (par) {
-            BSC_LDS_B128(yv_n, addr_kq, Y_OFF + 256);
-            BSC_LDS_B128(ids_n, addr_kq, G_OFF);
-        } else {
-            BSC_LDS_B128(yv_n, addr_kq, Y_OFF);
-            BSC_LDS_B128(ids_n, addr_kq, G_OFF + 256);
-        }
-    };
-    side_read(0);
+    w.side_read(0);
 
     // `par` = parity of the tile within this wave's sequence (y and ids are double-buffered)
     auto one_tile = [&](int par) {
         const int64_t row0 = tile * XT;
-        const auto rs_cur = x_tile_rsrc(X, ldx, D, N, row0);
-        const auto rs_next = x_tile_rsrc(X, ldx, D, N, (tile + n_waves) * XT);
+        const auto rs_cur = bsc_rows_rsrc(X, ldx, D, N, row0);
+        const auto rs_next = bsc_rows_rsrc(X, ldx, D, N, (tile + n_waves) * XT);
         // this tile's intercepts (C input) and y and the next tile's ids were requested from LDS
         // before the previous tile's epilogue (side_read): back long ago, the wait is for the compiler
-        __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
+        __builtin_amdgcn_s_waitcnt(BSC_LGKMCNT0);
         __builtin_amdgcn_sched_barrier(0);
         f32x4 acc[NSB];
-        const f32x4 yv = yv_n, ids_next = ids_n;
+        const f32x4 yv = w.yv_n, ids_next = w.ids_n;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
 #pragma unroll
-            for (int sb = 0; sb < NSB; ++sb) acc[sb][r] = q[r][sb];
+            for (int sb = 0; sb < NSB; ++sb) acc[sb][r] = w.q[r][sb];
         }
         // side DMAs of the tiles ahead, FIRST (DMA_SIDE = 6 of them): older than this tile's strips,
         // so the last strip wait of this tile also covers them
         if (!(DBG & 8)) {
-            row_dma(y, (tile + n_waves) * XT, Y_OFF + (par ^ 1) * 256);
-            row_dma(g, (tile + 2 * n_waves) * XT, G_OFF + par * 256);
-            bz_dma(ids_next);
+            w.row_dma(y, (tile + n_waves) * XT, Y_OFF + (par ^ 1) * 256);
+            w.row_dma(g, (tile + 2 * n_waves) * XT, G_OFF + par * 256);
+            w.bz_dma(ids_next);
         }
         int wo = lane;          // opaque once per tile: keeps the static B-operand reads inside the loop
         asm volatile("" : "+v"(wo));
@@ -438,11 +436,11 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
         for (int j = 0; j < 16; ++j) {
             // `an` was read a k-group ago, like this group's B operands: the wait finds them done --
             // placed BEFORE the next group's reads are issued, or it would wait for those as well.
-            // The builtin (0xC07F = lgkmcnt(0) alone), so that the compiler's own bookkeeping knows
+            // The builtin (lgkmcnt(0) alone), so that the compiler's own bookkeeping knows
             // its B reads are back: with an asm wait it would add lgkmcnt(N) waits that count the
             // asm read it cannot see, and stall on the reads just issued.
             if (j > 0) {
-                __builtin_amdgcn_s_waitcnt(0xC07F);
+                __builtin_amdgcn_s_waitcnt(BSC_LGKMCNT0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             f32x4 b[NSB];
@@ -462,11 +460,11 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
             // (pieces: strip j + 1 of an even j lies in the block that strip j was read from; behind an odd j = 2 c + 1
             // block c + 1 is followed by XR / 2 - 2 blocks of two pieces = XR - 4)
             if (j & 1) {
-                if ((j + 1) / 2 < XR / 2) __builtin_amdgcn_s_waitcnt(vmcnt_only(XR - 4 + ((DBG & 8) ? 0 : DMA_SIDE)));
-                else __builtin_amdgcn_s_waitcnt(vmcnt_only(XR - 4));
+                if ((j + 1) / 2 < XR / 2) __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(XR - 4 + ((DBG & 8) ? 0 : DMA_SIDE)));
+                else __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(XR - 4));
             }
             asm volatile("" ::: "memory");
-            if (!(DBG & 4)) an = a_read((j + 1) % 16);
+            if (!(DBG & 4)) an = w.a_read((j + 1) % 16);
             // MFMAs have no memory semantics and would float above the asm read (and the next group's
             // lgkmcnt wait would then sit right behind it): pin "reads, then MFMAs, then the DMA"
             __builtin_amdgcn_sched_barrier(0);
@@ -481,15 +479,15 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const int p = j - 1 + e;
-                    if (p + XR < 16) x_dma(rs_cur, p + XR);
-                    else x_dma(rs_next, p + XR - 16);
+                    if (p + XR < 16) w.x_dma(rs_cur, p + XR);
+                    else w.x_dma(rs_next, p + XR - 16);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         // the next tile's side data: its DMAs were this tile's first, and the last strip wait
         // (vmcnt <= XR - 2) has covered them; the epilogue below covers the LDS latency
-        if (!(DBG & 8)) side_read(par ^ 1);
+        if (!(DBG & 8)) w.side_read(par ^ 1);
         __builtin_amdgcn_sched_barrier(0);
         if (DBG & 2) {
 #pragma unroll
@@ -506,10 +504,9 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_kernel(
         one_tile(1);
     }
     // no LDS-DMA of this wave may still be in flight when the workgroup's LDS is released
-    __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
+    __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     loglik_finish<NSB>(acc_ll, red, wave, lane, tid, S, slab);
-#undef BSC_LDS_B128
 }
 
 template <bool FULL>
@@ -555,113 +552,36 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
 
     const int64_t n_waves = (int64_t)gridDim.x * XW;
     int64_t tile = (int64_t)blockIdx.x * XW + wave;
-    // X arrives in WHOLE 128-byte lines (pieces of 16 rows x 64 bytes read 23 % slower: tools/ab_skinny_nt.py, and see
-    // csrc/bsc_skinny.hip): piece s = 2 c + sp is rows 8 sp .. + 7 x columns 32 c .. + 31, DMA lane l = (row l >> 3,
-    // 16-byte position l & 7); the chunk fetched into position p of row a is p ^ f, f = (a >> 1) | (sp << 2), which
-    // keeps the operand read (lane (i16, kq) <- row i16, chunk kq + 4 t of block c = strip 2 c + t) conflict-free
-    const int x_row_bytes = (int)(ldx * 4);
-    const int x_voff0 = (lane >> 3) * x_row_bytes + 16 * ((lane & 7) ^ (lane >> 4));
-    const int x_voff1 = (lane >> 3) * x_row_bytes + 16 * ((lane & 7) ^ ((lane >> 4) | 4));
-    char* const my = dma + wave * DMA_WAVE_BYTES;                       // this wave's DMA region
-    const unsigned my_addr = (unsigned)(uintptr_t)(lds_ptr)my;
-    const unsigned addr_x0 = my_addr + 1024u * (i16 >> 3) + 128u * (i16 & 7) + 16u * (kq ^ (((i16 & 7) >> 1) | ((i16 >> 3) << 2)));
-    const unsigned addr_x1 = addr_x0 ^ 64u;
-    constexpr int BZ_OFF = XR * 1024, Y_OFF = BZ_OFF + 4096, G_OFF = Y_OFF + 512;
-
-    // ---- the DMAs (every one counts in vmcnt, in this order) ----
-    auto x_dma = [&](decltype(x_tile_rsrc(X, ldx, D, N, 0)) rs, int s) {            // piece s -> slot s % XR
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(my + (s % XR) * 1024), 16, (s & 1) ? x_voff1 : x_voff0,
-                                                 (s & 1) * 8 * x_row_bytes + 128 * (s >> 1), 0, 2);
-    };
-    auto row_dma = [&](const void* base, int64_t row0, int lds_off) {              // lane l <- 4 bytes of row0 + l
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(row_vec_rsrc(base, N, row0), (lds_ptr)(my + lds_off), 4, 4 * lane, 0, 0, 0);
-    };
-    const auto bz_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Bz, 0, (unsigned)n_groups * (unsigned)S * 4u,
-                                                           0x00020000);
-    const int row_b = S * 4, soff = 4 * NSB * i16;
-    auto bz_dma = [&](const f32x4 ids) {    // ids (as int bits) of rows 4 kq .. +3 -> intercepts [r][lane][NSB]
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(bz_rsrc, (lds_ptr)(my + BZ_OFF + r * 1024), 16,
-                                                     __float_as_int(ids[r]) * row_b + soff, 0, 0, 0);
-    };
-    // ---- reads of DMA'd bytes: inline asm (see the header), valid after lds_ready() ----
-    const unsigned addr_lane = my_addr + 16u * lane;     // lane l's 16 bytes of a 1-KiB block
-    const unsigned addr_kq = my_addr + 16u * kq;         // the 4 rows 4 kq .. 4 kq + 3 of a row vector
-#define BSC_LDS_B128(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
-    auto a_read = [&](int j) {          // strip j = 2 c + t: both of its pieces sit in slots (2 c) % XR, + 1
-        f32x4 f;
-        if (j & 1) BSC_LDS_B128(f, addr_x1, ((j & ~1) % XR) * 1024);
-        else BSC_LDS_B128(f, addr_x0, ((j & ~1) % XR) * 1024);
-        return f;
-    };
-
-    // ---- prologue: strips 0 .. XR-1, y, ids and intercepts of the first tile, ids of the second ----
-    {
-        const auto rs = x_tile_rsrc(X, ldx, D, N, tile * XT);
-#pragma unroll
-        for (int j = 0; j < XR; ++j) x_dma(rs, j);
-    }
-    row_dma(y, tile * XT, Y_OFF);
-    row_dma(g, tile * XT, G_OFF);
-    row_dma(g, (tile + n_waves) * XT, G_OFF + 256);
-    __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
-    asm volatile("" ::: "memory");
-    {
-        f32x4 ids;
-        BSC_LDS_B128(ids, addr_kq, G_OFF);
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_sched_barrier(0);
-        bz_dma(ids);
-    }
-    __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
-    asm volatile("" ::: "memory");
-    f32x4 an = a_read(0), an2 = a_read(1);      // the A operand of the next k-step, read one step ahead
+    DmaRegion<NSB> w(dma + wave * DMA_WAVE_BYTES, lane, i16, kq, ldx, N, Bz, n_groups, S);
+    w.prologue(bsc_rows_rsrc(X, ldx, D, N, tile * XT), y, g, tile, n_waves);
+    f32x4 an = w.a_read(0), an2 = w.a_read(1);      // the A operand of the next k-step, read one step ahead
 
     double acc_ll[NSB];
 #pragma unroll
     for (int sb = 0; sb < NSB; ++sb) acc_ll[sb] = 0.0;
-
-    // LDS -> registers for the tile of parity `par`: its intercepts q[r] (lane l's 16 bytes = samples
-    // NSB i16 .., the first NSB count), its y, and the ids of the tile after it.  Valid after the
-    // next lgkmcnt(0).
-    f32x4 q[4], yv_n, ids_n;
-    auto side_read = [&](int par) {
-        BSC_LDS_B128(q[0], addr_lane, BZ_OFF);
-        BSC_LDS_B128(q[1], addr_lane, BZ_OFF + 1024);
-        BSC_LDS_B128(q[2], addr_lane, BZ_OFF + 2048);
-        BSC_LDS_B128(q[3], addr_lane, BZ_OFF + 3072);
-        if (par) {
-            BSC_LDS_B128(yv_n, addr_kq, Y_OFF + 256);
-            BSC_LDS_B128(ids_n, addr_kq, G_OFF);
-        } else {
-            BSC_LDS_B128(yv_n, addr_kq, Y_OFF);
-            BSC_LDS_B128(ids_n, addr_kq, G_OFF + 256);
-        }
-    };
-    side_read(0);
+    w.side_read(0);
 
     // `par` = parity of the tile within this wave's sequence (y and ids are double-buffered)
     auto one_tile = [&](int par) {
         const int64_t row0 = tile * XT;
-        const auto rs_cur = x_tile_rsrc(X, ldx, D, N, row0);
-        const auto rs_next = x_tile_rsrc(X, ldx, D, N, (tile + n_waves) * XT);
+        const auto rs_cur = bsc_rows_rsrc(X, ldx, D, N, row0);
+        const auto rs_next = bsc_rows_rsrc(X, ldx, D, N, (tile + n_waves) * XT);
         // this tile's intercepts (C input) and y and the next tile's ids were requested from LDS
         // before the previous tile's epilogue (side_read): back long ago, the wait is for the compiler
-        __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
+        __builtin_amdgcn_s_waitcnt(BSC_LGKMCNT0);
         __builtin_amdgcn_sched_barrier(0);
         f32x4 acc[NSB];
-        const f32x4 yv = yv_n, ids_next = ids_n;
+        const f32x4 yv = w.yv_n, ids_next = w.ids_n;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
 #pragma unroll
-            for (int sb = 0; sb < NSB; ++sb) acc[sb][r] = q[r][sb];
+            for (int sb = 0; sb < NSB; ++sb) acc[sb][r] = w.q[r][sb];
         }
         // side DMAs of the tiles ahead, FIRST (DMA_SIDE = 6 of them): older than this tile's strips,
         // so the last strip wait of this tile also covers them
-        row_dma(y, (tile + n_waves) * XT, Y_OFF + (par ^ 1) * 256);
-        row_dma(g, (tile + 2 * n_waves) * XT, G_OFF + par * 256);
-        bz_dma(ids_next);
+        w.row_dma(y, (tile + n_waves) * XT, Y_OFF + (par ^ 1) * 256);
+        w.row_dma(g, (tile + 2 * n_waves) * XT, G_OFF + par * 256);
+        w.bz_dma(ids_next);
         int wo = lane;          // opaque once per tile: keeps the static B-operand reads inside the loop
         asm volatile("" : "+v"(wo));
         const bsc_u32x4* wp = wl + wo;
@@ -675,7 +595,7 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
             // `an`, `an2` (strips 2 jj, 2 jj + 1) were read a k-step ago, like this step's B operands: the wait finds them
             // done -- placed BEFORE the next step's reads are issued (see logreg_loglik_dma_kernel)
             if (jj > 0) {
-                __builtin_amdgcn_s_waitcnt(0xC07F);
+                __builtin_amdgcn_s_waitcnt(BSC_LGKMCNT0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             bsc_u32x4 b[NSB][SPLIT];
@@ -697,11 +617,11 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
             // DMA_WAIT: strips 2 jj + 2, 2 jj + 3 (of the next tile for jj = 7) must have landed.  LDS-DMA completes in
             // issue order: a strip issued in the previous tile (2 jj + 3 < XR) is followed by the rest of that batch,
             // this tile's side DMAs and this tile's 2 jj strips = XR - 4 + DMA_SIDE; one issued in this tile by XR - 4.
-            if (2 * jj + 3 < XR) __builtin_amdgcn_s_waitcnt(vmcnt_only(XR - 4 + DMA_SIDE));
-            else __builtin_amdgcn_s_waitcnt(vmcnt_only(XR - 4));
+            if (2 * jj + 3 < XR) __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(XR - 4 + DMA_SIDE));
+            else __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(XR - 4));
             asm volatile("" ::: "memory");
-            an = a_read((2 * jj + 2) % 16);
-            an2 = a_read((2 * jj + 3) % 16);
+            an = w.a_read((2 * jj + 2) % 16);
+            an2 = w.a_read((2 * jj + 3) % 16);
             __builtin_amdgcn_sched_barrier(0);
             // the A operand: eight f32 of the row as two bf16 terms
             bsc_u32x4 ah, am;
@@ -724,14 +644,14 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int j = 2 * jj + e;
-                if (j + XR < 16) x_dma(rs_cur, j + XR);
-                else x_dma(rs_next, j + XR - 16);
+                if (j + XR < 16) w.x_dma(rs_cur, j + XR);
+                else w.x_dma(rs_next, j + XR - 16);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         // the next tile's side data: its DMAs were this tile's first, and the last strip wait
         // (vmcnt <= XR - 2) has covered them; the epilogue below covers the LDS latency
-        side_read(par ^ 1);
+        w.side_read(par ^ 1);
         __builtin_amdgcn_sched_barrier(0);
         loglik_epilogue<NSB>(acc, yv, row0 + XT <= N, row0, N, kq, acc_ll);
         tile += n_waves;
@@ -743,10 +663,9 @@ __global__ __launch_bounds__(64 * XW, 2) void logreg_loglik_dma_bx_kernel(
         one_tile(1);
     }
     // no LDS-DMA of this wave may still be in flight when the workgroup's LDS is released
-    __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
+    __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     loglik_finish<NSB>(acc_ll, red, wave, lane, tid, S, slab);
-#undef BSC_LDS_B128
 }
 
 // ell[s] = sum over the workgroups' float64 partials, fixed order.  One wave per sample (a single

@@ -92,5 +92,3 @@ __device__ __forceinline__ unsigned bsc_img256_tr_addr(int lane, int r0, int c0)
 
 #define BSC_LDS_TR_B64(DST, ADDR, OFF) \
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
-#define BSC_LDS_B128(DST, ADDR, OFF) \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")

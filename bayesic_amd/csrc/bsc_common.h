@@ -247,6 +247,7 @@ __device__ __forceinline__ auto bsc_rows_rsrc(const float* X, int64_t ld, int wi
     const unsigned rec = xb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)xb;
     return __builtin_amdgcn_make_buffer_rsrc((void*)(X + (rem > 0 ? row0 : 0) * ld), 0, rec, 0x00020000);
 }
+typedef decltype(bsc_rows_rsrc(nullptr, 0, 0, 0, 0)) bsc_rsrc_t;
 // ... over a vector of 4-byte elements (one per row) from element `row0` on
 __device__ __forceinline__ auto bsc_vec_rsrc(const void* base, int64_t n, int64_t row0) {
     const int64_t rem = n - row0;
@@ -254,6 +255,48 @@ __device__ __forceinline__ auto bsc_vec_rsrc(const void* base, int64_t n, int64_
     const unsigned rec = b > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)b;
     return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + (rem > 0 ? row0 : 0) * 4), 0, rec, 0x00020000);
 }
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Reads of DMA'd bytes are inline asm: the compiler cannot tell the slots of a ring apart and would wait for
+// vmcnt(0) at every ds_read it can see next to a DMA in flight.  Valid after the next lgkmcnt(0), placed by hand.
+#define BSC_LDS_B128(DST, ADDR, OFF) \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
+#define BSC_LDS_B32(DST, ADDR, OFF) \
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
+
+// A wave's ring of 1-KiB slots for 16-row tiles of a row-major f32 matrix that arrive by LDS-DMA in WHOLE 128-byte
+// lines (csrc/bsc_bbvi.hip's two DMA kernels, gemm_skinny_nt_kernel).  Piece s = 2 c + sp of a tile is rows
+// 8 sp .. + 7 x columns 32 c .. + 31 (8 x 128 bytes; pieces shaped like one strip of MFMA operands, 16 rows x 64
+// bytes, read 23 % slower -- tools/ab_skinny_nt.py); lane l of the DMA = (row a = l >> 3, 16-byte position p = l & 7).
+// The 16-byte chunks of a row are XOR-permuted -- on the GLOBAL side, the fill stays lane-linear: the chunk fetched
+// into position p of row a is p ^ f, f = (a >> 1) | (sp << 2) (voff0 for sp = 0, voff1 for sp = 1).  That makes the
+// operand read of strip j = 2 c + t (the 16 columns of k-group j: lane (i16, kq) <- row i16, chunk kq + 4 t of column
+// block c) ONE ds_read_b128 free of bank conflicts in each of the instruction's four 16-lane groups: at addr0 (t = 0)
+// or addr1 = addr0 ^ 64 (t = 1), plus the offset of the slot that holds the block's piece sp = 0; piece sp = 1 is in
+// the slot behind it.  voff and addr must agree bit for bit, which is why they live together.  Which slot a piece
+// goes to, and the constant offsets of the reads, stay with the caller.  The constructor's i16 and kq MUST be
+// lane & 15 and lane >> 4; they come in as the kernels hold them because, derived from `lane` in here, the addresses
+// fold to other instructions and the kernels' set-up code moves.
+struct bsc_line_ring {
+    char* base;            // the wave's first slot
+    int row_bytes;         // distance of the matrix's rows
+    int voff0, voff1;      // the DMA's side, per lane: piece parity sp = 0, 1
+    unsigned addr0, addr1; // the reader's side, per lane: strip parity t = 0, 1
+    __device__ __forceinline__ bsc_line_ring(char* wave_base, int lane, int i16, int kq, int row_bytes_)
+        : base(wave_base), row_bytes(row_bytes_) {
+        const int ra = lane >> 3, rp = lane & 7;
+        voff0 = ra * row_bytes + 16 * (rp ^ (ra >> 1));
+        voff1 = ra * row_bytes + 16 * (rp ^ ((ra >> 1) | 4));
+        const int sp = i16 >> 3, ar = i16 & 7;
+        addr0 = (unsigned)(uintptr_t)(bsc_lds_ptr)base + 1024u * sp + 128u * ar + 16u * (kq ^ ((ar >> 1) | (sp << 2)));
+        addr1 = addr0 ^ 64u;
+    }
+    __device__ __forceinline__ void dma(bsc_rsrc_t rs, int piece, int slot) const {     // nt: the matrix is read once
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (bsc_lds_ptr)(base + slot * 1024), 16, (piece & 1) ? voff1 : voff0,
+                                                 (piece & 1) * 8 * row_bytes + 128 * (piece >> 1), 0, 2);
+    }
+};
 
 __device__ __forceinline__ float readlane_f32(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));

@@ -22,8 +22,6 @@ struct Dims {
     int64_t shape[MAXR];
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // streaming 16-byte load: the operands of a fused map are used once
 __device__ __forceinline__ float4 load4_nt(const float* p) {
     const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));

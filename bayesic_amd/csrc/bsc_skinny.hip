@@ -19,16 +19,10 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int SW = 8;          // waves per workgroup of the TN kernel (one workgroup per CU)
 constexpr int NTW = 4;         // ... of the NT kernel: one wave per SIMD streams faster (200 vs 236 us at 8 x 1M x 256)
 constexpr int ST = 16;         // rows of the large operand per wave tile
 constexpr int SR = 16;         // ring slots (1 KiB each) per wave: a whole tile ahead
-
-#define BSC_LDS_B128(DST, ADDR, OFF) \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
-#define BSC_LDS_B32(DST, ADDR, OFF) \
-    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
 
 // ---- NT: the large operand is B[n, k] (rows = n), 16-row tiles --------------------------------
 // v_mfma_f32_16x16x4_f32 with the SMALL matrix as the A operand: lane (i16, kq) holds A[m = 16 sb + i16][16 j + 4 kq + r]
@@ -37,11 +31,8 @@ constexpr int SR = 16;         // ring slots (1 KiB each) per wave: a whole tile
 // instruction writes 64-byte runs (with the operands the other way round a lane held four consecutive n of one m and a
 // store instruction was 64 separate 16-byte pieces: 54 of 226 us at 8 x 1M x 256, tools/ab_skinny_nt.py).
 //
-// The tile arrives by LDS-DMA in WHOLE 128-byte lines: piece s = 2 c + sp is rows 8 sp .. + 7 x columns 32 c .. + 31
-// (8 x 128 bytes; pieces of 16 rows x 64 bytes read 23 % slower, same tool), lane l of the DMA = (row l >> 3, 16-byte
-// position l & 7).  The 16-byte chunks of a row are XOR-permuted -- on the GLOBAL side, the fill stays lane-linear --
-// by f = (row >> 1) | (sp << 2), which makes the operand read (ds_read_b128, lane (i16, kq) <- row i16, chunk kq + 4 t
-// of column block c) free of bank conflicts in each of the instruction's four 16-lane groups.
+// The tile arrives by LDS-DMA in whole 128-byte lines, through bsc_line_ring (csrc/bsc_common.h: the piece shape and
+// the XOR image); piece s goes to slot s, so strip j = 2 c + t is read at addr_t + 2048 c.
 struct NtArgs {
     const float* A; int64_t sa_m, sa_k;     // small [M, K]
     const float* B; int64_t ldb;            // large [N, K], k-contiguous
@@ -77,30 +68,17 @@ __global__ __launch_bounds__(64 * NTW, 2) void gemm_skinny_nt_kernel(NtArgs a) {
     const int64_t n_waves = (int64_t)gridDim.x * NTW;
     int64_t tile = (int64_t)blockIdx.x * NTW + wave;
     const int64_t n_tiles = (a.N + ST - 1) / ST;
-    char* const my = ring + wave * SR * 1024;
-    // the DMA's side: row ra of the piece, position rp; the chunk fetched there is rp ^ f
-    const int ra = lane >> 3, rp = lane & 7;
-    const int row_bytes = (int)(a.ldb * 4);
-    const int voff0 = ra * row_bytes + 16 * (rp ^ (ra >> 1));
-    const int voff1 = ra * row_bytes + 16 * (rp ^ ((ra >> 1) | 4));
-    auto dma = [&](decltype(bsc_rows_rsrc(a.B, a.ldb, K, a.N, 0)) rs, int s) {      // piece s -> slot s
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (bsc_lds_ptr)(my + s * 1024), 16, (s & 1) ? voff1 : voff0,
-                                                 (s & 1) * 8 * row_bytes + 128 * (s >> 1), 0, 2);
-    };
-    // the reader's side: row i16 = (sp, a), chunk kq + 4 t: strip j = 2 c + t is at addr_t + 2048 c
-    const int sp = i16 >> 3, ar = i16 & 7;
-    const unsigned addr0 = (unsigned)(uintptr_t)(bsc_lds_ptr)my + 1024u * sp + 128u * ar + 16u * (kq ^ ((ar >> 1) | (sp << 2)));
-    const unsigned addr1 = addr0 ^ 64u;
+    const bsc_line_ring rg(ring + wave * SR * 1024, lane, i16, kq, (int)(a.ldb * 4));
 
     if (tile < n_tiles) {
         const auto rs = bsc_rows_rsrc(a.B, a.ldb, K, a.N, tile * ST);
 #pragma unroll
-        for (int s = 0; s < KS; ++s) dma(rs, s);
+        for (int s = 0; s < KS; ++s) rg.dma(rs, s, s);      // piece s -> slot s
     }
     __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(0));
     asm volatile("" ::: "memory");
     f32x4 an;
-    BSC_LDS_B128(an, addr0, 0);
+    BSC_LDS_B128(an, rg.addr0, 0);
 
     for (; tile < n_tiles; tile += n_waves) {
         const int64_t row0 = tile * ST;
@@ -127,7 +105,7 @@ __global__ __launch_bounds__(64 * NTW, 2) void gemm_skinny_nt_kernel(NtArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             f32x4 x = an;
             if (32 * c + 4 * kq >= K) x = f32x4{0.f, 0.f, 0.f, 0.f};     // columns past K (K % 32 != 0, or padded strips)
-            BSC_LDS_B128(an, addr1, c * 2048);
+            BSC_LDS_B128(an, rg.addr1, c * 2048);
             __builtin_amdgcn_sched_barrier(0);
             multiply(x, 2 * c);
             __builtin_amdgcn_sched_barrier(0);
@@ -141,11 +119,11 @@ __global__ __launch_bounds__(64 * NTW, 2) void gemm_skinny_nt_kernel(NtArgs a) {
             // counted here: a smaller count only waits for a few younger pieces as well, whatever order stores retire in
             __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(KS - 4));
             asm volatile("" ::: "memory");
-            BSC_LDS_B128(an, addr0, ((c + 1) % NCB) * 2048);
+            BSC_LDS_B128(an, rg.addr0, ((c + 1) % NCB) * 2048);
             __builtin_amdgcn_sched_barrier(0);
             multiply(x, 2 * c + 1);
-            dma(rs_next, 2 * c);            // both strips of the block are in registers: its two slots are free
-            dma(rs_next, 2 * c + 1);
+            rg.dma(rs_next, 2 * c, 2 * c);  // both strips of the block are in registers: its two slots are free
+            rg.dma(rs_next, 2 * c + 1, 2 * c + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
         // C[m = 16 sb + 4 kq + r][row0 + i16]
