@@ -67,7 +67,8 @@ struct XRow {
 };
 
 // lane l loads row (row0 + (l&31)): 16 floats; rows past the end and columns >= D read 0
-// NT: non-temporal loads (the default: X is read once).  Both half-waves load the SAME 32 rows -- the lower half
+// NT: non-temporal loads.  At D == 16 they are OFF by default (option mog_nt = 0, csrc/bsc_common.h; mog_nt = 1
+// selects them); the D < 16 kernel always uses them.  Both half-waves load the SAME 32 rows -- the lower half
 // contracts x, the upper x^2 -- and with the non-temporal policy the L2 does not keep a line for the second
 // requester: FETCH_SIZE reads 1.19 x the algorithmic bytes (profiles/pmc_traffic.json), 1.0 x with NT off
 // (BSC_MOG_NT=0, profiles/r03_pmc_mog_nt.txt); the kernel is MFMA-bound either way (HBM time 80 of 710 us).
@@ -95,8 +96,12 @@ __device__ __forceinline__ void load_rows(XRow& t, const float* __restrict__ X, 
 
 // VALU instructions issued between MFMAs cost the matrix pipe their full issue time on this
 // part (profiles/r01_ubench_mfma_valu_mix.txt), so the softmax is written for instruction
-// count: weights and biases are scaled by log2e once, so exp(l - m) is one subtract and one
-// v_exp_f32 (and a one-hot row stays exactly one-hot); the 1/sum of a row is folded into
+// count.  The logits are formed in NATURAL units from the weights and biases as they are given: scaling those by
+// log2e beforehand rounds every coefficient on its own, and a logit c - tau (x - mu)^2 / 2 is what is left of terms
+// thousands of times its size when the features are not centred, so those roundings (2^-24 of each TERM) do not
+// cancel -- 1e-4 of the bound term at |x| ~ 170 (tests/test_mixture_multi_tile_gpu.py).  exp(l - m) is one subtract
+// (exact where it matters: a one-hot row stays exactly one-hot), one multiply by log2e and one v_exp_f32, in
+// packed pairs; the 1/sum of a row is folded into
 // the backward B operand when the row is staged (x/sum and x^2/sum, 32 multiplies per tile)
 // rather than into its 64 responsibilities; row buffers alternate instead of being copied.
 template <bool FULL, bool NT>
@@ -121,7 +126,7 @@ __global__ __launch_bounds__(MOG_BLOCK, 2) void mog_estep_kernel(
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int comp = 32 * cb + drow(q, lane);
-            bias_q[cb][q] = comp < K ? cvec[comp] * LOG2E : -1.0e30f;
+            bias_q[cb][q] = comp < K ? cvec[comp] : -1.0e30f;
         }
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(MOG_BLOCK, 2) void mog_estep_kernel(
             const int d = f & (MD - 1);
             float v = 0.f;
             if (comp < K && d < D) v = Wmat[(int64_t)comp * 2 * D + (f < MD ? d : D + d)];
-            wreg[cb][s] = v * LOG2E;   // logits come out in log2 units: exp is v_exp_f32(l - m)
+            wreg[cb][s] = v;   // logits come out in natural units: exp is v_exp_f32((l - m) log2e)
         }
     }
 
@@ -179,13 +184,13 @@ __global__ __launch_bounds__(MOG_BLOCK, 2) void mog_estep_kernel(
         m = swap32_max(m);
         // Pairs of values go through v_pk_add / v_pk_fma / v_pk_mul: a packed instruction takes
         // the same ~5 cycles from the MFMA pipe as a scalar one (profiles/r01_ubench_mfma_valu_mix.txt)
-        const f32x2 m2 = {m, m};
+        const f32x2 m2 = {m, m}, log2e2 = {LOG2E, LOG2E};
         f32x2 ssum2 = {0.f, 0.f};
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int q = 0; q < 16; q += 2) {
-                const f32x2 d = f32x2{logit[cb][q], logit[cb][q + 1]} - m2;
+                const f32x2 d = (f32x2{logit[cb][q], logit[cb][q + 1]} - m2) * log2e2;
                 const f32x2 e = {__builtin_amdgcn_exp2f(d[0]), __builtin_amdgcn_exp2f(d[1])};
                 logit[cb][q] = e[0];
                 logit[cb][q + 1] = e[1];
@@ -193,7 +198,7 @@ __global__ __launch_bounds__(MOG_BLOCK, 2) void mog_estep_kernel(
             }
         const float ssum = swap32_sum(ssum2[0] + ssum2[1]);
         const float inv = valid ? 1.0f / ssum : 0.f;
-        if (valid && half == 0) lse_acc += LN2 * (m + __builtin_amdgcn_logf(ssum));
+        if (valid && half == 0) lse_acc += m + LN2 * __builtin_amdgcn_logf(ssum);
         // unnormalised e -> LDS as [row][comp] (registers 4g..4g+3 are 4 consecutive components);
         // R_k accumulates e * inv
         const f32x2 inv2 = {inv, inv};
@@ -309,7 +314,7 @@ __global__ __launch_bounds__(MOG_BLOCK, 2) void mog_estep_bx_kernel(
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int comp = 32 * cb + drow(q, lane);
-            bias_q[cb][q] = comp < K ? cvec[comp] * LOG2E : -1.0e30f;
+            bias_q[cb][q] = comp < K ? cvec[comp] : -1.0e30f;   // natural units, as in mog_estep_kernel
         }
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
@@ -320,7 +325,7 @@ __global__ __launch_bounds__(MOG_BLOCK, 2) void mog_estep_bx_kernel(
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int d = 8 * half + j;
-                w[j] = (comp < K && d < D) ? Wmat[(int64_t)comp * 2 * D + (ks ? D + d : d)] * LOG2E : 0.f;
+                w[j] = (comp < K && d < D) ? Wmat[(int64_t)comp * 2 * D + (ks ? D + d : d)] : 0.f;
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -430,12 +435,12 @@ __global__ __launch_bounds__(MOG_BLOCK, 2) void mog_estep_bx_kernel(
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                logit[cb][q] = __builtin_amdgcn_exp2f(logit[cb][q] - m);
+                logit[cb][q] = __builtin_amdgcn_exp2f((logit[cb][q] - m) * LOG2E);
                 ssum += logit[cb][q];
             }
         ssum = swap32_sum(ssum);
         const float inv = valid ? 1.0f / ssum : 0.f;
-        if (valid && half == 0) lse_acc += LN2 * (m + __builtin_amdgcn_logf(ssum));
+        if (valid && half == 0) lse_acc += m + LN2 * __builtin_amdgcn_logf(ssum);
         // ---- the responsibilities r = e / sum (two terms) and the features (the first two of the forward's three terms:
         // nothing to compute) to LDS.  Round 4: the 1 / sum went from the 16 features of a lane -- where it cost a second
         // split of x and x^2, 64 vector instructions -- to its 32 responsibilities (32 multiplies; packed ones were tried:
