@@ -68,10 +68,8 @@ const bsc_option OPTIONS[] = {
     {"blr_stamps", &bsc_ctx::blr_stamps, 0, 1, nullptr, false},
     {"fused_map_blocks_per_cu", &bsc_ctx::fused_map_blocks_per_cu, 1, 64, nullptr, false},
     {"fused_map_flat", &bsc_ctx::fused_map_flat, 0, 1, nullptr, false},
-    {"fused_map_unroll", &bsc_ctx::fused_map_unroll, 1, 2, nullptr, false},
     {"fused_nt_store", &bsc_ctx::fused_nt_store, 0, 1, nullptr, false},
     {"fused_waves_per_cu", &bsc_ctx::fused_waves_per_cu, 1, 64, nullptr, false},
-    {"gemm_pipe", &bsc_ctx::gemm_pipe, 0, 1, nullptr, false},
     {"gemm_skinny", &bsc_ctx::gemm_skinny, 0, 1, nullptr, false},
     {"gemm_fast", &bsc_ctx::gemm_fast, 0, 1, nullptr, false},
     {"gemm_dma", &bsc_ctx::gemm_dma, 0, 2, nullptr, false},

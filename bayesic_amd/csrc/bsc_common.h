@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -31,14 +32,12 @@ struct bsc_ctx {
     int skinny_nt_wg_per_cu = 1;      // gemm_skinny_nt_kernel: resident workgroups (4 waves, 64 KiB of rings each) per CU (BSC_SKINNY_NT_WG)
     int gemm_nt_c = 1;                // stream GEMM: results of 128 MiB and more leave by non-temporal stores (BSC_GEMM_NT_C=0 for A/B)
     int fused_map_flat = 1;           // pure maps with a contiguous float32 result: map_flat_f32_kernel (BSC_FUSED_MAP_FLAT=0: the round-1/2 kernels, for A/B)
-    int fused_map_unroll = 2;         // float4 per operand in flight per lane (1 | 2); 2 is +18% measured
     int gemm_fast = 1;                // GEMM: scalar-base loads for interior tiles (BSC_GEMM_FAST=0 turns them off)
     int gemm_skinny = 1;              // GEMM: the LDS-DMA kernels of csrc/bsc_skinny.hip for products with one tiny extent (BSC_GEMM_SKINNY=0 turns them off)
     int gemm_dma = 2;                 // GEMM: 2 = persistent stream-K on LDS-DMA operand tiles (gemm_f32_stream_kernel), 1 = one tile per workgroup with LDS-DMA operands (gemm_f32_dma_kernel), 0 = the register-staged kernel (BSC_GEMM_DMA)
     int lda_stream = 1;               // LDA statistic, K = 128: the persistent LDS-DMA kernel (BSC_LDA_STREAM=0: one column block per workgroup, register staging)
     int gemm_sym = 1;                 // GEMM: X^T X computes the tiles on and above the diagonal only (BSC_GEMM_SYM=0: all of them)
     int gemm_dbg = 0;                 // profiling only (BSC_GEMM_DBG): 1 = the stream kernel drops its whole-tile stores
-    int gemm_pipe = 1;                // GEMM: LDS operand reads one k-pair ahead of the MFMAs
     int fused_nt_store = 1;           // dense map: non-temporal stores of the result
     int bbvi_kernel = 1;         // bsc_logreg_bbvi_loglik (draws in LDS): 1 = X by LDS-DMA strips where eligible (S in 36..64, S % 4 == 0; X through VGPRs otherwise), 2 = X through VGPRs always
     int lda_dbg = 0;             // BSC_LDA_DBG: profiling-only deletion builds of the split-operand LDA kernel (1: no DMAs after the first two steps; 2: no arithmetic) -- wrong results
@@ -143,6 +142,23 @@ int bsc_gemm_skinny(bsc_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* 
             return bsc_fail(BSC_ERR_HIP, "kernel launch failed: %s (%s:%d)",     \
                             hipGetErrorString(err__), __FILE__, __LINE__);       \
     } while (0)
+
+// Kernel selection on the host: f receives the run-time flags (a count) as std::bool_constant (std::integral_constant)
+// arguments, so a launch site names its kernel once with them as template arguments: kernel<A(), B()>.
+template <class F>
+void bsc_with_flags(F&& f) { f(); }
+template <class F, class... Rest>
+void bsc_with_flags(F&& f, bool flag, Rest... rest) {
+    if (flag) bsc_with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else bsc_with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <int MAX, class F>
+void bsc_with_count(int n, F&& f) {      // n in 1 .. MAX; a larger n runs MAX
+    if constexpr (MAX > 1) {
+        if (n < MAX) return bsc_with_count<MAX - 1>(n, f);
+    }
+    f(std::integral_constant<int, MAX>{});
+}
 
 constexpr int BSC_WAVE = 64;
 

@@ -11,6 +11,7 @@
 // written.  Reductions accumulate in float64 in a fixed order (lane-strided
 // partial -> butterfly -> split partials summed in split order).
 #include "bsc_common.h"
+#include <algorithm>
 
 namespace {
 
@@ -933,13 +934,6 @@ void sort_axes(AxisGroup& g, int n_rows, int key) {
         }
 }
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 // every offset of the small map fits 32 bits, and pow (if any) is one of the cheap cases
 bool small_ok(const MapArgs& m, int rank, int n_in) {
     auto span = [&](const int64_t* strides) {
@@ -950,40 +944,58 @@ bool small_ok(const MapArgs& m, int rank, int n_in) {
         }
         return lo > -(int64_t(1) << 30) && hi < (int64_t(1) << 30);
     };
-    auto pow_ok = [](int op, double arg) {
-        return op != BSC_OP_POW || arg == -1.0 || arg == 2.0 || arg == 0.5 || arg == 1.0;
-    };
+    auto pow_ok = [](int op, double arg) { return op != BSC_OP_POW || arg == -1.0 || arg == 2.0 || arg == 0.5 || arg == 1.0; };
     if (!span(m.out_strides) || !pow_ok(m.post_op, m.post_arg)) return false;
     for (int k = 0; k < n_in; ++k)
         if (!span(m.keep_strides[k]) || !pow_ok(m.pre_op[k], m.pre_arg[k])) return false;
     return true;
 }
-}  // namespace
 
-extern "C" {
+// nothing after the combine, and before it copy, scale, abs, x^2, 1 / x or x^1 only: what the LINEAR instantiations inline
+bool linear_ops(const MapArgs& m, int n_in, int post_op) {
+    for (int k = 0; k < n_in; ++k) {
+        const int op = m.pre_op[k];
+        if (!(op == BSC_OP_COPY || op == BSC_OP_SCALE || op == BSC_OP_ABS ||
+              (op == BSC_OP_POW && (m.pre_arg[k] == 2.0 || m.pre_arg[k] == -1.0 || m.pre_arg[k] == 1.0))))
+            return false;
+    }
+    return post_op == BSC_OP_COPY;
+}
 
-int bsc_map_reduce(bsc_ctx* ctx, int dtype, int combine, int rank_keep,
-                   const int64_t* host_keep_shape, int rank_red, const int64_t* host_red_shape,
-                   int n_in, const void* const* host_in, const int64_t* host_in_keep_strides,
-                   const int64_t* host_in_red_strides, const int32_t* host_pre_op,
-                   const double* host_pre_arg, double scale, double shift, int post_op,
-                   double post_arg, void* out, const int64_t* host_out_strides) {
-    BSC_CHECK_CTX(ctx);
+// grid cap of the pure maps (256-thread blocks)
+int64_t map_grid_cap(const bsc_ctx* ctx) { return (int64_t)ctx->cu_count * ctx->fused_map_blocks_per_cu; }
+bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// A request after map_normalise: the kernels' arguments (a launch passes that part on), and what only the host looks at.
+struct MapCall : MapArgs {
+    int dtype;
+    bool special;      // lgamma / digamma among the ops: the generic kernels only
+    bool plain_f32() const { return !special && dtype == BSC_F32; }     // what every specialised kernel asks first
+};
+
+// the generic kernels: KERNEL<float | double, SPECIAL>
+#define BSC_LAUNCH_GENERIC(KERNEL, GRID, CTX, CALL)                                                                   \
+    bsc_with_flags([&](auto F32_, auto SPECIAL) {                                                                     \
+        hipLaunchKernelGGL((KERNEL<std::conditional_t<F32_(), float, double>, SPECIAL()>), dim3((unsigned)(GRID)),     \
+                           dim3(256), 0, (CTX)->stream, (const MapArgs&)(CALL));                                                    \
+    }, (CALL).dtype == BSC_F32, (CALL).special)
+
+// Validation, the axes sorted and coalesced, MapArgs filled (n_out == 0: nothing to run).
+int map_normalise(bsc_ctx* ctx, int dtype, int combine, int rank_keep, const int64_t* host_keep_shape, int rank_red,
+                  const int64_t* host_red_shape, int n_in, const void* const* host_in, const int64_t* host_in_keep_strides,
+                  const int64_t* host_in_red_strides, const int32_t* host_pre_op, const double* host_pre_arg, double scale,
+                  double shift, int post_op, double post_arg, void* out, const int64_t* host_out_strides, MapCall& m) {
     BSC_REQUIRE(dtype == BSC_F32 || dtype == BSC_F64, "bsc_map_reduce: unknown dtype %d", dtype);
-    BSC_REQUIRE(combine == BSC_OP_ADD || combine == BSC_OP_MUL,
-                "bsc_map_reduce: combine must be BSC_OP_ADD or BSC_OP_MUL, got %d", combine);
-    BSC_REQUIRE(rank_keep >= 0 && rank_keep <= MAXR && rank_red >= 0 && rank_red <= MAXR,
-                "bsc_map_reduce: rank exceeds %d", MAXR);
-    BSC_REQUIRE(n_in >= 1 && n_in <= MAXIN && host_in && host_pre_op && host_pre_arg && out,
-                "bsc_map_reduce: bad operands");
+    BSC_REQUIRE(combine == BSC_OP_ADD || combine == BSC_OP_MUL, "bsc_map_reduce: combine must be BSC_OP_ADD or BSC_OP_MUL, got %d", combine);
+    BSC_REQUIRE(rank_keep >= 0 && rank_keep <= MAXR && rank_red >= 0 && rank_red <= MAXR, "bsc_map_reduce: rank exceeds %d", MAXR);
+    BSC_REQUIRE(n_in >= 1 && n_in <= MAXIN && host_in && host_pre_op && host_pre_arg && out, "bsc_map_reduce: bad operands");
     auto unary_ok = [](int op) {
         return op == BSC_OP_COPY || op == BSC_OP_SCALE || op == BSC_OP_LOG || op == BSC_OP_EXP || op == BSC_OP_ABS ||
                op == BSC_OP_POW || op == BSC_OP_LGAMMA || op == BSC_OP_DIGAMMA;
     };
     BSC_REQUIRE(unary_ok(post_op), "bsc_map_reduce: post op %d is not unary", post_op);
     AxisGroup keep, red;
-    keep.rank = rank_keep;
-    red.rank = rank_red;
+    keep.rank = rank_keep; red.rank = rank_red;
     int64_t n_out = 1, n_red = 1;
     for (int a = 0; a < rank_keep; ++a) {
         BSC_REQUIRE(host_keep_shape[a] >= 0, "bsc_map_reduce: negative extent");
@@ -996,24 +1008,21 @@ int bsc_map_reduce(bsc_ctx* ctx, int dtype, int combine, int rank_keep,
         red.shape[a] = host_red_shape[a];
         n_red *= red.shape[a];
     }
-    MapArgs m{};
+    m.dtype = dtype;
+    m.special = post_op == BSC_OP_LGAMMA || post_op == BSC_OP_DIGAMMA;
     for (int k = 0; k < n_in; ++k) {
         BSC_REQUIRE(host_in[k] != nullptr || n_out * n_red == 0, "bsc_map_reduce: input %d is null", k);
         BSC_REQUIRE(unary_ok(host_pre_op[k]), "bsc_map_reduce: pre op %d is not unary", host_pre_op[k]);
-        m.in[k] = host_in[k];
-        m.pre_op[k] = host_pre_op[k];
-        m.pre_arg[k] = host_pre_arg[k];
+        m.in[k] = host_in[k]; m.pre_op[k] = host_pre_op[k]; m.pre_arg[k] = host_pre_arg[k];
         for (int a = 0; a < rank_keep; ++a) keep.strides[k][a] = host_in_keep_strides[k * rank_keep + a];
         for (int a = 0; a < rank_red; ++a) red.strides[k][a] = host_in_red_strides[k * rank_red + a];
+        m.special = m.special || host_pre_op[k] == BSC_OP_LGAMMA || host_pre_op[k] == BSC_OP_DIGAMMA;
     }
+    m.n_out = n_out;
     if (n_out == 0) return BSC_OK;
-    bool special = post_op == BSC_OP_LGAMMA || post_op == BSC_OP_DIGAMMA;
-    for (int k = 0; k < n_in; ++k)
-        special = special || host_pre_op[k] == BSC_OP_LGAMMA || host_pre_op[k] == BSC_OP_DIGAMMA;
     sort_axes(keep, n_in + 1, n_in);                  // by the output's strides
     if (red.rank > 1) {                               // by the strides of the biggest operand
-        int key = 0;
-        int64_t best = -1;
+        int key = 0; int64_t best = -1;
         for (int k = 0; k < n_in; ++k) {
             int64_t span = 0;
             for (int a = 0; a < red.rank; ++a) span += iabs(red.strides[k][a]) * (red.shape[a] - 1);
@@ -1021,10 +1030,8 @@ int bsc_map_reduce(bsc_ctx* ctx, int dtype, int combine, int rank_keep,
         }
         sort_axes(red, n_in, key);
     }
-    coalesce(keep, n_in + 1);
-    coalesce(red, n_in);
-    m.keep.rank = keep.rank;
-    m.red.rank = red.rank;
+    coalesce(keep, n_in + 1); coalesce(red, n_in);
+    m.keep.rank = keep.rank; m.red.rank = red.rank;
     for (int a = 0; a < MAXR; ++a) {
         m.keep.shape[a] = a < keep.rank ? keep.shape[a] : 1;
         m.red.shape[a] = a < red.rank ? red.shape[a] : 1;
@@ -1034,351 +1041,341 @@ int bsc_map_reduce(bsc_ctx* ctx, int dtype, int combine, int rank_keep,
             m.red_strides[k][a] = a < red.rank ? red.strides[k][a] : 0;
         }
     }
-    m.n_out = n_out;
-    m.n_red = n_red;
-    m.n_in = n_in;
-    m.combine = combine;
-    m.post_op = post_op;
-    m.post_arg = post_arg;
-    m.scale = scale;
-    m.shift = shift;
-    m.out = out;
-    m.splits = 1;
-    m.partial = nullptr;
-    m.nt_store = ctx->fused_nt_store;
+    m.n_red = n_red; m.n_in = n_in; m.combine = combine;
+    m.post_op = post_op; m.post_arg = post_arg; m.scale = scale; m.shift = shift;
+    m.out = out; m.splits = 1; m.partial = nullptr; m.nt_store = ctx->fused_nt_store;
+    return BSC_OK;
+}
 
-    if (rank_red == 0) {
-        // ---- pure map ----
-        // the flat kernel: contiguous float32 result, operands dense / one value / row vector / one value per row
-        if (!special && dtype == BSC_F32 && n_in <= 4 && n_out >= 4096 && n_out % 4 == 0 && n_out / 4 < ((int64_t)1 << 31) &&
-            (((uintptr_t)out) & 15) == 0 && ctx->fused_map_flat &&
-            (keep.rank == 1 ? m.out_strides[0] == 1
-                            : keep.rank == 2 && m.out_strides[1] == 1 && m.out_strides[0] == keep.shape[1] && keep.shape[1] % 4 == 0)) {
-            FlatArgs f{};
-            const int64_t C = keep.rank == 2 ? keep.shape[1] : n_out;
-            bool ok = true, linear = post_op == BSC_OP_COPY;
-            for (int k = 0; k < n_in && ok; ++k) {
-                const int64_t s0 = keep.rank == 2 ? m.keep_strides[k][0] : 0, s1 = m.keep_strides[k][keep.rank - 1];
-                int kind = -1;
-                if (keep.rank == 1) kind = s1 == 1 ? 0 : s1 == 0 ? 1 : -1;
-                else if (s0 == C && s1 == 1) kind = 0;
-                else if (s0 == 0 && s1 == 0) kind = 1;
-                else if (s0 == 0 && s1 == 1) kind = 2;
-                else if (s0 == 1 && s1 == 0) kind = 3;
-                if (kind < 0 || ((kind == 0 || kind == 2) && (((uintptr_t)m.in[k]) & 15) != 0)) ok = false;
-                f.in[k] = (const float*)m.in[k];
-                f.kind[k] = kind;
-                f.op[k] = m.pre_op[k];
-                f.arg[k] = (float)m.pre_arg[k];
-                const int op = m.pre_op[k];
-                if (!(op == BSC_OP_COPY || op == BSC_OP_SCALE || op == BSC_OP_ABS ||
-                      (op == BSC_OP_POW && (m.pre_arg[k] == 2.0 || m.pre_arg[k] == -1.0 || m.pre_arg[k] == 1.0))))
-                    linear = false;
-            }
-            if (ok) {
-                f.out = (float*)out;
-                f.n4 = (unsigned)(n_out / 4);
-                f.c4 = (unsigned)(C / 4);
-                f.combine = combine; f.post_op = post_op; f.nt_store = m.nt_store;
-                f.scale = (float)scale; f.shift = (float)shift; f.post_arg = (float)post_arg;
-                const unsigned blocks = (f.n4 + 1023u) / 1024u;
-#define BSC_FLAT(N_)                                                                                                   \
-    do {                                                                                                               \
-        if (linear) hipLaunchKernelGGL((map_flat_f32_kernel<N_, true>), dim3(blocks), dim3(256), 0, ctx->stream, f);   \
-        else hipLaunchKernelGGL((map_flat_f32_kernel<N_, false>), dim3(blocks), dim3(256), 0, ctx->stream, f);         \
-    } while (0)
-                switch (n_in) {
-                    case 1: BSC_FLAT(1); break;
-                    case 2: BSC_FLAT(2); break;
-                    case 3: BSC_FLAT(3); break;
-                    default: BSC_FLAT(4); break;
-                }
-#undef BSC_FLAT
-                BSC_LAUNCH_CHECK();
-                return BSC_OK;
-            }
-        }
-        bool dense = !special && dtype == BSC_F32 && keep.rank <= 1 && (n_out % 4) == 0 &&
-                     (((uintptr_t)out) & 15) == 0 && (keep.rank == 0 || m.out_strides[0] == 1);
-        int scalar_mask = 0;
-        for (int k = 0; k < n_in && dense; ++k) {
-            const int64_t s = keep.rank ? m.keep_strides[k][0] : 0;
-            if (s == 0) scalar_mask |= 1 << k;
-            else if (s != 1 || (((uintptr_t)m.in[k]) & 15) != 0) dense = false;
-        }
-        // a narrow [R, C] result (or more than three operands) whose operands are dense, one scalar,
-        // or a C-vector repeated down the rows (biases: dimshuffle(v, 'x', 0)): the flat dense kernel
-        // with periodic operands -- the row kernel below gives a whole wave to 64 columns
-        if (!dense && !special && dtype == BSC_F32 && keep.rank == 2 && m.out_strides[1] == 1 &&
-            m.out_strides[0] == keep.shape[1] && keep.shape[1] % 4 == 0 && keep.shape[1] <= (1 << 20) &&
-            (keep.shape[1] < 256 || n_in > 3) && (((uintptr_t)out) & 15) == 0) {
-            const int64_t C = keep.shape[1];
-            int smask = 0, pmask = 0;
-            bool ok = true;
-            for (int k = 0; k < n_in && ok; ++k) {
-                const int64_t s0 = m.keep_strides[k][0], s1 = m.keep_strides[k][1];
-                if (s0 == 0 && s1 == 0) smask |= 1 << k;
-                else if ((((uintptr_t)m.in[k]) & 15) != 0) ok = false;
-                else if (s0 == 0 && s1 == 1) pmask |= 1 << k;
-                else if (!(s0 == C && s1 == 1)) ok = false;
-            }
-            if (ok) {
-                const int64_t n4 = n_out / 4;
-                int64_t blocks = (n4 + 255) / 256;
-                const int64_t cap = (int64_t)ctx->cu_count * ctx->fused_map_blocks_per_cu;
-                if (blocks > cap) blocks = cap;
-                hipLaunchKernelGGL(map_dense_f32_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, m,
-                                   n4, smask, pmask, (int)(C / 4));
-                BSC_LAUNCH_CHECK();
-                return BSC_OK;
-            }
-        }
-        // two kept axes with row / column broadcasts
-        bool rows2d = !dense && !special && dtype == BSC_F32 && keep.rank == 2 && n_in <= 3 &&
-                      keep.shape[1] % 4 == 0 && keep.shape[1] >= 64 && m.out_strides[1] == 1 &&
-                      m.out_strides[0] % 4 == 0 && (((uintptr_t)out) & 15) == 0;
-        int bmask = 0;
-        for (int k = 0; k < n_in && rows2d; ++k) {
-            const int64_t sc = m.keep_strides[k][1];
-            if (sc == 0) bmask |= 1 << k;
-            else if (sc != 1 || m.keep_strides[k][0] % 4 != 0 || (((uintptr_t)m.in[k]) & 15) != 0)
-                rows2d = false;
-        }
-        if (rows2d) {
-            m.bcast = bmask;
-            int64_t blocks = (keep.shape[0] + 7) / 8;          // 4 waves x 2 rows per step
-            const int64_t cap = (int64_t)ctx->cu_count * ctx->fused_map_blocks_per_cu;
-            if (blocks > cap) blocks = cap;
-            if (blocks < 1) blocks = 1;
-            // few rows (an 8 x 1M matrix of per-sample values): also split the columns, or
-            // eight waves would walk 32 MB alone (10 ms instead of ~20 us)
-            int64_t chunks = 1;
-            if (blocks < cap) {
-                chunks = (cap + blocks - 1) / blocks;
-                const int64_t max_chunks = (keep.shape[1] + 1023) / 1024;      // >= 1024 columns per chunk
-                if (chunks > max_chunks) chunks = max_chunks;
-                if (chunks > 65535) chunks = 65535;
-                if (chunks < 1) chunks = 1;
-            }
-            m.col_chunk = ((keep.shape[1] + chunks - 1) / chunks + 255) / 256 * 256;
-            chunks = (keep.shape[1] + m.col_chunk - 1) / m.col_chunk;
-            const dim3 rgrid((unsigned)blocks, (unsigned)chunks);
-            switch (n_in) {
-                case 1: hipLaunchKernelGGL(map_rows_f32_kernel<1>, rgrid, dim3(256), 0, ctx->stream, m); break;
-                case 2: hipLaunchKernelGGL(map_rows_f32_kernel<2>, rgrid, dim3(256), 0, ctx->stream, m); break;
-                default: hipLaunchKernelGGL(map_rows_f32_kernel<3>, rgrid, dim3(256), 0, ctx->stream, m); break;
-            }
-            BSC_LAUNCH_CHECK();
-            return BSC_OK;
-        }
-        if (dense && n_out >= 4) {
-            const int64_t n4 = n_out / 4;
-            int64_t blocks = (n4 + 255) / 256;
-            const int64_t cap = (int64_t)ctx->cu_count * ctx->fused_map_blocks_per_cu;
-            if (blocks > cap) blocks = cap;
-            if (ctx->fused_map_unroll == 1)
-                hipLaunchKernelGGL(map_dense_f32_kernel<1>, dim3((unsigned)blocks), dim3(256), 0,
-                                   ctx->stream, m, n4, scalar_mask);
-            else
-                hipLaunchKernelGGL(map_dense_f32_kernel<2>, dim3((unsigned)blocks), dim3(256), 0,
-                                   ctx->stream, m, n4, scalar_mask);
-        } else if (!special && dtype == BSC_F32 && keep.rank <= 2 && n_out <= (1 << 20) && n_in <= 4 && small_ok(m, keep.rank, n_in)) {
-            const unsigned blocks = (unsigned)((n_out + 255) / 256);
-            switch (n_in) {
-                case 1: hipLaunchKernelGGL(map_small_f32_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, m); break;
-                case 2: hipLaunchKernelGGL(map_small_f32_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, m); break;
-                case 3: hipLaunchKernelGGL(map_small_f32_kernel<3>, dim3(blocks), dim3(256), 0, ctx->stream, m); break;
-                default: hipLaunchKernelGGL(map_small_f32_kernel<4>, dim3(blocks), dim3(256), 0, ctx->stream, m); break;
-            }
-        } else {
-            int64_t blocks = (n_out + 255) / 256;
-            const int64_t cap = (int64_t)ctx->cu_count * 8;
-            if (blocks > cap) blocks = cap;
-#define BSC_GENERIC(KERNEL, GRID)                                                              \
-    do {                                                                                       \
-        if (dtype == BSC_F32 && special)                                                       \
-            hipLaunchKernelGGL((KERNEL<float, true>), dim3((unsigned)(GRID)), dim3(256), 0, ctx->stream, m);  \
-        else if (dtype == BSC_F32)                                                             \
-            hipLaunchKernelGGL((KERNEL<float, false>), dim3((unsigned)(GRID)), dim3(256), 0, ctx->stream, m); \
-        else if (special)                                                                      \
-            hipLaunchKernelGGL((KERNEL<double, true>), dim3((unsigned)(GRID)), dim3(256), 0, ctx->stream, m); \
-        else                                                                                   \
-            hipLaunchKernelGGL((KERNEL<double, false>), dim3((unsigned)(GRID)), dim3(256), 0, ctx->stream, m); \
-    } while (0)
-            BSC_GENERIC(map_strided_kernel, blocks);
-        }
-        BSC_LAUNCH_CHECK();
+// ---- pure maps, in the order map_pure tries them: each takes the request (*took = 1) or declines it ----
+// the flat kernel: contiguous float32 result, operands dense / one value / row vector / one value per row
+int map_flat(bsc_ctx* ctx, const MapCall& m, int* took) {
+    const int rank = m.keep.rank, n_in = m.n_in;
+    if (!(m.plain_f32() && n_in <= 4 && m.n_out >= 4096 && m.n_out % 4 == 0 && m.n_out / 4 < ((int64_t)1 << 31) && aligned16(m.out) &&
+          ctx->fused_map_flat &&
+          (rank == 1 ? m.out_strides[0] == 1
+                     : rank == 2 && m.out_strides[1] == 1 && m.out_strides[0] == m.keep.shape[1] && m.keep.shape[1] % 4 == 0)))
         return BSC_OK;
+    FlatArgs f{};
+    const int64_t C = rank == 2 ? m.keep.shape[1] : m.n_out;
+    for (int k = 0; k < n_in; ++k) {
+        const int64_t s0 = rank == 2 ? m.keep_strides[k][0] : 0, s1 = m.keep_strides[k][rank - 1];
+        int kind = -1;
+        if (rank == 1) kind = s1 == 1 ? 0 : s1 == 0 ? 1 : -1;
+        else if (s0 == C && s1 == 1) kind = 0;
+        else if (s0 == 0 && s1 == 0) kind = 1;
+        else if (s0 == 0 && s1 == 1) kind = 2;
+        else if (s0 == 1 && s1 == 0) kind = 3;
+        if (kind < 0 || ((kind == 0 || kind == 2) && !aligned16(m.in[k]))) return BSC_OK;
+        f.in[k] = (const float*)m.in[k]; f.kind[k] = kind;
+        f.op[k] = m.pre_op[k]; f.arg[k] = (float)m.pre_arg[k];
     }
+    *took = 1;
+    const bool linear = linear_ops(m, n_in, m.post_op);
+    f.out = (float*)m.out; f.n4 = (unsigned)(m.n_out / 4); f.c4 = (unsigned)(C / 4);
+    f.combine = m.combine; f.post_op = m.post_op; f.nt_store = m.nt_store;
+    f.scale = (float)m.scale; f.shift = (float)m.shift; f.post_arg = (float)m.post_arg;
+    const unsigned blocks = (f.n4 + 1023u) / 1024u;
+    bsc_with_count<4>(n_in, [&](auto NV) {
+        if (linear) hipLaunchKernelGGL((map_flat_f32_kernel<NV(), true>), dim3(blocks), dim3(256), 0, ctx->stream, f);
+        else hipLaunchKernelGGL((map_flat_f32_kernel<NV(), false>), dim3(blocks), dim3(256), 0, ctx->stream, f);
+    });
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
 
-    // ---- map + reduce: which axis of the BIGGEST operand varies fastest? ----
-    // (a broadcast vector riding along -- sum_n f(X)_nd u_n -- must not decide the access
-    // pattern of the matrix it multiplies)
-    int big = 0;
-    double big_elems = -1.0;
+// every operand dense in the output's order or one value (bit k of *scalar_mask), the result contiguous
+bool map_is_dense(const MapCall& m, int* scalar_mask) {
+    if (!(m.plain_f32() && m.keep.rank <= 1 && (m.n_out % 4) == 0 && aligned16(m.out) && (m.keep.rank == 0 || m.out_strides[0] == 1)))
+        return false;
+    for (int k = 0; k < m.n_in; ++k) {
+        const int64_t s = m.keep.rank ? m.keep_strides[k][0] : 0;
+        if (s == 0) *scalar_mask |= 1 << k;
+        else if (s != 1 || !aligned16(m.in[k])) return false;
+    }
+    return true;
+}
+
+// a narrow [R, C] result (or more than three operands) whose operands are dense, one scalar,
+// or a C-vector repeated down the rows (biases: dimshuffle(v, 'x', 0)): the flat dense kernel
+// with periodic operands -- the row kernel below gives a whole wave to 64 columns
+int map_periodic(bsc_ctx* ctx, const MapCall& m, int* took) {
+    const int64_t C = m.keep.shape[1];
+    if (!(m.plain_f32() && m.keep.rank == 2 && m.out_strides[1] == 1 && m.out_strides[0] == C && C % 4 == 0 && C <= (1 << 20) &&
+          (C < 256 || m.n_in > 3) && aligned16(m.out)))
+        return BSC_OK;
+    int smask = 0, pmask = 0;
+    for (int k = 0; k < m.n_in; ++k) {
+        const int64_t s0 = m.keep_strides[k][0], s1 = m.keep_strides[k][1];
+        if (s0 == 0 && s1 == 0) smask |= 1 << k;
+        else if (!aligned16(m.in[k])) return BSC_OK;
+        else if (s0 == 0 && s1 == 1) pmask |= 1 << k;
+        else if (!(s0 == C && s1 == 1)) return BSC_OK;
+    }
+    *took = 1;
+    const int64_t n4 = m.n_out / 4, blocks = std::min((n4 + 255) / 256, map_grid_cap(ctx));
+    hipLaunchKernelGGL(map_dense_f32_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, m, n4, smask, pmask, (int)(C / 4));
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
+// two kept axes with row / column broadcasts
+int map_rows2d(bsc_ctx* ctx, MapCall& m, int* took) {
+    const int64_t R = m.keep.shape[0], C = m.keep.shape[1];
+    if (!(m.plain_f32() && m.keep.rank == 2 && m.n_in <= 3 && C % 4 == 0 && C >= 64 && m.out_strides[1] == 1 &&
+          m.out_strides[0] % 4 == 0 && aligned16(m.out)))
+        return BSC_OK;
+    int bmask = 0;
+    for (int k = 0; k < m.n_in; ++k) {
+        const int64_t sc = m.keep_strides[k][1];
+        if (sc == 0) bmask |= 1 << k;
+        else if (sc != 1 || m.keep_strides[k][0] % 4 != 0 || !aligned16(m.in[k])) return BSC_OK;
+    }
+    *took = 1;
+    m.bcast = bmask;
+    int64_t blocks = (R + 7) / 8;          // 4 waves x 2 rows per step
+    const int64_t cap = map_grid_cap(ctx);
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    // few rows (an 8 x 1M matrix of per-sample values): also split the columns, or
+    // eight waves would walk 32 MB alone (10 ms instead of ~20 us)
+    int64_t chunks = 1;
+    if (blocks < cap) {
+        chunks = (cap + blocks - 1) / blocks;
+        const int64_t max_chunks = (C + 1023) / 1024;      // >= 1024 columns per chunk
+        if (chunks > max_chunks) chunks = max_chunks;
+        if (chunks > 65535) chunks = 65535;
+        if (chunks < 1) chunks = 1;
+    }
+    m.col_chunk = ((C + chunks - 1) / chunks + 255) / 256 * 256;
+    chunks = (C + m.col_chunk - 1) / m.col_chunk;
+    const dim3 rgrid((unsigned)blocks, (unsigned)chunks);
+    bsc_with_count<3>(m.n_in, [&](auto NV) {
+        hipLaunchKernelGGL(map_rows_f32_kernel<NV()>, rgrid, dim3(256), 0, ctx->stream, m);
+    });
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
+// 16 bytes per lane, two float4 per operand in flight (n_out is a positive multiple of 4)
+int map_dense(bsc_ctx* ctx, const MapArgs& m, int scalar_mask) {
+    const int64_t n4 = m.n_out / 4, blocks = std::min((n4 + 255) / 256, map_grid_cap(ctx));
+    hipLaunchKernelGGL(map_dense_f32_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, m, n4, scalar_mask);
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
+// up to 2^20 outputs of any layout, 32-bit offsets
+int map_small(bsc_ctx* ctx, const MapCall& m, int* took) {
+    if (!(m.plain_f32() && m.keep.rank <= 2 && m.n_out <= (1 << 20) && m.n_in <= 4 && small_ok(m, m.keep.rank, m.n_in))) return BSC_OK;
+    *took = 1;
+    const unsigned blocks = (unsigned)((m.n_out + 255) / 256);
+    bsc_with_count<4>(m.n_in, [&](auto NV) {
+        hipLaunchKernelGGL(map_small_f32_kernel<NV()>, dim3(blocks), dim3(256), 0, ctx->stream, m);
+    });
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
+// whatever is left: float64, lgamma / digamma, more than two kept axes
+int map_strided(bsc_ctx* ctx, const MapCall& m) {
+    int64_t blocks = (m.n_out + 255) / 256;
+    const int64_t cap = (int64_t)ctx->cu_count * 8;
+    if (blocks > cap) blocks = cap;
+    BSC_LAUNCH_GENERIC(map_strided_kernel, blocks, ctx, m);
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
+int map_pure(bsc_ctx* ctx, MapCall& m) {
+    int took = 0, rc, scalar_mask = 0;
+    if ((rc = map_flat(ctx, m, &took)) != BSC_OK || took) return rc;
+    const bool dense = map_is_dense(m, &scalar_mask);
+    if (!dense && ((rc = map_periodic(ctx, m, &took)) != BSC_OK || took)) return rc;
+    if (!dense && ((rc = map_rows2d(ctx, m, &took)) != BSC_OK || took)) return rc;
+    if (dense) return map_dense(ctx, m, scalar_mask);
+    if ((rc = map_small(ctx, m, &took)) != BSC_OK || took) return rc;
+    return map_strided(ctx, m);
+}
+
+// ---- map + reduce ----
+struct ReducePlan {
+    bool lanes_over_outputs;     // consecutive lanes take consecutive outputs (else a wave per output)
+    bool dense_lane, dense_wave; // the 16-bytes-per-lane variants: one reduce axis, and for the lane variant one kept axis
+    bool narrow_lane;            // dense_lane with several rows per wave load
+    int64_t jobs, splits;        // blocks per split (lane kernels), ranges the reduce axis is cut into
+};
+
+// Which kernel family reduces, and in how many splits; sets m.bcast, m.lanes_per_row and m.splits.
+ReducePlan reduce_plan(const bsc_ctx* ctx, MapCall& m) {
+    const int n_in = m.n_in;
+    const int64_t n_out = m.n_out, n_red = m.n_red;
+    // which axis of the BIGGEST operand varies fastest?  (a broadcast vector riding along -- sum_n f(X)_nd u_n --
+    // must not decide the access pattern of the matrix it multiplies)
+    int big = 0; double big_elems = -1.0;
     for (int k = 0; k < n_in; ++k) {
         double elems = 1.0;
-        for (int a = 0; a < keep.rank; ++a) if (m.keep_strides[k][a] != 0) elems *= (double)m.keep.shape[a];
-        for (int a = 0; a < red.rank; ++a) if (m.red_strides[k][a] != 0) elems *= (double)m.red.shape[a];
+        for (int a = 0; a < m.keep.rank; ++a) if (m.keep_strides[k][a] != 0) elems *= (double)m.keep.shape[a];
+        for (int a = 0; a < m.red.rank; ++a) if (m.red_strides[k][a] != 0) elems *= (double)m.red.shape[a];
         if (elems > big_elems) { big_elems = elems; big = k; }
     }
     int64_t min_keep = INT64_MAX, min_red = INT64_MAX;
-    for (int a = 0; a < keep.rank; ++a) {
+    for (int a = 0; a < m.keep.rank; ++a) {
         const int64_t st = iabs(m.keep_strides[big][a]);
         if (st != 0 && st < min_keep) min_keep = st;
     }
-    for (int a = 0; a < red.rank; ++a) {
+    for (int a = 0; a < m.red.rank; ++a) {
         const int64_t st = iabs(m.red_strides[big][a]);
         if (st != 0 && st < min_red) min_red = st;
     }
-    const bool lanes_over_outputs = min_keep < min_red && n_out >= 16;
-    // dense variants (16 B per lane): one reduce axis, and for the lane variant one kept axis
-    bool dense_lane = !special && lanes_over_outputs && dtype == BSC_F32 && n_in <= 3 && keep.rank == 1 && red.rank == 1 &&
-                      (n_out % 4) == 0 && m.out_strides[0] == 1;
-    bool dense_wave = !special && !lanes_over_outputs && dtype == BSC_F32 && n_in <= 3 && red.rank == 1 &&
-                      (n_red % 4) == 0;
+    ReducePlan p;
+    p.lanes_over_outputs = min_keep < min_red && n_out >= 16;
+    p.dense_lane = m.plain_f32() && p.lanes_over_outputs && n_in <= 3 && m.keep.rank == 1 && m.red.rank == 1 && (n_out % 4) == 0 &&
+                   m.out_strides[0] == 1;
+    p.dense_wave = m.plain_f32() && !p.lanes_over_outputs && n_in <= 3 && m.red.rank == 1 && (n_red % 4) == 0;
     int bmask = 0;
     for (int k = 0; k < n_in; ++k) {
-        if (dense_lane) {
+        if (p.dense_lane) {
             const int64_t sk = m.keep_strides[k][0];
             if (sk == 0) bmask |= 1 << k;                         // one value per reduced row
-            else if (sk != 1 || (((uintptr_t)m.in[k]) & 15) != 0 || m.red_strides[k][0] % 4 != 0)
-                dense_lane = false;
+            else if (sk != 1 || !aligned16(m.in[k]) || m.red_strides[k][0] % 4 != 0) p.dense_lane = false;
         }
-        if (dense_wave) {
+        if (p.dense_wave) {
             const int64_t sr = m.red_strides[k][0];
             if (sr == 0) bmask |= 1 << k;                         // one value per output
             else {
-                if (sr != 1 || (((uintptr_t)m.in[k]) & 15) != 0) dense_wave = false;
-                for (int a = 0; a < keep.rank; ++a)
-                    if (m.keep_strides[k][a] % 4 != 0) dense_wave = false;
+                if (sr != 1 || !aligned16(m.in[k])) p.dense_wave = false;
+                for (int a = 0; a < m.keep.rank; ++a)
+                    if (m.keep_strides[k][a] % 4 != 0) p.dense_wave = false;
             }
         }
     }
-    if (bmask == (1 << n_in) - 1) dense_lane = dense_wave = false;   // nothing streams
-    m.bcast = (dense_lane || dense_wave) ? bmask : 0;
-    // split the reduce range until about fused_waves_per_cu waves per CU are in flight
-    // (a block is 4 waves: 4 (output, split) jobs in the wave kernels, one output group
-    // in the lane kernels)
-    const bool narrow_lane = dense_lane && n_out <= 128;       // several rows per wave load
-    m.lanes_per_row = narrow_lane ? (int)(n_out / 4) : 0;
-    const int64_t outs_per_block = lanes_over_outputs ? (dense_lane ? 256 : 64) : 4;
-    const int64_t jobs = (n_out + outs_per_block - 1) / outs_per_block;
-    int64_t splits = 1;
+    if (bmask == (1 << n_in) - 1) p.dense_lane = p.dense_wave = false;   // nothing streams
+    m.bcast = (p.dense_lane || p.dense_wave) ? bmask : 0;
+    // split the reduce range until about fused_waves_per_cu waves per CU are in flight (a block is 4 waves:
+    // 4 (output, split) jobs in the wave kernels, one output group in the lane kernels)
+    p.narrow_lane = p.dense_lane && n_out <= 128;
+    m.lanes_per_row = p.narrow_lane ? (int)(n_out / 4) : 0;
+    const int64_t outs_per_block = p.lanes_over_outputs ? (p.dense_lane ? 256 : 64) : 4;
+    p.jobs = (n_out + outs_per_block - 1) / outs_per_block;
+    p.splits = 1;
     const int64_t want_blocks = (int64_t)ctx->cu_count * ctx->fused_waves_per_cu / 4;
-    if (jobs < want_blocks) {
-        splits = lanes_over_outputs ? want_blocks / jobs : (want_blocks * 4) / n_out;
-        const int64_t max_splits = n_red / (narrow_lane ? 16 * (64 / m.lanes_per_row) * 4 : lanes_over_outputs ? 64 : 4096);
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-        if (splits > 16384) splits = 16384;
+    if (p.jobs < want_blocks) {
+        p.splits = p.lanes_over_outputs ? want_blocks / p.jobs : (want_blocks * 4) / n_out;
+        const int64_t max_splits = n_red / (p.narrow_lane ? 16 * (64 / m.lanes_per_row) * 4 : p.lanes_over_outputs ? 64 : 4096);
+        if (p.splits > max_splits) p.splits = max_splits;
+        if (p.splits < 1) p.splits = 1;
+        if (p.splits > 16384) p.splits = 16384;
     }
-    m.splits = (int)splits;
-    if (splits > 1) {
+    m.splits = (int)p.splits;
+    return p;
+}
+
+void reduce_narrow_lane(bsc_ctx* ctx, const MapArgs& m, int64_t blocks) {
+    bsc_with_count<3>(m.n_in, [&](auto NV) {
+        hipLaunchKernelGGL(map_reduce_lane_narrow_f32_kernel<NV()>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, m);
+    });
+}
+
+void reduce_dense_lane(bsc_ctx* ctx, const MapArgs& m, int64_t blocks) {
+    const bool lin = ctx->fused_map_flat && linear_ops(m, m.n_in, m.post_op);
+    bsc_with_count<3>(m.n_in, [&](auto NV) {
+        if (lin) hipLaunchKernelGGL((map_reduce_lane_dense_f32_kernel<NV(), true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, m);
+        else hipLaunchKernelGGL((map_reduce_lane_dense_f32_kernel<NV(), false>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, m);
+    });
+}
+
+// many short rows: persistent waves, four rows per step
+bool short_rows(const bsc_ctx* ctx, const MapArgs& m, const ReducePlan& p) {
+    return p.dense_wave && p.splits == 1 && m.keep.rank == 1 && m.n_red <= 1024 && m.n_out >= 4096 && ctx->fused_map_flat;
+}
+int reduce_short_rows(bsc_ctx* ctx, const MapArgs& m) {
+    const bool linear = linear_ops(m, m.n_in, m.post_op);
+    int64_t rblocks = (m.n_out + 15) / 16;
+    const int64_t cap = (int64_t)ctx->cu_count * ctx->rows_wg_per_cu;        // (0: one step per wave, not persistent)
+    if (cap > 0 && rblocks > cap) rblocks = cap;
+    const dim3 grid((unsigned)rblocks);
+    if (ctx->rows_dbg && m.n_in == 2 && linear) {
+        switch (ctx->rows_dbg) {
+            case 2: hipLaunchKernelGGL((map_reduce_rows_f32_kernel<2, true, 2>), grid, dim3(256), 0, ctx->stream, m); break;
+            case 3: hipLaunchKernelGGL((map_reduce_rows_f32_kernel<2, true, 3>), grid, dim3(256), 0, ctx->stream, m); break;
+            case 4: hipLaunchKernelGGL((map_reduce_rows_f32_kernel<2, true, 4>), grid, dim3(256), 0, ctx->stream, m); break;
+            case 8: hipLaunchKernelGGL((map_reduce_rows_f32_kernel<2, true, 8>), grid, dim3(256), 0, ctx->stream, m); break;
+            default: return bsc_fail(BSC_ERR_INVALID, "BSC_ROWS_DBG: 2, 3, 4 or 8");
+        }
+        return BSC_OK;
+    }
+    bsc_with_count<3>(m.n_in, [&](auto NV) {
+        if (linear) hipLaunchKernelGGL((map_reduce_rows_f32_kernel<NV(), true>), grid, dim3(256), 0, ctx->stream, m);
+        else hipLaunchKernelGGL((map_reduce_rows_f32_kernel<NV(), false>), grid, dim3(256), 0, ctx->stream, m);
+    });
+    return BSC_OK;
+}
+
+void reduce_dense_wave(bsc_ctx* ctx, const MapArgs& m, int64_t blocks) {
+    const bool wlin = ctx->fused_map_flat && linear_ops(m, m.n_in, m.post_op);
+    const dim3 grid((unsigned)blocks);
+    bsc_with_count<3>(m.n_in, [&](auto NV) {
+        if (m.n_red <= 256 * (int64_t)m.splits) hipLaunchKernelGGL((map_reduce_wave_dense_f32_kernel<NV(), 1>), grid, dim3(256), 0, ctx->stream, m);
+        else if (wlin) hipLaunchKernelGGL((map_reduce_wave_dense_f32_kernel<NV(), 4, true>), grid, dim3(256), 0, ctx->stream, m);
+        else hipLaunchKernelGGL((map_reduce_wave_dense_f32_kernel<NV(), 4>), grid, dim3(256), 0, ctx->stream, m);
+    });
+}
+
+// the split partials, added in split order
+void reduce_finish(bsc_ctx* ctx, const MapCall& m) {
+    const int wave_per_output = m.n_out < 4096;
+    const unsigned blocks = (unsigned)(wave_per_output ? (m.n_out + 3) / 4 : (m.n_out + 255) / 256);
+    const MapArgs& a = m;
+    if (m.dtype == BSC_F32) hipLaunchKernelGGL(map_reduce_finish_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, a, wave_per_output);
+    else hipLaunchKernelGGL(map_reduce_finish_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, a, wave_per_output);
+}
+
+int map_reduce(bsc_ctx* ctx, MapCall& m) {
+    const ReducePlan p = reduce_plan(ctx, m);
+    if (p.splits > 1) {
         void* ws = nullptr;
-        int rc = bsc_workspace(ctx, (size_t)splits * n_out * sizeof(double), &ws);
+        int rc = bsc_workspace(ctx, (size_t)p.splits * m.n_out * sizeof(double), &ws);
         if (rc != BSC_OK) return rc;
         m.partial = (double*)ws;
         ctx->slab_rows = 0;
     }
-    if (lanes_over_outputs) {
-        const int64_t blocks = jobs * splits;
-        if (narrow_lane) {
-#define BSC_NARROW(NV)                                                                            \
-    case NV:                                                                                     \
-        hipLaunchKernelGGL(map_reduce_lane_narrow_f32_kernel<NV>, dim3((unsigned)blocks), dim3(256), \
-                           0, ctx->stream, m);                                                   \
-        break;
-            switch (n_in) { BSC_NARROW(1) BSC_NARROW(2) BSC_NARROW(3) }
-#undef BSC_NARROW
-        } else if (dense_lane) {
-            bool lin = post_op == BSC_OP_COPY && ctx->fused_map_flat;
-            for (int k = 0; k < n_in; ++k) {
-                const int op = m.pre_op[k];
-                if (!(op == BSC_OP_COPY || op == BSC_OP_SCALE || op == BSC_OP_ABS ||
-                      (op == BSC_OP_POW && (m.pre_arg[k] == 2.0 || m.pre_arg[k] == -1.0 || m.pre_arg[k] == 1.0))))
-                    lin = false;
-            }
-#define BSC_LANE(NV)                                                                             \
-    case NV:                                                                                     \
-        if (lin) hipLaunchKernelGGL((map_reduce_lane_dense_f32_kernel<NV, true>), dim3((unsigned)blocks), dim3(256), \
-                                    0, ctx->stream, m);                                           \
-        else hipLaunchKernelGGL((map_reduce_lane_dense_f32_kernel<NV, false>), dim3((unsigned)blocks), dim3(256), \
-                                0, ctx->stream, m);                                               \
-        break;
-            switch (n_in) { BSC_LANE(1) BSC_LANE(2) BSC_LANE(3) }
-#undef BSC_LANE
-        } else {
-            BSC_GENERIC(map_reduce_lane_kernel, blocks);
-        }
+    if (p.lanes_over_outputs) {
+        const int64_t blocks = p.jobs * p.splits;
+        if (p.narrow_lane) reduce_narrow_lane(ctx, m, blocks);
+        else if (p.dense_lane) reduce_dense_lane(ctx, m, blocks);
+        else BSC_LAUNCH_GENERIC(map_reduce_lane_kernel, blocks, ctx, m);
     } else {
-        // the wave kernels run four (output, split) jobs per block
-        const int64_t blocks = (n_out * splits + 3) / 4;
-        if (dense_wave && splits == 1 && keep.rank == 1 && n_red <= 1024 && n_out >= 4096 && ctx->fused_map_flat) {
-            // many short rows: persistent waves, four rows per step
-            bool linear = post_op == BSC_OP_COPY;
-            for (int k = 0; k < n_in; ++k) {
-                const int op = m.pre_op[k];
-                if (!(op == BSC_OP_COPY || op == BSC_OP_SCALE || op == BSC_OP_ABS ||
-                      (op == BSC_OP_POW && (m.pre_arg[k] == 2.0 || m.pre_arg[k] == -1.0 || m.pre_arg[k] == 1.0))))
-                    linear = false;
-            }
-            int64_t rblocks = (n_out + 15) / 16;
-            const int64_t cap = (int64_t)ctx->cu_count * ctx->rows_wg_per_cu;        // (0: one step per wave, not persistent)
-            if (cap > 0 && rblocks > cap) rblocks = cap;
-            if (ctx->rows_dbg && n_in == 2 && linear) {
-#define BSC_ROWSD(DBG) case DBG: hipLaunchKernelGGL((map_reduce_rows_f32_kernel<2, true, DBG>), dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, m); break;
-                switch (ctx->rows_dbg) { BSC_ROWSD(2) BSC_ROWSD(3) BSC_ROWSD(4) BSC_ROWSD(8) default: return bsc_fail(BSC_ERR_INVALID, "BSC_ROWS_DBG: 2, 3, 4 or 8"); }
-#undef BSC_ROWSD
-                BSC_LAUNCH_CHECK();
-                return BSC_OK;
-            }
-#define BSC_ROWS(NV)                                                                                                  \
-    case NV:                                                                                                          \
-        if (linear) hipLaunchKernelGGL((map_reduce_rows_f32_kernel<NV, true>), dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, m);  \
-        else hipLaunchKernelGGL((map_reduce_rows_f32_kernel<NV, false>), dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, m);        \
-        break;
-            switch (n_in) { BSC_ROWS(1) BSC_ROWS(2) BSC_ROWS(3) }
-#undef BSC_ROWS
-        } else if (dense_wave) {
-            bool wlin = post_op == BSC_OP_COPY && ctx->fused_map_flat;
-            for (int k = 0; k < n_in; ++k) {
-                const int op = m.pre_op[k];
-                if (!(op == BSC_OP_COPY || op == BSC_OP_SCALE || op == BSC_OP_ABS ||
-                      (op == BSC_OP_POW && (m.pre_arg[k] == 2.0 || m.pre_arg[k] == -1.0 || m.pre_arg[k] == 1.0))))
-                    wlin = false;
-            }
-#define BSC_WAVE_CASE(NV)                                                                        \
-    case NV:                                                                                     \
-        if (n_red <= 256 * splits)                                                               \
-            hipLaunchKernelGGL((map_reduce_wave_dense_f32_kernel<NV, 1>), dim3((unsigned)blocks), \
-                               dim3(256), 0, ctx->stream, m);                                    \
-        else if (wlin)                                                                           \
-            hipLaunchKernelGGL((map_reduce_wave_dense_f32_kernel<NV, 4, true>), dim3((unsigned)blocks), \
-                               dim3(256), 0, ctx->stream, m);                                    \
-        else                                                                                     \
-            hipLaunchKernelGGL((map_reduce_wave_dense_f32_kernel<NV, 4>), dim3((unsigned)blocks), \
-                               dim3(256), 0, ctx->stream, m);                                    \
-        break;
-            switch (n_in) { BSC_WAVE_CASE(1) BSC_WAVE_CASE(2) BSC_WAVE_CASE(3) }
-#undef BSC_WAVE_CASE
-        } else {
-            BSC_GENERIC(map_reduce_wave_kernel, blocks);
-        }
+        const int64_t blocks = (m.n_out * p.splits + 3) / 4;     // the wave kernels run four (output, split) jobs per block
+        if (short_rows(ctx, m, p)) {
+            const int rc = reduce_short_rows(ctx, m);
+            if (rc != BSC_OK) return rc;
+        } else if (p.dense_wave) reduce_dense_wave(ctx, m, blocks);
+        else BSC_LAUNCH_GENERIC(map_reduce_wave_kernel, blocks, ctx, m);
     }
     BSC_LAUNCH_CHECK();
-    if (splits > 1) {
-        const int wave_per_output = n_out < 4096;
-        const unsigned blocks = (unsigned)(wave_per_output ? (n_out + 3) / 4 : (n_out + 255) / 256);
-        if (dtype == BSC_F32)
-            hipLaunchKernelGGL(map_reduce_finish_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream,
-                               m, wave_per_output);
-        else
-            hipLaunchKernelGGL(map_reduce_finish_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream,
-                               m, wave_per_output);
+    if (p.splits > 1) {
+        reduce_finish(ctx, m);
         BSC_LAUNCH_CHECK();
     }
     return BSC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bsc_map_reduce(bsc_ctx* ctx, int dtype, int combine, int rank_keep, const int64_t* host_keep_shape, int rank_red,
+                   const int64_t* host_red_shape, int n_in, const void* const* host_in, const int64_t* host_in_keep_strides,
+                   const int64_t* host_in_red_strides, const int32_t* host_pre_op, const double* host_pre_arg, double scale,
+                   double shift, int post_op, double post_arg, void* out, const int64_t* host_out_strides) {
+    BSC_CHECK_CTX(ctx);
+    MapCall m{};
+    const int rc = map_normalise(ctx, dtype, combine, rank_keep, host_keep_shape, rank_red, host_red_shape, n_in, host_in,
+                                 host_in_keep_strides, host_in_red_strides, host_pre_op, host_pre_arg, scale, shift, post_op,
+                                 post_arg, out, host_out_strides, m);
+    if (rc != BSC_OK || m.n_out == 0) return rc;
+    return rank_red == 0 ? map_pure(ctx, m) : map_reduce(ctx, m);
 }
 
 }  // extern "C"

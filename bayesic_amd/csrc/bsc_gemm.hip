@@ -255,7 +255,7 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, f32x16 (&acc)
         }
 }
 
-template <bool A_M_CONTIG, bool B_N_CONTIG, bool PIPE>
+template <bool A_M_CONTIG, bool B_N_CONTIG>
 __global__ __launch_bounds__(GEMM_BLOCK, 2) void gemm_f32_mfma_kernel(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) float lds[4 * TILE];   // As[2], Bs[2]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -296,45 +296,29 @@ __global__ __launch_bounds__(GEMM_BLOCK, 2) void gemm_f32_mfma_kernel(GemmArgs g
     auto compute = [&](int buf) {
         const float* As = lds + buf * TILE;
         const float* Bs = lds + 2 * TILE + buf * TILE;
-        if (PIPE) {
-            // operands one k-pair ahead in registers: the 4 MFMAs of pair kk (256 cycles)
-            // cover the LDS latency of pair kk+2 (sched_group_barrier pins that order --
-            // left alone the compiler reads, waits, then issues the MFMAs)
-            const float* ap = As + fk * LDA + wm * 64 + fr;
-            const float* bp = Bs + fk * LDA + wn * 64 + fr;
-            float a_n[2] = {ap[0], ap[32]}, b_n[2] = {bp[0], bp[32]};
+        // operands one k-pair ahead in registers: the 4 MFMAs of pair kk (256 cycles)
+        // cover the LDS latency of pair kk+2 (sched_group_barrier pins that order --
+        // left alone the compiler reads, waits, then issues the MFMAs)
+        const float* ap = As + fk * LDA + wm * 64 + fr;
+        const float* bp = Bs + fk * LDA + wn * 64 + fr;
+        float a_n[2] = {ap[0], ap[32]}, b_n[2] = {bp[0], bp[32]};
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            const float a[2] = {a_n[0], a_n[1]}, bq[2] = {b_n[0], b_n[1]};
+            if (kk + 2 < BK) {
+                a_n[0] = ap[(kk + 2) * LDA];
+                a_n[1] = ap[(kk + 2) * LDA + 32];
+                b_n[0] = bp[(kk + 2) * LDA];
+                b_n[1] = bp[(kk + 2) * LDA + 32];
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bq[j], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#pragma unroll
-            for (int kk = 0; kk < BK; kk += 2) {
-                const float a[2] = {a_n[0], a_n[1]}, bq[2] = {b_n[0], b_n[1]};
-                if (kk + 2 < BK) {
-                    a_n[0] = ap[(kk + 2) * LDA];
-                    a_n[1] = ap[(kk + 2) * LDA + 32];
-                    b_n[0] = bp[(kk + 2) * LDA];
-                    b_n[1] = bp[(kk + 2) * LDA + 32];
-                }
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bq[j], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-            }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < BK; kk += 2) {
-                float a[2], bq[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) a[i] = As[(kk + fk) * LDA + wm * 64 + i * 32 + fr];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) bq[j] = Bs[(kk + fk) * LDA + wn * 64 + j * 32 + fr];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bq[j], acc[i][j], 0, 0, 0);
-            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         }
     };
 
@@ -1265,237 +1249,239 @@ struct Epilogue {
     int* handled = nullptr;
 };
 
-static int gemm_impl(bsc_ctx* ctx, int dtype, int64_t batch, int64_t M, int64_t N,
-              int64_t K, const void* A, int64_t sa_b, int64_t sa_m, int64_t sa_k,
-              const void* B, int64_t sb_b, int64_t sb_k, int64_t sb_n, void* C,
-              int64_t sc_b, int64_t sc_m, int64_t sc_n, const Epilogue& epi) {
-    BSC_CHECK_CTX(ctx);
-    BSC_REQUIRE(dtype == BSC_F32 || dtype == BSC_F64, "bsc_gemm_strided_batched: unknown dtype %d",
-                dtype);
-    BSC_REQUIRE(batch >= 0 && M >= 0 && N >= 0 && K >= 0, "bsc_gemm_strided_batched: negative extent");
-    if (batch == 0 || M == 0 || N == 0) return BSC_OK;
-    BSC_REQUIRE(C && ((A && B) || K == 0), "bsc_gemm_strided_batched: null pointer");
-    if (batch > 65535) {  // the batch index is a grid dimension: run 65535 batches per launch
-        const size_t es = dtype == BSC_F64 ? 8 : 4;
-        for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
-            const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
-            Epilogue e2 = epi;
-            if (e2.E) e2.E += b0 * e2.se_b;
-            int rc = gemm_impl(
-                ctx, dtype, nb, M, N, K, A ? (const char*)A + (size_t)(b0 * sa_b) * es : nullptr, sa_b,
-                sa_m, sa_k, B ? (const char*)B + (size_t)(b0 * sb_b) * es : nullptr, sb_b, sb_k, sb_n,
-                (char*)C + (size_t)(b0 * sc_b) * es, sc_b, sc_m, sc_n, e2);
-            if (rc != BSC_OK) return rc;
-        }
-        return BSC_OK;
+// One product C[b] = A[b] B[b] as the entry points receive it (the fields in their argument order).
+struct Product {
+    int dtype;
+    int64_t batch, M, N, K;
+    const void* A;
+    int64_t sa_b, sa_m, sa_k;
+    const void* B;
+    int64_t sb_b, sb_k, sb_n;
+    void* C;
+    int64_t sc_b, sc_m, sc_n;
+    Epilogue epi;
+
+    bool pre() const { return epi.pre_a != 0 || epi.pre_b != 0; }
+    bool factor() const { return epi.pow && epi.E; }       // the epilogue multiplies by E
+    // the same product read as C^T = B^T A^T: the operands change places, every m becomes an n
+    Product transposed() const {
+        Product t = *this;
+        t.A = B; t.B = A; t.M = N; t.N = M;
+        t.sa_b = sb_b; t.sa_m = sb_n; t.sa_k = sb_k;
+        t.sb_b = sa_b; t.sb_n = sa_m; t.sb_k = sa_k;
+        t.sc_m = sc_n; t.sc_n = sc_m;
+        t.epi.se_m = epi.se_n; t.epi.se_n = epi.se_m;
+        t.epi.pre_a = epi.pre_b; t.epi.pre_b = epi.pre_a;
+        return t;
     }
-    const bool pre = epi.pre_a != 0 || epi.pre_b != 0;
-    if (epi.handled) *epi.handled = 0;
-    if (pre && (dtype == BSC_F64 || K == 0 || batch > 65535)) return BSC_OK;       // (not handled)
-    if (epi.pow && (dtype == BSC_F64 || K == 0))
-        return bsc_fail(BSC_ERR_UNSUPPORTED, "bsc_gemm_epilogue: float32 products with K > 0 only");
-    if (dtype == BSC_F64 || K == 0) {
-        const dim3 grid((unsigned)((M * N + 255) / 256), (unsigned)batch);
-        if (dtype == BSC_F64)
-            hipLaunchKernelGGL(gemm_naive_kernel<double>, grid, dim3(256), 0, ctx->stream, M, N, K,
-                               (const double*)A, sa_b, sa_m, sa_k, (const double*)B, sb_b, sb_k,
-                               sb_n, (double*)C, sc_b, sc_m, sc_n);
-        else
-            hipLaunchKernelGGL(gemm_naive_kernel<float>, grid, dim3(256), 0, ctx->stream, M, N, K,
-                               (const float*)A, sa_b, sa_m, sa_k, (const float*)B, sb_b, sb_k, sb_n,
-                               (float*)C, sc_b, sc_m, sc_n);
+};
+
+// What every MFMA kernel reads of a product; whatever a route does not set afterwards stays zero.
+static GemmArgs gemm_args(const bsc_ctx* ctx, const Product& p) {
+    GemmArgs g{};
+    g.A = (const float*)p.A; g.B = (const float*)p.B; g.C = (float*)p.C;
+    g.M = p.M; g.N = p.N; g.K = p.K;
+    g.sa_b = p.sa_b; g.sa_m = p.sa_m; g.sa_k = p.sa_k;
+    g.sb_b = p.sb_b; g.sb_k = p.sb_k; g.sb_n = p.sb_n;
+    g.sc_b = p.sc_b; g.sc_m = p.sc_m; g.sc_n = p.sc_n;
+    g.E = p.epi.E; g.se_b = p.epi.se_b; g.se_m = p.epi.se_m; g.se_n = p.epi.se_n;
+    g.epi_scale = p.epi.scale; g.epi_pow = p.epi.pow;
+    g.pre_a = p.epi.pre_a; g.pre_b = p.epi.pre_b;
+    g.nt_c = ctx->gemm_nt_c && (double)p.M * (double)p.N * (double)p.batch * 4.0 >= 128.0 * 1024.0 * 1024.0;
+    g.tiles_m = (int)((p.M + BM - 1) / BM);
+    g.tiles_n = (int)((p.N + BN - 1) / BN);
+    g.splits = 1;
+    return g;
+}
+
+constexpr int64_t OFFSET_LIMIT = (int64_t)1 << 31;     // byte offsets of a lane and tile / unit counts are 32-bit on the device
+
+// LDS-DMA staging of one operand (its free axis contiguous: mn, else k): 16-byte pieces wholly inside or outside the
+// operand, and the byte offsets of the lanes inside a [128 x 32] tile below 2^31
+static bool dma_ok(const void* p, bool mn, int64_t ext_mn, int64_t K, int64_t s_mn, int64_t s_k, int64_t s_b) {
+    if (((uintptr_t)p & 15) != 0 || s_b % 4 != 0 || s_mn < 0 || s_k < 0) return false;
+    if (mn) return s_mn == 1 && ext_mn % 4 == 0 && s_k % 4 == 0 && (31 * s_k + 128) * 4 < OFFSET_LIMIT;
+    return s_k == 1 && K % 4 == 0 && s_mn % 4 == 0 && (127 * s_mn + 32) * 4 < OFFSET_LIMIT;
+}
+// stream kernel, C and E: the byte offsets of a tile's 128 columns from its row must fit 32 bits
+static bool store_offsets_fit(int64_t s_n) { return s_n >= 0 && (127 * s_n + 128) * 4 < OFFSET_LIMIT; }
+// stream kernel: the tile index, and the index of a k-tile unit in a workgroup's share, must fit 32 bits
+static bool stream_counts_fit(const Product& p, int64_t slots) {
+    const int64_t tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.batch, n_kt = (p.K + BK - 1) / BK;
+    return tiles < OFFSET_LIMIT && tiles / slots * n_kt + slots * n_kt < OFFSET_LIMIT;
+}
+// register-staged kernel, interior tiles: lane offsets inside a [128 x 32] operand tile must fit 32 bits
+static bool stage_offsets_fit(int64_t s_mn, int64_t s_k) {
+    return s_mn >= 0 && s_k >= 0 && (127 * s_mn + 31 * s_k + 4) * 4 < OFFSET_LIMIT;
+}
+// 16-byte loads along the contiguous axis need that stride to be 1, the other strides multiples of 4 elements and
+// the base 16-byte aligned
+static int vec_ok(const void* p, bool mn, int64_t s_mn, int64_t s_k, int64_t s_b) {
+    const int64_t unit = mn ? s_mn : s_k, other = mn ? s_k : s_mn;
+    return (int)(unit == 1 && other % 4 == 0 && s_b % 4 == 0 && ((uintptr_t)p & 15) == 0);
+}
+// A contraction two to six k-tiles long over many full tiles, nothing folded into the store: what a
+// tile costs is its 64 KiB of stores, and one tile per workgroup (the hardware's dispatcher dealing
+// them, LDS-staged 512-byte rows) does that 7 % better than the persistent schedule -- config 4's
+// dot(Th, Bt), K = 128: 1.45 against 1.57 ms (profiles/r02_ab_gemm_stream_vs_tile_b64.txt)
+static bool short_k_plain(const bsc_ctx* ctx, const Product& p) {
+    const int64_t tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.batch;
+    return !p.pre() && p.K > 32 && p.K <= 6 * BK && !p.factor() && tiles >= 8 * (int64_t)ctx->cu_count && p.M >= 2 * BM &&
+           p.N >= 2 * BN;
+}
+
+// ---- the routes, in the order gemm_impl tries them: each takes the product (*took = 1) or declines it ----
+
+// float64 and K == 0: one thread per output
+static int gemm_naive(bsc_ctx* ctx, const Product& p) {
+    const dim3 grid((unsigned)((p.M * p.N + 255) / 256), (unsigned)p.batch);
+    if (p.dtype == BSC_F64)
+        hipLaunchKernelGGL(gemm_naive_kernel<double>, grid, dim3(256), 0, ctx->stream, p.M, p.N, p.K,
+                           (const double*)p.A, p.sa_b, p.sa_m, p.sa_k, (const double*)p.B, p.sb_b, p.sb_k,
+                           p.sb_n, (double*)p.C, p.sc_b, p.sc_m, p.sc_n);
+    else
+        hipLaunchKernelGGL(gemm_naive_kernel<float>, grid, dim3(256), 0, ctx->stream, p.M, p.N, p.K,
+                           (const float*)p.A, p.sa_b, p.sa_m, p.sa_k, (const float*)p.B, p.sb_b, p.sb_k, p.sb_n,
+                           (float*)p.C, p.sc_b, p.sc_m, p.sc_n);
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
+// matrix-vector: orient so that the matrix is "A[m,k]" and the vector "x[k]"
+static int gemm_matvec(bsc_ctx* ctx, const Product& p, int* took) {
+    if (!(p.batch == 1 && (p.N == 1 || p.M == 1) && p.K >= 64 && !p.epi.pow && !p.pre())) return BSC_OK;
+    *took = 1;
+    const Product q = p.N == 1 ? p : p.transposed();
+    GemvArgs v;
+    v.A = (const float*)q.A; v.M = q.M; v.sa_m = q.sa_m; v.sa_k = q.sa_k;
+    v.x = (const float*)q.B; v.sx = q.sb_k; v.sy = q.sc_m;
+    v.K = q.K;
+    v.y = (float*)q.C;
+    v.partial = nullptr;
+    v.splits = 1;
+    bsc_prof_scope prof(ctx);
+    if (v.sa_k == 1 || (v.sa_m != 1 && v.sa_k < v.sa_m)) {
+        hipLaunchKernelGGL(gemv_kcontig_kernel, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0,
+                           ctx->stream, v);
         BSC_LAUNCH_CHECK();
         return BSC_OK;
     }
-    if (batch == 1 && (N == 1 || M == 1) && K >= 64 && !epi.pow && !pre) {
-        // matrix-vector: orient so that the matrix is "A[m,k]" and the vector "x[k]"
-        GemvArgs v;
-        if (N == 1) {
-            v.A = (const float*)A; v.M = M; v.sa_m = sa_m; v.sa_k = sa_k;
-            v.x = (const float*)B; v.sx = sb_k; v.sy = sc_m;
-        } else {
-            v.A = (const float*)B; v.M = N; v.sa_m = sb_n; v.sa_k = sb_k;
-            v.x = (const float*)A; v.sx = sa_k; v.sy = sc_n;
-        }
-        v.K = K;
-        v.y = (float*)C;
-        v.partial = nullptr;
-        v.splits = 1;
+    const bool vec4 = v.sa_m == 1 && v.M % 4 == 0 && v.sa_k % 4 == 0 && (((uintptr_t)v.A) & 15) == 0;
+    const int64_t groups = vec4 ? (v.M + 255) / 256 : (v.M + 63) / 64;
+    int64_t splits = (4 * (int64_t)ctx->cu_count) / groups;
+    if (splits > v.K / 256) splits = v.K / 256;
+    if (splits < 1) splits = 1;
+    if (splits > 2048) splits = 2048;
+    v.splits = (int)splits;
+    if (splits > 1) {
+        void* ws = nullptr;
+        int rc = bsc_workspace(ctx, (size_t)splits * v.M * sizeof(double), &ws);
+        if (rc != BSC_OK) return rc;
+        v.partial = (double*)ws;
+        ctx->slab_rows = 0;
+    }
+    if (vec4)
+        hipLaunchKernelGGL(gemv_mcontig4_kernel, dim3((unsigned)(groups * splits)), dim3(256), 0,
+                           ctx->stream, v);
+    else
+        hipLaunchKernelGGL(gemv_mcontig_kernel, dim3((unsigned)(groups * splits)), dim3(256), 0,
+                           ctx->stream, v);
+    BSC_LAUNCH_CHECK();
+    if (splits > 1) {
+        if (v.M < 4096)
+            hipLaunchKernelGGL(gemv_finish_wave_kernel, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0,
+                               ctx->stream, (const double*)v.partial, v.splits, v.M, v.y, v.sy);
+        else
+            hipLaunchKernelGGL(gemv_finish_kernel, dim3((unsigned)((v.M + 255) / 256)), dim3(256), 0,
+                               ctx->stream, (const double*)v.partial, v.splits, v.M, v.y, v.sy);
+        BSC_LAUNCH_CHECK();
+    }
+    return BSC_OK;
+}
+
+// one tiny extent, the large operand streamed once by LDS-DMA (csrc/bsc_skinny.hip)
+static int gemm_skinny(bsc_ctx* ctx, const Product& p, int* took) {
+    if (!(p.batch == 1 && !p.epi.pow && !p.pre())) return BSC_OK;
+    return bsc_gemm_skinny(ctx, p.M, p.N, p.K, (const float*)p.A, p.sa_m, p.sa_k, (const float*)p.B, p.sb_k, p.sb_n,
+                           (float*)p.C, p.sc_m, p.sc_n, took);
+}
+
+// X^T X of a row-major X with the operands as two bf16 terms (csrc/bsc_gram.hip): bound by the read of X
+static int gemm_gram_split(bsc_ctx* ctx, const Product& p, int* took) {
+    if (!(ctx->mfma_split == 2 && p.batch == 1 && !p.pre() && p.A == p.B && p.M == p.N && p.sa_m == 1 && p.sb_n == 1 &&
+          p.sa_k == p.sb_k && !p.factor() && p.epi.pow >= 0))
+        return BSC_OK;
+    return bsc_gram_split(ctx, (const float*)p.A, p.sa_k, p.K, p.M, (float*)p.C, p.sc_m, p.sc_n,
+                          p.epi.pow ? p.epi.scale : 1.0f, took);
+}
+
+// q = t m >> sh for 0 <= t < 2^31, 1 <= d < 2^31
+static void magic_div(int64_t d, unsigned& m, int& sh) {
+    int l = 0;
+    while (((int64_t)1 << l) < d) ++l;
+    sh = 31 + l;
+    m = (unsigned)((((unsigned __int128)1) << sh) / (unsigned __int128)d + 1);
+}
+
+// persistent stream-K on the LDS-DMA pipeline; the A operand goes along C's contiguous axis
+static int gemm_stream(bsc_ctx* ctx, const Product& given, int* took) {
+    if (ctx->gemm_dma < 2) return BSC_OK;
+    const Product p = given.sc_n == 1 && given.sc_m != 1 ? given.transposed() : given;
+    const bool a_m = p.sa_m == 1, b_n = p.sb_n == 1, pre = p.pre();
+    const int64_t slots = 2 * (int64_t)ctx->cu_count;
+    if (!(dma_ok(p.A, a_m, p.M, p.K, p.sa_m, p.sa_k, p.sa_b) && dma_ok(p.B, b_n, p.N, p.K, p.sb_n, p.sb_k, p.sb_b) &&
+          store_offsets_fit(p.sc_n) && store_offsets_fit(p.epi.se_n) && stream_counts_fit(p, slots)))
+        return BSC_OK;
+    if (short_k_plain(ctx, p)) return BSC_OK;      // (the tile route takes it)
+    *took = 1;
+    GemmArgs s = gemm_args(ctx, p);
+    s.tiles_pb = s.tiles_m * s.tiles_n;
+    // X^T X: the same matrix on both sides, transposed -- half the tiles (plus the diagonal)
+    s.fix_lanes = 4;
+    s.sym = ctx->gemm_sym && s.A == s.B && s.M == s.N && s.sa_m == s.sb_n && s.sa_k == s.sb_k && s.sa_b == s.sb_b &&
+            !p.factor() && s.tiles_m > 1 && s.pre_a == s.pre_b;
+    if (s.sym) s.tiles_pb = s.tiles_m * (s.tiles_m + 1) / 2;
+    s.group = 8;
+    s.group_log2 = 3;
+    magic_div(s.tiles_pb, s.mg_pb, s.sh_pb);
+    magic_div((int64_t)s.group * s.tiles_m, s.mg_strip, s.sh_strip);
+    magic_div(s.tiles_n % s.group ? s.tiles_n % s.group : s.group, s.mg_last, s.sh_last);
+    s.dbg = ctx->gemm_dbg;
+    stream_plan(s, (int64_t)s.tiles_pb * p.batch, (int)((p.K + BK - 1) / BK), slots);
+    // one tile with both extents within a wave's 64 x 64 and a long contraction, split along it: the
+    // four waves of a workgroup split the k-groups (EDGE instantiation)
+    s.ksplit = s.sk_stream && s.tiles_pb * p.batch == 1 && s.M <= 64 && s.N <= 64 && s.n_wg > 1 && s.rounds == 0 &&
+               p.K % 32 == 0;
+    void* ws = nullptr;
+    int rc = bsc_workspace(ctx, (size_t)(s.ksplit ? 8 : 2) * s.n_wg * BM * BN * sizeof(float), &ws);
+    if (rc != BSC_OK) return rc;
+    s.slab = (float*)ws;
+    ctx->slab_rows = 0;
+    {
         bsc_prof_scope prof(ctx);
-        if (v.sa_k == 1 || (v.sa_m != 1 && v.sa_k < v.sa_m)) {
-            hipLaunchKernelGGL(gemv_kcontig_kernel, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0,
-                               ctx->stream, v);
-            BSC_LAUNCH_CHECK();
-            return BSC_OK;
-        }
-        const bool vec4 = v.sa_m == 1 && v.M % 4 == 0 && v.sa_k % 4 == 0 && (((uintptr_t)v.A) & 15) == 0;
-        const int64_t groups = vec4 ? (v.M + 255) / 256 : (v.M + 63) / 64;
-        int64_t splits = (4 * (int64_t)ctx->cu_count) / groups;
-        if (splits > K / 256) splits = K / 256;
-        if (splits < 1) splits = 1;
-        if (splits > 2048) splits = 2048;
-        v.splits = (int)splits;
-        if (splits > 1) {
-            void* ws = nullptr;
-            int rc = bsc_workspace(ctx, (size_t)splits * v.M * sizeof(double), &ws);
-            if (rc != BSC_OK) return rc;
-            v.partial = (double*)ws;
-            ctx->slab_rows = 0;
-        }
-        if (vec4)
-            hipLaunchKernelGGL(gemv_mcontig4_kernel, dim3((unsigned)(groups * splits)), dim3(256), 0,
-                               ctx->stream, v);
-        else
-            hipLaunchKernelGGL(gemv_mcontig_kernel, dim3((unsigned)(groups * splits)), dim3(256), 0,
-                               ctx->stream, v);
+        // mostly partial tiles?
+        const bool edge = (s.tiles_m == 1 && s.M <= 96) || (s.tiles_n == 1 && s.N <= 96) || p.K <= 24;
+        bsc_with_flags([&](auto AM, auto BN_, auto EDGE, auto PRE) {
+            hipLaunchKernelGGL((gemm_f32_stream_kernel<AM(), BN_(), EDGE(), PRE()>), dim3((unsigned)s.n_wg), dim3(GEMM_BLOCK), 0,
+                               ctx->stream, s);
+        }, a_m, b_n, edge, pre);
+    }
+    BSC_LAUNCH_CHECK();
+    if (stream_has_pieces(s)) {
+        // pieces per split tile: about n_wg / tail_tiles (x 4 with ksplit)
+        s.fix_lanes = (int64_t)s.n_wg * (s.ksplit ? 4 : 1) >= 64 * (int64_t)s.tail_tiles ? 64 : 4;
+        hipLaunchKernelGGL(stream_fixup_kernel, dim3((unsigned)s.tail_tiles, BM * BN / 4 / (256 / s.fix_lanes)), dim3(256), 0,
+                           ctx->stream, s);
         BSC_LAUNCH_CHECK();
-        if (splits > 1) {
-            if (v.M < 4096)
-                hipLaunchKernelGGL(gemv_finish_wave_kernel, dim3((unsigned)((v.M + 3) / 4)), dim3(256), 0,
-                                   ctx->stream, (const double*)v.partial, v.splits, v.M, v.y, v.sy);
-            else
-                hipLaunchKernelGGL(gemv_finish_kernel, dim3((unsigned)((v.M + 255) / 256)), dim3(256), 0,
-                                   ctx->stream, (const double*)v.partial, v.splits, v.M, v.y, v.sy);
-            BSC_LAUNCH_CHECK();
-        }
-        return BSC_OK;
     }
-    if (batch == 1 && !epi.pow && !pre) {
-        // one tiny extent, the large operand streamed once by LDS-DMA (csrc/bsc_skinny.hip)
-        int handled = 0;
-        int rc = bsc_gemm_skinny(ctx, M, N, K, (const float*)A, sa_m, sa_k, (const float*)B, sb_k, sb_n,
-                                 (float*)C, sc_m, sc_n, &handled);
-        if (rc != BSC_OK || handled) return rc;
-    }
-    if (ctx->mfma_split == 2 && batch == 1 && !pre && A == B && M == N && sa_m == 1 && sb_n == 1 && sa_k == sb_k &&
-        !(epi.pow && epi.E) && epi.pow >= 0) {
-        // X^T X of a row-major X with the operands as two bf16 terms (csrc/bsc_gram.hip): bound by the read of X
-        int handled = 0;
-        const int rc = bsc_gram_split(ctx, (const float*)A, sa_k, K, M, (float*)C, sc_m, sc_n, epi.pow ? epi.scale : 1.0f, &handled);
-        if (rc != BSC_OK || handled) return rc;
-    }
-    if (ctx->gemm_dma >= 2) {
-        // persistent stream-K on the LDS-DMA pipeline; the A operand goes along C's contiguous axis
-        const bool swap = sc_n == 1 && sc_m != 1;
-        GemmArgs s;
-        s.A = (const float*)(swap ? B : A); s.B = (const float*)(swap ? A : B);
-        s.M = swap ? N : M; s.N = swap ? M : N; s.K = K;
-        s.sa_b = swap ? sb_b : sa_b; s.sa_m = swap ? sb_n : sa_m; s.sa_k = swap ? sb_k : sa_k;
-        s.sb_b = swap ? sa_b : sb_b; s.sb_n = swap ? sa_m : sb_n; s.sb_k = swap ? sa_k : sb_k;
-        s.C = (float*)C; s.sc_b = sc_b; s.sc_m = swap ? sc_n : sc_m; s.sc_n = swap ? sc_m : sc_n;
-        s.E = epi.E; s.se_b = epi.se_b; s.se_m = swap ? epi.se_n : epi.se_m; s.se_n = swap ? epi.se_m : epi.se_n;
-        s.epi_scale = epi.scale; s.epi_pow = epi.pow;
-        s.pre_a = swap ? epi.pre_b : epi.pre_a; s.pre_b = swap ? epi.pre_a : epi.pre_b;
-        s.nt_c = ctx->gemm_nt_c && (double)M * (double)N * (double)batch * 4.0 >= 128.0 * 1024.0 * 1024.0;
-        s.splits = 1; s.k_chunk = 0; s.vec_a = s.vec_b = s.fast = 0;
-        const bool a_m = s.sa_m == 1, b_n = s.sb_n == 1;
-        auto dma_ok = [&](const void* p, bool mn, int64_t ext_mn, int64_t s_mn, int64_t s_k, int64_t s_b) {
-            if (((uintptr_t)p & 15) != 0 || s_b % 4 != 0 || s_mn < 0 || s_k < 0) return false;
-            if (mn) return ext_mn % 4 == 0 && s_k % 4 == 0 && (31 * s_k + 128) * 4 < ((int64_t)1 << 31);
-            return s_k == 1 && K % 4 == 0 && s_mn % 4 == 0 && (127 * s_mn + 32) * 4 < ((int64_t)1 << 31);
-        };
-        const int64_t c_span = 127 * (s.sc_n < 0 ? -s.sc_n : s.sc_n), e_span = 127 * (s.se_n < 0 ? -s.se_n : s.se_n);
-        if (dma_ok(s.A, a_m, s.M, s.sa_m, s.sa_k, s.sa_b) && dma_ok(s.B, b_n, s.N, s.sb_n, s.sb_k, s.sb_b) &&
-            (c_span + 128) * 4 < ((int64_t)1 << 31) && (e_span + 128) * 4 < ((int64_t)1 << 31) && s.sc_n >= 0 && s.se_n >= 0 &&
-            ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * batch < ((int64_t)1 << 31) &&
-            ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * batch / (2 * (int64_t)ctx->cu_count) * ((K + BK - 1) / BK) + 2 * (int64_t)ctx->cu_count * ((K + BK - 1) / BK) < ((int64_t)1 << 31)) {
-            s.tiles_m = (int)((s.M + BM - 1) / BM);
-            s.tiles_n = (int)((s.N + BN - 1) / BN);
-            s.tiles_pb = s.tiles_m * s.tiles_n;
-            // A contraction two to six k-tiles long over many full tiles, nothing folded into the store: what a
-            // tile costs is its 64 KiB of stores, and one tile per workgroup (the hardware's dispatcher dealing
-            // them, LDS-staged 512-byte rows) does that 7 % better than the persistent schedule -- config 4's
-            // dot(Th, Bt), K = 128: 1.45 against 1.57 ms (profiles/r02_ab_gemm_stream_vs_tile_b64.txt)
-            const bool short_k_plain = !pre && K > 32 && K <= 6 * BK && !(epi.pow && epi.E) &&
-                                       (int64_t)s.tiles_pb * batch >= 8 * (int64_t)ctx->cu_count && s.M >= 2 * BM && s.N >= 2 * BN;
-            if (!short_k_plain) {
-            // X^T X: the same matrix on both sides, transposed -- half the tiles (plus the diagonal)
-            s.ksplit = 0;
-            s.fix_lanes = 4;
-            s.sym = ctx->gemm_sym && s.A == s.B && s.M == s.N && s.sa_m == s.sb_n && s.sa_k == s.sb_k && s.sa_b == s.sb_b &&
-                    !(epi.pow && epi.E) && s.tiles_m > 1 && s.pre_a == s.pre_b;
-            if (s.sym) s.tiles_pb = s.tiles_m * (s.tiles_m + 1) / 2;
-            s.group = 8;
-            s.group_log2 = 3;
-            auto magic = [](int64_t d, unsigned& m, int& sh) {       // q = t m >> sh for 0 <= t < 2^31, 1 <= d < 2^31
-                int l = 0;
-                while (((int64_t)1 << l) < d) ++l;
-                sh = 31 + l;
-                m = (unsigned)((((unsigned __int128)1) << sh) / (unsigned __int128)d + 1);
-            };
-            magic(s.tiles_pb, s.mg_pb, s.sh_pb);
-            magic((int64_t)s.group * s.tiles_m, s.mg_strip, s.sh_strip);
-            magic(s.tiles_n % s.group ? s.tiles_n % s.group : s.group, s.mg_last, s.sh_last);
-            s.n_kt = (int)((K + BK - 1) / BK);
-            s.dbg = ctx->gemm_dbg;
-            stream_plan(s, (int64_t)s.tiles_pb * batch, s.n_kt, 2 * (int64_t)ctx->cu_count);
-            // one tile with both extents within a wave's 64 x 64 and a long contraction, split along it: the
-            // four waves of a workgroup split the k-groups (EDGE instantiation)
-            s.ksplit = s.sk_stream && s.tiles_pb * batch == 1 && s.M <= 64 && s.N <= 64 && s.n_wg > 1 && s.rounds == 0 &&
-                       K % 32 == 0;
-            void* ws = nullptr;
-            int rc = bsc_workspace(ctx, (size_t)(s.ksplit ? 8 : 2) * s.n_wg * BM * BN * sizeof(float), &ws);
-            if (rc != BSC_OK) return rc;
-            s.slab = (float*)ws;
-            ctx->slab_rows = 0;
-            {
-                bsc_prof_scope prof(ctx);
-                // mostly partial tiles?
-                const bool edge = (s.tiles_m == 1 && s.M <= 96) || (s.tiles_n == 1 && s.N <= 96) || K <= 24;
-#define BSC_GEMM_STREAM(AM, BN_)                                                                                          \
-    do {                                                                                                                  \
-        if (pre && edge)                                                                                                  \
-            hipLaunchKernelGGL((gemm_f32_stream_kernel<AM, BN_, true, true>), dim3((unsigned)s.n_wg), dim3(GEMM_BLOCK), 0, \
-                               ctx->stream, s);                                                                           \
-        else if (pre)                                                                                                     \
-            hipLaunchKernelGGL((gemm_f32_stream_kernel<AM, BN_, false, true>), dim3((unsigned)s.n_wg), dim3(GEMM_BLOCK), 0, \
-                               ctx->stream, s);                                                                           \
-        else if (edge)                                                                                                    \
-            hipLaunchKernelGGL((gemm_f32_stream_kernel<AM, BN_, true>), dim3((unsigned)s.n_wg), dim3(GEMM_BLOCK), 0,      \
-                               ctx->stream, s);                                                                           \
-        else                                                                                                              \
-            hipLaunchKernelGGL((gemm_f32_stream_kernel<AM, BN_, false>), dim3((unsigned)s.n_wg), dim3(GEMM_BLOCK), 0,     \
-                               ctx->stream, s);                                                                           \
-    } while (0)
-                if (a_m && b_n) BSC_GEMM_STREAM(true, true);
-                else if (a_m) BSC_GEMM_STREAM(true, false);
-                else if (b_n) BSC_GEMM_STREAM(false, true);
-                else BSC_GEMM_STREAM(false, false);
-#undef BSC_GEMM_STREAM
-            }
-            BSC_LAUNCH_CHECK();
-            if (stream_has_pieces(s)) {
-                // pieces per split tile: about n_wg / tail_tiles (x 4 with ksplit)
-                s.fix_lanes = (int64_t)s.n_wg * (s.ksplit ? 4 : 1) >= 64 * (int64_t)s.tail_tiles ? 64 : 4;
-                hipLaunchKernelGGL(stream_fixup_kernel, dim3((unsigned)s.tail_tiles, BM * BN / 4 / (256 / s.fix_lanes)), dim3(256), 0,
-                                   ctx->stream, s);
-                BSC_LAUNCH_CHECK();
-            }
-            if (pre && epi.handled) *epi.handled = 1;
-            return BSC_OK;
-            }   // !short_k_plain
-        }
-    }
-    if (pre) return BSC_OK;      // (not handled: the kernels below take their operands as they are)
-    GemmArgs g;
-    g.A = (const float*)A; g.B = (const float*)B;
-    g.M = M; g.N = N; g.K = K;
-    g.sa_b = sa_b; g.sa_m = sa_m; g.sa_k = sa_k;
-    g.sb_b = sb_b; g.sb_k = sb_k; g.sb_n = sb_n;
-    g.sc_b = sc_b; g.sc_m = sc_m; g.sc_n = sc_n;
-    g.E = epi.E; g.se_b = epi.se_b; g.se_m = epi.se_m; g.se_n = epi.se_n;
-    g.epi_scale = epi.scale; g.epi_pow = epi.pow;
-    g.n_kt = 0; g.sk_q = 0; g.sk_r = 0; g.sk_stream = 0; g.n_wg = 0; g.rounds = 0; g.tail_tiles = 0; g.tiles_pb = 0;
-    g.group = 1; g.dbg = 0; g.slab = nullptr;
-    g.mg_pb = g.mg_strip = g.mg_last = 0; g.sh_pb = g.sh_strip = g.sh_last = g.group_log2 = 0; g.sym = 0; g.ksplit = 0; g.fix_lanes = 4;
-    g.pre_a = g.pre_b = 0;
-    g.nt_c = ctx->gemm_nt_c && (double)M * (double)N * (double)batch * 4.0 >= 128.0 * 1024.0 * 1024.0;
-    g.tiles_m = (int)((M + BM - 1) / BM);
-    g.tiles_n = (int)((N + BN - 1) / BN);
-    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n * batch;
-    // split K until the grid has about two workgroups per CU, keeping >= 512 of K per split
+    if (pre && p.epi.handled) *p.epi.handled = 1;
+    return BSC_OK;
+}
+
+// tile route: how many ranges to cut K into
+static int64_t tile_k_splits(int64_t tiles, int64_t want, int64_t K) {
     int64_t splits = 1;
-    const int64_t want = 2 * (int64_t)ctx->cu_count;
+    // split K until the grid has about two workgroups per CU, keeping >= 512 of K per split
     if (tiles < want) {
         splits = want / tiles;
         const int64_t max_splits = K / 512;
@@ -1520,80 +1506,87 @@ static int gemm_impl(bsc_ctx* ctx, int dtype, int64_t batch, int64_t M, int64_t 
             }
         }
     }
+    return splits;
+}
+
+// one tile per workgroup, K split over the grid's y: operands by LDS-DMA (gemm_f32_dma_kernel) or through registers
+// (gemm_f32_mfma_kernel); takes whatever is left, as the caller stored it
+static int gemm_tile(bsc_ctx* ctx, const Product& p) {
+    GemmArgs g = gemm_args(ctx, p);
+    const int64_t M = p.M, N = p.N, K = p.K;
+    int64_t splits = tile_k_splits((int64_t)g.tiles_m * g.tiles_n * p.batch, 2 * (int64_t)ctx->cu_count, K);
     int64_t chunk = (K + splits - 1) / splits;
     chunk = (chunk + BK - 1) / BK * BK;
     splits = (K + chunk - 1) / chunk;
     g.splits = (int)splits;
     g.k_chunk = chunk;
-    g.C = (float*)C;
     float* slab = nullptr;
     if (splits > 1) {
         void* ws = nullptr;
-        int rc = bsc_workspace(ctx, (size_t)batch * splits * M * N * sizeof(float), &ws);
+        int rc = bsc_workspace(ctx, (size_t)p.batch * splits * M * N * sizeof(float), &ws);
         if (rc != BSC_OK) return rc;
         slab = (float*)ws;
         g.C = slab;
         ctx->slab_rows = 0;
     }
-    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)splits, (unsigned)batch);
-    const bool a_m = (sa_m == 1) || (sa_k != 1 && M >= K);   // which axis consecutive threads walk
-    const bool b_n = (sb_n == 1) || (sb_k != 1 && N >= K);
-    // 16-byte loads along the contiguous axis need that stride to be 1, the other
-    // strides multiples of 4 elements and the base 16-byte aligned
-    auto vec_ok = [](const void* p, bool mn, int64_t s_mn, int64_t s_k, int64_t s_b) {
-        const int64_t unit = mn ? s_mn : s_k, other = mn ? s_k : s_mn;
-        return (int)(unit == 1 && other % 4 == 0 && s_b % 4 == 0 && ((uintptr_t)p & 15) == 0);
-    };
-    g.vec_a = vec_ok(A, a_m, sa_m, sa_k, sa_b);
-    g.vec_b = vec_ok(B, b_n, sb_n, sb_k, sb_b);
-    // lane offsets inside a [128 x 32] operand tile must fit 32 bits
-    auto span_ok = [](int64_t s_mn, int64_t s_k) {
-        const int64_t span = (127 * (s_mn < 0 ? -s_mn : s_mn) + 31 * (s_k < 0 ? -s_k : s_k) + 4) * 4;
-        return s_mn >= 0 && s_k >= 0 && span < ((int64_t)1 << 31);
-    };
-    g.fast = ctx->gemm_fast && g.vec_a && g.vec_b && span_ok(sa_m, sa_k) && span_ok(sb_n, sb_k);
-    // LDS-DMA staging: 16-byte pieces wholly inside or outside the operand, lane offsets below 2^31
-    auto dma_ok = [&](const void* p, bool mn, int64_t ext_mn, int64_t s_mn, int64_t s_k, int64_t s_b) {
-        if (((uintptr_t)p & 15) != 0 || s_b % 4 != 0 || s_mn < 0 || s_k < 0) return false;
-        if (mn) return s_mn == 1 && ext_mn % 4 == 0 && s_k % 4 == 0 && (31 * s_k + 128) * 4 < ((int64_t)1 << 31);
-        return s_k == 1 && K % 4 == 0 && s_mn % 4 == 0 && (127 * s_mn + 32) * 4 < ((int64_t)1 << 31);
-    };
-    const bool dma = ctx->gemm_dma && dma_ok(A, a_m, M, sa_m, sa_k, sa_b) && dma_ok(B, b_n, N, sb_n, sb_k, sb_b);
+    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)splits, (unsigned)p.batch);
+    const bool a_m = (p.sa_m == 1) || (p.sa_k != 1 && M >= K);   // which axis consecutive threads walk
+    const bool b_n = (p.sb_n == 1) || (p.sb_k != 1 && N >= K);
+    g.vec_a = vec_ok(p.A, a_m, p.sa_m, p.sa_k, p.sa_b);
+    g.vec_b = vec_ok(p.B, b_n, p.sb_n, p.sb_k, p.sb_b);
+    g.fast = ctx->gemm_fast && g.vec_a && g.vec_b && stage_offsets_fit(p.sa_m, p.sa_k) && stage_offsets_fit(p.sb_n, p.sb_k);
+    const bool dma = ctx->gemm_dma && dma_ok(p.A, a_m, M, K, p.sa_m, p.sa_k, p.sa_b) &&
+                     dma_ok(p.B, b_n, N, K, p.sb_n, p.sb_k, p.sb_b);
     {
         bsc_prof_scope prof(ctx);
-#define BSC_GEMM_DMA(AM, BN_) \
-    hipLaunchKernelGGL((gemm_f32_dma_kernel<AM, BN_>), grid, dim3(GEMM_BLOCK), 0, ctx->stream, g)
-        if (dma) {
-            if (a_m && b_n) BSC_GEMM_DMA(true, true);
-            else if (a_m) BSC_GEMM_DMA(true, false);
-            else if (b_n) BSC_GEMM_DMA(false, true);
-            else BSC_GEMM_DMA(false, false);
-        } else {
-#undef BSC_GEMM_DMA
-#define BSC_GEMM(AM, BN_)                                                                       \
-    do {                                                                                        \
-        if (ctx->gemm_pipe)                                                                     \
-            hipLaunchKernelGGL((gemm_f32_mfma_kernel<AM, BN_, true>), grid, dim3(GEMM_BLOCK), 0, \
-                               ctx->stream, g);                                                 \
-        else                                                                                    \
-            hipLaunchKernelGGL((gemm_f32_mfma_kernel<AM, BN_, false>), grid, dim3(GEMM_BLOCK), 0, \
-                               ctx->stream, g);                                                 \
-    } while (0)
-        if (a_m && b_n) BSC_GEMM(true, true);
-        else if (a_m) BSC_GEMM(true, false);
-        else if (b_n) BSC_GEMM(false, true);
-        else BSC_GEMM(false, false);
-#undef BSC_GEMM
-        }
+        bsc_with_flags([&](auto AM, auto BN_) {
+            if (dma) hipLaunchKernelGGL((gemm_f32_dma_kernel<AM(), BN_()>), grid, dim3(GEMM_BLOCK), 0, ctx->stream, g);
+            else hipLaunchKernelGGL((gemm_f32_mfma_kernel<AM(), BN_()>), grid, dim3(GEMM_BLOCK), 0, ctx->stream, g);
+        }, a_m, b_n);
     }
     BSC_LAUNCH_CHECK();
     if (splits > 1) {
-        const dim3 rgrid((unsigned)((M * N + 255) / 256), (unsigned)batch);
+        const dim3 rgrid((unsigned)((M * N + 255) / 256), (unsigned)p.batch);
         hipLaunchKernelGGL(splitk_reduce_kernel, rgrid, dim3(256), 0, ctx->stream, slab, g.splits, M,
-                           N, (float*)C, sc_b, sc_m, sc_n, g);
+                           N, (float*)p.C, p.sc_b, p.sc_m, p.sc_n, g);
         BSC_LAUNCH_CHECK();
     }
     return BSC_OK;
+}
+
+static int gemm_impl(bsc_ctx* ctx, const Product& p) {
+    BSC_CHECK_CTX(ctx);
+    BSC_REQUIRE(p.dtype == BSC_F32 || p.dtype == BSC_F64, "bsc_gemm_strided_batched: unknown dtype %d", p.dtype);
+    BSC_REQUIRE(p.batch >= 0 && p.M >= 0 && p.N >= 0 && p.K >= 0, "bsc_gemm_strided_batched: negative extent");
+    if (p.batch == 0 || p.M == 0 || p.N == 0) return BSC_OK;
+    BSC_REQUIRE(p.C && ((p.A && p.B) || p.K == 0), "bsc_gemm_strided_batched: null pointer");
+    if (p.batch > 65535) {  // the batch index is a grid dimension: run 65535 batches per launch
+        const size_t es = p.dtype == BSC_F64 ? 8 : 4;
+        for (int64_t b0 = 0; b0 < p.batch; b0 += 65535) {
+            Product c = p;
+            c.batch = p.batch - b0 < 65535 ? p.batch - b0 : 65535;
+            if (c.A) c.A = (const char*)p.A + (size_t)(b0 * p.sa_b) * es;
+            if (c.B) c.B = (const char*)p.B + (size_t)(b0 * p.sb_b) * es;
+            c.C = (char*)p.C + (size_t)(b0 * p.sc_b) * es;
+            if (c.epi.E) c.epi.E += b0 * c.epi.se_b;
+            int rc = gemm_impl(ctx, c);
+            if (rc != BSC_OK) return rc;
+        }
+        return BSC_OK;
+    }
+    const bool naive = p.dtype == BSC_F64 || p.K == 0;
+    if (p.epi.handled) *p.epi.handled = 0;
+    if (p.pre() && naive) return BSC_OK;       // (not handled)
+    if (p.epi.pow && naive)
+        return bsc_fail(BSC_ERR_UNSUPPORTED, "bsc_gemm_epilogue: float32 products with K > 0 only");
+    if (naive) return gemm_naive(ctx, p);
+    int took = 0, rc;
+    if ((rc = gemm_matvec(ctx, p, &took)) != BSC_OK || took) return rc;
+    if ((rc = gemm_skinny(ctx, p, &took)) != BSC_OK || took) return rc;
+    if ((rc = gemm_gram_split(ctx, p, &took)) != BSC_OK || took) return rc;
+    if ((rc = gemm_stream(ctx, p, &took)) != BSC_OK || took) return rc;
+    if (p.pre()) return BSC_OK;      // (not handled: the tile kernels take their operands as they are)
+    return gemm_tile(ctx, p);
 }
 
 extern "C" {
@@ -1602,8 +1595,8 @@ int bsc_gemm_strided_batched(bsc_ctx* ctx, int dtype, int64_t batch, int64_t M, 
                              int64_t K, const void* A, int64_t sa_b, int64_t sa_m, int64_t sa_k,
                              const void* B, int64_t sb_b, int64_t sb_k, int64_t sb_n, void* C,
                              int64_t sc_b, int64_t sc_m, int64_t sc_n) {
-    return gemm_impl(ctx, dtype, batch, M, N, K, A, sa_b, sa_m, sa_k, B, sb_b, sb_k, sb_n, C, sc_b, sc_m, sc_n,
-                     Epilogue{});
+    return gemm_impl(ctx, Product{dtype, batch, M, N, K, A, sa_b, sa_m, sa_k, B, sb_b, sb_k, sb_n, C, sc_b, sc_m, sc_n,
+                                  Epilogue{}});
 }
 
 /* The persistent kernels' schedule, host side only (no device needed): how `tiles` tiles of `n_kt` units
@@ -1628,7 +1621,7 @@ int bsc_gemm_epilogue(bsc_ctx* ctx, int dtype, int64_t batch, int64_t M, int64_t
     e.scale = (float)scale;
     e.E = (const float*)E;
     e.se_b = se_b; e.se_m = se_m; e.se_n = se_n;
-    return gemm_impl(ctx, dtype, batch, M, N, K, A, sa_b, sa_m, sa_k, B, sb_b, sb_k, sb_n, C, sc_b, sc_m, sc_n, e);
+    return gemm_impl(ctx, Product{dtype, batch, M, N, K, A, sa_b, sa_m, sa_k, B, sb_b, sb_k, sb_n, C, sc_b, sc_m, sc_n, e});
 }
 
 int bsc_gemm_fused(bsc_ctx* ctx, int dtype, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t sa_b,
@@ -1649,7 +1642,7 @@ int bsc_gemm_fused(bsc_ctx* ctx, int dtype, int64_t batch, int64_t M, int64_t N,
     e.pre_a = pre_a; e.pre_b = pre_b;
     int h = 0;
     e.handled = &h;
-    const int rc = gemm_impl(ctx, dtype, batch, M, N, K, A, sa_b, sa_m, sa_k, B, sb_b, sb_k, sb_n, C, sc_b, sc_m, sc_n, e);
+    const int rc = gemm_impl(ctx, Product{dtype, batch, M, N, K, A, sa_b, sa_m, sa_k, B, sb_b, sb_k, sb_n, C, sc_b, sc_m, sc_n, e});
     *handled = h;
     return rc;
 }

@@ -251,14 +251,20 @@ def test_skinny_products_long_contraction_tn(dev, M, D, K):
                                           (64, 16, 96000, 1), (60, 64, 32768, 1), (8, 4, 40000, 1)])
 def test_gemm_operands_by_lds_dma_all_layouts(ctx, M, N, K, batch):
     """bsc_gemm_strided_batched in the four operand layouts (each operand contiguous along its
-    free axis or along k): the LDS-DMA kernel (gemm_f32_dma_kernel) wherever 16-byte pieces fall
-    wholly inside or outside an operand, the register-staged kernel otherwise -- ragged tiles,
-    a last k-tile shorter than 32, batches -- against float64, and the two kernels against each
-    other on the same operands."""
+    free axis or along k) -- ragged tiles, a last k-tile shorter than 32, batches -- in three contexts:
+    `ctx` (gemm_dma = 2, the default): the persistent stream kernel (gemm_f32_stream_kernel) wherever 16-byte
+    pieces fall wholly inside or outside both operands (dma_ok), the register-staged tile kernel
+    (gemm_f32_mfma_kernel) otherwise; `tile` (gemm_dma = 1): one tile per workgroup with the operands by LDS-DMA
+    (gemm_f32_dma_kernel) under the same condition, the register-staged kernel otherwise, K cut into splits
+    that splitk_reduce_kernel adds where the tiles are few (640x132x4100: eight); `staged` (gemm_dma = 0): the
+    register-staged kernel always.  Each against float64, the LDS-DMA kernels against the register-staged one on
+    the same operands
+    (profiles/gemm_tile_route_kernel_stats.csv: the kernels a trace of this test shows)."""
     import os
     import torch
     from bayesic_amd.device import Context
     staged = Context(0, options=dict(gemm_dma=0))
+    tile = Context(0, options=dict(gemm_dma=1))
     rs = np.random.RandomState(M + 3 * N + 7 * K)
     A_ = rs.standard_normal((batch, M, K)).astype(np.float32)
     B_ = rs.standard_normal((batch, K, N)).astype(np.float32)
@@ -273,21 +279,54 @@ def test_gemm_operands_by_lds_dma_all_layouts(ctx, M, N, K, batch):
             sa = (M * K, 1, M) if a_m else (M * K, K, 1)
             sb = (K * N, N, 1) if b_n else (K * N, 1, K)
             outs = []
-            for c in (ctx, staged):
+            for c in (ctx, staged, tile):
                 C = torch.full((batch, M, N), np.nan, dtype=torch.float32, device=dev)
                 c.call("bsc_gemm_strided_batched", 0, batch, M, N, K, At, sa[0], sa[1], sa[2], Bt, sb[0], sb[1], sb[2],
                        C, M * N, N, 1)
                 outs.append(C.cpu().numpy().astype(np.float64))
-            assert (np.abs(outs[0] - want) <= 1e-5 * bound + 1e-12).all(), (a_m, b_n, np.abs(outs[0] - want).max())
-            assert (np.abs(outs[0] - outs[1]) <= 2e-5 * bound + 1e-12).all()
-            # the epilogue on the same product: C = 0.5 * E / acc
             E = torch.from_numpy(rs.standard_normal((batch, M, N)).astype(np.float32)).to(dev)
-            C = torch.full((batch, M, N), np.nan, dtype=torch.float32, device=dev)
-            ctx.call("bsc_gemm_epilogue", 0, batch, M, N, K, At, sa[0], sa[1], sa[2], Bt, sb[0], sb[1], sb[2],
-                     C, M * N, N, 1, -1, 0.5, E, M * N, N, 1)
-            ref = 0.5 * E.cpu().numpy().astype(np.float64) / outs[0]
-            ok = np.abs(outs[0]) > 1e-2 * bound
-            npt.assert_allclose(C.cpu().numpy()[ok], ref[ok], rtol=2e-5)
+            for c, out in ((ctx, outs[0]), (tile, outs[2])):
+                assert (np.abs(out - want) <= 1e-5 * bound + 1e-12).all(), (a_m, b_n, np.abs(out - want).max())
+                assert (np.abs(out - outs[1]) <= 2e-5 * bound + 1e-12).all()
+                # the epilogue on the same product: C = 0.5 * E / acc
+                C = torch.full((batch, M, N), np.nan, dtype=torch.float32, device=dev)
+                c.call("bsc_gemm_epilogue", 0, batch, M, N, K, At, sa[0], sa[1], sa[2], Bt, sb[0], sb[1], sb[2],
+                       C, M * N, N, 1, -1, 0.5, E, M * N, N, 1)
+                ref = 0.5 * E.cpu().numpy().astype(np.float64) / out
+                ok = np.abs(out) > 1e-2 * bound
+                npt.assert_allclose(C.cpu().numpy()[ok], ref[ok], rtol=2e-5)
+
+
+@pytest.mark.parametrize("below", [0, 1], ids=["at-the-gate", "below-the-gate"])
+def test_gemm_short_contraction_over_many_full_tiles(ctx, below):
+    """The one way into gemm_f32_dma_kernel at default settings (short_k_plain, csrc/bsc_gemm.hip): a contraction two
+    to six k-tiles long over at least 8 x cu_count tiles, extents of two tiles and more, nothing but a scale folded
+    into the store.  batch = 2 x cu_count products of 256 x 256 x 36 are exactly 8 x cu_count tiles (two k-tiles, the
+    last one 4 deep); one batch fewer stays on gemm_f32_stream_kernel.  A k-contiguous and m-contiguous, B
+    n-contiguous; the plain product and the epilogue without a factor (C = 0.5 acc: halving is exact, so half the
+    bound) against torch.matmul in float64, everything on the device
+    (profiles/gemm_tile_route_kernel_stats.csv: the kernels a trace of the two cases shows)."""
+    import torch
+    cu = ctx.info()["cu_count"]
+    batch, M, N, K = 2 * cu - below, 256, 256, 36
+    tiles = batch * (M // 128) * (N // 128)
+    assert tiles == 8 * cu - 4 * below and (tiles >= 8 * cu) == (not below)
+    dev = ctx.device
+    g = torch.Generator(device=dev).manual_seed(cu + below)
+    A = torch.randn((batch, M, K), generator=g, device=dev)
+    B = torch.randn((batch, K, N), generator=g, device=dev)
+    A64, B64 = A.double(), B.double()
+    want = torch.matmul(A64, B64)
+    bound = A64.pow(2).sum(2).sqrt()[:, :, None] * B64.pow(2).sum(1).sqrt()[:, None, :]
+    for At, sa in ((A, (M * K, K, 1)), (A.transpose(1, 2).contiguous(), (M * K, 1, M))):
+        C = torch.full((batch, M, N), float("nan"), device=dev)
+        ctx.call("bsc_gemm_strided_batched", 0, batch, M, N, K, At, *sa, B, K * N, N, 1, C, M * N, N, 1)
+        ctx.sync()
+        assert bool(((C.double() - want).abs() <= 1e-5 * bound + 1e-12).all()), sa
+        C = torch.full((batch, M, N), float("nan"), device=dev)
+        ctx.call("bsc_gemm_epilogue", 0, batch, M, N, K, At, *sa, B, K * N, N, 1, C, M * N, N, 1, 1, 0.5, None, 0, 0, 0)
+        ctx.sync()
+        assert bool(((C.double() - 0.5 * want).abs() <= 0.5 * (1e-5 * bound) + 1e-12).all()), sa
 
 
 @pytest.mark.parametrize("rows,cols", [(100003, 64), (5000, 4), (70001, 128), (999, 36), (33, 8), (400000, 16)])

@@ -547,8 +547,9 @@ def test_profiling_only_builds_need_an_explicit_second_switch(monkeypatch):
         plain.set_option("blr_q", 0)
     with pytest.raises(BayesicHipError, match="not accepted"):
         plain.set_option("blr_mx", 1)
-    with pytest.raises(BayesicHipError, match="unknown option"):
-        plain.set_option("blr_fold", 1)
+    for gone in ("blr_fold", "gemm_pipe", "fused_map_unroll"):
+        with pytest.raises(BayesicHipError, match="unknown option"):
+            plain.set_option(gone, 1)
     assert plain.get_option("blr_mx") == 0
 
 

@@ -55,8 +55,8 @@ LIMITS = {
         "gram256_bx_kernel": (256, 0),                  # eight waves a CU = two per SIMD
     },
     "bsc_gemm.hip": {
-        "gemm_f32_mfma_kernelILb1ELb1ELb1E": (256, 0),
-        "gemm_f32_mfma_kernelILb0ELb1ELb1E": (256, 0),
+        "gemm_f32_mfma_kernelILb1ELb1EE": (256, 0),
+        "gemm_f32_mfma_kernelILb0ELb1EE": (256, 0),
         "gemm_f32_dma_kernel": (144, 0),
         # two workgroups per CU: <= 256; the few scratch bytes are spills in the guarded edge-tile
         # store path, outside the k-loop (the loop's own budget is checked in the ISA: DESIGN 12)

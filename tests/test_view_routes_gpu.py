@@ -16,63 +16,69 @@ sums of positive terms rtol 1e-5 = 84 eps_f32 * sum|terms| (test_fusion_gpu: sum
 element-wise maps and the float32 natural-gradient step (three roundings of positive terms) rtol 1e-6, atol
 1e-6 (test_fusion_gpu: X * u + 1).
 
-One row per gate: where it is, a case that takes the 16-byte / LDS-DMA side and one that takes the fall-back
-(ids as pytest prints them; kernel names as a kernel trace prints them, profiles/view_routes_kernel_stats.csv).
+One row per gate: the route function or predicate that holds it (names as in the source file, no line numbers),
+a case that takes the 16-byte / LDS-DMA side and one that takes the fall-back (ids as pytest prints them; kernel
+names as a kernel trace prints them, profiles/view_routes_kernel_stats.csv).
 WHAT THE TRACE SHOWS: where the two sides are DIFFERENT kernels (marked [K]) both names have a non-zero count in the
 CSV.  Where the gate is a branch inside ONE kernel (marked [B]) the trace cannot tell the sides apart: that both
-ran follows from the dispatcher / kernel source at the line given and from the cases' layouts, nothing more.
+ran follows from the dispatcher / kernel source at the place named and from the cases' layouts, nothing more.
 
-  [K] bsc_gemm.hip:1392 dma_ok, alignment (stream)   gemm_f32_stream_kernel <- test_gemm[plain-256x384x160-b1-ctl]
-                                                     gemm_f32_mfma_kernel <- test_gemm[plain-256x384x160-b1-Aoff1]
-  [K] bsc_gemm.hip:1394-1395 dma_ok, span            gemm_f32_stream_kernel <- test_span_gates[gemm-kcontig-below], [gemm-mcontig-below]
-                                                     gemm_f32_mfma_kernel <- test_span_gates[gemm-kcontig-above], [gemm-mcontig-above]
-  [-] bsc_gemm.hip:1556 dma_ok (tile kernels)        gemm_f32_dma_kernel: NOT reached by any case -- with the default gemm_dma >= 2 every
-                                                     layout that passes this gate has already passed line 1392 and left by the stream
-                                                     kernel (or the short_k_plain exception, which these shapes do not meet)
-  [B] bsc_gemm.hip:1545 vec_ok / g.fast (tile)       gemm_f32_mfma_kernel <- test_gemm[plain-129x257x33-b1-ctl] (16-byte loads)
-                                                     the same kernel <- test_gemm[plain-129x257x33-b1-Boff1-T] (4-byte loads)
-  [B] bsc_gemm.hip:836-837 c_vec / e_vec             gemm_f32_stream_kernel <- test_gemm[epilogue-256x384x160-b1-CT]
-                                                     the same kernel, scalar store <- test_gemm[epilogue-256x384x160-b1-Coff1-ld+1-T]
-  [B] bsc_gemm.hip:186 vec_e (tile epilogue)         gemm_f32_mfma_kernel <- test_gemm[epilogue-129x257x33-b1-ctl]
-                                                     the same kernel, scalar E <- test_gemm[epilogue-129x257x33-b1-Eoff1]
-  [B] bsc_gemm.hip:1415 sym (same pointer)           gemm_f32_stream_kernel with s.sym <- test_gemm[plain-256x256x160-b1-same-ctl]; the stream
-                                                     kernel also runs without sym, so only the fall-back is a trace fact:
-                                                     gemm_f32_mfma_kernel <- test_gemm[plain-256x256x160-b1-same-Aoff1-ld+1]
-  [B] bsc_gemm.hip:1108 gemv vec                     gemv_kcontig_kernel <- test_gemv[N1-100000x256-ctl]
-                                                     the same kernel, 4-byte loads <- test_gemv[N1-100000x256-Moff1]
-  [K] bsc_gemm.hip:1331 gemv vec4                    gemv_mcontig4_kernel <- test_gemv[M1-100000x256-ctl]
-                                                     gemv_mcontig_kernel <- test_gemv[M1-100000x256-Mld+1]
-  [K] bsc_skinny.hip:336 / 342 NT                    gemm_skinny_nt_kernel <- test_skinny[nt-ctl], test_skinny[nt_swapped-ctl]
-                                                     gemm_f32_* <- test_skinny[nt-big:off1], test_skinny[nt-ctl-skinny0]
-  [K] bsc_skinny.hip:370 / 377 TN, alignment         gemm_skinny_tn_kernel <- test_skinny[tn-ctl], test_skinny[tn_swapped-ctl]
-                                                     gemm_f32_* <- test_skinny[tn-big:ld+1], test_skinny[tn-ctl-skinny0]
-  [K] bsc_skinny.hip:371 TN, span (s * 15 + K)       gemm_skinny_tn_kernel <- test_span_gates[skinny-tn-below]
-                                                     gemm_f32_* <- test_span_gates[skinny-tn-above]
-  [-] bsc_skinny.hip:332 small_span (ld < 2^26)      NOT crossed: the NT routes need >= 4096 rows at that stride (1 TiB), and for TN the
-                                                     line-371 limit above binds first (s < 2^29 / 15)
-  [K] bsc_fused.hip:1055 map_flat                    map_flat_f32_kernel <- test_map_family[map-64x64-ctl]
-                                                     map_rows_f32_kernel / map_dense_f32_kernel <- test_map_family[map-64x64-ctl-flat0];
-                                                     map_small_f32_kernel <- test_map_family[map-64x64-x:off1]
-                                                     (map_strided_kernel: float64 or > 2^20 outputs only, not reached here)
-  [K] bsc_fused.hip short-row reducer                map_reduce_rows_f32_kernel <- test_map_family[rowsum-4096x7-ctl]
-                                                     map_reduce_wave_kernel <- test_map_family[rowsum-4096x7-x:off1]
-  [K] bsc_fused.hip:1240 dense_wave                  map_reduce_wave_dense_f32_kernel <- test_map_family[rowsum-4096x64-ctl]
-                                                     map_reduce_wave_kernel <- test_map_family[rowsum-4096x64-x:ld+1]
-  [K] bsc_fused.hip:1238 dense_lane                  map_reduce_lane_dense_f32_kernel <- test_map_family[colsum-64x4096-ctl]
-                                                     map_reduce_lane_kernel <- test_map_family[colsum-64x4096-x:off1]
-  [K] bsc_tensor.hip:288 dense element-wise          elemwise_dense_f32_kernel <- test_map_family[elemwise-64x64-ctl]
-                                                     elemwise_kernel <- test_map_family[elemwise-64x64-x:off1]
-  [B] bsc_stats.hip:23 head peel                     normal_stats_partial_kernel <- test_suffstats_normal[off0-n100001] ... [off3-n100001]
-  [B] bsc_stats.hip:109 / 192 row sums               row_sum_kernel / row_sum_bound_kernel <- test_dirichlet_expectation[7x33-ctl] vs [7x33-off1]
-  [K] bsc_stats.hip:500 vec4 softmax                 softmax_rows_vec4_kernel <- test_softmax_rows[4097x64-in:dense-out:dense]
-                                                     softmax_rows_small_kernel <- test_softmax_rows[4097x64-in:off1-out:dense];
-                                                     softmax_rows_wide_kernel <- test_softmax_rows[31x257-in:dense-out:dense]
-  [K] bsc_lda.hip:1325-1330 vec_c / vec_th / stream  lda_sstats_stream_kernel (_k64 / _k32 / _bound likewise) <- test_lda_sstats[K128-V1028-ctl]
-                                                     lda_sstats_kernel <- test_lda_sstats[K128-V1028-ctl-stream0], [K128-V1028-c:off1]
-                                                     (K = 96 has no stream kernel: lda_sstats_kernel always)
-  [B] bsc_lda.hip:1525 csc vec_th / csc_fast         lda_sstats_csc_kernel <- test_lda_sstats_csc[K64-ctl] (a.fast) vs [K64-th:off1], [K64-th:ld+1],
-                                                     [K64-ctl-fast0] (general loads)
-  [-] bsc_mog.hip:826 (no gate: 4-byte loads)        mog_estep_kernel, every layout
+  [K] bsc_gemm.hip gemm_stream: dma_ok, alignment       gemm_f32_stream_kernel <- test_gemm[plain-256x384x160-b1-ctl]
+                                                        gemm_f32_mfma_kernel <- test_gemm[plain-256x384x160-b1-Aoff1]
+  [K] bsc_gemm.hip gemm_stream: dma_ok, lane offsets    gemm_f32_stream_kernel <- test_span_gates[gemm-kcontig-below], [gemm-mcontig-below]
+                                                        gemm_f32_mfma_kernel <- test_span_gates[gemm-kcontig-above], [gemm-mcontig-above]
+  [K] bsc_gemm.hip gemm_tile: dma_ok (the same          gemm_f32_dma_kernel: not reached by the cases of this file -- with the default
+      predicate), after short_k_plain or gemm_dma = 1   gemm_dma = 2 every layout that passes dma_ok has left by gemm_stream, and these shapes
+                                                        do not meet short_k_plain.  Reached by test_algebra_gpu.py:
+                                                        test_gemm_operands_by_lds_dma_all_layouts (its context with gemm_dma = 1: gemm_f32_dma_kernel
+                                                        where dma_ok holds, gemm_f32_mfma_kernel where it does not: 130x257x1000, 257x129x20) and
+                                                        test_gemm_short_contraction_over_many_full_tiles[at-the-gate] (short_k_plain at default
+                                                        settings; [below-the-gate]: gemm_f32_stream_kernel) -- profiles/gemm_tile_route_kernel_stats.csv
+  [B] bsc_gemm.hip gemm_tile: vec_ok / g.fast           gemm_f32_mfma_kernel <- test_gemm[plain-129x257x33-b1-ctl] (16-byte loads)
+                                                        the same kernel <- test_gemm[plain-129x257x33-b1-Boff1-T] (4-byte loads)
+  [B] bsc_gemm.hip gemm_f32_stream_kernel: c_vec / e_vec  gemm_f32_stream_kernel <- test_gemm[epilogue-256x384x160-b1-CT]
+                                                        the same kernel, scalar store <- test_gemm[epilogue-256x384x160-b1-Coff1-ld+1-T]
+  [B] bsc_gemm.hip gemm_store_tile: vec_e               gemm_f32_mfma_kernel <- test_gemm[epilogue-129x257x33-b1-ctl]
+                                                        the same kernel, scalar E <- test_gemm[epilogue-129x257x33-b1-Eoff1]
+  [B] bsc_gemm.hip gemm_stream: s.sym (same pointer)    gemm_f32_stream_kernel with s.sym <- test_gemm[plain-256x256x160-b1-same-ctl]; the stream
+                                                        kernel also runs without sym, so only the fall-back is a trace fact:
+                                                        gemm_f32_mfma_kernel <- test_gemm[plain-256x256x160-b1-same-Aoff1-ld+1]
+  [B] bsc_gemm.hip gemv_kcontig_kernel: vec             gemv_kcontig_kernel <- test_gemv[N1-100000x256-ctl]
+                                                        the same kernel, 4-byte loads <- test_gemv[N1-100000x256-Moff1]
+  [K] bsc_gemm.hip gemm_matvec: vec4                    gemv_mcontig4_kernel <- test_gemv[M1-100000x256-ctl]
+                                                        gemv_mcontig_kernel <- test_gemv[M1-100000x256-Mld+1]
+  [K] bsc_skinny.hip bsc_gemm_skinny: NT conditions     gemm_skinny_nt_kernel <- test_skinny[nt-ctl], test_skinny[nt_swapped-ctl]
+                                                        gemm_f32_* <- test_skinny[nt-big:off1], test_skinny[nt-ctl-skinny0]
+  [K] bsc_skinny.hip bsc_gemm_skinny: TN, alignment     gemm_skinny_tn_kernel <- test_skinny[tn-ctl], test_skinny[tn_swapped-ctl]
+                                                        gemm_f32_* <- test_skinny[tn-big:ld+1], test_skinny[tn-ctl-skinny0]
+  [K] bsc_skinny.hip bsc_gemm_skinny: TN, s * 15 + K    gemm_skinny_tn_kernel <- test_span_gates[skinny-tn-below]
+                                                        gemm_f32_* <- test_span_gates[skinny-tn-above]
+  [-] bsc_skinny.hip small_span (ld < 2^26)             NOT crossed: the NT routes need >= 4096 rows at that stride (1 TiB), and for TN the
+                                                        s * 15 + K limit above binds first (s < 2^29 / 15)
+  [K] bsc_fused.hip map_flat                            map_flat_f32_kernel <- test_map_family[map-64x64-ctl]
+                                                        map_rows_f32_kernel / map_dense_f32_kernel (map_rows2d, map_is_dense) <-
+                                                        test_map_family[map-64x64-ctl-flat0]; map_small_f32_kernel (map_small) <-
+                                                        test_map_family[map-64x64-x:off1]
+                                                        (map_strided: float64 or > 2^20 outputs only, not reached here)
+  [K] bsc_fused.hip short_rows                          map_reduce_rows_f32_kernel <- test_map_family[rowsum-4096x7-ctl]
+                                                        map_reduce_wave_kernel <- test_map_family[rowsum-4096x7-x:off1]
+  [K] bsc_fused.hip reduce_plan: dense_wave             map_reduce_wave_dense_f32_kernel <- test_map_family[rowsum-4096x64-ctl]
+                                                        map_reduce_wave_kernel <- test_map_family[rowsum-4096x64-x:ld+1]
+  [K] bsc_fused.hip reduce_plan: dense_lane             map_reduce_lane_dense_f32_kernel <- test_map_family[colsum-64x4096-ctl]
+                                                        map_reduce_lane_kernel <- test_map_family[colsum-64x4096-x:off1]
+  [K] bsc_tensor.hip bsc_elemwise: dense                elemwise_dense_f32_kernel <- test_map_family[elemwise-64x64-ctl]
+                                                        elemwise_kernel <- test_map_family[elemwise-64x64-x:off1]
+  [B] bsc_stats.hip normal_stats_partial_kernel: head   normal_stats_partial_kernel <- test_suffstats_normal[off0-n100001] ... [off3-n100001]
+  [B] bsc_stats.hip row_sum_kernel(s): 16-byte loads    row_sum_kernel / row_sum_bound_kernel <- test_dirichlet_expectation[7x33-ctl] vs [7x33-off1]
+  [K] bsc_stats.hip bsc_softmax_rows: vec4              softmax_rows_vec4_kernel <- test_softmax_rows[4097x64-in:dense-out:dense]
+                                                        softmax_rows_small_kernel <- test_softmax_rows[4097x64-in:off1-out:dense];
+                                                        softmax_rows_wide_kernel <- test_softmax_rows[31x257-in:dense-out:dense]
+  [K] bsc_lda.hip a.vec_c / a.vec_th / lda_stream       lda_sstats_stream_kernel (_k64 / _k32 / _bound likewise) <- test_lda_sstats[K128-V1028-ctl]
+                                                        lda_sstats_kernel <- test_lda_sstats[K128-V1028-ctl-stream0], [K128-V1028-c:off1]
+                                                        (K = 96 has no stream kernel: lda_sstats_kernel always)
+  [B] bsc_lda.hip csc: a.vec_th / csc_fast              lda_sstats_csc_kernel <- test_lda_sstats_csc[K64-ctl] (a.fast) vs [K64-th:off1], [K64-th:ld+1],
+                                                        [K64-ctl-fast0] (general loads)
+  [-] bsc_mog.hip bsc_mog_estep (no gate: 4-byte loads) mog_estep_kernel, every layout
 """
 import ctypes
 
