@@ -1,0 +1,402 @@
+// The bodies of the GLM training-pass kernels (csrc/bsc_glm.hip's header comment describes the two tile shapes), as
+// __device__ templates with one compile-time flag so that two translation units can instantiate them:
+//
+//   OBS = false   csrc/bsc_glm.hip: glm_pass_kernel / glm_pass_mfma_kernel, the pass over (X, y) alone.  Every use of
+//                 the offset and the weight is behind `if (OBS)`, the tile structs carry no extra registers, and the
+//                 kernels come out as they did when the bodies lived in that file.
+//   OBS = true    csrc/bsc_glm_obs.hip: glm_obs_pass_kernel / glm_obs_pass_mfma_kernel, with a per-row offset o_n
+//                 (added to the logit before the link) and a per-row weight v_n >= 0:
+//                     l[n,s] = x_n . w_s + o[n],  ell[s] = sum_n v[n] (y[n] l[n,s] - A(l[n,s])),
+//                     G[s,:] = sum_n v[n] (y[n] - A'(l[n,s])) x_n
+//                 A row with v_n = 0 adds exactly nothing, by a select and not by a product (its link value may have
+//                 overflowed).  o and v ride in the tile struct next to y and are loaded the way y is; a null offset
+//                 is a zero-record descriptor (reads 0, costs nothing), a null weight a uniform select of 1.0f.
+//                 Rows past B read o = 0 and v = 0 through the descriptors.
+//
+// Header-only, internal linkage, like csrc/bsc_regress.h.
+#pragma once
+
+#include "bsc_regress.h"
+
+namespace {
+
+constexpr int SLAB_G = REG_SLAB_G;            // slab[b][d*8 + s], then ell at [SLAB_G + s]
+constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
+
+// ---- the link: ell += y l - A(l) for a real row, resid = y - A'(l) ------------------------------------------
+//
+// Logistic: A = softplus in the stable form max(l, 0) + log1p(e), e = exp(-|l|) <= 1 (exp at full float32 accuracy:
+// the tails at |l| = 80 are compared at rtol 1e-6), and A' = sigmoid from the
+// same e (1 / (1 + e) for l >= 0, e / (1 + e) below): finite for every finite l.  Poisson: A = A' = exp(l),
+// NOT clamped (a clamp would change the gradient silently): finite for l <= 88.
+// OBS: `l` already holds the offset; both terms are scaled by the weight vv where vv > 0 and are exactly 0 elsewhere.
+template <int LINK, bool OBS = false>
+__device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv = 1.0f) {
+    float a, da;
+    if (LINK == BSC_GLM_LOGISTIC) {
+        const float e = expf(-fabsf(l));
+        const float t = 1.0f + e;
+        const float r = __builtin_amdgcn_rcpf(t);
+        da = l >= 0.0f ? r : e * r;
+        // log1p(e) = log(t) e / (t - 1): the quotient undoes the rounding of t = 1 + e (t - 1 is exact); t == 1: e itself.
+        // Within 3e-7 of log1p over e in [0, 1], ten vector instructions where the library's log1pf is ~90.
+        const float lp = t == 1.0f ? e : __logf(t) * e * __builtin_amdgcn_rcpf(t - 1.0f);
+        a = fmaxf(l, 0.0f) + lp;
+    } else {
+        a = expf(l);
+        da = a;
+    }
+    if (OBS) {
+        const bool on = vv > 0.0f;
+        ell += (real_row && on) ? vv * fmaf(yv, l, -a) : 0.0f;
+        return on ? vv * (yv - da) : 0.0f;
+    }
+    ell += real_row ? fmaf(yv, l, -a) : 0.0f;
+    return yv - da;
+}
+
+// ---- 8-row tiles on the VALU (any D % 4 == 0 up to 256): blr_pass_kernel<., 8, .>'s tile (csrc/bsc_regress.h) ----
+constexpr int ROWS = 8;
+using G8 = Geo<ROWS>;
+
+template <bool OBS>
+struct GlmTile : RowTile<ROWS> {};
+template <>
+struct GlmTile<true> : RowTile<ROWS> {
+    float ov, vv;   // offset and weight of row lane_value(lane) >> 3, as yv
+};
+
+// One tile = ROWS rows from row0 on, through descriptors that cover exactly the rows [row0, B).
+template <bool FULL, bool OBS>
+__device__ __forceinline__ void load_tile(GlmTile<OBS>& t, const float* __restrict__ X, int64_t ldx,
+                                          const float* __restrict__ y, const float* __restrict__ o,
+                                          const float* __restrict__ v_, int64_t row0, int64_t B, int D, int lane) {
+    auto xs = bsc_rows_rsrc(X, ldx, D, B, row0);
+    auto ys = bsc_vec_rsrc(y, B, row0);
+    const int lane_off = 16 * lane;
+    const int row_bytes = (int)(ldx * 4);
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        auto v = __builtin_amdgcn_raw_buffer_load_b128(xs, lane_off, r * row_bytes, 2);   // non-temporal: X is read once
+        float4 f = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                               __uint_as_float(v[3]));
+        if (!FULL && 4 * lane >= D) f = make_float4(0.f, 0.f, 0.f, 0.f);  // the next row's bytes
+        t.x[r] = f;
+    }
+    t.yv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ys, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
+    if constexpr (OBS) {   // a null vector: no records, every lane reads 0
+        auto os = bsc_vec_rsrc(o, o ? B : 0, row0);
+        auto vs = bsc_vec_rsrc(v_, v_ ? B : 0, row0);
+        t.ov = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(os, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
+        t.vv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vs, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
+    }
+}
+
+// Forward + link + backward for one tile; `wl` is this wave's LDS region, `rows_left` = B - row0.  has_v: the weights
+// are set (uniform; without them every row weighs 1.0f and real_row alone masks the rows past B).
+template <int LINK, bool OBS>
+__device__ __forceinline__ void compute_tile(const GlmTile<OBS>& t, const float4 (&w)[SG], float4 (&acc)[SG],
+                                             float& ell, float* wl, int lane, int64_t rows_left, bool has_v) {
+    // 1. per-lane partial dots, row by row, into this lane's row of the buffer
+    float* mine = wl + lane * G8::PSTR;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        float4 lo, hi;
+        lo.x = dot4(t.x[r], w[0]); lo.y = dot4(t.x[r], w[1]);
+        lo.z = dot4(t.x[r], w[2]); lo.w = dot4(t.x[r], w[3]);
+        hi.x = dot4(t.x[r], w[4]); hi.y = dot4(t.x[r], w[5]);
+        hi.z = dot4(t.x[r], w[6]); hi.w = dot4(t.x[r], w[7]);
+        *reinterpret_cast<float4*>(mine + r * SG) = lo;
+        *reinterpret_cast<float4*>(mine + r * SG + 4) = hi;
+    }
+    wave_lds_sync();
+    // 2. lane k sums values 4g..4g+3 (g = k % 16) over the lane-rows 16 q .. 16 q + 15
+    const int g = lane & (G8::NGRP - 1), q = lane / G8::NGRP;
+    const float* col = wl + q * G8::RPQ * G8::PSTR + 4 * g;
+    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int part = 0; part < G8::RPQ / 8; ++part) {
+        float4 v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const float4*>(col + (8 * part + i) * G8::PSTR);
+#pragma unroll
+        for (int h = 4; h >= 1; h >>= 1) {
+#pragma unroll
+            for (int i = 0; i < h; ++i) {
+                v[i].x += v[i + h].x; v[i].y += v[i + h].y;
+                v[i].z += v[i + h].z; v[i].w += v[i + h].w;
+            }
+        }
+        s4.x += v[0].x; s4.y += v[0].y; s4.z += v[0].z; s4.w += v[0].w;
+    }
+    // 3. fold the row subsets (lane bits 4, 5): lane k ends with the logit of value lane_value(k)
+    const float t0 = swap_add32(s4.x, s4.z);
+    const float t1 = swap_add32(s4.y, s4.w);
+    const float logit = swap_add16(t0, t1);
+    const int val = lane_value<ROWS>(lane);
+    float resid;
+    if constexpr (OBS)
+        resid = glm_link<LINK, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell, has_v ? t.vv : 1.0f);
+    else
+        resid = glm_link<LINK>(logit, t.yv, (int64_t)(val >> 3) < rows_left, ell);
+    float* rb = wl + BSC_WAVE * G8::PSTR;
+    rb[val] = resid;
+    wave_lds_sync();
+    // 4. backward: acc[s] += resid(r, s) * x[r]; residuals arrive by LDS broadcast
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        if (r == 4) asm volatile("" ::: "memory");  // at most four rows of broadcast reads in flight
+        const float4 c0 = *reinterpret_cast<const float4*>(rb + r * SG);
+        const float4 c1 = *reinterpret_cast<const float4*>(rb + r * SG + 4);
+        axpy4(acc[0], c0.x, t.x[r]); axpy4(acc[1], c0.y, t.x[r]);
+        axpy4(acc[2], c0.z, t.x[r]); axpy4(acc[3], c0.w, t.x[r]);
+        axpy4(acc[4], c1.x, t.x[r]); axpy4(acc[5], c1.y, t.x[r]);
+        axpy4(acc[6], c1.z, t.x[r]); axpy4(acc[7], c1.w, t.x[r]);
+    }
+}
+
+// The block partial: fixed order over the waves, written in slab order [d][s] | ell[s].
+__device__ __forceinline__ void write_block_partial(const float* lds, float* __restrict__ slab, int tid) {
+    float* out = slab + (int64_t)blockIdx.x * SLAB_STRIDE;
+    for (int i = tid; i < SLAB_STRIDE; i += PASS_BLOCK) {
+        const int src = i < SLAB_G ? (i & 7) * GCOLS + (i >> 3) : i;
+        float v = lds[src];
+#pragma unroll
+        for (int k = 1; k < PASS_WAVES; ++k) v += lds[k * SLAB_STRIDE + src];
+        out[i] = v;
+    }
+}
+
+// FULL: D == 256.  n_iter: tiles per wave (the same for every wave; tiles past the end read zeros).
+// o, v_: the offset and the weight, each may be null; read only where OBS.
+template <int LINK, bool FULL, bool OBS>
+__device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const float* y, const float* o,
+                                              const float* v_, int64_t B, int D, const float* W, int S, float* slab,
+                                              int n_iter) {
+    constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > SLAB_STRIDE ? G8::WAVE_LDS : SLAB_STRIDE);
+    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float* wl = lds + wave * G8::WAVE_LDS;
+    const bool has_v = OBS && v_ != nullptr;
+
+    float4 w[SG], acc[SG];
+#pragma unroll
+    for (int s = 0; s < SG; ++s) {
+        w[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (4 * lane < D && s < S) w[s] = *reinterpret_cast<const float4*>(W + (int64_t)s * D + 4 * lane);
+        acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float ell = 0.f;
+
+    // This wave owns tiles first, first + stride, ...; every prefetch is unconditional.
+    const int64_t stride = (int64_t)gridDim.x * PASS_WAVES;
+    int64_t tile = (int64_t)blockIdx.x * PASS_WAVES + wave;
+    GlmTile<OBS> ta, tb;
+    load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane);
+    for (int k = 0; k + 1 < n_iter; k += 2) {
+        load_tile<FULL, OBS>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane);
+        compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
+        load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane);
+        compute_tile<LINK, OBS>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v);
+        tile += 2 * stride;
+    }
+    if (n_iter & 1) compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
+
+    __syncthreads();  // every wave is done with its private region
+    float* ep = lds + wave * SLAB_STRIDE;
+#pragma unroll
+    for (int s = 0; s < SG; ++s) *reinterpret_cast<float4*>(ep + s * GCOLS + 4 * lane) = acc[s];
+    // ell of lane k belongs to draw lane_value(k) & 7; fold the tile rows (lane bits 1 .. 3)
+    float ev = ell;
+    ev += __shfl_xor(ev, 2);
+    ev += __shfl_xor(ev, 4);
+    ev += __shfl_xor(ev, 8);
+    if ((lane & 14) == 0) ep[SLAB_G + (lane_value<ROWS>(lane) & 7)] = ev;
+    __syncthreads();
+    write_block_partial(lds, slab, tid);
+}
+
+// ---- 16-row tiles, both contractions on the MFMA pipe (D == 256, y [o, v] 16-byte aligned) ----------------------
+constexpr int MT_ROWS = 16;
+constexpr int MT_RS = GCOLS + 4;                                // LDS row stride (floats)
+constexpr int MT_WAVE_LDS = MT_ROWS * MT_RS + MT_ROWS * SG;     // tile + residuals [draw][row]
+
+typedef float mfma_f32x4 __attribute__((ext_vector_type(4)));
+
+struct MTileXY {
+    float4 x[MT_ROWS];
+    float4 yv;     // y[row0 + 4 kq .. + 3]: the rows of this lane's forward result registers
+};
+template <bool OBS>
+struct MTile : MTileXY {};
+template <>
+struct MTile<true> : MTileXY {
+    float4 ov, vv;   // offset and weight of the same four rows
+};
+
+__device__ __forceinline__ float4 load_rows4(const float* __restrict__ p, int64_t n, int64_t row0, int lane) {
+    auto rs = bsc_vec_rsrc(p, n, row0);
+    auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * (lane >> 4), 0, 0);
+    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+}
+
+template <bool OBS>
+__device__ __forceinline__ void load_mtile(MTile<OBS>& t, const float* __restrict__ X, int64_t ldx,
+                                           const float* __restrict__ y, const float* __restrict__ o,
+                                           const float* __restrict__ v_, int64_t row0, int64_t B, int lane) {
+    auto xs = bsc_rows_rsrc(X, ldx, GCOLS, B, row0);
+    auto ys = bsc_vec_rsrc(y, B, row0);
+    const int lane_off = 16 * lane;
+    const int row_bytes = (int)(ldx * 4);
+#pragma unroll
+    for (int r = 0; r < MT_ROWS; ++r) {
+        auto v = __builtin_amdgcn_raw_buffer_load_b128(xs, lane_off, r * row_bytes, 2);   // non-temporal
+        t.x[r] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                             __uint_as_float(v[3]));
+    }
+    auto v = __builtin_amdgcn_raw_buffer_load_b128(ys, 16 * (lane >> 4), 0, 0);
+    t.yv = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+    if constexpr (OBS) {   // a null vector: no records, every lane reads 0
+        t.ov = load_rows4(o, o ? B : 0, row0, lane);
+        t.vv = load_rows4(v_, v_ ? B : 0, row0, lane);
+    }
+}
+
+template <int LINK, bool OBS>
+__device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, const float* y, const float* o,
+                                                   const float* v_, int64_t B, const float* W, int S, float* slab,
+                                                   int n_iter) {
+    constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > SLAB_STRIDE ? MT_WAVE_LDS : SLAB_STRIDE);
+    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i16 = lane & 15, kq = lane >> 4;
+    float* tl = lds + wave * MT_WAVE_LDS;      // this wave's tile
+    float* rb = tl + MT_ROWS * MT_RS;          // residuals [draw][row]
+    const bool has_v = OBS && v_ != nullptr;
+
+    // forward B operand: W[draw i16][64 kq + 4 j + c]; MFMA columns 8 .. 15 and draws >= S are zero.  Lane group
+    // kq contracts columns 64 kq .. 64 kq + 63, which keeps the 16-byte A reads of a lane group conflict-free.
+    float wreg[GCOLS / 4];
+#pragma unroll
+    for (int j = 0; j < GCOLS / 16; ++j) {
+        float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i16 < S) w4 = *reinterpret_cast<const float4*>(W + (int64_t)i16 * GCOLS + 64 * kq + 4 * j);
+        wreg[4 * j + 0] = w4.x; wreg[4 * j + 1] = w4.y;
+        wreg[4 * j + 2] = w4.z; wreg[4 * j + 3] = w4.w;
+    }
+    mfma_f32x4 acc[2][4];                      // [draw group][column component]: register i = draw 4 sb + i
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[sb][q] = mfma_f32x4{0.f, 0.f, 0.f, 0.f};
+    float ell = 0.f;
+    const bool live = i16 < SG;                // lanes whose forward MFMA column is a draw
+
+    // iteration p of every wave reads one contiguous window of gridDim.x * 4 tiles; p == n_iter: the empty tile
+    const int64_t stride0 = (int64_t)gridDim.x * PASS_WAVES;
+    const int64_t slot = (int64_t)blockIdx.x * PASS_WAVES + wave;
+    auto row0_of = [=](int p) { return p < n_iter ? ((int64_t)p * stride0 + slot) * MT_ROWS : B; };
+
+    MTile<OBS> t;
+    load_mtile<OBS>(t, X, ldx, y, o, v_, row0_of(0), B, lane);
+    for (int p = 0; p < n_iter; ++p) {
+        // the tile to LDS, its registers take the next window's tile
+#pragma unroll
+        for (int r = 0; r < MT_ROWS; ++r) *reinterpret_cast<float4*>(tl + r * MT_RS + 4 * lane) = t.x[r];
+        const float4 yv = t.yv;
+        float4 ov = make_float4(0.f, 0.f, 0.f, 0.f), vv = make_float4(1.f, 1.f, 1.f, 1.f);
+        if constexpr (OBS) {   // this tile's offsets and weights, before the prefetch takes the registers
+            ov = t.ov;
+            if (has_v) vv = t.vv;
+        }
+        const int64_t rows_left = B - row0_of(p) - 4 * kq;     // rows 4 kq + reg < rows_left are real
+        load_mtile<OBS>(t, X, ldx, y, o, v_, row0_of(p + 1), B, lane);
+        wave_lds_sync();
+
+        // forward on v_mfma_f32_16x16x4_f32 (two accumulators: no MFMA waits on its predecessor)
+        mfma_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+        const float* arow = tl + i16 * MT_RS + 64 * kq;
+#pragma unroll
+        for (int j = 0; j < GCOLS / 16; j += 2) {
+            const float4 a0 = *reinterpret_cast<const float4*>(arow + 4 * j);
+            const float4 a1 = *reinterpret_cast<const float4*>(arow + 4 * j + 4);
+            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, wreg[4 * j + 0], d0, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, wreg[4 * j + 4], d1, 0, 0, 0);
+            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, wreg[4 * j + 1], d0, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, wreg[4 * j + 5], d1, 0, 0, 0);
+            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, wreg[4 * j + 2], d0, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, wreg[4 * j + 6], d1, 0, 0, 0);
+            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, wreg[4 * j + 3], d0, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, wreg[4 * j + 7], d1, 0, 0, 0);
+        }
+        // register reg of lane (i16, kq) = logit(row 4 kq + reg, draw i16): the link in the lane, the residuals
+        // to rb[draw][row] as one 16-byte store per live lane
+        if (live) {
+            float r0, r1, r2, r3;
+            if constexpr (OBS) {
+                r0 = glm_link<LINK, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x);
+                r1 = glm_link<LINK, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y);
+                r2 = glm_link<LINK, true>(d0[2] + d1[2] + ov.z, yv.z, rows_left > 2, ell, vv.z);
+                r3 = glm_link<LINK, true>(d0[3] + d1[3] + ov.w, yv.w, rows_left > 3, ell, vv.w);
+            } else {
+                r0 = glm_link<LINK>(d0[0] + d1[0], yv.x, rows_left > 0, ell);
+                r1 = glm_link<LINK>(d0[1] + d1[1], yv.y, rows_left > 1, ell);
+                r2 = glm_link<LINK>(d0[2] + d1[2], yv.z, rows_left > 2, ell);
+                r3 = glm_link<LINK>(d0[3] + d1[3], yv.w, rows_left > 3, ell);
+            }
+            *reinterpret_cast<float4*>(rb + i16 * MT_ROWS + 4 * kq) = make_float4(r0, r1, r2, r3);
+        }
+        wave_lds_sync();
+
+        // backward on v_mfma_f32_4x4x1_16B_f32: per row two draw groups x four column components
+#pragma unroll
+        for (int g = 0; g < MT_ROWS / 4; ++g) {
+            if (g) asm volatile("" ::: "memory");   // four rows of reads in flight
+            float4 ra[2];
+#pragma unroll
+            for (int sb = 0; sb < 2; ++sb)
+                ra[sb] = *reinterpret_cast<const float4*>(rb + (4 * sb + (lane & 3)) * MT_ROWS + 4 * g);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const float4 x4 = *reinterpret_cast<const float4*>(tl + (4 * g + rr) * MT_RS + 4 * lane);
+#pragma unroll
+                for (int sb = 0; sb < 2; ++sb) {
+                    const float a = rr == 0 ? ra[sb].x : rr == 1 ? ra[sb].y : rr == 2 ? ra[sb].z : ra[sb].w;
+                    acc[sb][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(a, x4.x, acc[sb][0], 0, 0, 0);
+                    acc[sb][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(a, x4.y, acc[sb][1], 0, 0, 0);
+                    acc[sb][2] = __builtin_amdgcn_mfma_f32_4x4x1f32(a, x4.z, acc[sb][2], 0, 0, 0);
+                    acc[sb][3] = __builtin_amdgcn_mfma_f32_4x4x1f32(a, x4.w, acc[sb][3], 0, 0, 0);
+                }
+            }
+        }
+        wave_lds_sync();   // the next iteration overwrites the tile
+    }
+
+    __syncthreads();
+    float* ep = lds + wave * SLAB_STRIDE;
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            *reinterpret_cast<float4*>(ep + (4 * sb + i) * GCOLS + 4 * lane) =
+                make_float4(acc[sb][0][i], acc[sb][1][i], acc[sb][2][i], acc[sb][3][i]);
+    float ev = live ? ell : 0.f;               // lane (i16, kq): rows 4 kq .. of draw i16
+    ev += __shfl_xor(ev, 16);
+    ev += __shfl_xor(ev, 32);
+    if (lane < SG) ep[SLAB_G + lane] = ev;
+    __syncthreads();
+    write_block_partial(lds, slab, tid);
+}
+
+// ---- host side: the launch of the OBS kernels, defined in csrc/bsc_glm_obs.hip and called from csrc/bsc_glm.hip ----
+
+}  // namespace
+
+// 16-row MFMA tiles when mfma != 0 (D == 256; y and the set ones of o, v 16-byte aligned), else 8-row VALU tiles.
+void bsc_glm_obs_launch_pass(bsc_ctx* ctx, int link, int mfma, const float* X, int64_t ldx, const float* y,
+                             const float* offset, const float* weight, int64_t B, int D, const float* W, int sg,
+                             int n_blocks, int n_iter, float* slab);

@@ -1,0 +1,294 @@
+// The body of the predictive pass (csrc/bsc_predict.hip's header comment describes it), as a __device__ template with
+// one compile-time flag so that two translation units can instantiate it: OFFS = false is predict_kernel of
+// csrc/bsc_predict.hip, unchanged; OFFS = true is predict_offset_kernel of csrc/bsc_predict_offset.hip, which adds a
+// per-row offset o_n to l_ns = x_n . w_s before the link (logistic and Poisson families: log E[y_n] = x_n . w +
+// log exposure_n).  Header-only, internal linkage, like csrc/bsc_regress.h.
+#pragma once
+
+#include "bsc_regress.h"
+
+namespace {
+
+constexpr int P_BLOCK = 512;
+constexpr int P_WAVES = P_BLOCK / BSC_WAVE;
+constexpr int T_ROWS = 16;                     // rows per tile = the MFMA's N
+constexpr int STRIP = 128;                     // columns per strip
+constexpr int XS = STRIP + 2;                  // LDS row stride of a strip (floats)
+constexpr int WCOLS = 256;                     // column capacity
+constexpr int WS = WCOLS + 2;                  // LDS row stride of the draws
+constexpr int P_MAX_S = 64;
+constexpr int LD_STRIP = STRIP * T_ROWS / (4 * BSC_WAVE);   // 16-byte loads per lane and strip: 8
+
+typedef float p_f32x4 __attribute__((ext_vector_type(4)));
+
+struct PredictArgs {
+    const float* X;
+    int64_t ldx;
+    const float* y;          // may be null
+    int64_t B;
+    const float* W;
+    const float* logvar;     // Gaussian only
+    float* mean;             // outputs, each may be null
+    float* var;
+    float* lpd;
+    double* partial;         // [gridDim.x] block sums of lpd
+    int D, S;
+    int n_iter;              // tiles per wave
+    int n_strips;            // strips per tile: 1 (D <= 128) or 2
+    int kw;                  // columns per lane group and strip (even)
+    int do_lp;               // y is set and lpd or lpd_sum is wanted
+};
+
+struct Strip {
+    float4 x[LD_STRIP];
+};
+
+// Strip h of the tile from row0 on: lane -> (row 2 r + lane / 32, columns 128 h + 4 (lane % 32) ..).
+__device__ __forceinline__ void load_strip(Strip& t, const PredictArgs& a, int64_t row0, int h, int lane) {
+    auto xs = bsc_rows_rsrc(a.X, a.ldx, a.D, a.B, row0);
+    const unsigned row_bytes = (unsigned)(a.ldx * 4);
+    const int col = STRIP * h + 4 * (lane & 31);
+    const int voff = (int)((unsigned)(lane >> 5) * row_bytes + 4u * (unsigned)col);
+#pragma unroll
+    for (int r = 0; r < LD_STRIP; ++r) {
+        auto v = __builtin_amdgcn_raw_buffer_load_b128(xs, voff, (int)(2u * r * row_bytes), 2);   // non-temporal
+        float4 f = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                               __uint_as_float(v[3]));
+        if (col >= a.D) f = make_float4(0.f, 0.f, 0.f, 0.f);   // padding, or the next row's bytes
+        t.x[r] = f;
+    }
+}
+
+__device__ __forceinline__ float load_y(const PredictArgs& a, int64_t row0, int i16) {
+    auto ys = bsc_vec_rsrc(a.y, a.y ? a.B : 0, row0);
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ys, 4 * i16, 0, 0));
+}
+
+__device__ __forceinline__ float load_offset(const float* __restrict__ offset, int64_t B, int64_t row0, int i16) {
+    auto os = bsc_vec_rsrc(offset, B, row0);
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(os, 4 * i16, 0, 0));
+}
+
+// mu, v and log p(y | l) of one draw.  p4 = (logvar, exp(logvar), exp(-logvar)) for the Gaussian family.
+// Logistic: csrc/bsc_glm.hip's stable forms from e = exp(-|l|) <= 1 -- sigmoid = 1 / (1 + e) or e / (1 + e),
+// v = mu (1 - mu) = e / (1 + e)^2 without the cancellation, softplus = max(l, 0) + log1p(e) with log1p(e) =
+// log(t) e / (t - 1), t = 1 + e (the quotient undoes the rounding of t): finite for every finite l.
+// Poisson: exp(l), not clamped; the row constant lnGamma(y + 1) is taken off after the log-mean-exp.
+template <int FAM>
+__device__ __forceinline__ void predict_link(float l, float yv, float lv, float ev, float iv, float& mu, float& v,
+                                             float& lp) {
+    if (FAM == BSC_PREDICT_GAUSSIAN) {
+        const float r = yv - l;
+        mu = l;
+        v = ev;
+        lp = fmaf(-0.5f * iv * r, r, -0.5f * (lv + (float)BSC_LOG_2PI));
+    } else if (FAM == BSC_PREDICT_LOGISTIC) {
+        const float e = expf(-fabsf(l));
+        const float t = 1.0f + e;
+        const float r = 1.0f / t;
+        mu = l >= 0.0f ? r : e * r;
+        v = e * r * r;
+        const float l1p = t == 1.0f ? e : logf(t) * e / (t - 1.0f);
+        lp = fmaf(yv, l, -(fmaxf(l, 0.0f) + l1p));
+    } else {
+        mu = expf(l);
+        v = mu;
+        lp = fmaf(yv, l, -mu);
+    }
+}
+
+// FULL: D == 256 (two strips, 32 columns per lane group, everything unrolled).
+// OFFS: `offset` [B] (not null) is loaded like y and added to every draw's l of its row before the link.
+template <int FAM, int NC, bool FULL, bool OFFS>
+__device__ __forceinline__ void predict_body(PredictArgs a, const float* offset) {
+    constexpr int W_FLOATS = NC * 16 * WS;
+    constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
+    __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + 3 * P_MAX_S];
+    __shared__ double red[P_WAVES];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i16 = lane & 15, kq = lane >> 4;
+    float* wl = lds;                                    // draws [16 NC][WS], zero-padded
+    float* xl = lds + W_FLOATS + wave * (T_ROWS * XS);  // this wave's strip [16][XS]
+    float* gp = lds + W_FLOATS + X_FLOATS;              // logvar | exp(logvar) | exp(-logvar), [64] each
+    const int S = a.S, D = a.D;
+
+    for (int row = wave; row < NC * 16; row += P_WAVES)
+        for (int col = lane; col < WS; col += BSC_WAVE)
+            wl[row * WS + col] = (row < S && col < D) ? a.W[(int64_t)row * D + col] : 0.f;
+    if (tid < P_MAX_S) {
+        const float lv = (FAM == BSC_PREDICT_GAUSSIAN && tid < S) ? a.logvar[tid] : 0.f;
+        gp[tid] = lv;
+        gp[P_MAX_S + tid] = expf(lv);
+        gp[2 * P_MAX_S + tid] = expf(-lv);
+    }
+    __syncthreads();
+
+    const int n_strips = FULL ? 2 : a.n_strips;
+    const int kw = FULL ? 32 : a.kw;
+    const int n_iter = a.n_iter;
+    const int64_t B = a.B;
+    const int64_t stride0 = (int64_t)gridDim.x * P_WAVES;
+    const int64_t slot = (int64_t)blockIdx.x * P_WAVES + wave;
+    auto row0_of = [=](int p) { return p < n_iter ? ((int64_t)p * stride0 + slot) * T_ROWS : B; };
+
+    const float inv_S = 1.0f / (float)S;
+    const float log_S = logf((float)S);
+    double lsum = 0.0;
+
+    p_f32x4 acc[NC][2];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = p_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    Strip t;
+    load_strip(t, a, row0_of(0), 0, lane);
+    float y_cur = load_y(a, row0_of(0), i16);
+    float o_cur = 0.f;
+    if constexpr (OFFS) o_cur = load_offset(offset, a.B, row0_of(0), i16);
+    int p = 0, h = 0;
+    while (p < n_iter) {
+        // the strip to LDS (row stride 130 floats: 8-byte aligned), its registers take the next strip
+        {
+            float* dst = xl + (lane >> 5) * XS + 4 * (lane & 31);
+#pragma unroll
+            for (int r = 0; r < LD_STRIP; ++r) {
+                *reinterpret_cast<float2*>(dst + 2 * r * XS) = make_float2(t.x[r].x, t.x[r].y);
+                *reinterpret_cast<float2*>(dst + 2 * r * XS + 2) = make_float2(t.x[r].z, t.x[r].w);
+            }
+        }
+        int hn = h + 1, pn = p;
+        if (hn == n_strips) {
+            hn = 0;
+            pn = p + 1;
+        }
+        load_strip(t, a, row0_of(pn), hn, lane);
+        const bool last = hn == 0;
+        float y_next = 0.f;
+        if (last) y_next = load_y(a, row0_of(pn), i16);
+        float o_next = 0.f;
+        if constexpr (OFFS) {
+            if (last) o_next = load_offset(offset, a.B, row0_of(pn), i16);
+        }
+        wave_lds_sync();
+
+        const float* xr = xl + i16 * XS + kq * kw;
+        const float* wr = wl + i16 * WS + h * STRIP + kq * kw;
+        if (FULL) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float2 b = *reinterpret_cast<const float2*>(xr + 2 * j);
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const float2 w2 = *reinterpret_cast<const float2*>(wr + c * 16 * WS + 2 * j);
+                    acc[c][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2.x, b.x, acc[c][0], 0, 0, 0);
+                    acc[c][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2.y, b.y, acc[c][1], 0, 0, 0);
+                }
+            }
+        } else {
+            const int nj = kw >> 1;
+            for (int j = 0; j < nj; ++j) {
+                const float2 b = *reinterpret_cast<const float2*>(xr + 2 * j);
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const float2 w2 = *reinterpret_cast<const float2*>(wr + c * 16 * WS + 2 * j);
+                    acc[c][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2.x, b.x, acc[c][0], 0, 0, 0);
+                    acc[c][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2.y, b.y, acc[c][1], 0, 0, 0);
+                }
+            }
+        }
+        wave_lds_sync();   // the next iteration overwrites the strip
+
+        if (last) {
+            // ---- the row's draws: register i = 4 c + reg of lane (i16, kq) is draw 16 c + 4 kq + reg ----
+            const float yv = y_cur;
+            float mu[4 * NC], lp[4 * NC];
+            float s_mu = 0.f, s_v = 0.f;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int d0 = 16 * c + 4 * kq;
+                float4 lv4 = make_float4(0.f, 0.f, 0.f, 0.f), ev4 = lv4, iv4 = lv4;
+                if (FAM == BSC_PREDICT_GAUSSIAN) {
+                    lv4 = *reinterpret_cast<const float4*>(gp + d0);
+                    ev4 = *reinterpret_cast<const float4*>(gp + P_MAX_S + d0);
+                    iv4 = *reinterpret_cast<const float4*>(gp + 2 * P_MAX_S + d0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float l = acc[c][0][r] + acc[c][1][r];
+                    if constexpr (OFFS) l += o_cur;
+                    const float lv = r == 0 ? lv4.x : r == 1 ? lv4.y : r == 2 ? lv4.z : lv4.w;
+                    const float ev = r == 0 ? ev4.x : r == 1 ? ev4.y : r == 2 ? ev4.z : ev4.w;
+                    const float iv = r == 0 ? iv4.x : r == 1 ? iv4.y : r == 2 ? iv4.z : iv4.w;
+                    float m_i, v_i, lp_i;
+                    predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i);
+                    const bool valid = d0 + r < S;
+                    mu[4 * c + r] = valid ? m_i : 0.f;
+                    lp[4 * c + r] = valid ? lp_i : -INFINITY;
+                    s_mu += valid ? m_i : 0.f;
+                    s_v += valid ? v_i : 0.f;
+                }
+                acc[c][0] = acc[c][1] = p_f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            // two-pass moments: every lane of the row ends with the same mean, the squares are taken about it
+            const float mean = fold4_sum(s_mu) / (float)S;
+            float m2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4 * NC; ++i) {
+                const int d = 16 * (i >> 2) + 4 * kq + (i & 3);
+                const float dv = mu[i] - mean;
+                m2 = fmaf(d < S ? dv : 0.f, dv, m2);
+            }
+            m2 = fold4_sum(m2);
+            s_v = fold4_sum(s_v);
+            const float var = (s_v + m2) * inv_S;
+            float lpd = 0.f;
+            if (a.do_lp) {
+                float mx = lp[0];
+#pragma unroll
+                for (int i = 1; i < 4 * NC; ++i) mx = fmaxf(mx, lp[i]);
+                mx = fold4_max(mx);
+                const float ms = mx == -INFINITY ? 0.f : mx;   // every draw at -inf: lpd = -inf, not NaN
+                float se = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4 * NC; ++i) se += __expf(lp[i] - ms);
+                se = fold4_sum(se);
+                lpd = ms + logf(se) - log_S;
+                if (FAM == BSC_PREDICT_POISSON) lpd -= (float)bsc_lgamma_f64((double)yv + 1.0);   // once per row
+            }
+            const int64_t row = row0_of(p) + i16;
+            if (kq == 0 && row < B) {     // lanes 0 .. 15: one row each, 64 contiguous bytes per output
+                if (a.mean) a.mean[row] = mean;
+                if (a.var) a.var[row] = var;
+                if (a.do_lp) {
+                    if (a.lpd) a.lpd[row] = lpd;
+                    lsum += (double)lpd;
+                }
+            }
+            y_cur = y_next;
+            if constexpr (OFFS) o_cur = o_next;
+        }
+        h = hn;
+        p = pn;
+    }
+
+    if (a.partial) {   // fixed order: lanes (butterfly) -> waves -> block
+        const double ws = wave_allsum_f64(lsum);
+        if (lane == 0) red[wave] = ws;
+        __syncthreads();
+        if (tid == 0) {
+            double tot = red[0];
+#pragma unroll
+            for (int k = 1; k < P_WAVES; ++k) tot += red[k];
+            a.partial[blockIdx.x] = tot;
+        }
+    }
+}
+
+}  // namespace
+
+// csrc/bsc_predict_offset.hip: the launch of predict_offset_kernel (family BSC_PREDICT_LOGISTIC or BSC_PREDICT_POISSON,
+// offset not null), called from bsc_predict_pass_offset in csrc/bsc_predict.hip.  `predict_args` points to a
+// PredictArgs: the struct has internal linkage in each translation unit (predict_kernel's mangled name carries it), so
+// it crosses between the two as an untyped pointer.
+void bsc_predict_offset_launch(bsc_ctx* ctx, int family, const void* predict_args, const float* offset, int n_blocks);

@@ -29,32 +29,44 @@ def linear_regression_log_joint(n_total_over_batch=1.0, alpha0=1.0, beta0=1.0, d
     return likelihood + prior_w + prior_xi, dict(X=X, y=y, W=W, xi=xi)
 
 
-def _glm_log_joint(link, n_total_over_batch, prior_precision, dtype):
+def _glm_log_joint(link, n_total_over_batch, prior_precision, dtype, offset=False, weights=False):
     import math
     X, y, W = A.var("X", 2, dtype), A.var("y", 1, dtype), A.var("W", 2, dtype)
+    names = dict(X=X, y=y, W=W)
     logits = A.dot(W, X.T)                                  # [S, N]
+    if offset:
+        names["offset"] = A.var("offset", 1, dtype)
+        logits = logits + A.dimshuffle(names["offset"], "x", 0)
     log_partition = A.log(1.0 + A.exp(logits)) if link == "logistic" else A.exp(logits)
-    likelihood = A.sum(A.dimshuffle(y, "x", 0) * logits - log_partition, axis=1) * float(n_total_over_batch)
+    rows = A.dimshuffle(y, "x", 0) * logits - log_partition
+    if weights:
+        names["weights"] = A.var("weights", 1, dtype)
+        rows = A.dimshuffle(names["weights"], "x", 0) * rows
+    likelihood = A.sum(rows, axis=1) * float(n_total_over_batch)
     tau = float(prior_precision)
     prior_w = A.sum(W * W, axis=1) * (-0.5 * tau) + A.shape(W, 1) * (0.5 * math.log(tau / (2.0 * math.pi)))
-    return likelihood + prior_w, dict(X=X, y=y, W=W)
+    return likelihood + prior_w, names
 
 
-def logistic_regression_log_joint(n_total_over_batch=1.0, prior_precision=1.0, dtype="float32"):
+def logistic_regression_log_joint(n_total_over_batch=1.0, prior_precision=1.0, dtype="float32", offset=False,
+                                  weights=False):
     """Bernoulli-logit regression: y_n ~ Bernoulli(sigmoid(x_n . w)), w ~ N(0, I / prior_precision), with a leading
     Monte-Carlo sample axis on the latent ``W`` [S, D]:
 
         log p(y, w) = scale * sum_n [y_n l_n - log(1 + exp(l_n))] + sum_d log N(w_d | 0, 1 / prior_precision),   l = X w
 
-    (an intercept is a column of ones in X).  Returns (log-joint [S], the vars ``X`` [N, D], ``y`` [N], ``W``)."""
-    return _glm_log_joint("logistic", n_total_over_batch, prior_precision, dtype)
+    (an intercept is a column of ones in X).  ``offset`` / ``weights``: the 1-D data vars ``offset`` and ``weights``
+    [N] enter as l = X w + offset and sum_n weights_n [...] (aggregated binomial rows: y = k / n, weights = n); the
+    defaults build the expression above.  Returns (log-joint [S], the vars ``X`` [N, D], ``y`` [N], ``W`` and those)."""
+    return _glm_log_joint("logistic", n_total_over_batch, prior_precision, dtype, offset, weights)
 
 
-def poisson_regression_log_joint(n_total_over_batch=1.0, prior_precision=1.0, dtype="float32"):
+def poisson_regression_log_joint(n_total_over_batch=1.0, prior_precision=1.0, dtype="float32", offset=False,
+                                 weights=False):
     """Poisson regression with the log link: y_n ~ Poisson(exp(x_n . w)), w ~ N(0, I / prior_precision):
 
         log p(y, w) = scale * sum_n [y_n l_n - exp(l_n)] + sum_d log N(w_d | 0, 1 / prior_precision),   l = X w
 
-    without the term -scale * sum_n lnGamma(y_n + 1), which depends on no latent.  Same return as
-    ``logistic_regression_log_joint``."""
-    return _glm_log_joint("poisson", n_total_over_batch, prior_precision, dtype)
+    without the term -scale * sum_n lnGamma(y_n + 1), which depends on no latent.  ``offset`` is the rate model's
+    log exposure.  Same arguments and return as ``logistic_regression_log_joint``."""
+    return _glm_log_joint("poisson", n_total_over_batch, prior_precision, dtype, offset, weights)

@@ -502,10 +502,12 @@ class GLMLinear(object):
     """What ``glm_linear`` found: log p(data, w_s) = scale * sum_n [y_n l_ns - A(l_ns)] - tau / 2 |w_s|^2 + (terms
     free of w), l_ns = x_n . w_s, with A = softplus (``link`` "logistic") or A = exp ("poisson") -- the model
     csrc/bsc_glm.hip's pass and finish compute.  X, y, W: the names of the design matrix [N, D], the targets [N]
-    and the latent weights [S, D]."""
+    and the latent weights [S, D].  ``offset`` / ``weights``: the names of the 1-D inputs [N] that enter as
+    l_ns = x_n . w_s + offset_n and sum_n weights_n [...] (csrc/bsc_glm_obs.hip), or None."""
 
-    def __init__(self, link, X, y, W, scale, tau):
+    def __init__(self, link, X, y, W, scale, tau, offset=None, weights=None):
         self.link, self.X, self.y, self.W, self.scale, self.tau = link, X, y, W, scale, tau
+        self.offset, self.weights = offset, weights
 
 
 _GLM_LINKS = (("logistic", lambda L: np.logaddexp(0.0, L), lambda rng, n: (rng.uniform(size=n) < 0.5).astype(np.float64)),
@@ -519,7 +521,11 @@ def glm_linear(log_joint, latents, data_shapes, n_samples, why=None):
     as ``logistic_hierarchy`` does it: scale and tau are fitted from differences in w on one instance -- terms free of
     w, such as the Poisson density's -sum_n lnGamma(y_n + 1), cancel -- and the fit is then checked at random other
     instances and weights.  Returns a ``GLMLinear`` or None; ``why`` (a list, optional) receives the reason.  More
-    latents than the weights, another prior, or another likelihood are declined."""
+    latents than the weights, another prior, or another likelihood are declined.
+    With two or three 1-D inputs next to the design matrix their roles -- targets, offset, row weights -- are decided
+    the same way: every assignment is a hypothesis (y with an offset or with weights, in both orders; the six
+    permutations of three) fitted and checked on probe instances whose offsets are normal and whose weights are
+    positive, not constant and not integers, so that no two hypotheses agree on them."""
     try:
         return _glm_linear(log_joint, latents, data_shapes, n_samples, why)
     except NOT_THIS_MODEL as e:
@@ -538,23 +544,65 @@ def _glm_linear(log_joint, latents, data_shapes, n_samples, why):
     used = sorted(n for n in types if n != Wv.name)
     two_d = [n for n in used if types[n][1] == 2 and n in data_shapes and data_shapes[n][1] == D]
     one_d = [n for n in used if types[n][1] == 1 and n in data_shapes]
-    if len(used) != 2 or len(two_d) != 1 or len(one_d) != 1 or data_shapes[two_d[0]][0] != data_shapes[one_d[0]][0]:
-        return _say(why, "the data inputs are not one design matrix [N, %d] and one target vector [N] (got %s)"
-                    % (D, ", ".join(used) or "none"))
-    Xn, yn = two_d[0], one_d[0]
+    if len(used) != 1 + len(one_d) or len(two_d) != 1 or not 1 <= len(one_d) <= 3 \
+            or any(data_shapes[n_][0] != data_shapes[two_d[0]][0] for n_ in one_d):
+        return _say(why, "the data inputs are not one design matrix [N, %d] and one target vector [N], with at most an "
+                         "offset [N] and row weights [N] (got %s)" % (D, ", ".join(used) or "none"))
+    Xn = two_d[0]
+    if len(one_d) == 1:
+        return _glm_fit(log_joint, Wv, D, Xn, one_d[0], None, None, why)
+    # the roles of the vectors: every assignment is tried, the first that fits every probe is the model
+    if len(one_d) == 2:
+        a, b = one_d
+        roles = [(a, b, None), (b, a, None), (a, None, b), (b, None, a)]
+    else:
+        import itertools
+        roles = list(itertools.permutations(one_d))
+    said = []
+    for yn, on, vn in roles:
+        tried = []
+        plan = _glm_fit(log_joint, Wv, D, Xn, yn, on, vn, tried)
+        if plan is not None:
+            return plan
+        said.append("[y = %s%s%s] %s" % (yn, ", offset = %s" % on if on else "", ", weights = %s" % vn if vn else "",
+                                         tried[-1] if tried else "declined"))
+        if tried and ("must be positive" in tried[-1] or "proper N(0" in tried[-1]):
+            return _say(why, tried[-1])     # the structure fits under these roles: the verdict is about scale or tau
+    return _say(why, "no assignment of the vectors %s to targets, offset (entering as l = dot(W, X.T) + offset, "
+                     "coefficient 1) and row weights (outside the link) fits: %s" % (", ".join(one_d), " | ".join(said)))
+
+
+def _glm_fit(log_joint, Wv, D, Xn, yn, on, vn, why):
+    """``_glm_linear`` under one assignment of the 1-D inputs: yn the targets, on the offset and vn the row weights
+    (names, or None)."""
     rng = np.random.RandomState(53)
     n, S = 7, 3
     reasons = []
     for link, A_fn, draw_y in _GLM_LINKS:
         def instance():
-            return rng.standard_normal((n, D)) / math.sqrt(D), draw_y(rng, n)
+            data = [rng.standard_normal((n, D)) / math.sqrt(D), draw_y(rng, n)]
+            if on is not None:
+                data.append(rng.standard_normal(n))
+            if vn is not None:
+                data.append(rng.uniform(0.5, 2.5, n))
+            return data
 
         def F(data, w):
-            return np.asarray(_PROBE.evaluate(log_joint, {Xn: data[0], yn: data[1], Wv.name: w}), np.float64).reshape(-1)
+            inputs = {Xn: data[0], yn: data[1], Wv.name: w}
+            if on is not None:
+                inputs[on] = data[2]
+            if vn is not None:
+                inputs[vn] = data[-1]
+            return np.asarray(_PROBE.evaluate(log_joint, inputs), np.float64).reshape(-1)
 
         def ell(data, w):
             L = data[0] @ w.T
-            return (data[1][:, None] * L - A_fn(L)).sum(axis=0)
+            if on is not None:
+                L = L + data[2][:, None]
+            rows = data[1][:, None] * L - A_fn(L)
+            if vn is not None:
+                rows = data[-1][:, None] * rows
+            return rows.sum(axis=0)
 
         def delta(data, w):
             """(F, ell, -|w|^2 / 2) at w minus the same at w = 0, per draw."""
@@ -584,5 +632,5 @@ def _glm_linear(log_joint, latents, data_shapes, n_samples, why):
             return _say(why, "the %s data term enters with the scale %g: it must be positive" % (link, scale))
         if not tau > 0.0:
             return _say(why, "the prior on the weights is not a proper N(0, I / tau): fitted tau = %g" % tau)
-        return GLMLinear(link, Xn, yn, Wv.name, scale, tau)
+        return GLMLinear(link, Xn, yn, Wv.name, scale, tau, offset=on, weights=vn)
     return _say(why, "; ".join(reasons))

@@ -45,7 +45,9 @@ with A = softplus or A = exp, over ONE latent block under an isotropic Gaussian 
 Bernoulli-logit and Poisson-log regression, ``inference/models.py``) is stepped by ``svi/glm.py``: one pass over X
 (csrc/bsc_glm.hip) and its fused finish: ``bsc_glm_update`` for the mean-field guide, ``bsc_glm_fullrank_update``
 (csrc/bsc_glm_full.hip; ``svi/glm.py``, ``covariance="full"``) for ``guide="full"`` -- over one latent block the engine's
-full layout is the driver's.  The draws are ``bsc_blr_noise``'s stream 0.
+full layout is the driver's.  The draws are ``bsc_blr_noise``'s stream 0.  Up to two more 1-D data inputs are read
+as an offset (``l = dot(W, X.T) + offset``) and as row weights (``sum_n weights_n [...]``), whatever they are called:
+the driver gets them (csrc/bsc_glm_obs.hip), ``set_data`` forwards them, ``predict`` takes them for new rows.
 
 **The pass route.**  When the data term is recognised but the parameter-sized remainder is NOT of that family
 (a known noise variance, another prior, more latents), the step still needs the data only through
@@ -386,7 +388,7 @@ class ReparamVI(object):
         D = int(X.shape[1])
         if not (isinstance(X, torch.Tensor) and X.dtype == torch.float32 and y.dtype == torch.float32):
             return "the fused pass streams float32 data"
-        why = _outside_pass_envelope(X, y, D, self.S)
+        why = _outside_pass_envelope(X, y, D, self.S) or self._glm_vectors_outside_envelope(plan)
         if why is not None:
             return why
         self.plan = plan
@@ -394,11 +396,28 @@ class ReparamVI(object):
         # lam = [mu (D) | rho (D)], or [mu (D) | packed L] over the one latent block, is the driver's own layout
         self._fused = GLMReparamSVI(X, y, link=plan.link, n_total=plan.scale * int(X.shape[0]), n_samples=self.S,
                                     seed=self.seed, lr=self.lr, prior_precision=plan.tau, ctx=self.backend.ctx,
-                                    lam0=self._lam, covariance=self.guide)
+                                    lam0=self._lam, covariance=self.guide,
+                                    offset=self._data[plan.offset] if plan.offset else None,
+                                    weights=self._data[plan.weights] if plan.weights else None)
         self._fused_D = D
         self._fused_glm = True
         finish = "bsc_glm_fullrank_update" if self.guide == "full" else "bsc_glm_update"
         self.route = "fused: bsc_glm_data_pass + %s (%s link)" % (finish, plan.link)
+        return None
+
+    def _glm_vectors_outside_envelope(self, plan):
+        """None, or why the pass would refuse the offset / the row weights of a recognised GLM (float32, [N],
+        contiguous: what it asks of y)."""
+        import torch
+        N = int(self._data[plan.X].shape[0])
+        for role, name in (("offset", plan.offset), ("weights", plan.weights)):
+            if name is None:
+                continue
+            v = self._data[name]
+            if not (isinstance(v, torch.Tensor) and v.dtype == torch.float32):
+                return "the fused pass streams float32 data (%s %r)" % (role, name)
+            if v.dim() != 1 or v.shape[0] != N or (N > 1 and v.stride(0) != 1):
+                return "outside the fused pass's envelope (contiguous %s %r [%d])" % (role, name, N)
         return None
 
     def _to_blr_layout(self, lam):
@@ -494,11 +513,17 @@ class ReparamVI(object):
                                  "the recognised coefficients); build a new engine for another batch size"
                                  % (("fused" if self._fused is not None else "pass",) + self._planned_shape))
             why = _outside_pass_envelope(X, y, self._planned_shape[1], self.S)
+            glm_obs = getattr(self, "_fused_glm", False) and (self.plan.offset or self.plan.weights)
+            if why is None and glm_obs:
+                why = self._glm_vectors_outside_envelope(self.plan)
             if why is not None:
                 for name, value in previous.items():
                     self._data[name] = value
                 raise ValueError("set_data: " + why)
-            if self._fused is not None:
+            if glm_obs:
+                self._fused.set_batch(X, y, offset=self._data[self.plan.offset] if self.plan.offset else None,
+                                      weights=self._data[self.plan.weights] if self.plan.weights else None)
+            elif self._fused is not None:
                 self._fused.set_batch(X, y)
 
     def draw(self, step):
@@ -629,13 +654,19 @@ class ReparamVI(object):
         grad = np.concatenate([g.mean(axis=0), (g * eps).mean(axis=0) * sigma + 1.0])
         return elbo, grad
 
-    def predict(self, X, y=None, n_samples=64, seed=None, draws=None):
+    def predict(self, X, y=None, n_samples=64, seed=None, draws=None, offset=None, weights=None):
         """Posterior predictive for new rows (svi/predict.py): on a fused regression route the driver's own
-        ``predict``; every other route has no likelihood the engine could name, and refuses."""
+        ``predict``; every other route has no likelihood the engine could name, and refuses.  ``offset`` /
+        ``weights``: for the new rows, on the fused GLM route (a model with an offset needs one to predict)."""
         if self._fused is None or not self.route.startswith(("fused: bsc_blr", "fused: bsc_glm")):
             raise NotImplementedError("predict needs a fused regression route (fused: bsc_blr... / bsc_glm...); this "
                                       "engine runs on route %r" % (self.route,))
-        return self._fused.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
+        if offset is None and weights is None:
+            return self._fused.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
+        if not getattr(self, "_fused_glm", False):
+            raise ValueError("predict: offset and weights belong to the fused GLM route; this engine runs on route %r"
+                             % (self.route,))
+        return self._fused.predict(X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, weights=weights)
 
     def step(self):
         if self._fused is not None:

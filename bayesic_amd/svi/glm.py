@@ -22,6 +22,13 @@ bsc_glm_fullrank_update, always behind data_pass() -> all_reduce(), so S up to 6
 mean-field driver's.  A mean-field guide cannot represent the posterior correlation of w that correlated features
 induce and shrinks its marginal variances; the full guide can.
 
+Offsets and row weights (``offset=``, ``weights=``, ``exposure=``): l_ns = x_n . w_s + o_n and every row's term of
+ell_s and G_s times v_n >= 0 (include/bayesic_hip.h, bsc_glm_data_pass_obs; csrc/bsc_glm_obs.hip).  ``exposure`` is
+the Poisson rate model's log E[y_n] = x_n . w + log exposure_n, kept as o = log(exposure).  Weights are part of the
+likelihood (trials of aggregated binomial rows with y = k / n, survey weights, a mask of zeros) and do not enter the
+mini-batch scale n_total / batch_rows.  A model built without them, and handed batches without them, calls the entry
+points it always has.
+
 Data parallelism is wired as in svi/blr.py: each rank holds a block of mini-batch rows, and the one exchange per
 update is an all-reduce(sum) of the float64 vector [ell (S) | G (S*D)] between the pass and the finish.  That branch
 (the one every update of the full guide takes) has been exercised at world size 1 only.
@@ -35,19 +42,56 @@ from ._reparam_base import ReparamRegressionBase, full_size
 LINKS = {"logistic": 0, "poisson": 1}
 
 
+def obs_vector(ctx, name, v, rows, log=False):
+    """``v`` (offset, weights or exposure; a tensor or a host array) as a float32 [rows] contiguous device tensor,
+    checked like y, or None; ``log``: an exposure, returned as its logarithm (computed once, on the device)."""
+    if v is None:
+        return None
+    if not isinstance(v, torch.Tensor):
+        v = ctx.to_device(v, torch.float32)
+    if v.dtype != torch.float32:
+        raise TypeError("%s must be float32" % name)
+    if v.dim() != 1 or v.shape[0] != rows:
+        raise ValueError("%s must be [%d], one entry per row of X" % (name, rows))
+    if rows > 1 and v.stride(0) != 1:
+        raise ValueError("%s must be contiguous" % name)
+    if log:
+        if not bool((v > 0).all() & torch.isfinite(v).all()):
+            raise ValueError("exposure must be finite and strictly positive")
+        v = torch.log(v)
+    return v
+
+
+def checked_weights(v):
+    """The weights' check, finite and >= 0: one synchronisation, so it sits outside step()."""
+    if v is not None and not bool((torch.isfinite(v) & (v >= 0)).all()):
+        raise ValueError("weights must be finite and >= 0")
+    return v
+
+
 class GLMReparamSVI(ReparamRegressionBase):
     def __init__(self, X, y, link="logistic", n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0,
-                 ctx=None, group=None, lam0=None, covariance="diag"):
+                 ctx=None, group=None, lam0=None, covariance="diag", *, offset=None, weights=None, exposure=None):
         """``covariance``: "diag" (the mean-field guide, default) or "full" (module docstring; ``lam0`` then in the
-        full layout, default: the mean-field default's mu and rho with zero off-diagonal entries)."""
+        full layout, default: the mean-field default's mu and rho with zero off-diagonal entries).
+        ``offset`` / ``weights``: float32 [B], as y (module docstring); ``exposure``: Poisson only, strictly positive,
+        instead of ``offset``.  The weights are checked here (finite, >= 0: one synchronisation), never in step()."""
         if covariance not in ("diag", "full"):
             raise ValueError("covariance must be 'diag' or 'full', got %r" % (covariance,))
         self.covariance_kind = covariance
         if link not in LINKS:
             raise ValueError("link must be 'logistic' or 'poisson', got %r" % (link,))
         self.link, self._link = link, LINKS[link]
+        if exposure is not None and link != "poisson":
+            raise ValueError("exposure belongs to the Poisson rate model; link=%r takes offset=" % (link,))
+        if exposure is not None and offset is not None:
+            raise ValueError("exposure and offset are mutually exclusive (exposure is stored as offset = log(exposure))")
         self.ctx = ctx or default_context()
         self._float_batch(X, y)
+        self._set_obs(obs_vector(self.ctx, "exposure" if offset is None else "offset",
+                                 exposure if offset is None else offset, self.B, log=offset is None),
+                      checked_weights(obs_vector(self.ctx, "weights", weights, self.B)))
+        self.has_offset = self._oarg is not None      # predict() refuses to run without one
         self.prior_precision = float(prior_precision)
         if not self.prior_precision > 0.0:
             raise ValueError("prior_precision must be positive")
@@ -58,18 +102,43 @@ class GLMReparamSVI(ReparamRegressionBase):
         self._init_state(D, n_total, n_samples, seed, lr, group, lam0,
                          slab_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 8) * 4)
 
+    # -- offsets and weights ----------------------------------------------------
+    def _set_obs(self, offset, weights):
+        """Tensors, raw device pointers or None."""
+        tensor = lambda v: v if isinstance(v, torch.Tensor) else None
+        self.offset, self.weights = tensor(offset), tensor(weights)
+        self._oarg = offset if offset is None or isinstance(offset, torch.Tensor) else int(offset)
+        self._varg = weights if weights is None or isinstance(weights, torch.Tensor) else int(weights)
+
+    def set_batch(self, X, y, rows=None, ldx=None, offset=None, weights=None):
+        """ReparamDriver.set_batch with the batch's offset and weights: tensors (weights checked: finite, >= 0) with
+        tensor X and y, raw device pointers (unchecked) with raw ones.  None drops the vector for this batch."""
+        if isinstance(X, torch.Tensor):
+            offset = obs_vector(self.ctx, "offset", offset, X.shape[0])
+            weights = checked_weights(obs_vector(self.ctx, "weights", weights, X.shape[0]))
+        super().set_batch(X, y, rows=rows, ldx=ldx)
+        self._set_obs(offset, weights)
+
     def data_pass(self):
-        self.ctx.call("bsc_glm_data_pass", self._link, self._Xarg, self._ldx, self._yarg, self.B, self.D, self.W,
-                      self.S, self.ell, self.G)
+        if self._oarg is None and self._varg is None:
+            self.ctx.call("bsc_glm_data_pass", self._link, self._Xarg, self._ldx, self._yarg, self.B, self.D, self.W,
+                          self.S, self.ell, self.G)
+        else:
+            self.ctx.call("bsc_glm_data_pass_obs", self._link, self._Xarg, self._ldx, self._yarg, self._oarg,
+                          self._varg, self.B, self.D, self.W, self.S, self.ell, self.G)
 
     def _pass_update(self):
-        """bsc_glm_pass_update: the pass and the finish in one call; flips the double buffer."""
+        """bsc_glm_pass_update[_obs]: the pass and the finish in one call; flips the double buffer."""
         c, n = self.cur, 1 - self.cur
         t = self.t + 1
         self._ensure_noise(t)
-        self.ctx.call("bsc_glm_pass_update", self._link, self._Xarg, self._ldx, self._yarg, self.B, self.D,
-                      self._lam[c], self._lam[n], self.m1, self.m2, self._eps[self.t % self._ring], self._W[c],
-                      self.S, *self._tail(t))
+        state = (self._lam[c], self._lam[n], self.m1, self.m2, self._eps[self.t % self._ring], self._W[c], self.S)
+        if self._oarg is None and self._varg is None:
+            self.ctx.call("bsc_glm_pass_update", self._link, self._Xarg, self._ldx, self._yarg, self.B, self.D,
+                          *state, *self._tail(t))
+        else:
+            self.ctx.call("bsc_glm_pass_update_obs", self._link, self._Xarg, self._ldx, self._yarg, self._oarg,
+                          self._varg, self.B, self.D, *state, *self._tail(t))
         self.t = t
 
     def step(self):
@@ -84,14 +153,16 @@ class GLMReparamSVI(ReparamRegressionBase):
             self._finish(self.stats)
 
     # -- posterior predictive (svi/predict.py: one bsc_predict_pass over X for all draws) --------
-    def predict(self, X, y=None, n_samples=64, seed=None, draws=None):
+    def predict(self, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):
         from .predict import predict
-        return predict(self, X, y, n_samples=n_samples, seed=seed, draws=draws)
+        return predict(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, exposure=exposure,
+                       weights=weights)
 
-    def heldout_lpd(self, X, y, n_samples=64, seed=None, draws=None):
-        """Mean log predictive density per held-out row (a host float)."""
+    def heldout_lpd(self, X, y, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):
+        """Mean log predictive density per held-out row (a host float); with weights sum v lpd / sum v."""
         from .predict import heldout_lpd
-        return heldout_lpd(self, X, y, n_samples=n_samples, seed=seed, draws=draws)
+        return heldout_lpd(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, exposure=exposure,
+                           weights=weights)
 
     # -- host views -----------------------------------------------------------
     def params(self):

@@ -17,6 +17,11 @@ GLMReparamSVI.sample() does.
     SoftmaxReparamSVI                 eps [S, K D]:    the two GLM transforms at width K D, W returned [S, K, D]
                                       (predict() below hands over to its predict(): bsc_softmax_predict_pass)
 xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass).
+
+Offsets and weights (logistic and Poisson models): ``offset`` (or, Poisson, ``exposure`` = e^offset) is added to the
+linear predictor in the pass (bsc_predict_pass_offset), so a Poisson ``mean`` is the expected count at that exposure.
+A model fitted with an offset refuses to predict without one.  ``weights`` leave every per-row output alone and make
+``lpd_sum`` the weighted sum_n v_n lpd_n (float64, on the device, from the lpd vector).
 """
 import numpy as np
 import torch
@@ -109,13 +114,36 @@ def _data(model, X, y):
     return X, y
 
 
-def predict(model, X, y=None, n_samples=64, seed=None, draws=None):
+def _obs(model, family, B, offset, exposure, weights):
+    """The checked offset (log exposure) and weights of a batch of B rows: float32 [B] device tensors or None."""
+    if offset is None and exposure is None and getattr(model, "has_offset", False):
+        raise ValueError("predict: the model was fitted with an offset (exposure); pass offset= or exposure= for the "
+                         "rows to predict -- a silent offset of 0 would return rates per unit exposure that look like "
+                         "counts")
+    if offset is None and exposure is None and weights is None:
+        return None, None
+    if family not in ("logistic", "poisson"):
+        raise ValueError("predict: offset, exposure and weights are for the logistic and Poisson models, not %s" % family)
+    if exposure is not None and family != "poisson":
+        raise ValueError("exposure belongs to the Poisson rate model; link=%r takes offset=" % (family,))
+    if exposure is not None and offset is not None:
+        raise ValueError("exposure and offset are mutually exclusive (exposure means offset = log(exposure))")
+    from .glm import checked_weights, obs_vector
+    o = obs_vector(model.ctx, "exposure" if offset is None else "offset", exposure if offset is None else offset, B,
+                   log=offset is None)
+    return o, checked_weights(obs_vector(model.ctx, "weights", weights, B))
+
+
+def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):
     """Posterior predictive of ``model`` for the rows of X: a dict of device tensors ``mean`` and ``var`` (float32
     [B]) and, with y, ``lpd`` (float32 [B]) and ``lpd_sum`` (float64 [1]).  ``draws`` = (W, logvar) reuses draws of
-    ``posterior_draws``; otherwise n_samples (at most 64) are drawn with ``seed`` (default: the model's)."""
+    ``posterior_draws``; otherwise n_samples (at most 64) are drawn with ``seed`` (default: the model's).
+    ``offset`` / ``exposure`` / ``weights``: float32 [B] (module docstring); with weights ``lpd_sum`` is the weighted
+    sum and ``weight_sum`` (float64 [1]) is sum_n v_n."""
     family = family_of(model)
     if family == "softmax":      # its own pass and outputs (prob [B, K] instead of mean and var)
         return model.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
+    offset, weights = _obs(model, family, int(X.shape[0]), offset, exposure, weights)
     if draws is None:
         draws = posterior_draws(model, n_samples, seed)
     W, logvar = draws
@@ -129,13 +157,26 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None):
            "var": torch.empty(B, dtype=torch.float32, device=dev)}
     if y is not None:
         out["lpd"] = torch.empty(B, dtype=torch.float32, device=dev)
-        out["lpd_sum"] = torch.zeros(1, dtype=torch.float64, device=dev)
-    ctx.call("bsc_predict_pass", FAMILIES[family], X, ldx, y, B, model.D, W, logvar, S, out["mean"], out["var"],
-             out.get("lpd"), out.get("lpd_sum"))
+        if weights is None:        # (the weighted sum is formed from the lpd vector below)
+            out["lpd_sum"] = torch.zeros(1, dtype=torch.float64, device=dev)
+    if offset is None:
+        ctx.call("bsc_predict_pass", FAMILIES[family], X, ldx, y, B, model.D, W, logvar, S, out["mean"], out["var"],
+                 out.get("lpd"), out.get("lpd_sum"))
+    else:
+        ctx.call("bsc_predict_pass_offset", FAMILIES[family], X, ldx, y, offset, B, model.D, W, logvar, S,
+                 out["mean"], out["var"], out.get("lpd"), out.get("lpd_sum"))
+    if weights is not None and y is not None:
+        w64 = weights.to(torch.float64)       # a row of weight 0 is dropped by a select, as in the training pass
+        out["lpd_sum"] = torch.where(weights > 0, w64 * out["lpd"].to(torch.float64), torch.zeros_like(w64)).sum().reshape(1)
+        out["weight_sum"] = w64.sum().reshape(1)
     return out
 
 
-def heldout_lpd(model, X, y, n_samples=64, seed=None, draws=None):
-    """Mean log predictive density per row of the held-out (X, y): lpd_sum / B, a host float (synchronises)."""
-    out = predict(model, X, y, n_samples=n_samples, seed=seed, draws=draws)
+def heldout_lpd(model, X, y, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):
+    """Mean log predictive density per row of the held-out (X, y): lpd_sum / B, a host float (synchronises).  With
+    weights: sum_n v_n lpd_n / sum_n v_n."""
+    out = predict(model, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, exposure=exposure,
+                  weights=weights)
+    if "weight_sum" in out:
+        return float(out["lpd_sum"].item()) / float(out["weight_sum"].item())
     return float(out["lpd_sum"].item()) / max(int(out["lpd"].shape[0]), 1)

@@ -400,6 +400,33 @@ int bsc_glm_pass_update(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx,
                         double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
                         float* W_next, double* elbo, double* grad);
 
+/* The same pass with a per-row offset o[B] and a per-row weight v[B] (csrc/bsc_glm_obs.hip; float32, contiguous, any
+ * 4-byte alignment; each may be NULL: o = 0, v = 1):
+ *      l[n,s]  = sum_d X[n,d] W[s,d] + o[n]
+ *      ell[s]  = sum_n v[n] ( y[n] l[n,s] - A(l[n,s]) )
+ *      G[s,d]  = sum_n v[n] ( y[n] - A'(l[n,s]) ) X[n,d]
+ * A and A' as above.  The offset carries an exposure (Poisson rate model: o[n] = log exposure[n]) or any fixed part
+ * of the linear predictor; the weights are the trials of aggregated binomial rows (y = k / n, v = n), survey or
+ * importance weights, or a row mask.  They are part of the likelihood: the mini-batch scale of the finish stays
+ * n_total / batch_rows.  A row with v[n] = 0 contributes EXACTLY nothing to ell and G -- a select, not a product --
+ * also when its link value overflows (a Poisson logit of 200); its x, y and o must be finite.  Negative weights are
+ * the caller's to exclude: the pass does not check them (a row with v[n] < 0 is dropped like one with v[n] = 0).
+ * The slab, the float64 reduction and the outputs are bsc_glm_data_pass's, and so are the envelope and its refusals.
+ * With offset == weight == NULL the kernels of bsc_glm_data_pass run and the outputs are bit-identical to it.  The
+ * 16-row MFMA kernel (D == 256) is taken when y and the vectors that are set are all 16-byte aligned, else the 8-row
+ * kernel. */
+int bsc_glm_data_pass_obs(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx, const float* y, const float* offset,
+                          const float* weight, int64_t B, int32_t D, const float* W, int32_t S, double* ell, double* G);
+
+/* bsc_glm_pass_update with offset and weight (bsc_glm_data_pass_obs) after y: the pass for S <= 8 followed by the
+ * finish with stats = NULL.  With both NULL it is bit-identical to bsc_glm_pass_update. */
+int bsc_glm_pass_update_obs(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx, const float* y,
+                            const float* offset, const float* weight, int64_t B, int32_t D, const double* lam_in,
+                            double* lam_out, double* m1, double* m2, const double* eps, const float* W, int32_t S,
+                            double scale, double prior_precision, int64_t t, double lr, double beta1, double beta2,
+                            double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
+                            float* W_next, double* elbo, double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
@@ -454,6 +481,16 @@ int bsc_glm_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam
 int bsc_predict_pass(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
                      const float* W, const float* logvar, int32_t S, float* mean, float* var, float* lpd,
                      double* lpd_sum);
+
+/* bsc_predict_pass with a per-row offset o[B] (csrc/bsc_predict_offset.hip; float32, contiguous, any 4-byte
+ * alignment) for the logistic and the Poisson family: l[n,s] = sum_d X[n,d] W[s,d] + o[n], everything else as above
+ * (a model fitted with bsc_glm_data_pass_obs's offset predicts with the same one: o[n] = log exposure[n] gives the
+ * expected COUNT of row n, not its rate).  offset == NULL: bsc_predict_pass, bit for bit.  BSC_PREDICT_GAUSSIAN with
+ * a non-NULL offset is BSC_ERR_INVALID.  Row weights need no pass of their own: a weighted score is sum_n v[n] lpd[n]
+ * over the lpd vector. */
+int bsc_predict_pass_offset(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, const float* y,
+                            const float* offset, int64_t B, int32_t D, const float* W, const float* logvar, int32_t S,
+                            float* mean, float* var, float* lpd, double* lpd_sum);
 
 /* ---- multi-class softmax regression (csrc/bsc_softmax.hip; ABSENT in the reference) ------------------------
  *
