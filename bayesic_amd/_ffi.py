@@ -113,6 +113,17 @@ SIGNATURES = {
                                         c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                         c_double, c_double, c_int64, c_double, c_double, c_double, c_double,
                                         c_uint64, c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_group_plan_size": (c_int64, [c_int64, c_int32]),
+    "bsc_glm_group_plan_host": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "bsc_glm_group_plan": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "bsc_glm_group_workspace_bytes": (c_int64, [c_void_p, c_int64, c_int32]),
+    "bsc_glm_data_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                         c_void_p, c_void_p]),
+    "bsc_glm_hier_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
+                                    c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_glm_fullrank_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_int32, c_double, c_double, c_int64, c_double, c_double, c_double,
                                         c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),

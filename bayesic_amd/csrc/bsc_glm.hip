@@ -215,15 +215,7 @@ __global__ __launch_bounds__(FIN_BLOCK) void glm_update_kernel(GlmArgs a) {
     }
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------
-
-bool aligned16(const float* p) { return (((uintptr_t)p) & 15) == 0; }
-
-// 16 = the MFMA kernel (needs the full 256-column layout and 16-byte aligned y, offset and weight -- null ones count
-// as aligned), else 8-row tiles.
-int pass_rows(int D, const float* y, const float* o = nullptr, const float* v = nullptr) {
-    return (D == GCOLS && aligned16(y) && aligned16(o) && aligned16(v)) ? MT_ROWS : ROWS;
-}
+// ---- host side (pass_rows and check_glm_obs_args: csrc/bsc_glm_pass.h, shared with csrc/bsc_glm_group.hip) ---------
 
 // the link, then the envelope of every regression pass
 int check_glm_args(const char* who, int32_t link, const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
@@ -231,17 +223,6 @@ int check_glm_args(const char* who, int32_t link, const float* X, int64_t ldx, c
     BSC_REQUIRE(link == BSC_GLM_LOGISTIC || link == BSC_GLM_POISSON,
                 "%s: link=%d must be BSC_GLM_LOGISTIC (0) or BSC_GLM_POISSON (1)", who, link);
     BSC_REQUIRE(y || B <= 0, "%s: null pointer", who);
-    return check_regress_args(who, X, ldx, B, D, W, S, max_s);
-}
-
-// ... of the entry points that take an offset and a weight: y by name, the vectors' alignment
-int check_glm_obs_args(const char* who, int32_t link, const float* X, int64_t ldx, const float* y, const float* o,
-                       const float* v, int64_t B, int32_t D, const float* W, int32_t S, int max_s) {
-    BSC_REQUIRE(link == BSC_GLM_LOGISTIC || link == BSC_GLM_POISSON,
-                "%s: link=%d must be BSC_GLM_LOGISTIC (0) or BSC_GLM_POISSON (1)", who, link);
-    BSC_REQUIRE(y || B <= 0, "%s: y is null with B=%lld", who, (long long)B);
-    BSC_REQUIRE((((uintptr_t)o) & 3) == 0 && (((uintptr_t)v) & 3) == 0, "%s: offset and weight must be 4-byte aligned",
-                who);
     return check_regress_args(who, X, ldx, B, D, W, S, max_s);
 }
 

@@ -1,0 +1,470 @@
+// Random-intercept logistic / Poisson regression on the fused pathwise pass: csrc/bsc_glm_pass.h's OBS bodies with the
+// group flag on, the per-group sums of the residuals, and the finish for the latent z = [w (D) | b (J) | zeta].
+//
+//     l[n,s] = x_n . w_s + b_s[g_n] + o_n
+//     ell[s] = sum_n v_n (y_n l_ns - A(l_ns))      G[s,:] = sum_n r_ns x_n      H[s,j] = sum_{n : g_n = j} r_ns
+// with r_ns = v_n (y_n - A'(l_ns)).  ell and G leave through the slab as in csrc/bsc_glm.hip.  H is a scatter; it is
+// done without float atomics, in an order that depends on the group plan alone:
+//
+//   plan     bsc_glm_group_plan (host, plain C++, once per batch): the rows in stable order by group, each group's run
+//            cut into segments of at most BSC_GLM_GROUP_SEG_ROWS rows, a (start, length, group) table and every
+//            group's first segment.  The only place ids are range-checked, which is why it synchronises.
+//   pass     the six kernels below; besides the slab they leave every residual in R, 32 bytes per row in 16-row blocks
+//            [block][draw][row] (the MFMA tile's live lanes store 16 bytes each).
+//   segment  glm_group_segment_kernel: one wave per plan segment, 8 row-lanes x 8 draws; a row-lane strides the
+//            segment's rows through the plan's permutation, accumulates in float64, and the eight row-lanes fold by a
+//            fixed shuffle tree.
+//   group    glm_group_sum_kernel: a group's segments added in segment order, in float64, into H[S][J]; a group
+//            without rows gets exactly 0.
+//
+// The finish (bsc_glm_hier_update) is two launches: the per-draw scalars in fixed order, then one thread per
+// coordinate of lam for the gradient, Adam and the next draws.
+#include <vector>
+
+#include "bsc_glm_pass.h"
+
+namespace {
+
+constexpr int MAX_S = 64;
+constexpr int SEG_ROWS = BSC_GLM_GROUP_SEG_ROWS;
+constexpr int PLAN_HDR = 8;               // [magic, B, J, n_seg, SEG_ROWS, 0, 0, 0]
+constexpr int32_t PLAN_MAGIC = 0x67726f75;
+
+// The plan, int32: header | perm [B] | first segment of group j [J + 1] | (start, length, group) per segment.
+// Every offset follows from (B, J), which the caller of the pass passes again: the kernels never trust the header for
+// an address, they only refuse a plan whose header names another batch.
+inline int64_t plan_perm_off() { return PLAN_HDR; }
+__host__ __device__ inline int64_t plan_grp_off(int64_t B) { return PLAN_HDR + B; }
+__host__ __device__ inline int64_t plan_seg_off(int64_t B, int J) { return PLAN_HDR + B + J + 1; }
+inline int64_t plan_seg_bound(int64_t B, int J) {   // sum_j ceil(c_j / SEG_ROWS) <= B / SEG_ROWS + min(J, B)
+    return B / SEG_ROWS + (B < J ? B : (int64_t)J);
+}
+
+// ---- the six pass kernels -------------------------------------------------------------------------------------------
+
+template <int LINK, bool FULL>
+__global__ __launch_bounds__(PASS_BLOCK, 2) void glm_group_pass_kernel(
+    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
+    const float* __restrict__ v, int64_t B, int D, const float* __restrict__ W, int S, float* __restrict__ slab,
+    int n_iter, GlmGroupArgs ga) {
+    glm_pass_body<LINK, FULL, true, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, &ga);
+}
+
+template <int LINK>
+__global__ __launch_bounds__(PASS_BLOCK, 2) void glm_group_pass_mfma_kernel(
+    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
+    const float* __restrict__ v, int64_t B, const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter,
+    GlmGroupArgs ga) {
+    glm_pass_mfma_body<LINK, true, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, &ga);
+}
+
+__global__ __launch_bounds__(RED_BLOCK) void glm_group_slab_reduce_kernel(const float* __restrict__ slab, int n_blocks,
+                                                                          int D, int S, int s_base,
+                                                                          double* __restrict__ ell,
+                                                                          double* __restrict__ G) {
+    regress_slab_reduce(slab, n_blocks, D, S, s_base, ell, G);
+}
+
+// ---- the group sums -------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ bool plan_matches(const int32_t* __restrict__ plan, int64_t B, int J) {
+    return plan[0] == PLAN_MAGIC && (int64_t)plan[1] == B && plan[2] == J && plan[4] == SEG_ROWS;
+}
+
+// One wave per segment: lane = (row-lane lane >> 3, draw lane & 7).  segsum[seg][draw], float64.
+constexpr int SEG_BLOCK = 256;
+__global__ __launch_bounds__(SEG_BLOCK) void glm_group_segment_kernel(const int32_t* __restrict__ plan, int64_t B,
+                                                                      int J, int64_t seg_bound,
+                                                                      const float* __restrict__ R,
+                                                                      double* __restrict__ segsum) {
+    const int lane = threadIdx.x & 63;
+    const int64_t seg = (int64_t)blockIdx.x * (SEG_BLOCK / BSC_WAVE) + (threadIdx.x >> 6);
+    if (!plan_matches(plan, B, J)) return;
+    int64_t n_seg = plan[3];
+    if (n_seg > seg_bound) n_seg = seg_bound;
+    if (seg >= n_seg) return;
+    const int32_t* __restrict__ perm = plan + PLAN_HDR;
+    const int32_t* __restrict__ tab = plan + plan_seg_off(B, J) + 3 * seg;
+    int64_t start = tab[0], len = tab[1];
+    if (start < 0 || len < 0 || len > SEG_ROWS || start + len > B) len = 0;   // not a plan of bsc_glm_group_plan
+    const int rl = lane >> 3, s = lane & 7;
+    double acc = 0.0;
+    for (int i0 = rl; i0 < len; i0 += 32) {      // four rows in flight per lane, added in row order
+        float r[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = i0 + 8 * u;
+            r[u] = 0.f;
+            if (i < len) {
+                const int64_t row = perm[start + i];
+                if (row >= 0 && row < B) r[u] = R[(row >> 4) * R_BLOCK + s * 16 + (row & 15)];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc += (double)r[u];
+    }
+    acc += __shfl_xor(acc, 8);
+    acc += __shfl_xor(acc, 16);
+    acc += __shfl_xor(acc, 32);
+    if (lane < 8) segsum[seg * SG + s] = acc;
+}
+
+// H[s_base + s][j] = the segments of group j in segment order; thread = (group, draw slot).
+__global__ __launch_bounds__(256) void glm_group_sum_kernel(const int32_t* __restrict__ plan, int64_t B, int J,
+                                                            int64_t seg_bound, const double* __restrict__ segsum,
+                                                            int S, int s_base, double* __restrict__ H) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int j = idx >> 3, s = idx & 7;
+    if (j >= J || s_base + s >= S) return;
+    double tot = 0.0;
+    if (!plan_matches(plan, B, J)) {
+        tot = __builtin_nan("");     // a plan built for another batch: loud, and nothing was read through it
+    } else {
+        const int32_t* __restrict__ grp = plan + plan_grp_off(B);
+        int64_t first = grp[j], last = grp[j + 1];
+        if (first < 0) first = 0;
+        if (last > seg_bound) last = seg_bound;
+        for (int64_t k = first; k < last; ++k) tot += segsum[k * SG + s];
+    }
+    H[(int64_t)(s_base + s) * J + j] = tot;
+}
+
+// ---- the finish -----------------------------------------------------------------------------------------------------
+
+struct HierArgs {
+    const double* stats;     // [ell (S) | G (S D) | H (S J)]
+    const double* lam_in;
+    double* lam_out;
+    double* m1;
+    double* m2;
+    const double* eps;       // [S, P]: columns 0 .. P - 2 stream 0, column P - 1 (zeta) stream 1
+    const float* W;          // [S, D]
+    const float* Bz;         // [ceil(S / 8)][J][8]
+    const double* eps_next;  // nullptr: no next draw
+    float* W_next;
+    float* Bz_next;
+    double* scal;            // [ez (64) | g_zeta (64) | f (64) | sum rho]
+    double* elbo;
+    double* grad;
+    int D, J, S;
+    double scale, tau, a0, b0;
+    double c0;               // the terms of log p(z) free of z: D/2 log(tau / 2 pi) - J/2 log 2 pi + a0 log b0 - lnGamma(a0)
+    bsc_adam adam;
+};
+
+constexpr int HIER_BLOCK = 256;
+constexpr int HIER_WAVES = HIER_BLOCK / BSC_WAVE;
+
+// the block's sum of one value per thread: waves in wave order
+__device__ __forceinline__ double hier_block_sum(double v, double* red) {
+    v = wave_allsum_f64(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = red[0];
+#pragma unroll
+    for (int k = 1; k < HIER_WAVES; ++k) t += red[k];
+    __syncthreads();
+    return t;
+}
+
+// Workgroup s < S: |w_s|^2, sum_j b_sj^2, zeta_s, g_zeta and f_s = scale ell_s + log p(z_s); workgroup S: sum rho.
+__global__ __launch_bounds__(HIER_BLOCK) void glm_hier_scalars_kernel(HierArgs a) {
+    __shared__ double red[HIER_WAVES];
+    const int tid = threadIdx.x;
+    const int D = a.D, J = a.J, S = a.S, P = D + J + 1;
+    const int s = (int)blockIdx.x;
+    if (s == S) {
+        double part = 0.0;
+        for (int i = tid; i < P; i += HIER_BLOCK) part += a.lam_in[P + i];
+        const double t = hier_block_sum(part, red);
+        if (tid == 0) a.scal[3 * MAX_S] = t;
+        return;
+    }
+    double pw = 0.0, pb = 0.0;
+    for (int d = tid; d < D; d += HIER_BLOCK) {
+        const double wv = (double)a.W[(int64_t)s * D + d];
+        pw += wv * wv;
+    }
+    const float* bz = a.Bz + (int64_t)(s >> 3) * J * SG + (s & 7);
+    for (int j = tid; j < J; j += HIER_BLOCK) {
+        const double bv = (double)bz[(int64_t)j * SG];
+        pb += bv * bv;
+    }
+    const double wsq = hier_block_sum(pw, red);
+    const double bsq = hier_block_sum(pb, red);
+    if (tid == 0) {
+        const double zeta = a.lam_in[P - 1] + exp(a.lam_in[2 * P - 1]) * a.eps[(int64_t)s * P + P - 1];
+        const double ez = exp(zeta);
+        a.scal[s] = ez;
+        a.scal[MAX_S + s] = 0.5 * (double)J + a.a0 - ez * (a.b0 + 0.5 * bsq);
+        a.scal[2 * MAX_S + s] = a.scale * a.stats[s] + a.c0 - 0.5 * a.tau * wsq + 0.5 * (double)J * zeta -
+                                0.5 * ez * bsq + a.a0 * zeta - a.b0 * ez;
+    }
+}
+
+// One thread per coordinate i of z: gradient over the draws in draw order, Adam, the next draws.
+__global__ __launch_bounds__(HIER_BLOCK) void glm_hier_coord_kernel(HierArgs a) {
+    const int D = a.D, J = a.J, S = a.S, P = D + J + 1;
+    const int i = blockIdx.x * HIER_BLOCK + threadIdx.x;
+    if (i >= P) return;
+    const double* G = a.stats + S;
+    const double* H = a.stats + S + (int64_t)S * D;
+    double gm = 0.0, gr = 0.0;
+    for (int s = 0; s < S; ++s) {
+        double g;
+        if (i < D) {
+            g = a.scale * G[(int64_t)s * D + i] - a.tau * (double)a.W[(int64_t)s * D + i];
+        } else if (i < P - 1) {
+            const int j = i - D;
+            const double bv = (double)a.Bz[((int64_t)(s >> 3) * J + j) * SG + (s & 7)];
+            g = a.scale * H[(int64_t)s * J + j] - a.scal[s] * bv;
+        } else {
+            g = a.scal[MAX_S + s];
+        }
+        gm += g;
+        gr += g * a.eps[(int64_t)s * P + i];
+    }
+    const double inv_S = 1.0 / (double)S;
+    const double p_m = a.lam_in[i], p_rho = a.lam_in[P + i];
+    const double g_m = gm * inv_S;
+    const double g_r = gr * inv_S * exp(p_rho) + 1.0;
+    a.grad[i] = g_m;
+    a.grad[P + i] = g_r;
+    double q1 = a.m1[i], q2 = a.m2[i];
+    const double nm = bsc_adam_ascent(p_m, g_m, q1, q2, a.adam);
+    a.m1[i] = q1; a.m2[i] = q2;
+    q1 = a.m1[P + i]; q2 = a.m2[P + i];
+    const double nr = bsc_adam_ascent(p_rho, g_r, q1, q2, a.adam);
+    a.m1[P + i] = q1; a.m2[P + i] = q2;
+    a.lam_out[i] = nm;
+    a.lam_out[P + i] = nr;
+    if (i == P - 1) {
+        double fsum = 0.0;
+        for (int s = 0; s < S; ++s) fsum += a.scal[2 * MAX_S + s];
+        a.elbo[0] = fsum * inv_S + a.scal[3 * MAX_S] + 0.5 * (double)P * (1.0 + BSC_LOG_2PI);
+        return;     // zeta's next draw is made where it is used, in float64
+    }
+    if (!a.eps_next) return;
+    const double sd = exp(nr);
+    if (i < D) {
+        for (int s = 0; s < S; ++s) a.W_next[(int64_t)s * D + i] = (float)(nm + sd * a.eps_next[(int64_t)s * P + i]);
+    } else {
+        const int j = i - D;
+        const int s_pad = (S + SG - 1) / SG * SG;      // the unused slots of the last chunk stay zero
+        for (int s = 0; s < s_pad; ++s)
+            a.Bz_next[((int64_t)(s >> 3) * J + j) * SG + (s & 7)] =
+                s < S ? (float)(nm + sd * a.eps_next[(int64_t)s * P + i]) : 0.f;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+
+template <int LINK>
+void launch_group_link(bsc_ctx* ctx, int rows, const float* X, int64_t ldx, const float* y, const float* o,
+                       const float* v, int64_t B, int D, const float* W, int sg, PassGrid g, float* slab,
+                       const GlmGroupArgs& ga) {
+    const dim3 grid(g.n_blocks), block(PASS_BLOCK);
+    if (rows == MT_ROWS)
+        hipLaunchKernelGGL((glm_group_pass_mfma_kernel<LINK>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, W, sg,
+                           slab, g.n_iter, ga);
+    else if (D == GCOLS)
+        hipLaunchKernelGGL((glm_group_pass_kernel<LINK, true>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, D, W,
+                           sg, slab, g.n_iter, ga);
+    else
+        hipLaunchKernelGGL((glm_group_pass_kernel<LINK, false>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, D, W,
+                           sg, slab, g.n_iter, ga);
+}
+
+size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int64_t bsc_glm_group_plan_size(int64_t B, int32_t J) {
+    if (B < 0 || B > BSC_GLM_GROUP_MAX_ROWS || J < 1 || J > BSC_GLM_GROUP_MAX_J) return -1;
+    return plan_seg_off(B, J) + 3 * plan_seg_bound(B, J);
+}
+
+int bsc_glm_group_plan_host(const int32_t* g, int64_t B, int32_t J, int32_t* plan, int32_t* n_segments) {
+    const char* who = "bsc_glm_group_plan_host";
+    BSC_REQUIRE(J >= 1 && J <= BSC_GLM_GROUP_MAX_J, "%s: J=%d must be in [1,%d]", who, J, BSC_GLM_GROUP_MAX_J);
+    BSC_REQUIRE(B >= 0 && B <= BSC_GLM_GROUP_MAX_ROWS, "%s: B=%lld must be in [0,%lld]", who, (long long)B,
+                (long long)BSC_GLM_GROUP_MAX_ROWS);
+    BSC_REQUIRE(plan && (g || B == 0), "%s: null pointer", who);
+    // counting sort: counts, then every row to the next free slot of its group, rows ascending
+    std::vector<int64_t> next((size_t)J + 1, 0);
+    for (int64_t n = 0; n < B; ++n) {
+        BSC_REQUIRE(g[n] >= 0 && g[n] < J, "%s: row %lld has group id %d outside [0,%d)", who, (long long)n, g[n], J);
+        ++next[(size_t)g[n] + 1];
+    }
+    for (int j = 0; j < J; ++j) next[j + 1] += next[j];   // next[j]: where group j starts
+    int32_t* perm = plan + plan_perm_off();
+    int32_t* grp = plan + plan_grp_off(B);
+    int32_t* tab = plan + plan_seg_off(B, J);
+    int64_t n_seg = 0;
+    for (int j = 0; j < J; ++j) {
+        grp[j] = (int32_t)n_seg;
+        for (int64_t at = next[j]; at < next[j + 1]; at += SEG_ROWS) {
+            const int64_t len = next[j + 1] - at < SEG_ROWS ? next[j + 1] - at : SEG_ROWS;
+            tab[3 * n_seg] = (int32_t)at;
+            tab[3 * n_seg + 1] = (int32_t)len;
+            tab[3 * n_seg + 2] = j;
+            ++n_seg;
+        }
+    }
+    grp[J] = (int32_t)n_seg;
+    for (int64_t n = 0; n < B; ++n) perm[next[g[n]]++] = (int32_t)n;
+    plan[0] = PLAN_MAGIC;
+    plan[1] = (int32_t)B;
+    plan[2] = J;
+    plan[3] = (int32_t)n_seg;
+    plan[4] = SEG_ROWS;
+    plan[5] = plan[6] = plan[7] = 0;
+    if (n_segments) *n_segments = (int32_t)n_seg;
+    return BSC_OK;
+}
+
+int bsc_glm_group_plan(bsc_ctx* ctx, const int32_t* g, int64_t B, int32_t J, int32_t* plan, int32_t* n_segments) {
+    BSC_CHECK_CTX(ctx);
+    const char* who = "bsc_glm_group_plan";
+    BSC_REQUIRE(!ctx->capturing, "%s inside a graph capture", who);
+    const int64_t n = bsc_glm_group_plan_size(B, J);
+    BSC_REQUIRE(n >= 0, "%s: B=%lld J=%d (B in [0,%lld], J in [1,%d])", who, (long long)B, J,
+                (long long)BSC_GLM_GROUP_MAX_ROWS, BSC_GLM_GROUP_MAX_J);
+    BSC_REQUIRE(plan && (g || B == 0), "%s: null pointer", who);
+    std::vector<int32_t> hg((size_t)B), hp((size_t)n, 0);
+    BSC_HIP(hipStreamSynchronize(ctx->stream));      // g may have been written on the stream
+    if (B) BSC_HIP(hipMemcpy(hg.data(), g, (size_t)B * 4, hipMemcpyDeviceToHost));
+    int32_t n_seg = 0;
+    const int rc = bsc_glm_group_plan_host(hg.data(), B, J, hp.data(), &n_seg);
+    if (rc != BSC_OK) return rc;
+    BSC_HIP(hipMemcpy(plan, hp.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    if (n_segments) *n_segments = n_seg;
+    return BSC_OK;
+}
+
+int64_t bsc_glm_group_workspace_bytes(bsc_ctx* ctx, int64_t B, int32_t J) {
+    if (!ctx || B < 0 || J < 1) return -1;
+    const PassGrid g8 = pass_grid(ctx, B, ROWS), g16 = pass_grid(ctx, B, MT_ROWS);
+    const int nb = g8.n_blocks > g16.n_blocks ? g8.n_blocks : g16.n_blocks;
+    return (int64_t)(round256((size_t)nb * SLAB_STRIDE * 4) + round256((size_t)((B + 15) / 16) * R_BLOCK * 4) +
+                     (size_t)(plan_seg_bound(B, J) + 1) * SG * 8);
+}
+
+int bsc_glm_data_pass_groups(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx, const float* y,
+                             const float* offset, const float* weight, const int32_t* g, const int32_t* plan, int64_t B,
+                             int32_t D, int32_t J, const float* W, const float* Bz, int32_t S, double* ell, double* G,
+                             double* H) {
+    BSC_CHECK_CTX(ctx);
+    const char* who = "bsc_glm_data_pass_groups";
+    const int rc0 = check_glm_obs_args(who, link, X, ldx, y, offset, weight, B, D, W, S, MAX_S);
+    if (rc0 != BSC_OK) return rc0;
+    BSC_REQUIRE(J >= 1 && J <= BSC_GLM_GROUP_MAX_J, "%s: J=%d must be in [1,%d]", who, J, BSC_GLM_GROUP_MAX_J);
+    BSC_REQUIRE(B <= BSC_GLM_GROUP_MAX_ROWS, "%s: B=%lld is more than a group plan holds (%lld)", who, (long long)B,
+                (long long)BSC_GLM_GROUP_MAX_ROWS);
+    BSC_REQUIRE(g || B == 0, "%s: g is null with B=%lld", who, (long long)B);
+    BSC_REQUIRE((((uintptr_t)g) & 3) == 0, "%s: g must be 4-byte aligned", who);
+    BSC_REQUIRE(plan, "%s: plan is null (bsc_glm_group_plan builds it)", who);
+    BSC_REQUIRE(Bz && (((uintptr_t)Bz) & 3) == 0, "%s: Bz is null or not 4-byte aligned", who);
+    BSC_REQUIRE(ell && G, "%s: null output", who);
+    BSC_REQUIRE(H, "%s: H is null", who);
+
+    const int rows = pass_rows(D, y, offset, weight, g);
+    const PassGrid pg = pass_grid(ctx, B, rows);
+    const int64_t r_blocks = (B + 15) / 16;
+    const int64_t seg_bound = plan_seg_bound(B, J);
+    const size_t slab_bytes = round256((size_t)pg.n_blocks * SLAB_STRIDE * 4);
+    const size_t r_bytes = round256((size_t)r_blocks * R_BLOCK * 4);
+    void* ws = nullptr;
+    const int rc = bsc_workspace(ctx, slab_bytes + r_bytes + (size_t)(seg_bound + 1) * SG * 8, &ws);
+    if (rc != BSC_OK) return rc;
+    ctx->slab_rows = 0;  // the slab is consumed here
+    float* slab = (float*)ws;
+    GlmGroupArgs ga;
+    ga.g = g;
+    ga.J = J;
+    ga.R = (float*)((char*)ws + slab_bytes);
+    ga.r_blocks = r_blocks;
+    double* segsum = (double*)((char*)ws + slab_bytes + r_bytes);
+
+    const dim3 rgrid((SLAB_STRIDE + BSC_WAVE - 1) / BSC_WAVE);
+    const unsigned seg_grid = (unsigned)((seg_bound + SEG_BLOCK / BSC_WAVE - 1) / (SEG_BLOCK / BSC_WAVE));
+    const unsigned sum_grid = (unsigned)(((int64_t)J * SG + 255) / 256);
+    for (int s0 = 0; s0 < S; s0 += SG) {   // eight draws per launch: the pass, its slab reduce, its group sums
+        const int sg = S - s0 < SG ? S - s0 : SG;
+        ga.Bz = Bz + (int64_t)(s0 / SG) * J * SG;
+        {
+            bsc_prof_scope prof(ctx);  // times the pass kernel alone
+            if (link == BSC_GLM_LOGISTIC)
+                launch_group_link<BSC_GLM_LOGISTIC>(ctx, rows, X, ldx, y, offset, weight, B, D, W + (int64_t)s0 * D, sg,
+                                                    pg, slab, ga);
+            else
+                launch_group_link<BSC_GLM_POISSON>(ctx, rows, X, ldx, y, offset, weight, B, D, W + (int64_t)s0 * D, sg,
+                                                   pg, slab, ga);
+        }
+        BSC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(glm_group_slab_reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, slab, pg.n_blocks,
+                           (int)D, (int)S, s0, ell, G);
+        BSC_LAUNCH_CHECK();
+        if (seg_grid) {
+            hipLaunchKernelGGL(glm_group_segment_kernel, dim3(seg_grid), dim3(SEG_BLOCK), 0, ctx->stream, plan, B,
+                               (int)J, seg_bound, (const float*)ga.R, segsum);
+            BSC_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(glm_group_sum_kernel, dim3(sum_grid), dim3(256), 0, ctx->stream, plan, B, (int)J, seg_bound,
+                           (const double*)segsum, (int)S, s0, H);
+        BSC_LAUNCH_CHECK();
+    }
+    return BSC_OK;
+}
+
+int bsc_glm_hier_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                        double* m2, const double* eps, const float* W, const float* Bz, int32_t D, int32_t J, int32_t S,
+                        double scale, double prior_precision, double a0, double b0, int64_t t, double lr, double beta1,
+                        double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
+                        int32_t eps_next_ready, float* W_next, float* Bz_next, double* elbo, double* grad) {
+    BSC_CHECK_CTX(ctx);
+    const char* who = "bsc_glm_hier_update";
+    BSC_REQUIRE(stats, "%s: stats is null (pending pass partials are not read: pass [ell | G | H])", who);
+    BSC_REQUIRE(lam_in && lam_out && m1 && m2 && eps && W && Bz && elbo && grad, "%s: null pointer", who);
+    BSC_REQUIRE(lam_in != lam_out, "%s: lam_in and lam_out must differ", who);
+    BSC_REQUIRE(D > 0 && S >= 1 && S <= MAX_S, "%s: D=%d S=%d (S<=%d)", who, D, S, MAX_S);
+    BSC_REQUIRE(J >= 1 && J <= BSC_GLM_GROUP_MAX_J, "%s: J=%d must be in [1,%d]", who, J, BSC_GLM_GROUP_MAX_J);
+    BSC_REQUIRE(prior_precision > 0.0, "%s: prior_precision=%g must be positive", who, prior_precision);
+    BSC_REQUIRE(a0 > 0.0 && b0 > 0.0, "%s: a0=%g b0=%g must be positive", who, a0, b0);
+    BSC_REQUIRE(scale > 0.0, "%s: scale=%g must be positive", who, scale);
+    BSC_REQUIRE(t >= 1, "%s: the Adam step count starts at 1", who);
+    BSC_REQUIRE((eps_next && W_next && Bz_next) || (!eps_next && !W_next && !Bz_next),
+                "%s: next-draw buffers must be all set or all null", who);
+    BSC_REQUIRE(!eps_next || (eps_next != eps && W_next != W && Bz_next != Bz),
+                "%s: next-draw buffers must not alias the current draws", who);
+    const int P = D + J + 1;
+    void* ws = nullptr;
+    int rc = bsc_workspace(ctx, (3 * MAX_S + 8) * sizeof(double), &ws);
+    if (rc != BSC_OK) return rc;
+    if (eps_next && !eps_next_ready) {   // the noise of next_step first (off the default path: drivers draw ahead)
+        rc = bsc_blr_noise(ctx, P - 1, S, seed, next_step, 1, eps_next);
+        if (rc != BSC_OK) return rc;
+    }
+    HierArgs a;
+    a.stats = stats; a.lam_in = lam_in; a.lam_out = lam_out; a.m1 = m1; a.m2 = m2;
+    a.eps = eps; a.W = W; a.Bz = Bz; a.eps_next = eps_next; a.W_next = W_next; a.Bz_next = Bz_next;
+    a.scal = (double*)ws; a.elbo = elbo; a.grad = grad;
+    a.D = D; a.J = J; a.S = S;
+    a.scale = scale; a.tau = prior_precision; a.a0 = a0; a.b0 = b0;
+    a.c0 = 0.5 * (double)D * (log(prior_precision) - BSC_LOG_2PI) - 0.5 * (double)J * BSC_LOG_2PI + a0 * log(b0) -
+           lgamma(a0);
+    a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
+    ctx->slab_rows = 0;   // the workspace is this finish's now
+    {
+        bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish, timed apart from the pass
+        hipLaunchKernelGGL(glm_hier_scalars_kernel, dim3(S + 1), dim3(HIER_BLOCK), 0, ctx->stream, a);
+        hipLaunchKernelGGL(glm_hier_coord_kernel, dim3((P + HIER_BLOCK - 1) / HIER_BLOCK), dim3(HIER_BLOCK), 0,
+                           ctx->stream, a);
+    }
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
+}  // extern "C"

@@ -12,6 +12,16 @@
 //                 overflowed).  o and v ride in the tile struct next to y and are loaded the way y is; a null offset
 //                 is a zero-record descriptor (reads 0, costs nothing), a null weight a uniform select of 1.0f.
 //                 Rows past B read o = 0 and v = 0 through the descriptors.
+//   GRP = true    csrc/bsc_glm_group.hip (always with OBS): a per-row group id g_n and one intercept per (group, draw),
+//                     l[n,s] = x_n . w_s + Bz[g_n][s] + o[n]
+//                 The id rides in the tile next to y (rows past B read id 0); the intercept is gathered through a
+//                 descriptor of exactly J * 32 bytes -- no id can read outside the table -- BEFORE the forward
+//                 contraction and before the next tile's loads are issued (loads return in order: behind them the
+//                 gather would wait for the whole prefetch).  Besides the slab the pass leaves every residual
+//                 r_ns = v_n (y_n - A'(l_ns)) in a workspace R, 32 bytes per row in 16-row blocks [block][draw][row],
+//                 through a descriptor over what is left of R from the tile's block on: the tail tiles of n_iter run
+//                 past the batch and their stores do not land.  Everything of it is behind `if constexpr (GRP)`; the
+//                 flag defaults to off and the kernels of the two files above compile as they did without it.
 //
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
@@ -59,18 +69,41 @@ __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, floa
 constexpr int ROWS = 8;
 using G8 = Geo<ROWS>;
 
-template <bool OBS>
+template <bool OBS, bool GRP = false>
 struct GlmTile : RowTile<ROWS> {};
 template <>
-struct GlmTile<true> : RowTile<ROWS> {
+struct GlmTile<true, false> : RowTile<ROWS> {
     float ov, vv;   // offset and weight of row lane_value(lane) >> 3, as yv
 };
+template <>
+struct GlmTile<true, true> : RowTile<ROWS> {
+    float ov, vv;
+    int gv;         // group id of the same row
+    float bz;       // Bz[gv][lane_value(lane) & 7], gathered by gather_tile
+};
+
+// What the GRP bodies need besides the pass's own arguments (unused, and never touched, without the flag).
+struct GlmGroupArgs {
+    const int* g;        // [B] group ids, each in [0, J) (checked where the plan is built)
+    const float* Bz;     // [J][8]: this launch's chunk of the intercept draws
+    int J;
+    float* R;            // residuals, [r_blocks][8][16]
+    int64_t r_blocks;    // ceil(B / 16)
+};
+constexpr int R_BLOCK = 16 * SG;   // floats per 16-row block of R
+
+// The intercept table: exactly J records of 32 bytes.  The whole offset of a gather goes into the per-lane operand,
+// which is the one the range check covers.
+__device__ __forceinline__ auto glm_bz_rsrc(const GlmGroupArgs& ga) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)ga.Bz, 0, (unsigned)ga.J * 32u, 0x00020000);
+}
 
 // One tile = ROWS rows from row0 on, through descriptors that cover exactly the rows [row0, B).
-template <bool FULL, bool OBS>
-__device__ __forceinline__ void load_tile(GlmTile<OBS>& t, const float* __restrict__ X, int64_t ldx,
+template <bool FULL, bool OBS, bool GRP = false>
+__device__ __forceinline__ void load_tile(GlmTile<OBS, GRP>& t, const float* __restrict__ X, int64_t ldx,
                                           const float* __restrict__ y, const float* __restrict__ o,
-                                          const float* __restrict__ v_, int64_t row0, int64_t B, int D, int lane) {
+                                          const float* __restrict__ v_, int64_t row0, int64_t B, int D, int lane,
+                                          const int* __restrict__ g_ = nullptr) {
     auto xs = bsc_rows_rsrc(X, ldx, D, B, row0);
     auto ys = bsc_vec_rsrc(y, B, row0);
     const int lane_off = 16 * lane;
@@ -90,13 +123,25 @@ __device__ __forceinline__ void load_tile(GlmTile<OBS>& t, const float* __restri
         t.ov = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(os, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
         t.vv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vs, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
     }
+    if constexpr (GRP) {
+        auto gs = bsc_vec_rsrc(g_, B, row0);
+        t.gv = (int)__builtin_amdgcn_raw_buffer_load_b32(gs, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0);
+    }
+}
+
+// GRP: the intercept of this lane's (row, draw), requested before the next tile's loads are issued.
+__device__ __forceinline__ void gather_tile(GlmTile<true, true>& t, const GlmGroupArgs& ga, int lane) {
+    t.bz = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+        glm_bz_rsrc(ga), 32 * t.gv + 4 * (lane_value<ROWS>(lane) & 7), 0, 0));
 }
 
 // Forward + link + backward for one tile; `wl` is this wave's LDS region, `rows_left` = B - row0.  has_v: the weights
 // are set (uniform; without them every row weighs 1.0f and real_row alone masks the rows past B).
-template <int LINK, bool OBS>
-__device__ __forceinline__ void compute_tile(const GlmTile<OBS>& t, const float4 (&w)[SG], float4 (&acc)[SG],
-                                             float& ell, float* wl, int lane, int64_t rows_left, bool has_v) {
+// GRP: `row0` is the tile's first row (a multiple of 8), its residuals also go to ga.R.
+template <int LINK, bool OBS, bool GRP = false>
+__device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP>& t, const float4 (&w)[SG], float4 (&acc)[SG],
+                                             float& ell, float* wl, int lane, int64_t rows_left, bool has_v,
+                                             const GlmGroupArgs* ga = nullptr, int64_t row0 = 0) {
     // 1. per-lane partial dots, row by row, into this lane's row of the buffer
     float* mine = wl + lane * G8::PSTR;
 #pragma unroll
@@ -135,7 +180,15 @@ __device__ __forceinline__ void compute_tile(const GlmTile<OBS>& t, const float4
     const float logit = swap_add16(t0, t1);
     const int val = lane_value<ROWS>(lane);
     float resid;
-    if constexpr (OBS)
+    if constexpr (GRP) {
+        resid = glm_link<LINK, true>(logit + t.bz + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell,
+                                     has_v ? t.vv : 1.0f);
+        // row row0 + (val >> 3) of block row0 >> 4, draw val & 7; nothing lands from the block r_blocks on
+        const int64_t blk = row0 >> 4;
+        auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(resid), rs,
+                                              4 * ((val & 7) * 16 + (int)(row0 & 8) + (val >> 3)), 0, 0);
+    } else if constexpr (OBS)
         resid = glm_link<LINK, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell, has_v ? t.vv : 1.0f);
     else
         resid = glm_link<LINK>(logit, t.yv, (int64_t)(val >> 3) < rows_left, ell);
@@ -169,10 +222,10 @@ __device__ __forceinline__ void write_block_partial(const float* lds, float* __r
 
 // FULL: D == 256.  n_iter: tiles per wave (the same for every wave; tiles past the end read zeros).
 // o, v_: the offset and the weight, each may be null; read only where OBS.
-template <int LINK, bool FULL, bool OBS>
+template <int LINK, bool FULL, bool OBS, bool GRP = false>
 __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const float* y, const float* o,
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
-                                              int n_iter) {
+                                              int n_iter, const GlmGroupArgs* ga = nullptr) {
     constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > SLAB_STRIDE ? G8::WAVE_LDS : SLAB_STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
@@ -193,16 +246,37 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     // This wave owns tiles first, first + stride, ...; every prefetch is unconditional.
     const int64_t stride = (int64_t)gridDim.x * PASS_WAVES;
     int64_t tile = (int64_t)blockIdx.x * PASS_WAVES + wave;
-    GlmTile<OBS> ta, tb;
-    load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane);
-    for (int k = 0; k + 1 < n_iter; k += 2) {
-        load_tile<FULL, OBS>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane);
-        compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
-        load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane);
-        compute_tile<LINK, OBS>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v);
-        tile += 2 * stride;
+    if constexpr (GRP) {
+        // the same rotation; every tile's gather goes out before the loads of the tile after it
+        const int* g_ = ga->g;
+        GlmTile<OBS, GRP> ta, tb;
+        load_tile<FULL, OBS, GRP>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane, g_);
+        for (int k = 0; k + 1 < n_iter; k += 2) {
+            gather_tile(ta, *ga, lane);
+            load_tile<FULL, OBS, GRP>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane, g_);
+            compute_tile<LINK, OBS, GRP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS);
+            gather_tile(tb, *ga, lane);
+            load_tile<FULL, OBS, GRP>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane, g_);
+            compute_tile<LINK, OBS, GRP>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, ga,
+                                         (tile + stride) * ROWS);
+            tile += 2 * stride;
+        }
+        if (n_iter & 1) {
+            gather_tile(ta, *ga, lane);
+            compute_tile<LINK, OBS, GRP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS);
+        }
+    } else {
+        GlmTile<OBS> ta, tb;
+        load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane);
+        for (int k = 0; k + 1 < n_iter; k += 2) {
+            load_tile<FULL, OBS>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane);
+            compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
+            load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane);
+            compute_tile<LINK, OBS>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v);
+            tile += 2 * stride;
+        }
+        if (n_iter & 1) compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
     }
-    if (n_iter & 1) compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
 
     __syncthreads();  // every wave is done with its private region
     float* ep = lds + wave * SLAB_STRIDE;
@@ -229,11 +303,16 @@ struct MTileXY {
     float4 x[MT_ROWS];
     float4 yv;     // y[row0 + 4 kq .. + 3]: the rows of this lane's forward result registers
 };
-template <bool OBS>
+template <bool OBS, bool GRP = false>
 struct MTile : MTileXY {};
 template <>
-struct MTile<true> : MTileXY {
+struct MTile<true, false> : MTileXY {
     float4 ov, vv;   // offset and weight of the same four rows
+};
+template <>
+struct MTile<true, true> : MTileXY {
+    float4 ov, vv;
+    int4 gv;         // group ids of the same four rows
 };
 
 __device__ __forceinline__ float4 load_rows4(const float* __restrict__ p, int64_t n, int64_t row0, int lane) {
@@ -242,10 +321,11 @@ __device__ __forceinline__ float4 load_rows4(const float* __restrict__ p, int64_
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
 }
 
-template <bool OBS>
-__device__ __forceinline__ void load_mtile(MTile<OBS>& t, const float* __restrict__ X, int64_t ldx,
+template <bool OBS, bool GRP = false>
+__device__ __forceinline__ void load_mtile(MTile<OBS, GRP>& t, const float* __restrict__ X, int64_t ldx,
                                            const float* __restrict__ y, const float* __restrict__ o,
-                                           const float* __restrict__ v_, int64_t row0, int64_t B, int lane) {
+                                           const float* __restrict__ v_, int64_t row0, int64_t B, int lane,
+                                           const int* __restrict__ g_ = nullptr) {
     auto xs = bsc_rows_rsrc(X, ldx, GCOLS, B, row0);
     auto ys = bsc_vec_rsrc(y, B, row0);
     const int lane_off = 16 * lane;
@@ -262,12 +342,17 @@ __device__ __forceinline__ void load_mtile(MTile<OBS>& t, const float* __restric
         t.ov = load_rows4(o, o ? B : 0, row0, lane);
         t.vv = load_rows4(v_, v_ ? B : 0, row0, lane);
     }
+    if constexpr (GRP) {
+        auto gs = bsc_vec_rsrc(g_, B, row0);
+        auto gi = __builtin_amdgcn_raw_buffer_load_b128(gs, 16 * (lane >> 4), 0, 0);
+        t.gv = make_int4((int)gi[0], (int)gi[1], (int)gi[2], (int)gi[3]);
+    }
 }
 
-template <int LINK, bool OBS>
+template <int LINK, bool OBS, bool GRP = false>
 __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, const float* y, const float* o,
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
-                                                   int n_iter) {
+                                                   int n_iter, const GlmGroupArgs* ga = nullptr) {
     constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > SLAB_STRIDE ? MT_WAVE_LDS : SLAB_STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
@@ -301,8 +386,10 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     const int64_t slot = (int64_t)blockIdx.x * PASS_WAVES + wave;
     auto row0_of = [=](int p) { return p < n_iter ? ((int64_t)p * stride0 + slot) * MT_ROWS : B; };
 
-    MTile<OBS> t;
-    load_mtile<OBS>(t, X, ldx, y, o, v_, row0_of(0), B, lane);
+    const int* g_ = nullptr;
+    if constexpr (GRP) g_ = ga->g;
+    MTile<OBS, GRP> t;
+    load_mtile<OBS, GRP>(t, X, ldx, y, o, v_, row0_of(0), B, lane, g_);
     for (int p = 0; p < n_iter; ++p) {
         // the tile to LDS, its registers take the next window's tile
 #pragma unroll
@@ -314,7 +401,16 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
             if (has_v) vv = t.vv;
         }
         const int64_t rows_left = B - row0_of(p) - 4 * kq;     // rows 4 kq + reg < rows_left are real
-        load_mtile<OBS>(t, X, ldx, y, o, v_, row0_of(p + 1), B, lane);
+        float4 bz = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (GRP) {   // the intercepts of this lane's four rows, ahead of the prefetch and of the forward
+            auto bs = glm_bz_rsrc(*ga);
+            const int so = 4 * (i16 & 7);
+            bz.x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bs, 32 * t.gv.x + so, 0, 0));
+            bz.y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bs, 32 * t.gv.y + so, 0, 0));
+            bz.z = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bs, 32 * t.gv.z + so, 0, 0));
+            bz.w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bs, 32 * t.gv.w + so, 0, 0));
+        }
+        load_mtile<OBS, GRP>(t, X, ldx, y, o, v_, row0_of(p + 1), B, lane, g_);
         wave_lds_sync();
 
         // forward on v_mfma_f32_16x16x4_f32 (two accumulators: no MFMA waits on its predecessor)
@@ -337,7 +433,19 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
         // to rb[draw][row] as one 16-byte store per live lane
         if (live) {
             float r0, r1, r2, r3;
-            if constexpr (OBS) {
+            if constexpr (GRP) {
+                r0 = glm_link<LINK, true>(d0[0] + d1[0] + bz.x + ov.x, yv.x, rows_left > 0, ell, vv.x);
+                r1 = glm_link<LINK, true>(d0[1] + d1[1] + bz.y + ov.y, yv.y, rows_left > 1, ell, vv.y);
+                r2 = glm_link<LINK, true>(d0[2] + d1[2] + bz.z + ov.z, yv.z, rows_left > 2, ell, vv.z);
+                r3 = glm_link<LINK, true>(d0[3] + d1[3] + bz.w + ov.w, yv.w, rows_left > 3, ell, vv.w);
+                // block row0 / 16 of R, [draw][row]: nothing lands from the block r_blocks on
+                const int64_t blk = row0_of(p) >> 4;
+                auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);
+                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    u32x4{__float_as_uint(r0), __float_as_uint(r1), __float_as_uint(r2), __float_as_uint(r3)}, rs,
+                    4 * (i16 * MT_ROWS + 4 * kq), 0, 0);
+            } else if constexpr (OBS) {
                 r0 = glm_link<LINK, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x);
                 r1 = glm_link<LINK, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y);
                 r2 = glm_link<LINK, true>(d0[2] + d1[2] + ov.z, yv.z, rows_left > 2, ell, vv.z);
@@ -392,9 +500,31 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     write_block_partial(lds, slab, tid);
 }
 
-// ---- host side: the launch of the OBS kernels, defined in csrc/bsc_glm_obs.hip and called from csrc/bsc_glm.hip ----
+// ---- host side ---------------------------------------------------------------------------------------------------
+
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// 16 = the MFMA kernel (needs the full 256-column layout and 16-byte aligned y, offset, weight and group ids -- null
+// ones count as aligned), else 8-row tiles.
+inline int pass_rows(int D, const float* y, const float* o = nullptr, const float* v = nullptr,
+                     const int32_t* g = nullptr) {
+    return (D == GCOLS && aligned16(y) && aligned16(o) && aligned16(v) && aligned16(g)) ? MT_ROWS : ROWS;
+}
+
+// The envelope of the entry points that take an offset and a weight: y by name, the vectors' alignment.
+inline int check_glm_obs_args(const char* who, int32_t link, const float* X, int64_t ldx, const float* y, const float* o,
+                              const float* v, int64_t B, int32_t D, const float* W, int32_t S, int max_s) {
+    BSC_REQUIRE(link == BSC_GLM_LOGISTIC || link == BSC_GLM_POISSON,
+                "%s: link=%d must be BSC_GLM_LOGISTIC (0) or BSC_GLM_POISSON (1)", who, link);
+    BSC_REQUIRE(y || B <= 0, "%s: y is null with B=%lld", who, (long long)B);
+    BSC_REQUIRE((((uintptr_t)o) & 3) == 0 && (((uintptr_t)v) & 3) == 0, "%s: offset and weight must be 4-byte aligned",
+                who);
+    return check_regress_args(who, X, ldx, B, D, W, S, max_s);
+}
 
 }  // namespace
+
+// The launch of the OBS kernels, defined in csrc/bsc_glm_obs.hip and called from csrc/bsc_glm.hip:
 
 // 16-row MFMA tiles when mfma != 0 (D == 256; y and the set ones of o, v 16-byte aligned), else 8-row VALU tiles.
 void bsc_glm_obs_launch_pass(bsc_ctx* ctx, int link, int mfma, const float* X, int64_t ldx, const float* y,

@@ -112,20 +112,11 @@ class ScoreFunctionVI(object):
         G = Gm.shape[1]
         if D > 256 or D % 4 or self.S > 128 or X.stride(1) != 1:
             return "outside the fused pass's envelope (D <= 256 and a multiple of 4, S <= 128, row-major X)"
-        # the group matrix must be one-hot: every entry 0 or 1 (sum of squares = sum) and one per row (sum = N,
-        # every row sum 1) -- reductions through the executor; the index vector is the matrix times 0 .. G - 1
+        # the group matrix must be one-hot; the kernels take the index vector (recognise.onehot_group_ids)
         b = self.backend
-        from .. import algebra as A
-        Gv = A.var("Gm", 2)
-        ramp = b.from_host(np.arange(G, dtype=np.float32), "float32", 1)
-        # (no negative entry: sum |x| = sum x; rows sum to one: sum_n r_n = sum_n r_n^2 = N; then sum x^2 = N iff one-hot)
-        checks = [A.sum(Gv), A.sum(Gv * Gv), A.sum(A.sum(Gv, axis=1) * A.sum(Gv, axis=1)), A.sum(A.abs_(Gv))]
-        total, squares, row_squares, absolute = (float(np.asarray(b.to_host(e.compile(b).device_fn(Gm=Gm))))
-                                                 for e in checks)
-        if not (total == float(N) and squares == float(N) and row_squares == float(N) and absolute == float(N)):
+        g = recognise.onehot_group_ids(b, Gm)
+        if g is None:
             return "the group matrix %s is not one-hot" % plan.onehot
-        g = b.materialize(A.dot(Gv, A.var("ramp", 1)).compile(b).device_fn(Gm=Gm, ramp=ramp))
-        g = g.round().to(torch.int32)                     # (dtype conversion: plumbing)
         order = [v.name for v, _ in self.latents]
         if order != [plan.W, plan.B, plan.zeta]:
             return "latents must be listed as (weights, group intercepts, log precision) for the fused layout"

@@ -496,6 +496,26 @@ def logistic_hierarchy(log_joint, latents, data_shapes, n_samples, why=None):
     return _say(why, reason)
 
 
+def onehot_group_ids(backend, Gm):
+    """The int32 index vector [N] of a one-hot group matrix Gm [N, G] on the device, or None when Gm is not one-hot:
+    every entry 0 or 1 (sum of squares = sum) and one per row (sum = N, every row sum 1) -- reductions through the
+    executor; the index vector is the matrix times 0 .. G - 1."""
+    import torch
+    from .. import algebra as A
+    b = backend
+    N, G = int(Gm.shape[0]), int(Gm.shape[1])
+    Gv = A.var("Gm", 2)
+    ramp = b.from_host(np.arange(G, dtype=np.float32), "float32", 1)
+    # (no negative entry: sum |x| = sum x; rows sum to one: sum_n r_n = sum_n r_n^2 = N; then sum x^2 = N iff one-hot)
+    checks = [A.sum(Gv), A.sum(Gv * Gv), A.sum(A.sum(Gv, axis=1) * A.sum(Gv, axis=1)), A.sum(A.abs_(Gv))]
+    total, squares, row_squares, absolute = (float(np.asarray(b.to_host(e.compile(b).device_fn(Gm=Gm))))
+                                             for e in checks)
+    if not (total == float(N) and squares == float(N) and row_squares == float(N) and absolute == float(N)):
+        return None
+    g = b.materialize(A.dot(Gv, A.var("ramp", 1)).compile(b).device_fn(Gm=Gm, ramp=ramp))
+    return g.round().to(torch.int32)                     # (dtype conversion: plumbing)
+
+
 # ---- canonical-link GLMs with an isotropic Gaussian prior (svi/glm.py) ---------------------------------------------
 
 class GLMLinear(object):

@@ -49,6 +49,13 @@ full layout is the driver's.  The draws are ``bsc_blr_noise``'s stream 0.  Up to
 as an offset (``l = dot(W, X.T) + offset``) and as row weights (``sum_n weights_n [...]``), whatever they are called:
 the driver gets them (csrc/bsc_glm_obs.hip), ``set_data`` forwards them, ``predict`` takes them for new rows.
 
+**The fused random-intercept route.**  Three latent blocks (weights, group intercepts, log precision) whose log-joint
+is BASELINE config 5's hierarchical logistic regression in any parameterisation (``recognise.logistic_hierarchy``, the
+recogniser ``ScoreFunctionVI`` asks) are stepped by ``svi/hier_glm.py``: the grouped pass (csrc/bsc_glm_group.hip) and
+``bsc_glm_hier_update``, with the one-hot group matrix turned into an index vector and scale, a0, b0 read off the
+plan.  ``route="auto"`` takes it (no model of three latent blocks had a fused or pass route before, and none is
+pinned to the general route by a test); the guide is mean-field, ``set_data`` and ``predict`` are refused there.
+
 **The pass route.**  When the data term is recognised but the parameter-sized remainder is NOT of that family
 (a known noise variance, another prior, more latents), the step still needs the data only through
 Q_s = sum_n (y_n - x_n . w_s)^2 and G_s = sum_n (y_n - x_n . w_s) x_n: ONE ``bsc_blr_data_pass_sweep`` gives
@@ -337,6 +344,13 @@ class ReparamVI(object):
             glm = recognise.glm_linear(self.log_joint, self.latents, shapes, self.S)
             if glm is not None:
                 return self._route_glm(glm)
+            if len(self.latents) == 3:      # (weights, group intercepts, log precision): the random-intercept model
+                hier_said = []
+                hier = recognise.logistic_hierarchy(self.log_joint, self.latents, shapes, self.S, why=hier_said)
+                if hier is not None:
+                    return self._route_hierarchy(hier)
+                return ("three latent blocks, but not the random-intercept logistic regression in any parameterisation: %s"
+                        % (hier_said[-1] if hier_said else "no reason recorded"))
             return ("the data do not enter the log-joint as coefficient_s * sum_n (y_n - x_n . w_s)^2: %s"
                     % (said[-1] if said else "no reason recorded"))
         self.plan = plan
@@ -405,6 +419,41 @@ class ReparamVI(object):
         self.route = "fused: bsc_glm_data_pass + %s (%s link)" % (finish, plan.link)
         return None
 
+    def _route_hierarchy(self, plan):
+        """The svi/hier_glm.py driver behind this engine for a recognised hierarchical logistic regression
+        (``recognise.logistic_hierarchy``: BASELINE config 5 in any parameterisation), as ``ScoreFunctionVI`` takes it to
+        svi/bbvi.py: the one-hot group matrix goes to an index vector, scale, a0 and b0 come from the plan.  Returns
+        None, or the reason the driver cannot take the model."""
+        import torch
+        from . import recognise
+        from ..svi.hier_glm import MAX_GROUPS, HierGLMReparamSVI
+        if self.guide != "diag":
+            return "the random-intercept route has the mean-field guide only (guide='diag')"
+        X, y, Gm = self._data[plan.X], self._data[plan.y], self._data[plan.onehot]
+        if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 for t in (X, y, Gm)):
+            return "the fused pass streams float32 data"
+        N, D, J = int(X.shape[0]), int(X.shape[1]), int(Gm.shape[1])
+        why = _outside_pass_envelope(X, y, D, self.S)
+        if why is not None:
+            return why
+        if J > MAX_GROUPS:
+            return "outside the grouped pass's envelope (%d groups at most)" % MAX_GROUPS
+        if [v.name for v, _ in self.latents] != [plan.W, plan.B, plan.zeta]:
+            return "latents must be listed as (weights, group intercepts, log precision) for the fused layout"
+        g = recognise.onehot_group_ids(self.backend, Gm)
+        if g is None:
+            return "the group matrix %s is not one-hot" % plan.onehot
+        self.plan = plan
+        self._planned_shape = (N, D)
+        # lam = [m (P) | rho (P)] over [w | b | zeta] in the order of ``latents`` is the driver's own layout
+        self._fused = HierGLMReparamSVI(X, y, g, J, link="logistic", n_total=plan.scale * N, n_samples=self.S,
+                                        seed=self.seed, lr=self.lr, prior_precision=1.0, a0=plan.a0, b0=plan.b0,
+                                        ctx=self.backend.ctx, lam0=self._lam)
+        self._fused_D = D
+        self._fused_hier = True
+        self.route = "fused: bsc_glm_data_pass_groups + bsc_glm_hier_update (logistic link)"
+        return None
+
     def _glm_vectors_outside_envelope(self, plan):
         """None, or why the pass would refuse the offset / the row weights of a recognised GLM (float32, [N],
         contiguous: what it asks of y)."""
@@ -438,7 +487,8 @@ class ReparamVI(object):
 
     def _from_fused(self, v):
         v = v.cpu().numpy()
-        return v if self.guide == "full" or getattr(self, "_fused_glm", False) else self._from_blr_layout(v)
+        own = self.guide == "full" or getattr(self, "_fused_glm", False) or getattr(self, "_fused_hier", False)
+        return v if own else self._from_blr_layout(v)
 
     @property
     def lam(self):
@@ -471,7 +521,11 @@ class ReparamVI(object):
     def elbo(self):
         """Monte-Carlo ELBO estimate of the last step (fused route: reads the device scalar, synchronises)."""
         if self._fused is not None:
-            return float(self._fused.elbo.item()) if self._fused.t else None
+            if not self._fused.t:
+                return None
+            if getattr(self, "_fused_hier", False):      # the constant the recognised log-joint carries past the closed form
+                return float(self._fused.elbo.item()) + self.plan.offset
+            return float(self._fused.elbo.item())
         if getattr(self, "_resident", None) is not None:
             e = self._resident["elbo"]
             return None if e is None else float(e.reshape(-1)[0].item())
@@ -496,6 +550,9 @@ class ReparamVI(object):
 
     def set_data(self, **arrays):
         """Replace data inputs (the next mini-batch; write the data term times N / B)."""
+        if getattr(self, "_fused_hier", False):         # (before anything is touched: the engine stays as it was)
+            raise NotImplementedError("set_data on the random-intercept route: build a new engine for another mini-batch "
+                                      "(the one-hot group matrix is converted to an index vector at construction)")
         for name in arrays:
             if name not in self._types or name in {v.name for v, _ in self.latents}:
                 raise TypeError("%s is not a data input of the log-joint" % name)

@@ -427,6 +427,71 @@ int bsc_glm_pass_update_obs(bsc_ctx* ctx, int32_t link, const float* X, int64_t 
                             double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
                             float* W_next, double* elbo, double* grad);
 
+/* ---- random-intercept logistic / Poisson regression on the same pass (csrc/bsc_glm_group.hip) ---------------------
+ *
+ *      y_n ~ Bernoulli(sigmoid(l_n)) or Poisson(exp(l_n)),   l[n,s] = sum_d X[n,d] W[s,d] + b_s[g[n]] + o[n]
+ *      w ~ N(0, I / prior_precision),   b_j | zeta ~ N(0, e^{-zeta}),   tau = e^{zeta} ~ Gamma(a0, b0)
+ * with g[n] in [0, J) the row's group.  The latent is z = [w (D) | b (J) | zeta], P = D + J + 1, the guide mean-field:
+ * lam = [m (P) | rho (P)].  From the data one update needs, per draw s,
+ *      ell[s]  = sum_n v[n] ( y[n] l[n,s] - A(l[n,s]) )
+ *      G[s,d]  = sum_n r[n,s] X[n,d]                         r[n,s] = v[n] ( y[n] - A'(l[n,s]) )
+ *      H[s,j]  = sum_{n : g[n] = j} r[n,s]
+ * offset and weight are bsc_glm_data_pass_obs's (each may be NULL; a row with v[n] = 0 adds exactly nothing).
+ *
+ * The group plan.  H is a scatter; it is summed without float atomics in an order the PLAN fixes: the rows in stable
+ * order by group (ascending row within a group), each group's run cut into segments of at most BSC_GLM_GROUP_SEG_ROWS
+ * rows, a (start, length, group) table and every group's range of segments -- an opaque int32 array of
+ * bsc_glm_group_plan_size(B, J) entries (-1: B or J outside the plan's range).  bsc_glm_group_plan builds it from
+ * device g[B] into device memory: g is copied down, counting-sorted on the host and the plan copied up, so the call is
+ * SYNCHRONOUS like bsc_malloc -- call it when a batch is set, never inside an update.  It is the one place ids are
+ * range-checked: an id outside [0, J) is refused with the first offending row named.  *n_segments (may be NULL)
+ * receives the segment count.  bsc_glm_group_plan_host is its core on host pointers (no device, no context). */
+#define BSC_GLM_GROUP_SEG_ROWS 512
+#define BSC_GLM_GROUP_MAX_J 65536
+#define BSC_GLM_GROUP_MAX_ROWS ((int64_t)1 << 30)
+int64_t bsc_glm_group_plan_size(int64_t B, int32_t J);
+int bsc_glm_group_plan_host(const int32_t* g, int64_t B, int32_t J, int32_t* plan, int32_t* n_segments);
+int bsc_glm_group_plan(bsc_ctx* ctx, const int32_t* g, int64_t B, int32_t J, int32_t* plan, int32_t* n_segments);
+
+/* The pass.  Bz holds the intercept draws in float32 as [ceil(S / 8)][J][8] -- chunk of eight draws, group, draw slot;
+ * unused slots are zero -- so that one launch (eight draws) gathers Bz[chunk][g[n]][slot] through a descriptor of
+ * exactly J * 32 bytes: no id can read outside the table.  Outputs float64: ell [S], G [S, D], H [S, J]; a group
+ * without rows gets exactly 0.  Per chunk of eight draws: the pass kernel (it also leaves every residual in the
+ * workspace, 32 bytes per row), the float64 slab reduction, one wave per plan segment summing its rows' residuals in
+ * float64, and the groups' segments added in segment order.  Every order of summation depends on the plan alone:
+ * results are reproducible bit for bit.  With Bz = 0, ell and G are bit-identical to bsc_glm_data_pass_obs on the same
+ * inputs.
+ * The envelope is bsc_glm_data_pass_obs's, and 1 <= J <= BSC_GLM_GROUP_MAX_J, B <= BSC_GLM_GROUP_MAX_ROWS; g int32,
+ * contiguous; plan the one built for this g, B and J (a plan whose header names another B or J is not read: H comes
+ * back NaN).  The 16-row MFMA kernel (D == 256) is taken when y, g and the set ones of offset and weight are 16-byte
+ * aligned, else the 8-row kernel.  The workspace (bsc_glm_group_workspace_bytes(ctx, B, J): slab, residuals, segment
+ * sums) grows on demand -- synchronously; bsc_ctx_reserve it first to keep updates asynchronous. */
+int64_t bsc_glm_group_workspace_bytes(bsc_ctx* ctx, int64_t B, int32_t J);
+int bsc_glm_data_pass_groups(bsc_ctx* ctx, int32_t link, const float* X, int64_t ldx, const float* y,
+                             const float* offset, const float* weight, const int32_t* g, const int32_t* plan, int64_t B,
+                             int32_t D, int32_t J, const float* W, const float* Bz, int32_t S, double* ell, double* G,
+                             double* H);
+
+/* The finish, two launches.  stats = [ell (S) | G (S*D) | H (S*J)] as the pass and the all-reduce leave them (NULL is
+ * refused); eps in bsc_blr_noise's [S, (P-1)+1] layout (the last column is zeta's noise); W [S, D] and Bz (the layout
+ * above) the float32-rounded draws the pass read; zeta_s = m_zeta + e^{rho_zeta} eps_s,P-1 in float64:
+ *     g_w    = scale G_s - prior_precision w_s
+ *     g_b    = scale H_s - e^{zeta_s} b_s
+ *     g_zeta = J/2 + a0 - e^{zeta_s} (b0 + 1/2 sum_j b_sj^2)
+ *     ELBO   = mean_s [scale ell_s + log p(z_s)] + sum rho + P/2 (1 + log 2 pi)
+ *     d/d m  = mean_s g_s,     d/d rho_i = mean_s g_si eps_si e^{rho_i} + 1
+ * (log p(z) with every normaliser: at prior_precision = 1 it is the log-prior of the score-function route,
+ * bsc_logreg_bbvi_*), then Adam ascent step t (bsc_adam_ascent's form; lam_in is not modified, m1 and m2 in place)
+ * and, when the *_next buffers are set (all or none), W_next [S, D] and Bz_next (chunked, unused slots zeroed) from
+ * eps_next; eps_next_ready = 0 draws the noise of next_step into eps_next first.  lam_in != lam_out; the *_next buffers
+ * must not alias the current ones.  Requires 1 <= S <= 64, 1 <= J <= BSC_GLM_GROUP_MAX_J, t >= 1 and
+ * prior_precision, a0, b0, scale > 0.  Fixed-order sums, no atomics. */
+int bsc_glm_hier_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                        double* m2, const double* eps, const float* W, const float* Bz, int32_t D, int32_t J, int32_t S,
+                        double scale, double prior_precision, double a0, double b0, int64_t t, double lr, double beta1,
+                        double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
+                        int32_t eps_next_ready, float* W_next, float* Bz_next, double* elbo, double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
