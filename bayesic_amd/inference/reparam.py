@@ -67,6 +67,7 @@ device, ``step()`` is asynchronous and returns None, ``elbo`` / ``grad`` / ``lam
 the draws are ``bsc_blr_noise``'s (Philox streams 0 and 1, as ``oracle.svi.blr_sample``) -- with the
 same seed the update equals ``oracle.svi.blr_step``.
 """
+import collections
 import math
 
 import numpy as np
@@ -74,6 +75,14 @@ import numpy as np
 from ..algebra.autodiff import value_and_grad
 
 _LOG_2PI = math.log(2.0 * math.pi)
+
+# What the engine has to know about the driver behind ``_fused`` (one record per route; the default is every route
+# without a driver): whether lam and grad are already in the engine's layout, the constant the recognised log-joint
+# carries past the driver's ELBO, why set_data is refused (None: it is not), the names of the data inputs read as offset
+# and row weights, whether there is a predict() to hand over to and whether it takes offset= and weights=.
+_Route = collections.namedtuple("_Route", "own_layout elbo_offset set_data_refusal offset weights predict predict_obs")
+_NO_DRIVER = _Route(own_layout=True, elbo_offset=0.0, set_data_refusal=None, offset=None, weights=None, predict=False,
+                    predict_obs=False)
 
 
 def _outside_pass_envelope(X, y, D, S):
@@ -144,12 +153,13 @@ class ReparamVI(object):
         if guide not in ("diag", "full"):
             raise ValueError("guide must be 'diag' or 'full', got %r" % (guide,))
         self.guide = guide
-        self._fused = None
+        self._fused, self._fused_info = None, _NO_DRIVER
         P = self.P
         if guide == "full":
+            from ..svi._reparam_base import diag_slots, full_size
             self._tril = np.tril_indices(P)                 # the packed order: row-major lower triangle
-            self._diag_slots = P + np.arange(P) * (np.arange(P) + 1) // 2 + np.arange(P)
-            self._lam = np.zeros(P + P * (P + 1) // 2)
+            self._diag_slots = diag_slots(P)
+            self._lam = np.zeros(full_size(P))
             if lam0 is None:
                 self._lam[self._diag_slots] = math.log(0.05)
         else:
@@ -384,12 +394,12 @@ class ReparamVI(object):
             # [mu | packed L] over [w | xi]: the latents' order IS svi/blr.py's full layout
             self._fused = BLRReparamSVI(X, y, n_samples=self.S, seed=self.seed, lr=self.lr, ctx=self.backend.ctx,
                                         lam0=self._lam, family=(c0, c_xi, s_q, k_w, beta), covariance="full")
-            self._fused_D = D
+            self._fused_info = _NO_DRIVER._replace(predict=True)
             self.route = "fused: bsc_blr_data_pass + bsc_blr_fullrank_update"
             return None
         self._fused = BLRReparamSVI(X, y, n_samples=self.S, seed=self.seed, lr=self.lr, ctx=self.backend.ctx,
                                     lam0=self._to_blr_layout(self._lam), family=(c0, c_xi, s_q, k_w, beta))
-        self._fused_D = D
+        self._fused_info = _NO_DRIVER._replace(own_layout=False, predict=True)
         self.route = "fused: bsc_blr_data_pass + bsc_blr_fused_update_general"
         return None
 
@@ -413,8 +423,7 @@ class ReparamVI(object):
                                     lam0=self._lam, covariance=self.guide,
                                     offset=self._data[plan.offset] if plan.offset else None,
                                     weights=self._data[plan.weights] if plan.weights else None)
-        self._fused_D = D
-        self._fused_glm = True
+        self._fused_info = _NO_DRIVER._replace(offset=plan.offset, weights=plan.weights, predict=True, predict_obs=True)
         finish = "bsc_glm_fullrank_update" if self.guide == "full" else "bsc_glm_update"
         self.route = "fused: bsc_glm_data_pass + %s (%s link)" % (finish, plan.link)
         return None
@@ -449,8 +458,11 @@ class ReparamVI(object):
         self._fused = HierGLMReparamSVI(X, y, g, J, link="logistic", n_total=plan.scale * N, n_samples=self.S,
                                         seed=self.seed, lr=self.lr, prior_precision=1.0, a0=plan.a0, b0=plan.b0,
                                         ctx=self.backend.ctx, lam0=self._lam)
-        self._fused_D = D
-        self._fused_hier = True
+        # (predict: the driver's own refusal says what is missing)
+        self._fused_info = _NO_DRIVER._replace(
+            elbo_offset=plan.offset, predict=True,
+            set_data_refusal="set_data on the random-intercept route: build a new engine for another mini-batch (the "
+                             "one-hot group matrix is converted to an index vector at construction)")
         self.route = "fused: bsc_glm_data_pass_groups + bsc_glm_hier_update (logistic link)"
         return None
 
@@ -487,8 +499,7 @@ class ReparamVI(object):
 
     def _from_fused(self, v):
         v = v.cpu().numpy()
-        own = self.guide == "full" or getattr(self, "_fused_glm", False) or getattr(self, "_fused_hier", False)
-        return v if own else self._from_blr_layout(v)
+        return v if self._fused_info.own_layout else self._from_blr_layout(v)
 
     @property
     def lam(self):
@@ -523,9 +534,7 @@ class ReparamVI(object):
         if self._fused is not None:
             if not self._fused.t:
                 return None
-            if getattr(self, "_fused_hier", False):      # the constant the recognised log-joint carries past the closed form
-                return float(self._fused.elbo.item()) + self.plan.offset
-            return float(self._fused.elbo.item())
+            return float(self._fused.elbo.item()) + self._fused_info.elbo_offset
         if getattr(self, "_resident", None) is not None:
             e = self._resident["elbo"]
             return None if e is None else float(e.reshape(-1)[0].item())
@@ -550,9 +559,9 @@ class ReparamVI(object):
 
     def set_data(self, **arrays):
         """Replace data inputs (the next mini-batch; write the data term times N / B)."""
-        if getattr(self, "_fused_hier", False):         # (before anything is touched: the engine stays as it was)
-            raise NotImplementedError("set_data on the random-intercept route: build a new engine for another mini-batch "
-                                      "(the one-hot group matrix is converted to an index vector at construction)")
+        route = self._fused_info
+        if route.set_data_refusal:          # (before anything is touched: the engine stays as it was)
+            raise NotImplementedError(route.set_data_refusal)
         for name in arrays:
             if name not in self._types or name in {v.name for v, _ in self.latents}:
                 raise TypeError("%s is not a data input of the log-joint" % name)
@@ -570,7 +579,7 @@ class ReparamVI(object):
                                  "the recognised coefficients); build a new engine for another batch size"
                                  % (("fused" if self._fused is not None else "pass",) + self._planned_shape))
             why = _outside_pass_envelope(X, y, self._planned_shape[1], self.S)
-            glm_obs = getattr(self, "_fused_glm", False) and (self.plan.offset or self.plan.weights)
+            glm_obs = route.offset or route.weights
             if why is None and glm_obs:
                 why = self._glm_vectors_outside_envelope(self.plan)
             if why is not None:
@@ -578,8 +587,8 @@ class ReparamVI(object):
                     self._data[name] = value
                 raise ValueError("set_data: " + why)
             if glm_obs:
-                self._fused.set_batch(X, y, offset=self._data[self.plan.offset] if self.plan.offset else None,
-                                      weights=self._data[self.plan.weights] if self.plan.weights else None)
+                self._fused.set_batch(X, y, offset=self._data[route.offset] if route.offset else None,
+                                      weights=self._data[route.weights] if route.weights else None)
             elif self._fused is not None:
                 self._fused.set_batch(X, y)
 
@@ -715,12 +724,12 @@ class ReparamVI(object):
         """Posterior predictive for new rows (svi/predict.py): on a fused regression route the driver's own
         ``predict``; every other route has no likelihood the engine could name, and refuses.  ``offset`` /
         ``weights``: for the new rows, on the fused GLM route (a model with an offset needs one to predict)."""
-        if self._fused is None or not self.route.startswith(("fused: bsc_blr", "fused: bsc_glm")):
+        if not self._fused_info.predict:
             raise NotImplementedError("predict needs a fused regression route (fused: bsc_blr... / bsc_glm...); this "
                                       "engine runs on route %r" % (self.route,))
         if offset is None and weights is None:
             return self._fused.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
-        if not getattr(self, "_fused_glm", False):
+        if not self._fused_info.predict_obs:
             raise ValueError("predict: offset and weights belong to the fused GLM route; this engine runs on route %r"
                              % (self.route,))
         return self._fused.predict(X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, weights=weights)

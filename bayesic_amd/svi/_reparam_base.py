@@ -1,16 +1,19 @@
-"""What the reparameterised regression drivers (svi/glm.py, svi/softmax.py, svi/blr.py) share.
+"""What the reparameterised regression drivers (svi/blr.py, svi/glm.py, svi/softmax.py, svi/hier_glm.py) share.
 
 A Gaussian guide over P flattened parameters: ``covariance="diag"`` lam = [m (P) | rho (P)], ``"full"`` lam =
 [mu (P) | L packed row-major, lower triangle incl. the diagonal, rho_i = log L_ii in the diagonal slots]
 (include/bayesic_hip.h, bsc_glm_fullrank_update).  lam and the draws are double-buffered (index t & 1 is current at the
 start of step t + 1) and the noise is drawn NOISE_BLOCK steps ahead by bsc_blr_noise into a ring of two blocks, in its
-[S, P + 1] layout (the last column belongs to BLR's scalar latent).
+[S, noise width + 1] layout (the last column belongs to a scalar latent: BLR's xi, the hierarchy's zeta).
 
-Two classes, not one: ``ReparamDriver`` is what all three drivers share (batch pointers, noise ring, views) and is all
-that BLRReparamSVI can take without bending -- it has a scalar latent, sweeps, shards and its own finishes;
-``ReparamRegressionBase`` adds the state, first draw, finish and host views of the two drivers whose finish is
-bsc_glm_update.  The module-level helpers are pure numpy; torch is imported where a method needs it, so that they can
-be used (and tested) without it.
+``ReparamDriver`` is what all four drivers are built on: the batch pointers and their checks, ONE state set-up
+(``_init_state``, told sizes and never who is calling), the noise ring, the host side of the first draw, the exchange
+and the default step() = sample once, data_pass -> all_reduce -> _finish.  A driver adds what is its own: BLR its
+scalar latent xi, sweeps, shards and finishes; the hierarchy Bz, the group plan and H; softmax its labels.
+``ReparamRegressionBase`` adds, for the two drivers whose P weights ARE the draws W and whose finish is bsc_glm_update
+(GLM, softmax), that finish and its host views.  ``first_draw`` is the one transform from noise to draws that the
+drivers' first step and svi/predict.py's predictive draws both use.  The module-level helpers are pure numpy; torch is
+imported where a function needs it, so that they can be used (and tested) without it.
 """
 import math
 
@@ -54,24 +57,79 @@ def default_lam0(P, covariance):
     return lam
 
 
+def first_draw(lam, eps, P, covariance):
+    """Noise eps [S, P] -> draws z [S, P] of the guide lam (host float64): z_s = m + e^rho eps_s of the mean-field
+    layout, z_s = mu + L eps_s of the full one.  The drivers' first step (every later draw comes out of a finish) and
+    the predictive draws of svi/predict.py; the callers slice, round to float32 and upload."""
+    if covariance == "full":
+        mu, L = unpack_full(lam, P)
+        return mu[None, :] + eps @ L.T
+    return lam[None, :P] + np.exp(lam[None, P:]) * eps
+
+
+def float_batch(ctx, X, y, need_y=True):
+    """X [B, D] and y [B] (``need_y=False``: or None) as float32 device tensors: the checks of a real-valued batch."""
+    import torch
+    X = X if isinstance(X, torch.Tensor) else ctx.to_device(X, torch.float32)
+    if need_y or y is not None:
+        y = y if isinstance(y, torch.Tensor) else ctx.to_device(y, torch.float32)
+    if X.dtype != torch.float32 or (y is not None and y.dtype != torch.float32):
+        raise TypeError("X and y must be float32")
+    if X.dim() != 2 or (y is not None and (y.dim() != 1 or X.shape[0] != y.shape[0])):
+        raise ValueError("X must be [B, D] and y [B]")
+    if X.stride(1) != 1:
+        raise ValueError("X must be row-major (unit stride along columns)")
+    return X, y
+
+
 class ReparamDriver:
-    """What all three drivers do alike: the batch pointers, the noise ring and the double-buffer views.  Wants
-    self.ctx, .D, .S, .seed, .t, ._lam, ._W and ._noise_dim (the parameter count bsc_blr_noise is called with)."""
+    """What all four drivers do alike.  A subclass checks its arguments, sets ctx, covariance_kind and the batch (X, y,
+    B, D, _Xarg, _yarg, _ldx: _float_batch for a real-valued response), calls _init_state and supplies data_pass() and
+    _finish(stats); sample() where its draws are more than W, step() where there is a shorter way than the default."""
     NOISE_BLOCK = 32
 
     def _float_batch(self, X, y):
-        """X [B, D] and y [B] as float32 device tensors (the constructor's checks for a real-valued response)."""
-        import torch
-        self.X = X if isinstance(X, torch.Tensor) else self.ctx.to_device(X, torch.float32)
-        self.y = y if isinstance(y, torch.Tensor) else self.ctx.to_device(y, torch.float32)
-        if self.X.dtype != torch.float32 or self.y.dtype != torch.float32:
-            raise TypeError("X and y must be float32")
-        if self.X.dim() != 2 or self.y.dim() != 1 or self.X.shape[0] != self.y.shape[0]:
-            raise ValueError("X must be [B, D] and y [B]")
-        if self.X.stride(1) != 1:
-            raise ValueError("X must be row-major (unit stride along columns)")
+        self.X, self.y = float_batch(self.ctx, X, y)
         self.B, self.D = self.X.shape
         self._Xarg, self._yarg, self._ldx = self.X, self.y, self.X.stride(0)
+
+    def _init_state(self, P, lam0, n_total, n_samples, seed, lr, group, reserve_bytes=0, noise_dim=None, w_cols=None,
+                    n_stats=None):
+        """Everything behind the argument checks: the exchange and the mini-batch scale, lam [2, n] of a guide over P
+        parameters (n = 2 P, or full_size(P)) started at ``lam0`` (None: default_lam0), the noise ring of
+        bsc_blr_noise(noise_dim), the draws W [2, S w_cols] (both widths default to P), the Adam moments, grad, elbo and
+        stats = [ell (S) | G (S w_cols)] (``n_stats``: longer than that).  ``reserve_bytes`` sizes the pass's
+        workspace once so that step() never allocates."""
+        import torch
+        from .exchange import Exchange
+        dev = self.ctx.device
+        self.P, self._noise_dim = P, P if noise_dim is None else noise_dim
+        self.S, self.seed, self.lr = int(n_samples), int(seed), float(lr)
+        self.group = group
+        self.exchange = Exchange(self.ctx, group)   # RCCL behind the C ABI when ctx has a communicator
+        self.world = self.exchange.world
+        # global mini-batch rows (all ranks); ranks may hold unequal blocks
+        self.batch_rows = self.exchange.global_count(self.B, dev)
+        self.n_total = float(n_total) if n_total is not None else self.batch_rows
+        S, f64 = self.S, torch.float64
+        w_cols = P if w_cols is None else w_cols
+        n_lam = full_size(P) if self.covariance_kind == "full" else 2 * P
+        # double-buffered state: index t & 1 is current at the start of step t + 1
+        self._lam = torch.zeros((2, n_lam), dtype=f64, device=dev)
+        self._lam[0].copy_(torch.as_tensor(default_lam0(P, self.covariance_kind) if lam0 is None else lam0, dtype=f64))
+        self._alloc_noise(dev)
+        self._W = torch.zeros((2, S * w_cols), dtype=torch.float32, device=dev)
+        self.m1 = torch.zeros(n_lam, dtype=f64, device=dev)
+        self.m2 = torch.zeros(n_lam, dtype=f64, device=dev)
+        self.grad = torch.zeros(n_lam, dtype=f64, device=dev)
+        self.elbo = torch.zeros(1, dtype=f64, device=dev)
+        self.stats = torch.zeros(S * (1 + w_cols) if n_stats is None else n_stats, dtype=f64, device=dev)
+        self.ell = self.stats[:S]
+        self.G = self.stats[S:S + S * w_cols]
+        self.t = 0
+        self._drawn = False
+        if reserve_bytes:
+            self.ctx.reserve(reserve_bytes)
 
     def set_batch(self, X, y, rows=None, ldx=None):
         """Point the next update at another device-resident mini-batch of the same width: torch tensors, or raw
@@ -93,10 +151,6 @@ class ReparamDriver:
         self.X = self.y = None
         self._Xarg, self._yarg = int(X), int(y)
         self._ldx, self.B = int(ldx if ldx is not None else self.D), int(rows)
-
-    def _unpack_full(self, lam):
-        """unpack_full at this guide's width (self._guide_dim)."""
-        return unpack_full(lam, self._guide_dim)
 
     def _alloc_noise(self, dev):
         import torch
@@ -130,70 +184,40 @@ class ReparamDriver:
     def eps(self):
         return self._eps[self.t % self._ring]
 
-
-class ReparamRegressionBase(ReparamDriver):
-    """Driver state, phases and host views for a model whose P weights have the prior N(0, I / prior_precision) and
-    whose data enter through stats = [ell (S) | G (S P)]: the finish is bsc_glm_update / bsc_glm_fullrank_update with
-    D := P.  A subclass checks its arguments (lam0's size among them), sets ctx, X, y, B, D, prior_precision and
-    covariance_kind, calls _init_state and supplies data_pass() and step()."""
-
-    def _init_state(self, P, n_total, n_samples, seed, lr, group, lam0, slab_bytes):
-        """Everything behind the argument checks.  ``slab_bytes`` sizes the pass's workspace once so that step()
-        never allocates."""
-        import torch
-        from .exchange import Exchange
-        dev = self.ctx.device
-        self.P = self._noise_dim = self._guide_dim = P
-        self.S = int(n_samples)
-        self.seed = int(seed)
-        self.lr = float(lr)
-        self.group = group
-        self.exchange = Exchange(self.ctx, group)   # RCCL behind the C ABI when ctx has a communicator
-        self.world = self.exchange.world
-        # global mini-batch rows (all ranks); ranks may hold unequal blocks
-        self.batch_rows = self.exchange.global_count(self.B, dev)
-        self.n_total = float(n_total) if n_total is not None else self.batch_rows
-        S, f64 = self.S, torch.float64
-        n_lam = full_size(P) if self.covariance_kind == "full" else 2 * P
-        # double-buffered state: index t & 1 is current at the start of step t + 1
-        self._lam = torch.zeros((2, n_lam), dtype=f64, device=dev)
-        self._lam[0].copy_(torch.as_tensor(default_lam0(P, self.covariance_kind) if lam0 is None else lam0, dtype=f64))
-        self._alloc_noise(dev)
-        self._W = torch.zeros((2, S * P), dtype=torch.float32, device=dev)
-        self.m1 = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.m2 = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.grad = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.elbo = torch.zeros(1, dtype=f64, device=dev)
-        self.stats = torch.zeros(S * (P + 1), dtype=f64, device=dev)  # [ell | G]
-        self.ell = self.stats[:S]
-        self.G = self.stats[S:]
-        self.t = 0
-        self._drawn = False
-        self.ctx.reserve(slab_bytes)
-
     @property
     def scale(self):
         return self.n_total / self.batch_rows
 
     # -- phases ------------------------------------------------------------------
-    def sample(self, step):
-        """The first draw w_s = m + e^rho eps_s (every later one comes out of the finish): once per model, in
-        float64 on the host from bsc_blr_noise's draws, rounded to float32 as the finish rounds."""
-        import torch
-        c, P, S = self.cur, self.P, self.S
+    def _first_draw(self, step):
+        """first_draw of the current lam from bsc_blr_noise's draws of `step`: host float64 z [S, P], once per model."""
         self._ensure_noise(step)
-        eps = self._eps[step % self._ring].cpu().numpy().reshape(S, P + 1)[:, :P]
-        lam = self._lam[c].cpu().numpy()
-        if self.covariance_kind == "full":      # w_s = mu + L eps_s
-            mu, L = unpack_full(lam, P)
-            W = (mu[None, :] + eps @ L.T).astype(np.float32)
-        else:
-            W = (lam[None, :P] + np.exp(lam[None, P:]) * eps).astype(np.float32)
-        self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(W).reshape(-1)))
-        self._drawn = True
+        eps = self._eps[step % self._ring].cpu().numpy().reshape(self.S, self._noise_dim + 1)[:, :self.P]
+        return first_draw(self._lam[self.cur].cpu().numpy(), eps, self.P, self.covariance_kind)
 
     def all_reduce(self):
         self.exchange.all_reduce(self.stats)
+
+    def step(self):
+        """One ELBO-gradient update; asynchronous on the context stream."""
+        if not self._drawn:
+            self.sample(self.t)  # Philox step index == number of completed updates
+        self.data_pass()
+        self.all_reduce()
+        self._finish(self.stats)
+
+
+class ReparamRegressionBase(ReparamDriver):
+    """The finish and the host views of a model whose P weights have the prior N(0, I / prior_precision), are the draws
+    W themselves, and meet the data through stats = [ell (S) | G (S P)]: bsc_glm_update / bsc_glm_fullrank_update with
+    D := P.  A subclass sets prior_precision besides what ReparamDriver asks."""
+
+    def sample(self, step):
+        """The first draw (first_draw), rounded to float32 as the finish rounds."""
+        import torch
+        W = self._first_draw(step).astype(np.float32)
+        self._W[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(W).reshape(-1)))
+        self._drawn = True
 
     def _tail(self, t):
         """The arguments the finishing entry points share; t = Adam step count = Philox step of the NEXT draw."""

@@ -23,7 +23,9 @@ forward with non-temporal loads.
 
 One update is two launches on one GPU -- the streaming data pass and a fused
 finish (float64 reduction of the pass partials, ELBO + pathwise gradient, Adam
-step, next step's Philox draws) -- with lam and the draws double-buffered.
+step, next step's Philox draws) -- with lam and the draws double-buffered.  That state, the noise ring and the
+exchange are ReparamDriver's (svi/_reparam_base.py), as for the other reparameterised drivers; the scalar latent xi, the
+sweeps, the shards and the finishes are this driver's own.
 
 ``reproducible=True``: results are bit-identical on 1, 2, 4 and 8 GPUs.
 The global mini-batch is cut into V = 8 virtual shards of equal size; a rank runs one data pass
@@ -44,8 +46,7 @@ import math
 import torch
 
 from ..device import default_context
-from ._reparam_base import ReparamDriver, default_lam0, unpack_full
-from .exchange import Exchange
+from ._reparam_base import ReparamDriver, full_size, unpack_full
 
 # include/bayesic_hip.h: BSC_SWEEP_*
 SWEEP_STREAM, SWEEP_FORWARD_KEEP, SWEEP_BACKWARD_KEEP = 0, 1, 2
@@ -67,29 +68,32 @@ class BLRReparamSVI(ReparamDriver):
         if covariance not in ("diag", "full"):
             raise ValueError("covariance must be 'diag' or 'full', got %r" % (covariance,))
         self.covariance_kind = covariance
-        self.ctx = ctx or default_context()
-        dev = self.ctx.device
-        self._float_batch(X, y)
-        self.S = int(n_samples)
-        self.seed = int(seed)
-        self.lr = float(lr)
-        self.alpha0, self.beta0 = float(alpha0), float(beta0)
         self.family = None if family is None else tuple(float(v) for v in family)
         if self.family is not None and len(self.family) != 5:
             raise ValueError("family must be (c0, c_xi, s_q, k_w, beta)")
-        self.group = group
-        self.exchange = Exchange(self.ctx, group)   # RCCL behind the C ABI when ctx has a communicator
-        self.world = self.exchange.world
-        # global mini-batch rows (all ranks); ranks may hold unequal blocks
-        self.batch_rows = self.exchange.global_count(self.B, dev)
-        self.n_total = float(n_total) if n_total is not None else self.batch_rows
+        if sweep not in ("alternate", "stream"):
+            raise ValueError("sweep must be 'alternate' or 'stream'")
+        self.ctx = ctx or default_context()
+        self._float_batch(X, y)
+        D = self.D
+        if lam0 is None and covariance == "diag":       # lam = [m | rho | a | b]: every standard deviation 0.1
+            lam0 = torch.zeros(2 * D + 2, dtype=torch.float64)
+            lam0[D:2 * D] = lam0[2 * D + 1] = math.log(0.1)
+        elif lam0 is not None and covariance == "full" and torch.as_tensor(lam0).numel() != full_size(D + 1):
+            raise ValueError("lam0 has %d entries; covariance='full' at D = %d needs %d"
+                             % (torch.as_tensor(lam0).numel(), D, full_size(D + 1)))
+        # z = [w | xi]: W holds w and stats = [Q | G] its statistics; the slab is sized once so step() never allocates
+        self._init_state(D + 1, lam0, n_total, n_samples, seed, lr, group, noise_dim=D, w_cols=D,
+                         reserve_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 8) * 4)
+        dev, S = self.ctx.device, self.S
+        self.Q = self.ell
+        self._xi = torch.zeros((2, S), dtype=torch.float64, device=dev)
+        self.alpha0, self.beta0 = float(alpha0), float(beta0)
         self.fused = bool(fused)
         # one call per update (bsc_blr_pass_update: the pass, then the finish from its slab) where the library offers the
         # entry point; a test double without it, or one_launch = False, makes the two calls itself
         self.one_launch = hasattr(getattr(self.ctx, "lib", None), "bsc_blr_pass_update")
         self.reproducible = bool(reproducible)
-        if sweep not in ("alternate", "stream"):
-            raise ValueError("sweep must be 'alternate' or 'stream'")
         # "alternate": successive passes over the SAME resident mini-batch walk it forward, then
         # backward, ..., each leaving the rows it read last in the 256 MiB Infinity Cache for the
         # pass that starts there (include/bayesic_hip.h, bsc_blr_data_pass_sweep).  A batch that
@@ -110,40 +114,7 @@ class BLRReparamSVI(ReparamDriver):
                                  "(this rank: rows %d..%d)" % (self._shard_rows, first, first + self.B))
             self._first_shard = first // self._shard_rows
             self._n_shards = self.B // self._shard_rows
-        D, S = self.D, self.S
-        f64 = torch.float64
-        # double-buffered state: index t & 1 is current at the start of step t+1
-        P = D + 1
-        n_lam = P + P * (P + 1) // 2 if covariance == "full" else 2 * D + 2
-        self._lam = torch.zeros((2, n_lam), dtype=f64, device=dev)
-        if lam0 is None:
-            if covariance == "full":
-                self._lam[0].copy_(torch.as_tensor(default_lam0(P, "full"), dtype=f64))
-            else:
-                self._lam[0, D:2 * D] = math.log(0.1)
-                self._lam[0, 2 * D + 1] = math.log(0.1)
-        else:
-            lam0 = torch.as_tensor(lam0, dtype=f64)
-            if covariance == "full" and lam0.numel() != n_lam:
-                raise ValueError("lam0 has %d entries; covariance='full' at D = %d needs %d" % (lam0.numel(), D, n_lam))
-            self._lam[0].copy_(lam0)
-        self._noise_dim, self._guide_dim = D, D + 1
-        self._alloc_noise(dev)
-        self._W = torch.zeros((2, S * D), dtype=torch.float32, device=dev)
-        self._xi = torch.zeros((2, S), dtype=f64, device=dev)
-        self.m1 = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.m2 = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.grad = torch.zeros(n_lam, dtype=f64, device=dev)
-        self.elbo = torch.zeros(1, dtype=f64, device=dev)
-        self.stats = torch.zeros(S * (D + 1), dtype=f64, device=dev)  # [Q | G]
-        if self.reproducible:
-            self._vstats = torch.zeros((self.VIRTUAL_SHARDS, S * (D + 1)), dtype=f64, device=dev)
-        self.Q = self.stats[:S]
-        self.G = self.stats[S:]
-        self.t = 0
-        self._drawn = False
-        # size the slab once so step() never allocates
-        self.ctx.reserve((4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 8) * 4)
+            self._vstats = torch.zeros((V, S * (D + 1)), dtype=torch.float64, device=dev)
 
     def set_batch(self, X, y, rows=None, ldx=None):
         super().set_batch(X, y, rows, ldx)
@@ -196,14 +167,10 @@ class BLRReparamSVI(ReparamDriver):
         self._drawn = True
 
     def _sample_full(self, step):
-        """The first draw z_s = mu + L eps_s of the full guide (every later one comes out of the finish): once per
-        model, in float64 on the host from bsc_blr_noise's draws."""
+        """The first draw (first_draw) of the full guide over z = [w | xi]: w rounded to float32, xi kept float64."""
         import numpy as np
-        c, D, S = self.cur, self.D, self.S
-        self._ensure_noise(step)
-        eps = self._eps[step % self._ring].cpu().numpy().reshape(S, D + 1)
-        m, L = unpack_full(self._lam[c].cpu().numpy(), D + 1)
-        z = m[None, :] + eps @ L.T
+        c, D = self.cur, self.D
+        z = self._first_draw(step)
         self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :D], np.float32).reshape(-1)))
         self._xi[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, D])))
         self._drawn = True
@@ -229,8 +196,7 @@ class BLRReparamSVI(ReparamDriver):
 
     def all_reduce(self):
         if not self.reproducible:
-            self.exchange.all_reduce(self.stats)
-            return
+            return super().all_reduce()
         import ctypes
         self.exchange.all_reduce(self._vstats)          # every row is non-zero on one rank only: exact
         V, n = self._vstats.shape

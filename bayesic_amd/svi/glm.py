@@ -27,7 +27,9 @@ ell_s and G_s times v_n >= 0 (include/bayesic_hip.h, bsc_glm_data_pass_obs; csrc
 the Poisson rate model's log E[y_n] = x_n . w + log exposure_n, kept as o = log(exposure).  Weights are part of the
 likelihood (trials of aggregated binomial rows with y = k / n, survey weights, a mask of zeros) and do not enter the
 mini-batch scale n_total / batch_rows.  A model built without them, and handed batches without them, calls the entry
-points it always has.
+points it always has.  The argument checks and the checked vectors of a batch are svi/_obs.py's, shared with
+svi/hier_glm.py and svi/predict.py; the driver state, the first draw and the pass -> all-reduce -> finish step are
+svi/_reparam_base.py's.
 
 Data parallelism is wired as in svi/blr.py: each rank holds a block of mini-batch rows, and the one exchange per
 update is an all-reduce(sum) of the float64 vector [ell (S) | G (S*D)] between the pass and the finish.  That branch
@@ -36,40 +38,11 @@ update is an all-reduce(sum) of the float64 vector [ell (S) | G (S*D)] between t
 import torch
 
 from ..device import default_context
+from ._obs import LINKS, ObsBatch, batch_obs, check_link
 from ._reparam_base import ReparamRegressionBase, full_size
 
-# include/bayesic_hip.h: BSC_GLM_*
-LINKS = {"logistic": 0, "poisson": 1}
 
-
-def obs_vector(ctx, name, v, rows, log=False):
-    """``v`` (offset, weights or exposure; a tensor or a host array) as a float32 [rows] contiguous device tensor,
-    checked like y, or None; ``log``: an exposure, returned as its logarithm (computed once, on the device)."""
-    if v is None:
-        return None
-    if not isinstance(v, torch.Tensor):
-        v = ctx.to_device(v, torch.float32)
-    if v.dtype != torch.float32:
-        raise TypeError("%s must be float32" % name)
-    if v.dim() != 1 or v.shape[0] != rows:
-        raise ValueError("%s must be [%d], one entry per row of X" % (name, rows))
-    if rows > 1 and v.stride(0) != 1:
-        raise ValueError("%s must be contiguous" % name)
-    if log:
-        if not bool((v > 0).all() & torch.isfinite(v).all()):
-            raise ValueError("exposure must be finite and strictly positive")
-        v = torch.log(v)
-    return v
-
-
-def checked_weights(v):
-    """The weights' check, finite and >= 0: one synchronisation, so it sits outside step()."""
-    if v is not None and not bool((torch.isfinite(v) & (v >= 0)).all()):
-        raise ValueError("weights must be finite and >= 0")
-    return v
-
-
-class GLMReparamSVI(ReparamRegressionBase):
+class GLMReparamSVI(ObsBatch, ReparamRegressionBase):
     def __init__(self, X, y, link="logistic", n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0,
                  ctx=None, group=None, lam0=None, covariance="diag", *, offset=None, weights=None, exposure=None):
         """``covariance``: "diag" (the mean-field guide, default) or "full" (module docstring; ``lam0`` then in the
@@ -79,18 +52,11 @@ class GLMReparamSVI(ReparamRegressionBase):
         if covariance not in ("diag", "full"):
             raise ValueError("covariance must be 'diag' or 'full', got %r" % (covariance,))
         self.covariance_kind = covariance
-        if link not in LINKS:
-            raise ValueError("link must be 'logistic' or 'poisson', got %r" % (link,))
+        check_link(link, offset, exposure)
         self.link, self._link = link, LINKS[link]
-        if exposure is not None and link != "poisson":
-            raise ValueError("exposure belongs to the Poisson rate model; link=%r takes offset=" % (link,))
-        if exposure is not None and offset is not None:
-            raise ValueError("exposure and offset are mutually exclusive (exposure is stored as offset = log(exposure))")
         self.ctx = ctx or default_context()
         self._float_batch(X, y)
-        self._set_obs(obs_vector(self.ctx, "exposure" if offset is None else "offset",
-                                 exposure if offset is None else offset, self.B, log=offset is None),
-                      checked_weights(obs_vector(self.ctx, "weights", weights, self.B)))
+        self._set_obs(*batch_obs(self.ctx, self.B, offset, weights, exposure))
         self.has_offset = self._oarg is not None      # predict() refuses to run without one
         self.prior_precision = float(prior_precision)
         if not self.prior_precision > 0.0:
@@ -99,23 +65,14 @@ class GLMReparamSVI(ReparamRegressionBase):
         if lam0 is not None and covariance == "full" and torch.as_tensor(lam0).numel() != full_size(D):
             raise ValueError("lam0 has %d entries; covariance='full' at D = %d needs %d"
                              % (torch.as_tensor(lam0).numel(), D, full_size(D)))
-        self._init_state(D, n_total, n_samples, seed, lr, group, lam0,
-                         slab_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 8) * 4)
-
-    # -- offsets and weights ----------------------------------------------------
-    def _set_obs(self, offset, weights):
-        """Tensors, raw device pointers or None."""
-        tensor = lambda v: v if isinstance(v, torch.Tensor) else None
-        self.offset, self.weights = tensor(offset), tensor(weights)
-        self._oarg = offset if offset is None or isinstance(offset, torch.Tensor) else int(offset)
-        self._varg = weights if weights is None or isinstance(weights, torch.Tensor) else int(weights)
+        self._init_state(D, lam0, n_total, n_samples, seed, lr, group,
+                         reserve_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 8) * 4)
 
     def set_batch(self, X, y, rows=None, ldx=None, offset=None, weights=None):
         """ReparamDriver.set_batch with the batch's offset and weights: tensors (weights checked: finite, >= 0) with
         tensor X and y, raw device pointers (unchecked) with raw ones.  None drops the vector for this batch."""
         if isinstance(X, torch.Tensor):
-            offset = obs_vector(self.ctx, "offset", offset, X.shape[0])
-            weights = checked_weights(obs_vector(self.ctx, "weights", weights, X.shape[0]))
+            offset, weights = batch_obs(self.ctx, X.shape[0], offset, weights)
         super().set_batch(X, y, rows=rows, ldx=ldx)
         self._set_obs(offset, weights)
 
@@ -143,14 +100,12 @@ class GLMReparamSVI(ReparamRegressionBase):
 
     def step(self):
         """One ELBO-gradient update; asynchronous on the context stream."""
-        if not self._drawn:
-            self.sample(self.t)  # Philox step index == number of completed updates
         if self.world == 1 and not self.exchange.rccl and self.S <= 8 and self.covariance_kind == "diag":
-            self._pass_update()
+            if not self._drawn:
+                self.sample(self.t)  # Philox step index == number of completed updates
+            self._pass_update()     # the pass and the finish in one call
         else:
-            self.data_pass()
-            self.all_reduce()
-            self._finish(self.stats)
+            super().step()
 
     # -- posterior predictive (svi/predict.py: one bsc_predict_pass over X for all draws) --------
     def predict(self, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):

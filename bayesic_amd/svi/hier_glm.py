@@ -15,7 +15,8 @@ PLAN (bsc_glm_group_plan) -- built when a batch is set, never inside step(): the
 place the ids are range-checked.  step() = pass -> all-reduce of [ell | G | H] -> bsc_glm_hier_update (ELBO, gradient,
 Adam, next draws).  lam and the draws (W [S, D] and Bz, the intercepts in the pass's [ceil(S / 8)][J][8] layout) are
 double-buffered; the noise comes a block ahead from bsc_blr_noise with D + J stream-0 columns and zeta's in the last
-one; the first draw is made on the host.  Offsets, exposure and row weights are svi/glm.py's.
+one; the first draw is made on the host.  The state, the first draw and step() are ReparamDriver's
+(svi/_reparam_base.py); offsets, exposure and row weights are svi/glm.py's (svi/_obs.py).
 
 Limits, by design of this version: the guide is mean-field (``covariance="full"`` is refused: P = D + J + 1 is past the
 full finish's 256 columns), and there is no predict() / heldout_lpd(): the predictive needs a per-draw, per-group
@@ -26,9 +27,9 @@ import ctypes
 
 import numpy as np
 
-from ._reparam_base import ReparamDriver, default_lam0
+from ._obs import LINKS, ObsBatch, batch_obs, check_link
+from ._reparam_base import ReparamDriver
 
-LINKS = {"logistic": 0, "poisson": 1}
 MAX_GROUPS = 65536          # include/bayesic_hip.h: BSC_GLM_GROUP_MAX_J
 
 
@@ -37,12 +38,7 @@ def check_arguments(link, n_groups, prior_precision, a0, b0, covariance, offset,
     if covariance != "diag":
         raise ValueError("covariance=%r: HierGLMReparamSVI has the mean-field guide only (covariance='diag'); the "
                          "full-covariance finish stops at 256 columns and P = D + J + 1 is past it" % (covariance,))
-    if link not in LINKS:
-        raise ValueError("link must be 'logistic' or 'poisson', got %r" % (link,))
-    if exposure is not None and link != "poisson":
-        raise ValueError("exposure belongs to the Poisson rate model; link=%r takes offset=" % (link,))
-    if exposure is not None and offset is not None:
-        raise ValueError("exposure and offset are mutually exclusive (exposure is stored as offset = log(exposure))")
+    check_link(link, offset, exposure)
     if int(n_groups) != n_groups or not 1 <= int(n_groups) <= MAX_GROUPS:
         raise ValueError("n_groups must be an integer in [1, %d], got %r" % (MAX_GROUPS, n_groups))
     if not float(prior_precision) > 0.0:
@@ -51,7 +47,7 @@ def check_arguments(link, n_groups, prior_precision, a0, b0, covariance, offset,
         raise ValueError("a0 and b0 (the Gamma prior of the intercepts' precision) must be positive")
 
 
-class HierGLMReparamSVI(ReparamDriver):
+class HierGLMReparamSVI(ObsBatch, ReparamDriver):
     def __init__(self, X, y, groups, n_groups, link="logistic", n_total=None, n_samples=8, seed=1234, lr=1e-2,
                  prior_precision=1.0, a0=1.0, b0=1.0, offset=None, weights=None, exposure=None, ctx=None, group=None,
                  lam0=None, covariance="diag"):
@@ -60,61 +56,29 @@ class HierGLMReparamSVI(ReparamDriver):
         check_arguments(link, n_groups, prior_precision, a0, b0, covariance, offset, exposure)
         if not 1 <= int(n_samples) <= 64:
             raise ValueError("n_samples must be in [1, 64]")
-        import torch
         from ..device import default_context
-        from .exchange import Exchange
-        from .glm import checked_weights, obs_vector
         self.link, self._link = link, LINKS[link]
         self.covariance_kind = "diag"
         self.J = int(n_groups)
         self.prior_precision, self.a0, self.b0 = float(prior_precision), float(a0), float(b0)
         self.ctx = ctx or default_context()
         self._float_batch(X, y)
-        self._set_obs(obs_vector(self.ctx, "exposure" if offset is None else "offset",
-                                 exposure if offset is None else offset, self.B, log=offset is None),
-                      checked_weights(obs_vector(self.ctx, "weights", weights, self.B)))
+        self._set_obs(*batch_obs(self.ctx, self.B, offset, weights, exposure))
         groups = self._checked_groups(groups, self.B)
         D, J, S = self.D, self.J, int(n_samples)
         P = D + J + 1
         if lam0 is not None and np.asarray(lam0).size != 2 * P:
             raise ValueError("lam0 has %d entries; [m | rho] over [w (%d) | b (%d) | zeta] needs %d"
                              % (np.asarray(lam0).size, D, J, 2 * P))
-        dev = self.ctx.device
-        self.P, self._guide_dim, self._noise_dim = P, P, D + J
-        self.S, self.seed, self.lr = S, int(seed), float(lr)
-        self.group = group
-        self.exchange = Exchange(self.ctx, group)
-        self.world = self.exchange.world
-        self.batch_rows = self.exchange.global_count(self.B, dev)
-        self.n_total = float(n_total) if n_total is not None else self.batch_rows
-        f64 = torch.float64
-        self._chunks = (S + 7) // 8
-        self._lam = torch.zeros((2, 2 * P), dtype=f64, device=dev)
-        self._lam[0].copy_(torch.as_tensor(default_lam0(P, "diag") if lam0 is None else np.asarray(lam0), dtype=f64))
-        self._alloc_noise(dev)
-        self._W = torch.zeros((2, S * D), dtype=torch.float32, device=dev)
-        self._Bz = torch.zeros((2, self._chunks * J * 8), dtype=torch.float32, device=dev)
-        self.m1 = torch.zeros(2 * P, dtype=f64, device=dev)
-        self.m2 = torch.zeros(2 * P, dtype=f64, device=dev)
-        self.grad = torch.zeros(2 * P, dtype=f64, device=dev)
-        self.elbo = torch.zeros(1, dtype=f64, device=dev)
-        self.stats = torch.zeros(S * (1 + D + J), dtype=f64, device=dev)     # [ell | G | H]
-        self.ell = self.stats[:S]
-        self.G = self.stats[S:S + S * D]
+        import torch
+        # stats = [ell | G | H]; the pass's workspace is reserved with the plan (_build_plan)
+        self._init_state(P, lam0, n_total, S, seed, lr, group, noise_dim=D + J, w_cols=D, n_stats=S * (1 + D + J))
         self.H = self.stats[S + S * D:]
-        self.t = 0
-        self._drawn = False
+        self._chunks = (S + 7) // 8
+        self._Bz = torch.zeros((2, self._chunks * J * 8), dtype=torch.float32, device=self.ctx.device)
         self._set_groups(groups)
 
     # -- the batch ----------------------------------------------------------------------------------------------
-    def _set_obs(self, offset, weights):
-        """Tensors, raw device pointers or None (svi/glm.py)."""
-        import torch
-        tensor = lambda v: v if isinstance(v, torch.Tensor) else None
-        self.offset, self.weights = tensor(offset), tensor(weights)
-        self._oarg = offset if offset is None or isinstance(offset, torch.Tensor) else int(offset)
-        self._varg = weights if weights is None or isinstance(weights, torch.Tensor) else int(weights)
-
     def _checked_groups(self, groups, B):
         """The ids of a batch of B rows: a tensor or a host array (checked like y, uploaded as int32), or a raw device
         pointer to B int32 (taken as it is)."""
@@ -155,13 +119,11 @@ class HierGLMReparamSVI(ReparamDriver):
         """ReparamDriver.set_batch with the batch's group ids (required: the plan is rebuilt here, one
         synchronisation) and its offset and weights as in GLMReparamSVI.set_batch."""
         import torch
-        from .glm import checked_weights, obs_vector
         if groups is None:
             raise ValueError("set_batch needs groups=: the ids of the new rows (the group plan is rebuilt)")
         if isinstance(X, torch.Tensor):
-            offset = obs_vector(self.ctx, "offset", offset, X.shape[0])
-            weights = checked_weights(obs_vector(self.ctx, "weights", weights, X.shape[0]))
             B = int(X.shape[0])
+            offset, weights = batch_obs(self.ctx, B, offset, weights)
         elif rows is None:
             raise ValueError("raw device pointers need `rows`")
         else:
@@ -171,10 +133,6 @@ class HierGLMReparamSVI(ReparamDriver):
         super().set_batch(X, y, rows=rows, ldx=ldx)
         self._set_obs(offset, weights)
         self._set_groups(garg, built)
-
-    @property
-    def scale(self):
-        return self.n_total / self.batch_rows
 
     @property
     def Bz(self):
@@ -190,14 +148,11 @@ class HierGLMReparamSVI(ReparamDriver):
         return out.reshape(-1)
 
     def sample(self, step):
-        """The first draw z_s = m + e^rho eps_s of w and b (every later one comes out of the finish): on the host in
-        float64 from bsc_blr_noise's draws, rounded to float32 as the finish rounds.  zeta is drawn where it is used."""
+        """The first draw (first_draw) of w and b, rounded to float32 as the finish rounds.  zeta is drawn where it is
+        used."""
         import torch
-        c, D, J, S, P = self.cur, self.D, self.J, self.S, self.P
-        self._ensure_noise(step)
-        eps = self._eps[step % self._ring].cpu().numpy().reshape(S, P)
-        lam = self._lam[c].cpu().numpy()
-        z = (lam[None, :P] + np.exp(lam[None, P:]) * eps).astype(np.float32)
+        c, D, J = self.cur, self.D, self.J
+        z = self._first_draw(step).astype(np.float32)
         self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :D]).reshape(-1)))
         self._Bz[c].copy_(torch.from_numpy(self.chunked(z[:, D:D + J])))
         self._drawn = True
@@ -205,9 +160,6 @@ class HierGLMReparamSVI(ReparamDriver):
     def data_pass(self):
         self.ctx.call("bsc_glm_data_pass_groups", self._link, self._Xarg, self._ldx, self._yarg, self._oarg, self._varg,
                       self._garg, self.plan, self.B, self.D, self.J, self.W, self.Bz, self.S, self.ell, self.G, self.H)
-
-    def all_reduce(self):
-        self.exchange.all_reduce(self.stats)
 
     def _finish(self, stats):
         """Gradient + Adam + next draws from all-reduced statistics; flips the double buffer."""
@@ -219,14 +171,6 @@ class HierGLMReparamSVI(ReparamDriver):
                       self.prior_precision, self.a0, self.b0, t, self.lr, 0.9, 0.999, 1e-8, self.seed, t,
                       self._eps[t % self._ring], 1, self._W[n], self._Bz[n], self.elbo, self.grad)
         self.t = t
-
-    def step(self):
-        """One ELBO-gradient update; asynchronous on the context stream."""
-        if not self._drawn:
-            self.sample(self.t)  # Philox step index == number of completed updates
-        self.data_pass()
-        self.all_reduce()
-        self._finish(self.stats)
 
     # -- what this version does not do ----------------------------------------------------------------------------
     def predict(self, *args, **kwargs):

@@ -8,11 +8,12 @@ float64 sum is the held-out score.
 Draws (``posterior_draws``): standard normals from bsc_philox_normal on Philox stream 2, step 0, counter and key
 as oracle/philox.py lays them out (its streams 0 and 1 belong to the training entry points: 0 = the weights and
 every draw of bsc_blr_noise, 1 = the scale latent of bsc_blr_sample), so predicting never repeats training noise.
-The transform is parameter-sized and runs once per call: float64 on the host, rounded to float32, as
-GLMReparamSVI.sample() does.
+The transform is parameter-sized and runs once per call: ``_reparam_base.first_draw``, the drivers' own first draw
+(float64 on the host), rounded to float32.
     GLMReparamSVI(covariance="diag")  eps [S, D]:      w = m + e^rho eps
     GLMReparamSVI(covariance="full")  eps [S, D]:      w = mu + L eps
     BLRReparamSVI(covariance="diag")  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  xi = a + e^b eps[:, D]
+                                      (lam = [m | rho | a | b] re-ordered to the mean-field layout over z = [w | xi])
     BLRReparamSVI(covariance="full")  eps [S, D + 1]:  z = mu + L eps over z = [w | xi]
     SoftmaxReparamSVI                 eps [S, K D]:    the two GLM transforms at width K D, W returned [S, K, D]
                                       (predict() below hands over to its predict(): bsc_softmax_predict_pass)
@@ -26,7 +27,8 @@ A model fitted with an offset refuses to predict without one.  ``weights`` leave
 import numpy as np
 import torch
 
-from ._reparam_base import unpack_full
+from ._obs import batch_obs, check_link
+from ._reparam_base import first_draw, float_batch
 
 # include/bayesic_hip.h: BSC_PREDICT_*
 FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
@@ -75,19 +77,11 @@ def posterior_draws(model, n_samples=64, seed=None):
     ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P, eps_d)
     eps = eps_d.cpu().numpy()
     lam = model.lam.cpu().numpy()
-    logvar = None
-    if family != "gaussian" and getattr(model, "covariance_kind", "diag") == "full":
-        mu, L = unpack_full(lam, P)
-        W = mu[None, :] + eps @ L.T
-    elif family != "gaussian":
-        W = lam[None, :D] + np.exp(lam[D:2 * D])[None, :] * eps
-    elif model.covariance_kind == "full":
-        mu, L = unpack_full(lam, P)
-        z = mu[None, :] + eps @ L.T
-        W, logvar = z[:, :D], z[:, D]
-    else:
-        W = lam[None, :D] + np.exp(lam[D:2 * D])[None, :] * eps[:, :D]
-        logvar = lam[2 * D] + np.exp(lam[2 * D + 1]) * eps[:, D]
+    kind = getattr(model, "covariance_kind", "diag")
+    if family == "gaussian" and kind == "diag":         # [m | rho | a | b] -> [m a | rho b] over z = [w | xi]
+        lam = np.concatenate([lam[:D], lam[2 * D:2 * D + 1], lam[D:2 * D], lam[2 * D + 1:]])
+    z = first_draw(lam, eps, P, kind)
+    W, logvar = (z[:, :D], z[:, D]) if family == "gaussian" else (z, None)
     if family == "softmax":
         W = W.reshape(S, model.n_classes, model.D)
     Wd = ctx.to_device(np.ascontiguousarray(W, np.float32))
@@ -97,16 +91,7 @@ def posterior_draws(model, n_samples=64, seed=None):
 
 def _data(model, X, y):
     """The drivers' own checks and messages for a batch (GLMReparamSVI.__init__)."""
-    ctx = model.ctx
-    X = X if isinstance(X, torch.Tensor) else ctx.to_device(X, torch.float32)
-    if y is not None:
-        y = y if isinstance(y, torch.Tensor) else ctx.to_device(y, torch.float32)
-    if X.dtype != torch.float32 or (y is not None and y.dtype != torch.float32):
-        raise TypeError("X and y must be float32")
-    if X.dim() != 2 or (y is not None and (y.dim() != 1 or X.shape[0] != y.shape[0])):
-        raise ValueError("X must be [B, D] and y [B]")
-    if X.stride(1) != 1:
-        raise ValueError("X must be row-major (unit stride along columns)")
+    X, y = float_batch(model.ctx, X, y, need_y=False)
     if X.shape[1] != model.D:
         raise ValueError("X has %d columns; the model was fitted at D = %d" % (X.shape[1], model.D))
     if y is not None and y.numel() > 1 and y.stride(0) != 1:
@@ -124,14 +109,8 @@ def _obs(model, family, B, offset, exposure, weights):
         return None, None
     if family not in ("logistic", "poisson"):
         raise ValueError("predict: offset, exposure and weights are for the logistic and Poisson models, not %s" % family)
-    if exposure is not None and family != "poisson":
-        raise ValueError("exposure belongs to the Poisson rate model; link=%r takes offset=" % (family,))
-    if exposure is not None and offset is not None:
-        raise ValueError("exposure and offset are mutually exclusive (exposure means offset = log(exposure))")
-    from .glm import checked_weights, obs_vector
-    o = obs_vector(model.ctx, "exposure" if offset is None else "offset", exposure if offset is None else offset, B,
-                   log=offset is None)
-    return o, checked_weights(obs_vector(model.ctx, "weights", weights, B))
+    check_link(family, offset, exposure, kept="means")
+    return batch_obs(model.ctx, B, offset, weights, exposure)
 
 
 def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):

@@ -14,7 +14,7 @@ the finish is svi/glm.py's -- bsc_glm_update with D := K D on stats = [ell (S) |
 hold for any model of the form "P Gaussian-prior weights, data through ell and G").  lam and the draws are
 double-buffered and the noise is drawn a block ahead by bsc_blr_noise(D := K D) in its [S, K D + 1] layout (Philox
 stream 0; the last column is not read), as in svi/glm.py.  There is no one-call slab route: every update is
-data_pass() -> all_reduce() -> finish.  An intercept is a column of ones in X.
+ReparamDriver's step(), data_pass() -> all_reduce() -> finish.  An intercept is a column of ones in X.
 
 Labels are int32.  A label outside [0, K) raises ValueError at construction and in set_batch(tensors) (one min/max,
 outside step()); raw-pointer batches are the caller's responsibility -- the pass skips such rows, it never uses a
@@ -100,8 +100,8 @@ class SoftmaxReparamSVI(ReparamRegressionBase):
         self.B, self.D = int(self.X.shape[0]), D
         self._Xarg, self._yarg, self._ldx = self.X, self.y, self.X.stride(0)
         # the slab is sized for two workgroups per CU at most
-        self._init_state(P, n_total, n_samples, seed, lr, group, lam0,
-                         slab_bytes=(2 * self.ctx.info()["cu_count"] + 8) * SLAB_FLOATS * 4)
+        self._init_state(P, lam0, n_total, n_samples, seed, lr, group,
+                         reserve_bytes=(2 * self.ctx.info()["cu_count"] + 8) * SLAB_FLOATS * 4)
 
     def set_batch(self, X, y, rows=None, ldx=None):
         """Point the next update at another device-resident mini-batch of the same width: torch tensors (the labels
@@ -123,14 +123,6 @@ class SoftmaxReparamSVI(ReparamRegressionBase):
     def data_pass(self):
         self.ctx.call("bsc_softmax_data_pass", self._Xarg, self._ldx, self._yarg, self.B, self.D, self.K, self.W,
                       self.S, self.ell, self.G)
-
-    def step(self):
-        """One ELBO-gradient update; asynchronous on the context stream."""
-        if not self._drawn:
-            self.sample(self.t)  # Philox step index == number of completed updates
-        self.data_pass()
-        self.all_reduce()
-        self._finish(self.stats)
 
     # -- posterior predictive (one bsc_softmax_predict_pass over X for all draws) --------
     def predict(self, X, y=None, n_samples=64, seed=None, draws=None):

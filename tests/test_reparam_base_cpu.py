@@ -1,6 +1,7 @@
 """The host helpers of bayesic_amd/svi/_reparam_base.py against the packing of tests/_glm_full_ref.py (numpy only):
 the full layout lam = [mu (P) | L packed row-major, lower triangle incl. the diagonal, rho_i in the diagonal slots] is
-what every full-covariance driver, the predictive draws and the finishes agree on."""
+what every full-covariance driver, the predictive draws and the finishes agree on; and first_draw, the one transform from
+noise to draws, against the two expressions the drivers and svi/predict.py wrote out before they shared it."""
 import importlib.util
 import math
 import os
@@ -69,3 +70,20 @@ def test_default_lam0_puts_log_tenth_on_exactly_the_diagonal_slots(P):
     npt.assert_array_equal(diag, np.concatenate([np.zeros(P), np.full(P, math.log(0.1))]))
     # the two defaults are the same guide
     npt.assert_array_equal(ref.from_mean_field(diag, P), full)
+
+
+@pytest.mark.parametrize("P", SIZES)
+def test_first_draw_is_the_two_expressions_bit_for_bit(P):
+    rng = np.random.default_rng(13 + P)
+    S = 5
+    eps = rng.standard_normal((S, P))
+    lam = rng.standard_normal(2 * P)
+    npt.assert_array_equal(base.first_draw(lam, eps, P, "diag"), lam[None, :P] + np.exp(lam[None, P:]) * eps)
+    lam = 0.5 * rng.standard_normal(full_size(P))
+    mu, L = unpack_full(lam, P)
+    z = base.first_draw(lam, eps, P, "full")
+    npt.assert_array_equal(z, mu[None, :] + eps @ L.T)
+    assert z.dtype == np.float64 and z.shape == (S, P)
+    # the drivers hand over the first P columns of bsc_blr_noise's [S, P + 1] rows as a view
+    wide = rng.standard_normal((S, P + 1))
+    npt.assert_array_equal(base.first_draw(lam, wide[:, :P], P, "full"), mu[None, :] + wide[:, :P] @ L.T)
