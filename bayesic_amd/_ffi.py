@@ -124,6 +124,12 @@ SIGNATURES = {
                                     c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
                                     c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_nb_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                     c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_nb_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64, c_double,
+                                  c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
     "bsc_glm_fullrank_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_int32, c_double, c_double, c_int64, c_double, c_double, c_double,
                                         c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -131,6 +137,8 @@ SIGNATURES = {
                                  c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_predict_pass_offset": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32,
                                         c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_nb_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_softmax_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_int32, c_void_p, c_void_p]),
     "bsc_softmax_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,

@@ -23,15 +23,42 @@
 //                 past the batch and their stores do not land.  Everything of it is behind `if constexpr (GRP)`; the
 //                 flag defaults to off and the kernels of the two files above compile as they did without it.
 //
+//   DSP = true    csrc/bsc_glm_nb.hip (always with OBS and LINK = GLM_NEGBIN): the negative binomial with one
+//                 dispersion draw per weight draw, tau_s = log phi_s as float32 [S].  A lane owns ONE draw in both tile
+//                 shapes, so tau_s, phi_s = exp(tau_s), lnGamma(phi_s) and psi(phi_s) are made once per launch (the two
+//                 special values in float64, then rounded) and stay in four registers; T[s] = d ell[s] / d tau_s is one
+//                 more lane accumulator next to ell.  The slab has no room for it, so these kernels write block
+//                 partials of NB_SLAB_STRIDE = REG_SLAB_G + 16 floats: ell at [SLAB_G + s], T at [SLAB_G + 8 + s].
+//                 Everything of it is behind `if constexpr (DSP)`; the flag defaults to off.
+//
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
 #include "bsc_regress.h"
+#include "bsc_special_f32.h"
 
 namespace {
 
 constexpr int SLAB_G = REG_SLAB_G;            // slab[b][d*8 + s], then ell at [SLAB_G + s]
 constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
+constexpr int NB_SLAB_STRIDE = REG_SLAB_G + 2 * SG;   // DSP: ell at [SLAB_G + s], T at [SLAB_G + 8 + s]
+constexpr int GLM_NEGBIN = 2;                 // the third link; internal: the BSC_GLM_* entry points refuse it
+
+// DSP: what a lane keeps of its draw's dispersion.
+struct GlmDisp {
+    float tau, phi;     // log phi_s as the pass read it, exp(tau)
+    float lg, psi;      // lnGamma(phi), psi(phi)
+};
+
+// Draw s of this launch's chunk (s >= S: a dead slot, phi = 1).  The special values in float64, once per launch.
+__device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi, int s, int S) {
+    GlmDisp d;
+    d.tau = s < S ? logphi[s] : 0.0f;
+    d.phi = expf(d.tau);
+    d.lg = (float)bsc_lgamma_f64((double)d.phi);
+    d.psi = (float)bsc_digamma_f64((double)d.phi);
+    return d;
+}
 
 // ---- the link: ell += y l - A(l) for a real row, resid = y - A'(l) ------------------------------------------
 //
@@ -40,8 +67,40 @@ constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
 // same e (1 / (1 + e) for l >= 0, e / (1 + e) below): finite for every finite l.  Poisson: A = A' = exp(l),
 // NOT clamped (a clamp would change the gradient silently): finite for l <= 88.
 // OBS: `l` already holds the offset; both terms are scaled by the weight vv where vv > 0 and are exactly 0 elsewhere.
+// GLM_NEGBIN (always OBS; dp and T set): with u = l - tau, phi = e^tau, z = y + phi and the logistic forms at u,
+//     ell  += v [ dlnGamma(y, phi) + y u - z softplus(u) ]          dlnGamma = lnGamma(z) - lnGamma(phi)
+//     resid = v [ y - z sigmoid(u) ]                                                           (= d / d l)
+//     T    += v [ phi dpsi(y, phi) - phi softplus(u) ] - resid       dpsi = psi(z) - psi(phi)   (= d / d tau)
+// finite for every finite l; both differences are exactly 0 at y = 0 (csrc/bsc_special_f32.h: an empty product).
 template <int LINK, bool OBS = false>
-__device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv = 1.0f) {
+__device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv = 1.0f,
+                                          const GlmDisp* dp = nullptr, float* T = nullptr) {
+    if constexpr (LINK == GLM_NEGBIN) {
+        // The selects sit on the INPUTS: a dropped row (weight 0, or past B) is evaluated at y = 0, u = 0 -- finite
+        // whatever it held -- and its terms are multiplied by an exact 0.  A select on the results turns into a
+        // branch around the whole evaluation, which splits the loop body and spills.
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const float yq = keep ? yv : 0.0f;
+        const float u = keep ? l - dp->tau : 0.0f;
+        const float e = expf(-fabsf(u));
+        const float t = 1.0f + e;
+        const float r = __builtin_amdgcn_rcpf(t);
+        const float sig = u >= 0.0f ? r : e * r;
+        // log1p(e) from the full-accuracy log and a true division: softplus is multiplied by y + phi and the products
+        // cancel against lnGamma(y + phi) and y u, so the 3e-7 of the logistic link's fast form would show in ell
+        // (t == 1: log(t) = 0 and the quotient is over 1, e itself is added -- selects between values at hand)
+        const bool tiny = t == 1.0f;
+        const float lp = logf(t) * (e / (tiny ? 1.0f : t - 1.0f)) + (tiny ? e : 0.0f);
+        const float sp = fmaxf(u, 0.0f) + lp;
+        const float z = yq + dp->phi;
+        float dlg, dps;                                  // exactly 0 at y = 0
+        bsc_dlgamma_dpsi_f32(yq, dp->phi, dp->lg, dp->psi, dlg, dps);
+        const float res = fmaf(-z, sig, yq);
+        ell = fmaf(vq, dlg + fmaf(yq, u, -z * sp), ell);
+        *T = fmaf(vq, fmaf(dp->phi, dps - sp, -res), *T);
+        return vq * res;
+    }
     float a, da;
     if (LINK == BSC_GLM_LOGISTIC) {
         const float e = expf(-fabsf(l));
@@ -138,10 +197,12 @@ __device__ __forceinline__ void gather_tile(GlmTile<true, true>& t, const GlmGro
 // Forward + link + backward for one tile; `wl` is this wave's LDS region, `rows_left` = B - row0.  has_v: the weights
 // are set (uniform; without them every row weighs 1.0f and real_row alone masks the rows past B).
 // GRP: `row0` is the tile's first row (a multiple of 8), its residuals also go to ga.R.
-template <int LINK, bool OBS, bool GRP = false>
+// DSP: `dp` is the dispersion of this lane's draw, `T` its accumulator.
+template <int LINK, bool OBS, bool GRP = false, bool DSP = false>
 __device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP>& t, const float4 (&w)[SG], float4 (&acc)[SG],
                                              float& ell, float* wl, int lane, int64_t rows_left, bool has_v,
-                                             const GlmGroupArgs* ga = nullptr, int64_t row0 = 0) {
+                                             const GlmGroupArgs* ga = nullptr, int64_t row0 = 0,
+                                             const GlmDisp* dp = nullptr, float* T = nullptr) {
     // 1. per-lane partial dots, row by row, into this lane's row of the buffer
     float* mine = wl + lane * G8::PSTR;
 #pragma unroll
@@ -188,7 +249,10 @@ __device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP>& t, const f
         auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(resid), rs,
                                               4 * ((val & 7) * 16 + (int)(row0 & 8) + (val >> 3)), 0, 0);
-    } else if constexpr (OBS)
+    } else if constexpr (DSP)
+        resid = glm_link<LINK, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell, has_v ? t.vv : 1.0f,
+                                     dp, T);
+    else if constexpr (OBS)
         resid = glm_link<LINK, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell, has_v ? t.vv : 1.0f);
     else
         resid = glm_link<LINK>(logit, t.yv, (int64_t)(val >> 3) < rows_left, ell);
@@ -208,31 +272,39 @@ __device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP>& t, const f
     }
 }
 
-// The block partial: fixed order over the waves, written in slab order [d][s] | ell[s].
+// The block partial: fixed order over the waves, written in slab order [d][s] | ell[s] (| T[s] at NB_SLAB_STRIDE).
+template <int STRIDE = SLAB_STRIDE>
 __device__ __forceinline__ void write_block_partial(const float* lds, float* __restrict__ slab, int tid) {
-    float* out = slab + (int64_t)blockIdx.x * SLAB_STRIDE;
-    for (int i = tid; i < SLAB_STRIDE; i += PASS_BLOCK) {
+    float* out = slab + (int64_t)blockIdx.x * STRIDE;
+    for (int i = tid; i < STRIDE; i += PASS_BLOCK) {
         const int src = i < SLAB_G ? (i & 7) * GCOLS + (i >> 3) : i;
         float v = lds[src];
 #pragma unroll
-        for (int k = 1; k < PASS_WAVES; ++k) v += lds[k * SLAB_STRIDE + src];
+        for (int k = 1; k < PASS_WAVES; ++k) v += lds[k * STRIDE + src];
         out[i] = v;
     }
 }
 
 // FULL: D == 256.  n_iter: tiles per wave (the same for every wave; tiles past the end read zeros).
 // o, v_: the offset and the weight, each may be null; read only where OBS.
-template <int LINK, bool FULL, bool OBS, bool GRP = false>
+// DSP: logphi [S] (this launch's chunk of the dispersion draws); the slab is NB_SLAB_STRIDE floats per block.
+template <int LINK, bool FULL, bool OBS, bool GRP = false, bool DSP = false>
 __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const float* y, const float* o,
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
-                                              int n_iter, const GlmGroupArgs* ga = nullptr) {
-    constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > SLAB_STRIDE ? G8::WAVE_LDS : SLAB_STRIDE);
+                                              int n_iter, const GlmGroupArgs* ga = nullptr,
+                                              const float* logphi = nullptr) {
+    static_assert(!DSP || (OBS && !GRP && LINK == GLM_NEGBIN), "the dispersion rides with OBS and its own link");
+    constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
+    constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > STRIDE ? G8::WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float* wl = lds + wave * G8::WAVE_LDS;
     const bool has_v = OBS && v_ != nullptr;
+    GlmDisp dp;
+    float tacc = 0.f;
+    if constexpr (DSP) dp = glm_disp_of(logphi, lane_value<ROWS>(lane) & 7, S);   // before anything fills the file
 
     float4 w[SG], acc[SG];
 #pragma unroll
@@ -265,21 +337,25 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
             gather_tile(ta, *ga, lane);
             compute_tile<LINK, OBS, GRP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS);
         }
-    } else {
+    } else {   // (dp and tacc: untouched without DSP)
         GlmTile<OBS> ta, tb;
         load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane);
         for (int k = 0; k + 1 < n_iter; k += 2) {
             load_tile<FULL, OBS>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane);
-            compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
+            compute_tile<LINK, OBS, false, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, nullptr, 0, &dp,
+                                                &tacc);
             load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane);
-            compute_tile<LINK, OBS>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v);
+            compute_tile<LINK, OBS, false, DSP>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, nullptr,
+                                                0, &dp, &tacc);
             tile += 2 * stride;
         }
-        if (n_iter & 1) compute_tile<LINK, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v);
+        if (n_iter & 1)
+            compute_tile<LINK, OBS, false, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, nullptr, 0, &dp,
+                                                &tacc);
     }
 
     __syncthreads();  // every wave is done with its private region
-    float* ep = lds + wave * SLAB_STRIDE;
+    float* ep = lds + wave * STRIDE;
 #pragma unroll
     for (int s = 0; s < SG; ++s) *reinterpret_cast<float4*>(ep + s * GCOLS + 4 * lane) = acc[s];
     // ell of lane k belongs to draw lane_value(k) & 7; fold the tile rows (lane bits 1 .. 3)
@@ -288,8 +364,15 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     ev += __shfl_xor(ev, 4);
     ev += __shfl_xor(ev, 8);
     if ((lane & 14) == 0) ep[SLAB_G + (lane_value<ROWS>(lane) & 7)] = ev;
+    if constexpr (DSP) {   // T folds like ell
+        float tv = tacc;
+        tv += __shfl_xor(tv, 2);
+        tv += __shfl_xor(tv, 4);
+        tv += __shfl_xor(tv, 8);
+        if ((lane & 14) == 0) ep[SLAB_G + SG + (lane_value<ROWS>(lane) & 7)] = tv;
+    }
     __syncthreads();
-    write_block_partial(lds, slab, tid);
+    write_block_partial<STRIDE>(lds, slab, tid);
 }
 
 // ---- 16-row tiles, both contractions on the MFMA pipe (D == 256, y [o, v] 16-byte aligned) ----------------------
@@ -349,11 +432,14 @@ __device__ __forceinline__ void load_mtile(MTile<OBS, GRP>& t, const float* __re
     }
 }
 
-template <int LINK, bool OBS, bool GRP = false>
+template <int LINK, bool OBS, bool GRP = false, bool DSP = false>
 __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, const float* y, const float* o,
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
-                                                   int n_iter, const GlmGroupArgs* ga = nullptr) {
-    constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > SLAB_STRIDE ? MT_WAVE_LDS : SLAB_STRIDE);
+                                                   int n_iter, const GlmGroupArgs* ga = nullptr,
+                                                   const float* logphi = nullptr) {
+    static_assert(!DSP || (OBS && !GRP && LINK == GLM_NEGBIN), "the dispersion rides with OBS and its own link");
+    constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
+    constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > STRIDE ? MT_WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -362,6 +448,9 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     float* tl = lds + wave * MT_WAVE_LDS;      // this wave's tile
     float* rb = tl + MT_ROWS * MT_RS;          // residuals [draw][row]
     const bool has_v = OBS && v_ != nullptr;
+    GlmDisp dp;
+    float tacc = 0.f;
+    if constexpr (DSP) dp = glm_disp_of(logphi, i16, S);   // lane (i16, kq) owns draw i16 (live lanes: i16 < 8)
 
     // forward B operand: W[draw i16][64 kq + 4 j + c]; MFMA columns 8 .. 15 and draws >= S are zero.  Lane group
     // kq contracts columns 64 kq .. 64 kq + 63, which keeps the 16-byte A reads of a lane group conflict-free.
@@ -445,6 +534,11 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
                 __builtin_amdgcn_raw_buffer_store_b128(
                     u32x4{__float_as_uint(r0), __float_as_uint(r1), __float_as_uint(r2), __float_as_uint(r3)}, rs,
                     4 * (i16 * MT_ROWS + 4 * kq), 0, 0);
+            } else if constexpr (DSP) {
+                r0 = glm_link<LINK, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x, &dp, &tacc);
+                r1 = glm_link<LINK, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y, &dp, &tacc);
+                r2 = glm_link<LINK, true>(d0[2] + d1[2] + ov.z, yv.z, rows_left > 2, ell, vv.z, &dp, &tacc);
+                r3 = glm_link<LINK, true>(d0[3] + d1[3] + ov.w, yv.w, rows_left > 3, ell, vv.w, &dp, &tacc);
             } else if constexpr (OBS) {
                 r0 = glm_link<LINK, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x);
                 r1 = glm_link<LINK, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y);
@@ -485,7 +579,7 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     }
 
     __syncthreads();
-    float* ep = lds + wave * SLAB_STRIDE;
+    float* ep = lds + wave * STRIDE;
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
@@ -496,8 +590,14 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     ev += __shfl_xor(ev, 16);
     ev += __shfl_xor(ev, 32);
     if (lane < SG) ep[SLAB_G + lane] = ev;
+    if constexpr (DSP) {
+        float tv = live ? tacc : 0.f;
+        tv += __shfl_xor(tv, 16);
+        tv += __shfl_xor(tv, 32);
+        if (lane < SG) ep[SLAB_G + SG + lane] = tv;
+    }
     __syncthreads();
-    write_block_partial(lds, slab, tid);
+    write_block_partial<STRIDE>(lds, slab, tid);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------

@@ -6,8 +6,14 @@
 #pragma once
 
 #include "bsc_regress.h"
+#include "bsc_special_f32.h"
 
 namespace {
+
+// The fourth family, internal: csrc/bsc_glm_nb.hip's predict_nb_kernel (bsc_nb_predict_pass).  bsc_predict_pass and
+// bsc_predict_pass_offset refuse it.  Always with OFFS (a null offset reads 0 through an empty descriptor); `logvar`
+// carries tau_s = log phi_s.
+constexpr int PREDICT_NEGBIN = 3;
 
 constexpr int P_BLOCK = 512;
 constexpr int P_WAVES = P_BLOCK / BSC_WAVE;
@@ -27,7 +33,7 @@ struct PredictArgs {
     const float* y;          // may be null
     int64_t B;
     const float* W;
-    const float* logvar;     // Gaussian only
+    const float* logvar;     // Gaussian: log s2 per draw; PREDICT_NEGBIN: log phi per draw
     float* mean;             // outputs, each may be null
     float* var;
     float* lpd;
@@ -74,9 +80,25 @@ __device__ __forceinline__ float load_offset(const float* __restrict__ offset, i
 // v = mu (1 - mu) = e / (1 + e)^2 without the cancellation, softplus = max(l, 0) + log1p(e) with log1p(e) =
 // log(t) e / (t - 1), t = 1 + e (the quotient undoes the rounding of t): finite for every finite l.
 // Poisson: exp(l), not clamped; the row constant lnGamma(y + 1) is taken off after the log-mean-exp.
+// PREDICT_NEGBIN: p4 = (tau, phi = exp(tau), 1 / phi) and lgp = lnGamma(phi).  mu = exp(l) (not clamped),
+// v = mu + mu^2 / phi; log p from the logistic forms at u = l - tau, finite for every finite l:
+// lnGamma(y + phi) - lnGamma(phi) + y u - (y + phi) softplus(u), the difference exactly 0 at y = 0; the row
+// constant lnGamma(y + 1) is taken off after the log-mean-exp.
 template <int FAM>
 __device__ __forceinline__ void predict_link(float l, float yv, float lv, float ev, float iv, float& mu, float& v,
-                                             float& lp) {
+                                             float& lp, float lgp = 0.0f) {
+    if constexpr (FAM == PREDICT_NEGBIN) {
+        mu = expf(l);
+        v = fmaf(mu * iv, mu, mu);
+        const float u = l - lv;
+        const float e = expf(-fabsf(u));
+        const float t = 1.0f + e;
+        const float l1p = t == 1.0f ? e : logf(t) * e / (t - 1.0f);
+        float dlg, dps;
+        bsc_dlgamma_dpsi_f32(yv, ev, lgp, 0.0f, dlg, dps);      // (dpsi is not used and folds away)
+        lp = dlg + fmaf(yv, u, -(yv + ev) * (fmaxf(u, 0.0f) + l1p));
+        return;
+    }
     if (FAM == BSC_PREDICT_GAUSSIAN) {
         const float r = yv - l;
         mu = l;
@@ -103,7 +125,9 @@ template <int FAM, int NC, bool FULL, bool OFFS>
 __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset) {
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
-    __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + 3 * P_MAX_S];
+    constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || FAM == PREDICT_NEGBIN;   // a scalar rides with every draw
+    constexpr int GP_SLOTS = FAM == PREDICT_NEGBIN ? 4 : 3;                           // ... and lnGamma(phi)
+    __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + GP_SLOTS * P_MAX_S];
     __shared__ double red[P_WAVES];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -118,10 +142,11 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
         for (int col = lane; col < WS; col += BSC_WAVE)
             wl[row * WS + col] = (row < S && col < D) ? a.W[(int64_t)row * D + col] : 0.f;
     if (tid < P_MAX_S) {
-        const float lv = (FAM == BSC_PREDICT_GAUSSIAN && tid < S) ? a.logvar[tid] : 0.f;
+        const float lv = (PER_DRAW && tid < S) ? a.logvar[tid] : 0.f;
         gp[tid] = lv;
         gp[P_MAX_S + tid] = expf(lv);
         gp[2 * P_MAX_S + tid] = expf(-lv);
+        if constexpr (FAM == PREDICT_NEGBIN) gp[3 * P_MAX_S + tid] = (float)bsc_lgamma_f64((double)expf(lv));
     }
     __syncthreads();
 
@@ -145,7 +170,8 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
     load_strip(t, a, row0_of(0), 0, lane);
     float y_cur = load_y(a, row0_of(0), i16);
     float o_cur = 0.f;
-    if constexpr (OFFS) o_cur = load_offset(offset, a.B, row0_of(0), i16);
+    [[maybe_unused]] const int64_t o_rows = (FAM == PREDICT_NEGBIN && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
+    if constexpr (OFFS) o_cur = load_offset(offset, o_rows, row0_of(0), i16);
     int p = 0, h = 0;
     while (p < n_iter) {
         // the strip to LDS (row stride 130 floats: 8-byte aligned), its registers take the next strip
@@ -168,7 +194,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
         if (last) y_next = load_y(a, row0_of(pn), i16);
         float o_next = 0.f;
         if constexpr (OFFS) {
-            if (last) o_next = load_offset(offset, a.B, row0_of(pn), i16);
+            if (last) o_next = load_offset(offset, o_rows, row0_of(pn), i16);
         }
         wave_lds_sync();
 
@@ -208,11 +234,13 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
             for (int c = 0; c < NC; ++c) {
                 const int d0 = 16 * c + 4 * kq;
                 float4 lv4 = make_float4(0.f, 0.f, 0.f, 0.f), ev4 = lv4, iv4 = lv4;
-                if (FAM == BSC_PREDICT_GAUSSIAN) {
+                [[maybe_unused]] float4 lg4 = lv4;
+                if (PER_DRAW) {
                     lv4 = *reinterpret_cast<const float4*>(gp + d0);
                     ev4 = *reinterpret_cast<const float4*>(gp + P_MAX_S + d0);
                     iv4 = *reinterpret_cast<const float4*>(gp + 2 * P_MAX_S + d0);
                 }
+                if constexpr (FAM == PREDICT_NEGBIN) lg4 = *reinterpret_cast<const float4*>(gp + 3 * P_MAX_S + d0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float l = acc[c][0][r] + acc[c][1][r];
@@ -221,7 +249,11 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
                     const float ev = r == 0 ? ev4.x : r == 1 ? ev4.y : r == 2 ? ev4.z : ev4.w;
                     const float iv = r == 0 ? iv4.x : r == 1 ? iv4.y : r == 2 ? iv4.z : iv4.w;
                     float m_i, v_i, lp_i;
-                    predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i);
+                    if constexpr (FAM == PREDICT_NEGBIN)
+                        predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i,
+                                          r == 0 ? lg4.x : r == 1 ? lg4.y : r == 2 ? lg4.z : lg4.w);
+                    else
+                        predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i);
                     const bool valid = d0 + r < S;
                     mu[4 * c + r] = valid ? m_i : 0.f;
                     lp[4 * c + r] = valid ? lp_i : -INFINITY;
@@ -254,7 +286,8 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
                 for (int i = 0; i < 4 * NC; ++i) se += __expf(lp[i] - ms);
                 se = fold4_sum(se);
                 lpd = ms + logf(se) - log_S;
-                if (FAM == BSC_PREDICT_POISSON) lpd -= (float)bsc_lgamma_f64((double)yv + 1.0);   // once per row
+                if (FAM == BSC_PREDICT_POISSON || FAM == PREDICT_NEGBIN)
+                    lpd -= (float)bsc_lgamma_f64((double)yv + 1.0);   // once per row
             }
             const int64_t row = row0_of(p) + i16;
             if (kq == 0 && row < B) {     // lanes 0 .. 15: one row each, 64 contiguous bytes per output

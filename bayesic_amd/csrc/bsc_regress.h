@@ -165,33 +165,40 @@ __device__ __forceinline__ void slab_run_sum(const float* __restrict__ slab, int
 
 // Sum block partials of the [d * 8 + s | 8 scalars] slab in float64, fixed order: the body of blr_slab_reduce_kernel
 // and glm_slab_reduce_kernel.  One output per lane; the 16 waves of a block split the slab rows, then combine through
-// LDS in wave order.  `scalar` is Q (BLR) or ell (GLM).
+// LDS in wave order.  `scalar` is Q (BLR) or ell (GLM).  STRIDE = REG_SLAB_G + 16 (csrc/bsc_glm_nb.hip): a second run
+// of eight scalars behind the first goes to `scalar2`.
 constexpr int RED_BLOCK = 1024;
 constexpr int RED_WAVES = RED_BLOCK / BSC_WAVE;
 
+template <int STRIDE = REG_SLAB_STRIDE>
 __device__ __forceinline__ void regress_slab_reduce(const float* __restrict__ slab, int n_blocks, int D, int S,
-                                                    int s_base, double* __restrict__ scalar, double* __restrict__ G) {
+                                                    int s_base, double* __restrict__ scalar, double* __restrict__ G,
+                                                    double* __restrict__ scalar2 = nullptr) {
+    static_assert(STRIDE == REG_SLAB_STRIDE || STRIDE == REG_SLAB_G + 2 * SG, "one or two runs of eight scalars");
     __shared__ double part[RED_WAVES][BSC_WAVE];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int i = blockIdx.x * BSC_WAVE + lane;
     double s4[4];
-    slab_run_sum<REG_SLAB_STRIDE, RED_WAVES>(slab, n_blocks, blockIdx.x * BSC_WAVE, wave, lane, s4, [] {});
+    slab_run_sum<STRIDE, RED_WAVES>(slab, n_blocks, blockIdx.x * BSC_WAVE, wave, lane, s4, [] {});
     if (lane < 16) {   // (columns past the stride in the last workgroup are read but never written out)
 #pragma unroll
         for (int k = 0; k < 4; ++k) part[wave][4 * lane + k] = s4[k];
     }
     __syncthreads();
-    if (wave == 0 && i < REG_SLAB_STRIDE) {
+    if (wave == 0 && i < STRIDE) {
         double tot = part[0][lane];
 #pragma unroll
         for (int k = 1; k < RED_WAVES; ++k) tot += part[k][lane];
         if (i < REG_SLAB_G) {
             int s = i & 7, d = i >> 3;
             if (s_base + s < S && d < D) G[(int64_t)(s_base + s) * D + d] = tot;
-        } else {
+        } else if (STRIDE == REG_SLAB_STRIDE || i < REG_SLAB_G + SG) {
             int s = i - REG_SLAB_G;
             if (s_base + s < S) scalar[s_base + s] = tot;
+        } else {
+            int s = i - REG_SLAB_G - SG;
+            if (s_base + s < S) scalar2[s_base + s] = tot;
         }
     }
 }

@@ -17,9 +17,12 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
     BLRReparamSVI(covariance="full")  eps [S, D + 1]:  z = mu + L eps over z = [w | xi]
     SoftmaxReparamSVI                 eps [S, K D]:    the two GLM transforms at width K D, W returned [S, K, D]
                                       (predict() below hands over to its predict(): bsc_softmax_predict_pass)
-xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass).
+    NegBinReparamSVI                  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  tau = m_tau + e^{rho_tau} eps[:, D]
+                                      (lam is already [m | rho] over z = [w | tau]; bsc_nb_predict_pass)
+xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass); tau = log phi is the log-dispersion
+of the negative binomial and travels in the same slot of the returned pair.
 
-Offsets and weights (logistic and Poisson models): ``offset`` (or, Poisson, ``exposure`` = e^offset) is added to the
+Offsets and weights (logistic, Poisson and negative-binomial models): ``offset`` (or, Poisson, ``exposure`` = e^offset) is added to the
 linear predictor in the pass (bsc_predict_pass_offset), so a Poisson ``mean`` is the expected count at that exposure.
 A model fitted with an offset refuses to predict without one.  ``weights`` leave every per-row output alone and make
 ``lpd_sum`` the weighted sum_n v_n lpd_n (float64, on the device, from the lpd vector).
@@ -39,8 +42,8 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 
 
 def family_of(model):
-    """The likelihood family of a driver: its GLM link, "softmax" for SoftmaxReparamSVI, or "gaussian" for
-    BLRReparamSVI."""
+    """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI), "softmax" for
+    SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
     if getattr(model, "n_classes", None) is not None:
         return "softmax"
     link = getattr(model, "link", None)
@@ -65,14 +68,16 @@ def _check_samples(n_samples):
 
 def posterior_draws(model, n_samples=64, seed=None):
     """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q; W is [S, K, D] for
-    SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d)."""
+    SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d); for NegBinReparamSVI the second
+    entry is logphi float32 [S]."""
     S = _check_samples(n_samples)
     family = family_of(model)
     ctx, D = model.ctx, model.D
     if family == "softmax":
         D = model.n_classes * model.D          # the guide's width; the transforms below are the GLM ones
     seed = model.seed if seed is None else int(seed)
-    P = D + 1 if family == "gaussian" else D
+    scalar = family in ("gaussian", "negbin")           # a scalar latent rides behind the weights
+    P = D + 1 if scalar else D
     eps_d = torch.zeros((S, P), dtype=torch.float64, device=ctx.device)
     ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P, eps_d)
     eps = eps_d.cpu().numpy()
@@ -81,7 +86,7 @@ def posterior_draws(model, n_samples=64, seed=None):
     if family == "gaussian" and kind == "diag":         # [m | rho | a | b] -> [m a | rho b] over z = [w | xi]
         lam = np.concatenate([lam[:D], lam[2 * D:2 * D + 1], lam[D:2 * D], lam[2 * D + 1:]])
     z = first_draw(lam, eps, P, kind)
-    W, logvar = (z[:, :D], z[:, D]) if family == "gaussian" else (z, None)
+    W, logvar = (z[:, :D], z[:, D]) if scalar else (z, None)
     if family == "softmax":
         W = W.reshape(S, model.n_classes, model.D)
     Wd = ctx.to_device(np.ascontiguousarray(W, np.float32))
@@ -107,9 +112,9 @@ def _obs(model, family, B, offset, exposure, weights):
                          "counts")
     if offset is None and exposure is None and weights is None:
         return None, None
-    if family not in ("logistic", "poisson"):
+    if family not in ("logistic", "poisson", "negbin"):
         raise ValueError("predict: offset, exposure and weights are for the logistic and Poisson models, not %s" % family)
-    check_link(family, offset, exposure, kept="means")
+    check_link("poisson" if family == "negbin" else family, offset, exposure, kept="means")   # a count model's rules
     return batch_obs(model.ctx, B, offset, weights, exposure)
 
 
@@ -138,7 +143,10 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
         out["lpd"] = torch.empty(B, dtype=torch.float32, device=dev)
         if weights is None:        # (the weighted sum is formed from the lpd vector below)
             out["lpd_sum"] = torch.zeros(1, dtype=torch.float64, device=dev)
-    if offset is None:
+    if family == "negbin":       # its own entry point; the offset may be None
+        ctx.call("bsc_nb_predict_pass", X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"],
+                 out.get("lpd"), out.get("lpd_sum"))
+    elif offset is None:
         ctx.call("bsc_predict_pass", FAMILIES[family], X, ldx, y, B, model.D, W, logvar, S, out["mean"], out["var"],
                  out.get("lpd"), out.get("lpd_sum"))
     else:

@@ -492,6 +492,55 @@ int bsc_glm_hier_update(bsc_ctx* ctx, const double* stats, const double* lam_in,
                         double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
                         int32_t eps_next_ready, float* W_next, float* Bz_next, double* elbo, double* grad);
 
+/* ---- negative-binomial regression with a learned dispersion on the same pass (csrc/bsc_glm_nb.hip) ----------------
+ *
+ *      y_n ~ NegBin(mean mu_n = exp(l_n), dispersion phi),   Var y_n = mu_n + mu_n^2 / phi,   l[n,s] = sum_d X[n,d] W[s,d] + o[n]
+ *      w ~ N(0, I / prior_precision),   phi = e^tau ~ Gamma(a0, b0):  log p(tau) = a0 log b0 - lnGamma(a0) + a0 tau - b0 e^tau
+ * The latent is z = [w (D) | tau], P = D + 1, the guide mean-field: lam = [m (P) | rho (P)].  One dispersion draw rides
+ * with every weight draw: logphi[s] = tau_s, float32 [S], any 4-byte alignment.  With u = l - tau_s, phi_s = e^{tau_s}
+ * (float32 expf of the value read), sp = softplus and sg = sigmoid in bsc_glm_data_pass's stable forms -- the
+ * log-density is the logistic link at a shifted logit and is finite for EVERY finite l, which the Poisson link is not --
+ *      ell[s]  = sum_n v[n] ( dlnGamma(y[n], phi_s) + y[n] u - (y[n] + phi_s) sp(u) )      dlnGamma(y, phi) = lnGamma(y + phi) - lnGamma(phi)
+ *      G[s,d]  = sum_n r[n,s] X[n,d]             r[n,s] = v[n] ( y[n] - (y[n] + phi_s) sg(u) )                  (= d / d l)
+ *      T[s]    = sum_n v[n] ( phi_s dpsi(y[n], phi_s) - phi_s sp(u) ) - sum_n r[n,s]          dpsi(y, phi) = psi(y + phi) - psi(phi)
+ * (T[s] = d ell[s] / d tau_s; ell leaves the constant -sum_n v[n] lnGamma(y[n] + 1) out, as the Poisson link does.)
+ * Outputs float64: ell [S], G [S, D], T [S].  offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0,
+ * v = 1; a row with v[n] = 0 adds EXACTLY nothing to ell, G and T, by a select); y >= 0, not necessarily an integer; both
+ * differences are exactly 0 at y = 0.  They are evaluated in float32 per (row, draw), csrc/bsc_special_f32.h: for a whole
+ * y <= 8 as the product and the sum they are, log prod_{i<y} (phi_s + i) and sum_{i<y} 1 / (phi_s + i); otherwise from a
+ * shift of y + phi_s up to >= 8 and three asymptotic terms, against lnGamma(phi_s) and psi(phi_s) made once per launch
+ * in float64.
+ * ACCURACY ENVELOPE: tau in [-2.5, 5] (phi in [0.08, 148]).  Above it T's terms cancel (phi dpsi - phi sp - r -> 0 as
+ * phi -> infinity) beyond what float32 holds, and lnGamma(y + phi) - lnGamma(phi) loses its digits to lnGamma(phi);
+ * past tau = 10 the eight-factor product overflows.
+ * The envelope and its refusals are bsc_glm_data_pass_obs's (D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 with eight draws
+ * and their eight tau per launch, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26); logphi == NULL is
+ * refused.  The 16-row MFMA kernel (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned,
+ * else the 8-row kernel.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block partials of
+ * 8 * 256 + 16 floats (ell and T behind G), fixed-order float64 finish, no float atomics. */
+int bsc_glm_nb_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                         const float* weight, int64_t B, int32_t D, const float* W, const float* logphi, int32_t S,
+                         double* ell, double* G, double* T);
+
+/* The finish, two launches.  stats = [ell (S) | G (S*D) | T (S)] as the pass and the all-reduce leave them (NULL is
+ * refused); eps in bsc_blr_noise's [S, D+1] layout, column D (tau's noise, Philox stream 1) READ here; W [S, D] and
+ * logphi [S] the float32 draws the pass read -- tau_s enters as that float32 value, exactly as w_s does:
+ *     g_w    = scale G_s - prior_precision w_s
+ *     g_tau  = scale T_s + a0 - b0 e^{tau_s}
+ *     ELBO   = mean_s [ scale ell_s - prior_precision/2 |w_s|^2 + log p(tau_s) ] + D/2 log(prior_precision / 2 pi)
+ *              + sum rho + P/2 (1 + log 2 pi)
+ *     d/d m  = mean_s g_s,     d/d rho_i = mean_s g_si eps_si e^{rho_i} + 1
+ * then Adam ascent step t (bsc_adam_ascent's form; lam_in is not modified, m1 and m2 in place) and, when the *_next
+ * buffers are set (all or none), W_next [S, D] and logphi_next [S] from eps_next, rounded to float32;
+ * eps_next_ready = 0 draws the noise of next_step into eps_next first.  lam_in != lam_out; the *_next buffers must not
+ * alias the current ones.  Requires 1 <= S <= 64, t >= 1 and prior_precision, a0, b0, scale > 0.  Fixed-order sums, no
+ * atomics. */
+int bsc_glm_nb_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1, double* m2,
+                      const double* eps, const float* W, const float* logphi, int32_t D, int32_t S, double scale,
+                      double prior_precision, double a0, double b0, int64_t t, double lr, double beta1, double beta2,
+                      double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
+                      float* W_next, float* logphi_next, double* elbo, double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
@@ -556,6 +605,20 @@ int bsc_predict_pass(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, 
 int bsc_predict_pass_offset(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, const float* y,
                             const float* offset, int64_t B, int32_t D, const float* W, const float* logvar, int32_t S,
                             float* mean, float* var, float* lpd, double* lpd_sum);
+
+/* The predictive of the negative-binomial model (csrc/bsc_glm_nb.hip: bsc_predict_pass's kernel with a fourth family
+ * that only this entry point reaches; bsc_predict_pass and bsc_predict_pass_offset refuse it).  Per draw, with
+ * phi_s = exp(logphi[s]) and l[n,s] = sum_d X[n,d] W[s,d] + o[n] (offset may be NULL):
+ *      mu = exp(l)    v = mu + mu^2 / phi_s    log p(y | l, phi_s) = the full log-pmf, -lnGamma(y + 1) included
+ *      mean[n] = 1/S sum_s mu,     var[n] = 1/S sum_s (mu + mu^2 / phi_s) + 1/S sum_s (mu - mean[n])^2
+ *      lpd[n]  = logsumexp_s log p(y[n] | l[n,s], phi_s) - log S,     lpd_sum = sum_n lpd[n]     (float64 [1])
+ * lpd comes from the softplus form (bsc_glm_nb_data_pass) and is finite for every finite l.  exp is NOT clamped, as for
+ * the Poisson family: mean stops being finite at l > 88 and var at l > 44 (mu^2 overflows float32).  Outputs, refusals,
+ * envelope and determinism are bsc_predict_pass_offset's; logphi == NULL is BSC_ERR_INVALID.  Accuracy envelope of
+ * lpd: logphi in [-2.5, 5]. */
+int bsc_nb_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
+                        int32_t D, const float* W, const float* logphi, int32_t S, float* mean, float* var, float* lpd,
+                        double* lpd_sum);
 
 /* ---- multi-class softmax regression (csrc/bsc_softmax.hip; ABSENT in the reference) ------------------------
  *
