@@ -1411,10 +1411,10 @@ int fused_update_impl(bsc_ctx* ctx, const char* who, const double* stats, const 
     BSC_REQUIRE(lam_in != lam_out, "%s: lam_in and lam_out must differ", who);
     BSC_REQUIRE(D > 0 && S >= 1 && S <= FIN_MAX_S, "%s: D=%d S=%d (S<=%d)", who, D, S, FIN_MAX_S);
     BSC_REQUIRE(t >= 1, "%s: the Adam step count starts at 1", who);
-    BSC_REQUIRE((eps_next && W_next && xi_next) || (!eps_next && !W_next && !xi_next),
-                "%s: next-draw buffers must be all set or all null", who);
-    BSC_REQUIRE(!eps_next || (eps_next != eps && W_next != W && xi_next != xi),
-                "%s: next-draw buffers must not alias the current draws", who);
+    // (the kernel draws the next step's noise itself where the caller has not: nothing is drawn here)
+    const int rc = next_draw_noise(ctx, who, /*has_extra=*/true, eps, W, xi, eps_next, W_next, xi_next, D, S, seed,
+                                   next_step, /*eps_next_ready=*/1);
+    if (rc != BSC_OK) return rc;
     FusedArgs a;
     a.stats = stats;
     a.slab = nullptr;

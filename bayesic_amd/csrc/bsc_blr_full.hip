@@ -128,8 +128,8 @@ int bsc_blr_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam
                             lam_out, D, FR_MAX_P - 1, S, t);
     if (rc != BSC_OK) return rc;
     BSC_REQUIRE(s_q >= 0.0 && k_w >= 0.0, "%s: s_q=%g k_w=%g must not be negative", who, s_q, k_w);
-    rc = fr_next_noise(ctx, who, /*has_xi=*/true, eps, W, xi, eps_next, W_next, xi_next, D, S, seed, next_step,
-                       eps_next_ready);
+    rc = next_draw_noise(ctx, who, /*has_extra=*/true, eps, W, xi, eps_next, W_next, xi_next, D, S, seed, next_step,
+                         eps_next_ready);
     if (rc != BSC_OK) return rc;
     FullArgs a;
     a.stats = stats;

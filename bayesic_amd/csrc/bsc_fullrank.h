@@ -87,7 +87,8 @@ __device__ __forceinline__ void fr_next_draw(const fr_rows& rp, int E, int S, co
 
 // ---- host side: what the two entry points check and do alike ------------------------------------------------------
 
-// The state and size checks; `stats_layout` names the data pass's statistics ("Q | G", "ell | G").
+// The state and size checks (the next-draw buffers and the noise: next_draw_noise, csrc/bsc_regress.h);
+// `stats_layout` names the data pass's statistics ("Q | G", "ell | G").
 inline int fr_check_state(const char* who, const char* stats_layout, const double* stats, bool pointers_set,
                           const double* lam_in, const double* lam_out, int32_t D, int max_d, int32_t S, int64_t t) {
     BSC_REQUIRE(stats, "%s: stats must be the [%s] of the data pass (pending partials are not read)", who,
@@ -97,20 +98,6 @@ inline int fr_check_state(const char* who, const char* stats_layout, const doubl
     BSC_REQUIRE(D >= 4 && D <= max_d && D % 4 == 0, "%s: D=%d must be a multiple of 4 in [4,%d]", who, D, max_d);
     BSC_REQUIRE(S >= 1 && S <= FR_MAX_S, "%s: S=%d must be in [1,%d]", who, S, FR_MAX_S);
     BSC_REQUIRE(t >= 1, "%s: the Adam step count starts at 1", who);
-    return BSC_OK;
-}
-
-// The next-draw buffers (all set or all null, none of them its current twin; has_xi: the model has a scalar latent
-// with buffers of its own), then the next step's noise in bsc_blr_noise's layout unless the caller has drawn it.
-inline int fr_next_noise(bsc_ctx* ctx, const char* who, bool has_xi, const double* eps, const float* W,
-                         const double* xi, double* eps_next, float* W_next, double* xi_next, int32_t D, int32_t S,
-                         uint64_t seed, uint32_t next_step, int32_t eps_next_ready) {
-    const char* how_many = has_xi ? "all" : "both";
-    BSC_REQUIRE((eps_next && W_next && (xi_next || !has_xi)) || (!eps_next && !W_next && !xi_next),
-                "%s: next-draw buffers must be %s set or %s null", who, how_many, how_many);
-    BSC_REQUIRE(!eps_next || (eps_next != eps && W_next != W && (!has_xi || xi_next != xi)),
-                "%s: next-draw buffers must not alias the current draws", who);
-    if (eps_next && !eps_next_ready) return bsc_blr_noise(ctx, D, S, seed, next_step, 1, eps_next);
     return BSC_OK;
 }
 

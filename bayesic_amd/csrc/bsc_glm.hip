@@ -229,22 +229,16 @@ int check_glm_args(const char* who, int32_t link, const float* X, int64_t ldx, c
 template <int LINK>
 void launch_pass_link(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, int64_t B, int D, const float* W,
                       int sg, PassGrid g, float* slab) {
-    const dim3 grid(g.n_blocks), block(PASS_BLOCK);
-    if (pass_rows(D, y) == MT_ROWS)
-        hipLaunchKernelGGL((glm_pass_mfma_kernel<LINK>), grid, block, 0, ctx->stream, X, ldx, y, B, W, sg, slab,
-                           g.n_iter);
-    else if (D == GCOLS)
-        hipLaunchKernelGGL((glm_pass_kernel<LINK, true>), grid, block, 0, ctx->stream, X, ldx, y, B, D, W, sg,
-                           slab, g.n_iter);
-    else
-        hipLaunchKernelGGL((glm_pass_kernel<LINK, false>), grid, block, 0, ctx->stream, X, ldx, y, B, D, W, sg,
-                           slab, g.n_iter);
+    const auto go = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y, B, tail...);
+    };
+    launch_pass_shape(pass_rows(D, y), D, [&] { go(glm_pass_mfma_kernel<LINK>, W, sg, slab, g.n_iter); },
+                      [&](auto full) { go(glm_pass_kernel<LINK, decltype(full)::value>, D, W, sg, slab, g.n_iter); });
 }
 
 // o, v: the offset and the weight; with neither, the kernels of this file
 void launch_pass(bsc_ctx* ctx, int link, const float* X, int64_t ldx, const float* y, const float* o, const float* v,
                  int64_t B, int D, const float* W, int sg, PassGrid g, float* slab) {
-    bsc_prof_scope prof(ctx);  // times the pass kernel alone
     if (o || v)
         bsc_glm_obs_launch_pass(ctx, link, pass_rows(D, y, o, v) == MT_ROWS, X, ldx, y, o, v, B, D, W, sg, g.n_blocks,
                                 g.n_iter, slab);
@@ -266,7 +260,10 @@ int pass_partial_impl(bsc_ctx* ctx, int link, const float* X, int64_t ldx, const
     float* slab = nullptr;
     const int rc = slab_for(ctx, g, &slab);
     if (rc != BSC_OK) return rc;
-    launch_pass(ctx, link, X, ldx, y, o, v, B, (int)D, W, (int)S, g, slab);
+    {
+        bsc_prof_scope prof(ctx);  // times the pass kernel alone
+        launch_pass(ctx, link, X, ldx, y, o, v, B, (int)D, W, (int)S, g, slab);
+    }
     BSC_LAUNCH_CHECK();
     ctx->slab_rows = g.n_blocks;
     return BSC_OK;
@@ -282,31 +279,22 @@ int data_pass_impl(bsc_ctx* ctx, const char* who, int link, const float* X, int6
     if (rc != BSC_OK) return rc;
     ctx->slab_rows = 0;  // the slab is consumed here
     const dim3 rgrid((SLAB_STRIDE + BSC_WAVE - 1) / BSC_WAVE);
-    for (int s0 = 0; s0 < S; s0 += SG) {   // eight draws per launch
-        const int sg = S - s0 < SG ? S - s0 : SG;
-        launch_pass(ctx, link, X, ldx, y, o, v, B, (int)D, W + (int64_t)s0 * D, sg, g, slab);
-        BSC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(glm_slab_reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, slab, g.n_blocks, (int)D,
-                           (int)S, s0, ell, G);
-        BSC_LAUNCH_CHECK();
-    }
-    return BSC_OK;
+    return for_draw_chunks(
+        ctx, S,
+        [&](int s0, int sg) { launch_pass(ctx, link, X, ldx, y, o, v, B, (int)D, W + (int64_t)s0 * D, sg, g, slab); },
+        [&](int s0) {
+            hipLaunchKernelGGL(glm_slab_reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, slab, g.n_blocks, (int)D,
+                               (int)S, s0, ell, G);
+        });
 }
 
 int update_impl(bsc_ctx* ctx, const char* who, const double* stats, const double* lam_in, double* lam_out, double* m1,
                 double* m2, const double* eps, const float* W, int32_t D, int32_t S, double scale, double tau, int64_t t,
                 double lr, double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
                 double* eps_next, int32_t eps_next_ready, float* W_next, double* elbo, double* grad) {
-    BSC_REQUIRE(lam_in && lam_out && m1 && m2 && eps && W && elbo && grad, "%s: null pointer", who);
-    BSC_REQUIRE(lam_in != lam_out, "%s: lam_in and lam_out must differ", who);
-    BSC_REQUIRE(D > 0 && S >= 1 && S <= MAX_S, "%s: D=%d S=%d (S<=%d)", who, D, S, MAX_S);
-    BSC_REQUIRE(tau > 0.0, "%s: prior_precision=%g must be positive", who, tau);
-    BSC_REQUIRE(scale > 0.0, "%s: scale=%g must be positive", who, scale);
-    BSC_REQUIRE(t >= 1, "%s: the Adam step count starts at 1", who);
-    BSC_REQUIRE((eps_next && W_next) || (!eps_next && !W_next), "%s: next-draw buffers must be both set or both null",
-                who);
-    BSC_REQUIRE(!eps_next || (eps_next != eps && W_next != W), "%s: next-draw buffers must not alias the current draws",
-                who);
+    int rc = check_meanfield_update(who, lam_in && lam_out && m1 && m2 && eps && W && elbo && grad, lam_in, lam_out, D, S,
+                                    MAX_S, tau, /*has_gamma=*/false, 0.0, 0.0, scale, t);
+    if (rc != BSC_OK) return rc;
     GlmArgs a;
     a.stats = stats;
     a.slab = nullptr;
@@ -317,10 +305,10 @@ int update_impl(bsc_ctx* ctx, const char* who, const double* stats, const double
         a.slab = (const float*)ctx->workspace;
         a.n_slab = ctx->slab_rows;
     }
-    if (eps_next && !eps_next_ready) {   // the noise of next_step first (off the default path: drivers draw ahead)
-        const int rc = bsc_blr_noise(ctx, D, S, seed, next_step, 1, eps_next);
-        if (rc != BSC_OK) return rc;
-    }
+    // (the noise of next_step is drawn here off the default path only: drivers draw ahead)
+    rc = next_draw_noise(ctx, who, /*has_extra=*/false, eps, W, nullptr, eps_next, W_next, nullptr, D, S, seed, next_step,
+                         eps_next_ready);
+    if (rc != BSC_OK) return rc;
     a.lam_in = lam_in; a.lam_out = lam_out; a.m1 = m1; a.m2 = m2;
     a.eps = eps; a.W = W; a.eps_next = eps_next; a.W_next = W_next;
     a.elbo = elbo; a.grad = grad;

@@ -114,8 +114,8 @@ int bsc_glm_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam
     if (rc != BSC_OK) return rc;
     BSC_REQUIRE(prior_precision > 0.0, "%s: prior_precision=%g must be positive", who, prior_precision);
     BSC_REQUIRE(scale > 0.0, "%s: scale=%g must be positive", who, scale);
-    rc = fr_next_noise(ctx, who, /*has_xi=*/false, eps, W, nullptr, eps_next, W_next, nullptr, D, S, seed, next_step,
-                       eps_next_ready);
+    rc = next_draw_noise(ctx, who, /*has_extra=*/false, eps, W, nullptr, eps_next, W_next, nullptr, D, S, seed,
+                         next_step, eps_next_ready);
     if (rc != BSC_OK) return rc;
     GlmFullArgs a;
     a.stats = stats;

@@ -18,10 +18,12 @@
 //            without rows gets exactly 0.
 //
 // The finish (bsc_glm_hier_update) is two launches: the per-draw scalars in fixed order, then one thread per
-// coordinate of lam for the gradient, Adam and the next draws.
+// coordinate of lam for the gradient, Adam and the next draws.  Both bodies are csrc/bsc_meanfield.h's, shared with
+// csrc/bsc_glm_nb.hip; HierModel below is what this model adds to them.
 #include <vector>
 
 #include "bsc_glm_pass.h"
+#include "bsc_meanfield.h"
 
 namespace {
 
@@ -131,131 +133,62 @@ __global__ __launch_bounds__(256) void glm_group_sum_kernel(const int32_t* __res
 
 // ---- the finish -----------------------------------------------------------------------------------------------------
 
-struct HierArgs {
-    const double* stats;     // [ell (S) | G (S D) | H (S J)]
-    const double* lam_in;
-    double* lam_out;
-    double* m1;
-    double* m2;
-    const double* eps;       // [S, P]: columns 0 .. P - 2 stream 0, column P - 1 (zeta) stream 1
-    const float* W;          // [S, D]
+// z = [w (D) | b (J) | zeta]; scal = [ez (64) | g_zeta (64) | f (64) | sum rho];
+// c0 = D/2 log(prec / 2 pi) - J/2 log 2 pi + a0 log b0 - lnGamma(a0).
+struct HierModel : MeanfieldArgs {
     const float* Bz;         // [ceil(S / 8)][J][8]
-    const double* eps_next;  // nullptr: no next draw
-    float* W_next;
     float* Bz_next;
-    double* scal;            // [ez (64) | g_zeta (64) | f (64) | sum rho]
-    double* elbo;
-    double* grad;
-    int D, J, S;
-    double scale, tau, a0, b0;
-    double c0;               // the terms of log p(z) free of z: D/2 log(tau / 2 pi) - J/2 log 2 pi + a0 log b0 - lnGamma(a0)
-    bsc_adam adam;
-};
+    int J;
 
-constexpr int HIER_BLOCK = 256;
-constexpr int HIER_WAVES = HIER_BLOCK / BSC_WAVE;
+    static constexpr int N_SLOTS = 3;
+    static constexpr bool LAST_HAS_NEXT = false;   // zeta's next draw is made where it is used, in float64
 
-// the block's sum of one value per thread: waves in wave order
-__device__ __forceinline__ double hier_block_sum(double v, double* red) {
-    v = wave_allsum_f64(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-#pragma unroll
-    for (int k = 1; k < HIER_WAVES; ++k) t += red[k];
-    __syncthreads();
-    return t;
-}
+    // sum_j b_sj^2
+    static __device__ __forceinline__ double extra_sq(const HierModel& a, int s, double* red) {
+        const int J = a.J;
+        double pb = 0.0;
+        const float* bz = a.Bz + (int64_t)(s >> 3) * J * SG + (s & 7);
+        for (int j = threadIdx.x; j < J; j += MF_BLOCK) {
+            const double bv = (double)bz[(int64_t)j * SG];
+            pb += bv * bv;
+        }
+        return block_sum_f64<MF_WAVES>(pb, red);
+    }
 
-// Workgroup s < S: |w_s|^2, sum_j b_sj^2, zeta_s, g_zeta and f_s = scale ell_s + log p(z_s); workgroup S: sum rho.
-__global__ __launch_bounds__(HIER_BLOCK) void glm_hier_scalars_kernel(HierArgs a) {
-    __shared__ double red[HIER_WAVES];
-    const int tid = threadIdx.x;
-    const int D = a.D, J = a.J, S = a.S, P = D + J + 1;
-    const int s = (int)blockIdx.x;
-    if (s == S) {
-        double part = 0.0;
-        for (int i = tid; i < P; i += HIER_BLOCK) part += a.lam_in[P + i];
-        const double t = hier_block_sum(part, red);
-        if (tid == 0) a.scal[3 * MAX_S] = t;
-        return;
-    }
-    double pw = 0.0, pb = 0.0;
-    for (int d = tid; d < D; d += HIER_BLOCK) {
-        const double wv = (double)a.W[(int64_t)s * D + d];
-        pw += wv * wv;
-    }
-    const float* bz = a.Bz + (int64_t)(s >> 3) * J * SG + (s & 7);
-    for (int j = tid; j < J; j += HIER_BLOCK) {
-        const double bv = (double)bz[(int64_t)j * SG];
-        pb += bv * bv;
-    }
-    const double wsq = hier_block_sum(pw, red);
-    const double bsq = hier_block_sum(pb, red);
-    if (tid == 0) {
+    // zeta_s, g_zeta and f_s = scale ell_s + log p(z_s)
+    static __device__ __forceinline__ void draw_scalars(const HierModel& a, int s, double wsq, double bsq) {
+        const int J = a.J, P = a.P;
         const double zeta = a.lam_in[P - 1] + exp(a.lam_in[2 * P - 1]) * a.eps[(int64_t)s * P + P - 1];
         const double ez = exp(zeta);
         a.scal[s] = ez;
-        a.scal[MAX_S + s] = 0.5 * (double)J + a.a0 - ez * (a.b0 + 0.5 * bsq);
-        a.scal[2 * MAX_S + s] = a.scale * a.stats[s] + a.c0 - 0.5 * a.tau * wsq + 0.5 * (double)J * zeta -
-                                0.5 * ez * bsq + a.a0 * zeta - a.b0 * ez;
+        a.scal[MF_MAX_S + s] = 0.5 * (double)J + a.a0 - ez * (a.b0 + 0.5 * bsq);
+        a.scal[2 * MF_MAX_S + s] = a.scale * a.stats[s] + a.c0 - 0.5 * a.prec * wsq + 0.5 * (double)J * zeta -
+                                   0.5 * ez * bsq + a.a0 * zeta - a.b0 * ez;
     }
-}
 
-// One thread per coordinate i of z: gradient over the draws in draw order, Adam, the next draws.
-__global__ __launch_bounds__(HIER_BLOCK) void glm_hier_coord_kernel(HierArgs a) {
-    const int D = a.D, J = a.J, S = a.S, P = D + J + 1;
-    const int i = blockIdx.x * HIER_BLOCK + threadIdx.x;
-    if (i >= P) return;
-    const double* G = a.stats + S;
-    const double* H = a.stats + S + (int64_t)S * D;
-    double gm = 0.0, gr = 0.0;
-    for (int s = 0; s < S; ++s) {
-        double g;
-        if (i < D) {
-            g = a.scale * G[(int64_t)s * D + i] - a.tau * (double)a.W[(int64_t)s * D + i];
-        } else if (i < P - 1) {
-            const int j = i - D;
-            const double bv = (double)a.Bz[((int64_t)(s >> 3) * J + j) * SG + (s & 7)];
-            g = a.scale * H[(int64_t)s * J + j] - a.scal[s] * bv;
-        } else {
-            g = a.scal[MAX_S + s];
-        }
-        gm += g;
-        gr += g * a.eps[(int64_t)s * P + i];
-    }
-    const double inv_S = 1.0 / (double)S;
-    const double p_m = a.lam_in[i], p_rho = a.lam_in[P + i];
-    const double g_m = gm * inv_S;
-    const double g_r = gr * inv_S * exp(p_rho) + 1.0;
-    a.grad[i] = g_m;
-    a.grad[P + i] = g_r;
-    double q1 = a.m1[i], q2 = a.m2[i];
-    const double nm = bsc_adam_ascent(p_m, g_m, q1, q2, a.adam);
-    a.m1[i] = q1; a.m2[i] = q2;
-    q1 = a.m1[P + i]; q2 = a.m2[P + i];
-    const double nr = bsc_adam_ascent(p_rho, g_r, q1, q2, a.adam);
-    a.m1[P + i] = q1; a.m2[P + i] = q2;
-    a.lam_out[i] = nm;
-    a.lam_out[P + i] = nr;
-    if (i == P - 1) {
-        double fsum = 0.0;
-        for (int s = 0; s < S; ++s) fsum += a.scal[2 * MAX_S + s];
-        a.elbo[0] = fsum * inv_S + a.scal[3 * MAX_S] + 0.5 * (double)P * (1.0 + BSC_LOG_2PI);
-        return;     // zeta's next draw is made where it is used, in float64
-    }
-    if (!a.eps_next) return;
-    const double sd = exp(nr);
-    if (i < D) {
-        for (int s = 0; s < S; ++s) a.W_next[(int64_t)s * D + i] = (float)(nm + sd * a.eps_next[(int64_t)s * P + i]);
-    } else {
+    // b_j from H (behind G in stats) and the draw's precision e^zeta; zeta from g_zeta
+    static __device__ __forceinline__ double grad_term(const HierModel& a, int i, int s) {
+        const int D = a.D, J = a.J, S = a.S;
+        if (i == a.P - 1) return a.scal[MF_MAX_S + s];
+        const double* H = a.stats + S + (int64_t)S * D;
         const int j = i - D;
+        const double bv = (double)a.Bz[((int64_t)(s >> 3) * J + j) * SG + (s & 7)];
+        return a.scale * H[(int64_t)s * J + j] - a.scal[s] * bv;
+    }
+
+    static __device__ __forceinline__ void store_next(const HierModel& a, int i, double nm, double sd) {
+        const int J = a.J, S = a.S, P = a.P;
+        const int j = i - a.D;
         const int s_pad = (S + SG - 1) / SG * SG;      // the unused slots of the last chunk stay zero
         for (int s = 0; s < s_pad; ++s)
             a.Bz_next[((int64_t)(s >> 3) * J + j) * SG + (s & 7)] =
                 s < S ? (float)(nm + sd * a.eps_next[(int64_t)s * P + i]) : 0.f;
     }
-}
+};
+
+__global__ __launch_bounds__(MF_BLOCK) void glm_hier_scalars_kernel(HierModel a) { meanfield_scalars_body(a); }
+
+__global__ __launch_bounds__(MF_BLOCK) void glm_hier_coord_kernel(HierModel a) { meanfield_coord_body(a); }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
@@ -263,16 +196,12 @@ template <int LINK>
 void launch_group_link(bsc_ctx* ctx, int rows, const float* X, int64_t ldx, const float* y, const float* o,
                        const float* v, int64_t B, int D, const float* W, int sg, PassGrid g, float* slab,
                        const GlmGroupArgs& ga) {
-    const dim3 grid(g.n_blocks), block(PASS_BLOCK);
-    if (rows == MT_ROWS)
-        hipLaunchKernelGGL((glm_group_pass_mfma_kernel<LINK>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, W, sg,
-                           slab, g.n_iter, ga);
-    else if (D == GCOLS)
-        hipLaunchKernelGGL((glm_group_pass_kernel<LINK, true>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, D, W,
-                           sg, slab, g.n_iter, ga);
-    else
-        hipLaunchKernelGGL((glm_group_pass_kernel<LINK, false>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, D, W,
-                           sg, slab, g.n_iter, ga);
+    const auto go = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y, o, v, B, tail...);
+    };
+    launch_pass_shape(
+        rows, D, [&] { go(glm_group_pass_mfma_kernel<LINK>, W, sg, slab, g.n_iter, ga); },
+        [&](auto full) { go(glm_group_pass_kernel<LINK, decltype(full)::value>, D, W, sg, slab, g.n_iter, ga); });
 }
 
 size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -391,32 +320,32 @@ int bsc_glm_data_pass_groups(bsc_ctx* ctx, int32_t link, const float* X, int64_t
     const dim3 rgrid((SLAB_STRIDE + BSC_WAVE - 1) / BSC_WAVE);
     const unsigned seg_grid = (unsigned)((seg_bound + SEG_BLOCK / BSC_WAVE - 1) / (SEG_BLOCK / BSC_WAVE));
     const unsigned sum_grid = (unsigned)(((int64_t)J * SG + 255) / 256);
-    for (int s0 = 0; s0 < S; s0 += SG) {   // eight draws per launch: the pass, its slab reduce, its group sums
-        const int sg = S - s0 < SG ? S - s0 : SG;
-        ga.Bz = Bz + (int64_t)(s0 / SG) * J * SG;
-        {
-            bsc_prof_scope prof(ctx);  // times the pass kernel alone
+    return for_draw_chunks(
+        ctx, S,
+        [&](int s0, int sg) {
+            ga.Bz = Bz + (int64_t)(s0 / SG) * J * SG;
             if (link == BSC_GLM_LOGISTIC)
                 launch_group_link<BSC_GLM_LOGISTIC>(ctx, rows, X, ldx, y, offset, weight, B, D, W + (int64_t)s0 * D, sg,
                                                     pg, slab, ga);
             else
                 launch_group_link<BSC_GLM_POISSON>(ctx, rows, X, ldx, y, offset, weight, B, D, W + (int64_t)s0 * D, sg,
                                                    pg, slab, ga);
-        }
-        BSC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(glm_group_slab_reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, slab, pg.n_blocks,
-                           (int)D, (int)S, s0, ell, G);
-        BSC_LAUNCH_CHECK();
-        if (seg_grid) {
-            hipLaunchKernelGGL(glm_group_segment_kernel, dim3(seg_grid), dim3(SEG_BLOCK), 0, ctx->stream, plan, B,
-                               (int)J, seg_bound, (const float*)ga.R, segsum);
+        },
+        [&](int s0) {
+            hipLaunchKernelGGL(glm_group_slab_reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, slab, pg.n_blocks,
+                               (int)D, (int)S, s0, ell, G);
+        },
+        [&](int s0) -> int {   // the chunk's group sums
+            if (seg_grid) {
+                hipLaunchKernelGGL(glm_group_segment_kernel, dim3(seg_grid), dim3(SEG_BLOCK), 0, ctx->stream, plan, B,
+                                   (int)J, seg_bound, (const float*)ga.R, segsum);
+                BSC_LAUNCH_CHECK();
+            }
+            hipLaunchKernelGGL(glm_group_sum_kernel, dim3(sum_grid), dim3(256), 0, ctx->stream, plan, B, (int)J,
+                               seg_bound, (const double*)segsum, (int)S, s0, H);
             BSC_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(glm_group_sum_kernel, dim3(sum_grid), dim3(256), 0, ctx->stream, plan, B, (int)J, seg_bound,
-                           (const double*)segsum, (int)S, s0, H);
-        BSC_LAUNCH_CHECK();
-    }
-    return BSC_OK;
+            return BSC_OK;
+        });
 }
 
 int bsc_glm_hier_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
@@ -427,41 +356,31 @@ int bsc_glm_hier_update(bsc_ctx* ctx, const double* stats, const double* lam_in,
     BSC_CHECK_CTX(ctx);
     const char* who = "bsc_glm_hier_update";
     BSC_REQUIRE(stats, "%s: stats is null (pending pass partials are not read: pass [ell | G | H])", who);
-    BSC_REQUIRE(lam_in && lam_out && m1 && m2 && eps && W && Bz && elbo && grad, "%s: null pointer", who);
-    BSC_REQUIRE(lam_in != lam_out, "%s: lam_in and lam_out must differ", who);
-    BSC_REQUIRE(D > 0 && S >= 1 && S <= MAX_S, "%s: D=%d S=%d (S<=%d)", who, D, S, MAX_S);
-    BSC_REQUIRE(J >= 1 && J <= BSC_GLM_GROUP_MAX_J, "%s: J=%d must be in [1,%d]", who, J, BSC_GLM_GROUP_MAX_J);
-    BSC_REQUIRE(prior_precision > 0.0, "%s: prior_precision=%g must be positive", who, prior_precision);
-    BSC_REQUIRE(a0 > 0.0 && b0 > 0.0, "%s: a0=%g b0=%g must be positive", who, a0, b0);
-    BSC_REQUIRE(scale > 0.0, "%s: scale=%g must be positive", who, scale);
-    BSC_REQUIRE(t >= 1, "%s: the Adam step count starts at 1", who);
-    BSC_REQUIRE((eps_next && W_next && Bz_next) || (!eps_next && !W_next && !Bz_next),
-                "%s: next-draw buffers must be all set or all null", who);
-    BSC_REQUIRE(!eps_next || (eps_next != eps && W_next != W && Bz_next != Bz),
-                "%s: next-draw buffers must not alias the current draws", who);
-    const int P = D + J + 1;
-    void* ws = nullptr;
-    int rc = bsc_workspace(ctx, (3 * MAX_S + 8) * sizeof(double), &ws);
+    int rc = check_meanfield_update(who, lam_in && lam_out && m1 && m2 && eps && W && Bz && elbo && grad, lam_in, lam_out,
+                                    D, S, MAX_S, prior_precision, /*has_gamma=*/true, a0, b0, scale, t);
     if (rc != BSC_OK) return rc;
-    if (eps_next && !eps_next_ready) {   // the noise of next_step first (off the default path: drivers draw ahead)
-        rc = bsc_blr_noise(ctx, P - 1, S, seed, next_step, 1, eps_next);
-        if (rc != BSC_OK) return rc;
-    }
-    HierArgs a;
+    BSC_REQUIRE(J >= 1 && J <= BSC_GLM_GROUP_MAX_J, "%s: J=%d must be in [1,%d]", who, J, BSC_GLM_GROUP_MAX_J);
+    const int P = D + J + 1;
+    rc = next_draw_noise(ctx, who, /*has_extra=*/true, eps, W, Bz, eps_next, W_next, Bz_next, P - 1, S, seed, next_step,
+                         eps_next_ready);
+    if (rc != BSC_OK) return rc;
+    void* ws = nullptr;
+    rc = bsc_workspace(ctx, (HierModel::N_SLOTS * MAX_S + 8) * sizeof(double), &ws);
+    if (rc != BSC_OK) return rc;
+    HierModel a;
     a.stats = stats; a.lam_in = lam_in; a.lam_out = lam_out; a.m1 = m1; a.m2 = m2;
     a.eps = eps; a.W = W; a.Bz = Bz; a.eps_next = eps_next; a.W_next = W_next; a.Bz_next = Bz_next;
     a.scal = (double*)ws; a.elbo = elbo; a.grad = grad;
-    a.D = D; a.J = J; a.S = S;
-    a.scale = scale; a.tau = prior_precision; a.a0 = a0; a.b0 = b0;
+    a.D = D; a.J = J; a.S = S; a.P = P;
+    a.scale = scale; a.prec = prior_precision; a.a0 = a0; a.b0 = b0;
     a.c0 = 0.5 * (double)D * (log(prior_precision) - BSC_LOG_2PI) - 0.5 * (double)J * BSC_LOG_2PI + a0 * log(b0) -
            lgamma(a0);
     a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
     ctx->slab_rows = 0;   // the workspace is this finish's now
     {
         bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish, timed apart from the pass
-        hipLaunchKernelGGL(glm_hier_scalars_kernel, dim3(S + 1), dim3(HIER_BLOCK), 0, ctx->stream, a);
-        hipLaunchKernelGGL(glm_hier_coord_kernel, dim3((P + HIER_BLOCK - 1) / HIER_BLOCK), dim3(HIER_BLOCK), 0,
-                           ctx->stream, a);
+        hipLaunchKernelGGL(glm_hier_scalars_kernel, dim3(S + 1), dim3(MF_BLOCK), 0, ctx->stream, a);
+        hipLaunchKernelGGL(glm_hier_coord_kernel, dim3((P + MF_BLOCK - 1) / MF_BLOCK), dim3(MF_BLOCK), 0, ctx->stream, a);
     }
     BSC_LAUNCH_CHECK();
     return BSC_OK;

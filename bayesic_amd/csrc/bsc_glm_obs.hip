@@ -32,16 +32,11 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_obs_pass_mfma_kernel(
 template <int LINK>
 void launch_obs_link(bsc_ctx* ctx, int mfma, const float* X, int64_t ldx, const float* y, const float* o,
                      const float* v, int64_t B, int D, const float* W, int sg, int n_blocks, int n_iter, float* slab) {
-    const dim3 grid(n_blocks), block(PASS_BLOCK);
-    if (mfma)
-        hipLaunchKernelGGL((glm_obs_pass_mfma_kernel<LINK>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, W, sg,
-                           slab, n_iter);
-    else if (D == GCOLS)
-        hipLaunchKernelGGL((glm_obs_pass_kernel<LINK, true>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, D, W,
-                           sg, slab, n_iter);
-    else
-        hipLaunchKernelGGL((glm_obs_pass_kernel<LINK, false>), grid, block, 0, ctx->stream, X, ldx, y, o, v, B, D, W,
-                           sg, slab, n_iter);
+    const auto go = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y, o, v, B, tail...);
+    };
+    launch_pass_shape(mfma ? MT_ROWS : ROWS, D, [&] { go(glm_obs_pass_mfma_kernel<LINK>, W, sg, slab, n_iter); },
+                      [&](auto full) { go(glm_obs_pass_kernel<LINK, decltype(full)::value>, D, W, sg, slab, n_iter); });
 }
 
 }  // namespace

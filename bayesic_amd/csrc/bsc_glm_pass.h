@@ -622,6 +622,39 @@ inline int check_glm_obs_args(const char* who, int32_t link, const float* X, int
     return check_regress_args(who, X, ldx, B, D, W, S, max_s);
 }
 
+// The three kernels of a route: 16-row MFMA tiles, else 8-row tiles with D == 256 (FULL) or any D.  rows8 takes FULL
+// as std::true_type / std::false_type, so that the launch site names its 8-row kernel once.
+template <class Mfma, class Rows8>
+void launch_pass_shape(int rows, int D, Mfma mfma, Rows8 rows8) {
+    if (rows == MT_ROWS) mfma();
+    else if (D == GCOLS) rows8(std::true_type{});
+    else rows8(std::false_type{});
+}
+
+// All S draws, eight per launch: pass(s0, sg) launches the pass over draws s0 .. s0 + sg - 1 (timed alone),
+// reduce(s0) its slab reduction; tail(s0) is what else the chunk needs (the group sums) and returns a status.
+template <class Pass, class Reduce, class Tail>
+int for_draw_chunks(bsc_ctx* ctx, int S, Pass pass, Reduce reduce, Tail tail) {
+    for (int s0 = 0; s0 < S; s0 += SG) {
+        const int sg = S - s0 < SG ? S - s0 : SG;
+        {
+            bsc_prof_scope prof(ctx);  // times the pass kernel alone
+            pass(s0, sg);
+        }
+        BSC_LAUNCH_CHECK();
+        reduce(s0);
+        BSC_LAUNCH_CHECK();
+        const int rc = tail(s0);
+        if (rc != BSC_OK) return rc;
+    }
+    return BSC_OK;
+}
+
+template <class Pass, class Reduce>
+int for_draw_chunks(bsc_ctx* ctx, int S, Pass pass, Reduce reduce) {
+    return for_draw_chunks(ctx, S, pass, reduce, [](int) { return (int)BSC_OK; });
+}
+
 }  // namespace
 
 // The launch of the OBS kernels, defined in csrc/bsc_glm_obs.hip and called from csrc/bsc_glm.hip:

@@ -47,18 +47,10 @@ void launch_predict_nc(bsc_ctx* ctx, const PredictArgs& a, int n_blocks) {
     else hipLaunchKernelGGL((predict_kernel<FAM, NC, false>), grid, block, 0, ctx->stream, a);
 }
 
-// 16 draws per accumulator chunk: 1, 2 or 4 chunks (S in 33 .. 48 runs four, one of them empty).
 template <int FAM>
 void launch_predict(bsc_ctx* ctx, const PredictArgs& a, int n_blocks) {
-    if (a.S <= 16) launch_predict_nc<FAM, 1>(ctx, a, n_blocks);
-    else if (a.S <= 32) launch_predict_nc<FAM, 2>(ctx, a, n_blocks);
-    else launch_predict_nc<FAM, 4>(ctx, a, n_blocks);
+    predict_launch_chunks(a.S, [&](auto nc) { launch_predict_nc<FAM, decltype(nc)::value>(ctx, a, n_blocks); });
 }
-
-#define PREDICT_UNSUPPORTED(cond, ...)                                    \
-    do {                                                                  \
-        if (!(cond)) return bsc_fail(BSC_ERR_UNSUPPORTED, __VA_ARGS__);   \
-    } while (0)
 
 // Both entry points; `offset` is null for bsc_predict_pass.
 int predict_impl(bsc_ctx* ctx, const char* who, int32_t family, const float* X, int64_t ldx, const float* y,
@@ -67,47 +59,16 @@ int predict_impl(bsc_ctx* ctx, const char* who, int32_t family, const float* X, 
     BSC_REQUIRE(family == BSC_PREDICT_GAUSSIAN || family == BSC_PREDICT_LOGISTIC || family == BSC_PREDICT_POISSON,
                 "%s: family=%d must be BSC_PREDICT_GAUSSIAN (0), BSC_PREDICT_LOGISTIC (1) or BSC_PREDICT_POISSON (2)",
                 who, family);
-    BSC_REQUIRE(B >= 0, "%s: B=%lld", who, (long long)B);
-    BSC_REQUIRE((X || B == 0) && W, "%s: null pointer", who);
-    BSC_REQUIRE(mean || var || lpd || lpd_sum, "%s: no output requested", who);
-    BSC_REQUIRE(y || B == 0 || (!lpd && !lpd_sum), "%s: lpd and lpd_sum need y", who);
+    int rc = predict_check_batch(who, X, y, B, W, mean, var, lpd, lpd_sum);
+    if (rc != BSC_OK) return rc;
     BSC_REQUIRE(family != BSC_PREDICT_GAUSSIAN || logvar, "%s: the Gaussian family needs logvar[S]", who);
     BSC_REQUIRE(family != BSC_PREDICT_GAUSSIAN || !offset,
                 "%s: offset is for BSC_PREDICT_LOGISTIC and BSC_PREDICT_POISSON; the Gaussian family takes none", who);
     BSC_REQUIRE((((uintptr_t)offset) & 3) == 0, "%s: offset must be 4-byte aligned", who);
-    PREDICT_UNSUPPORTED(D > 0 && D <= WCOLS && D % 4 == 0, "%s: D=%d must be a multiple of 4 in [4,%d]", who, D, WCOLS);
-    PREDICT_UNSUPPORTED(S >= 1 && S <= P_MAX_S, "%s: S=%d must be in [1,%d]", who, S, P_MAX_S);
-    PREDICT_UNSUPPORTED(ldx >= D && ldx % 4 == 0 && ldx < ((int64_t)1 << 26),
-                        "%s: ldx=%lld must be >= D, %% 4 == 0 and < 2^26", who, (long long)ldx);
-    PREDICT_UNSUPPORTED(((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: X and W must be 16-byte aligned",
-                        who);
-    if (B == 0) {
-        if (lpd_sum) BSC_HIP(hipMemsetAsync(lpd_sum, 0, sizeof(double), ctx->stream));
-        return BSC_OK;
-    }
-    // one workgroup per CU; every wave runs the same number of tiles
-    const int64_t n_tiles = (B + T_ROWS - 1) / T_ROWS;
-    const int64_t max_waves = (int64_t)P_WAVES * ctx->cu_count;
-    const int64_t n_iter = (n_tiles + max_waves - 1) / max_waves;
-    PREDICT_UNSUPPORTED(n_iter < ((int64_t)1 << 30), "%s: B=%lld is too large", who, (long long)B);
-    const int64_t waves = (n_tiles + n_iter - 1) / n_iter;
-    const int n_blocks = (int)((waves + P_WAVES - 1) / P_WAVES);
-
     PredictArgs a;
-    a.X = X; a.ldx = ldx; a.y = y; a.B = B; a.W = W; a.logvar = logvar;
-    a.mean = mean; a.var = var; a.lpd = lpd; a.partial = nullptr;
-    a.D = D; a.S = S;
-    a.n_iter = (int)n_iter;
-    a.n_strips = D > STRIP ? 2 : 1;
-    a.kw = D > STRIP ? STRIP / 4 : ((D + 7) / 8) * 2;
-    a.do_lp = (y && (lpd || lpd_sum)) ? 1 : 0;
-    if (lpd_sum) {
-        void* ws = nullptr;
-        const int rc = bsc_workspace(ctx, (size_t)n_blocks * sizeof(double), &ws);
-        if (rc != BSC_OK) return rc;
-        ctx->slab_rows = 0;   // pass partials that were pending in the workspace are gone
-        a.partial = (double*)ws;
-    }
+    int n_blocks = 0;
+    rc = predict_setup(ctx, who, X, ldx, y, B, D, W, logvar, S, mean, var, lpd, lpd_sum, &a, &n_blocks);
+    if (rc != BSC_OK || n_blocks == 0) return rc;
     {
         bsc_prof_scope prof(ctx);
         if (offset) bsc_predict_offset_launch(ctx, family, &a, offset, n_blocks);

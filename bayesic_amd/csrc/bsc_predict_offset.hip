@@ -18,12 +18,9 @@ void launch_offset_nc(bsc_ctx* ctx, const PredictArgs& a, const float* offset, i
     else hipLaunchKernelGGL((predict_offset_kernel<FAM, NC, false>), grid, block, 0, ctx->stream, a, offset);
 }
 
-// 16 draws per accumulator chunk, as launch_predict
 template <int FAM>
 void launch_offset(bsc_ctx* ctx, const PredictArgs& a, const float* offset, int n_blocks) {
-    if (a.S <= 16) launch_offset_nc<FAM, 1>(ctx, a, offset, n_blocks);
-    else if (a.S <= 32) launch_offset_nc<FAM, 2>(ctx, a, offset, n_blocks);
-    else launch_offset_nc<FAM, 4>(ctx, a, offset, n_blocks);
+    predict_launch_chunks(a.S, [&](auto nc) { launch_offset_nc<FAM, decltype(nc)::value>(ctx, a, offset, n_blocks); });
 }
 
 }  // namespace

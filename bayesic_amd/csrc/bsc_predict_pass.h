@@ -2,7 +2,9 @@
 // one compile-time flag so that two translation units can instantiate it: OFFS = false is predict_kernel of
 // csrc/bsc_predict.hip, unchanged; OFFS = true is predict_offset_kernel of csrc/bsc_predict_offset.hip, which adds a
 // per-row offset o_n to l_ns = x_n . w_s before the link (logistic and Poisson families: log E[y_n] = x_n . w +
-// log exposure_n).  Header-only, internal linkage, like csrc/bsc_regress.h.
+// log exposure_n).  The host side at the end is the envelope of the entry points (predict_check_batch, predict_setup,
+// predict_launch_chunks), shared by csrc/bsc_predict.hip and csrc/bsc_glm_nb.hip.  Header-only, internal linkage, like
+// csrc/bsc_regress.h.
 #pragma once
 
 #include "bsc_regress.h"
@@ -316,6 +318,73 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
             a.partial[blockIdx.x] = tot;
         }
     }
+}
+
+// ---- host side: the envelope of the predictive entry points, in two halves around the family's own checks ----------
+
+#define PREDICT_UNSUPPORTED(cond, ...)                                    \
+    do {                                                                  \
+        if (!(cond)) return bsc_fail(BSC_ERR_UNSUPPORTED, __VA_ARGS__);   \
+    } while (0)
+
+inline int predict_check_batch(const char* who, const float* X, const float* y, int64_t B, const float* W,
+                               const float* mean, const float* var, const float* lpd, const double* lpd_sum) {
+    BSC_REQUIRE(B >= 0, "%s: B=%lld", who, (long long)B);
+    BSC_REQUIRE((X || B == 0) && W, "%s: null pointer", who);
+    BSC_REQUIRE(mean || var || lpd || lpd_sum, "%s: no output requested", who);
+    BSC_REQUIRE(y || B == 0 || (!lpd && !lpd_sum), "%s: lpd and lpd_sum need y", who);
+    return BSC_OK;
+}
+
+// The shapes the kernels take, the grid, the arguments and the workspace of lpd_sum's block partials.  *n_blocks = 0:
+// an empty batch, lpd_sum is zeroed and there is nothing to launch.
+inline int predict_setup(bsc_ctx* ctx, const char* who, const float* X, int64_t ldx, const float* y, int64_t B,
+                         int32_t D, const float* W, const float* logvar, int32_t S, float* mean, float* var, float* lpd,
+                         double* lpd_sum, PredictArgs* args, int* n_blocks) {
+    PREDICT_UNSUPPORTED(D > 0 && D <= WCOLS && D % 4 == 0, "%s: D=%d must be a multiple of 4 in [4,%d]", who, D, WCOLS);
+    PREDICT_UNSUPPORTED(S >= 1 && S <= P_MAX_S, "%s: S=%d must be in [1,%d]", who, S, P_MAX_S);
+    PREDICT_UNSUPPORTED(ldx >= D && ldx % 4 == 0 && ldx < ((int64_t)1 << 26),
+                        "%s: ldx=%lld must be >= D, %% 4 == 0 and < 2^26", who, (long long)ldx);
+    PREDICT_UNSUPPORTED(((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: X and W must be 16-byte aligned",
+                        who);
+    *n_blocks = 0;
+    if (B == 0) {
+        if (lpd_sum) BSC_HIP(hipMemsetAsync(lpd_sum, 0, sizeof(double), ctx->stream));
+        return BSC_OK;
+    }
+    // one workgroup per CU; every wave runs the same number of tiles
+    const int64_t n_tiles = (B + T_ROWS - 1) / T_ROWS;
+    const int64_t max_waves = (int64_t)P_WAVES * ctx->cu_count;
+    const int64_t n_iter = (n_tiles + max_waves - 1) / max_waves;
+    PREDICT_UNSUPPORTED(n_iter < ((int64_t)1 << 30), "%s: B=%lld is too large", who, (long long)B);
+    const int64_t waves = (n_tiles + n_iter - 1) / n_iter;
+    *n_blocks = (int)((waves + P_WAVES - 1) / P_WAVES);
+
+    PredictArgs& a = *args;
+    a.X = X; a.ldx = ldx; a.y = y; a.B = B; a.W = W; a.logvar = logvar;
+    a.mean = mean; a.var = var; a.lpd = lpd; a.partial = nullptr;
+    a.D = D; a.S = S;
+    a.n_iter = (int)n_iter;
+    a.n_strips = D > STRIP ? 2 : 1;
+    a.kw = D > STRIP ? STRIP / 4 : ((D + 7) / 8) * 2;
+    a.do_lp = (y && (lpd || lpd_sum)) ? 1 : 0;
+    if (lpd_sum) {
+        void* ws = nullptr;
+        const int rc = bsc_workspace(ctx, (size_t)*n_blocks * sizeof(double), &ws);
+        if (rc != BSC_OK) return rc;
+        ctx->slab_rows = 0;   // pass partials that were pending in the workspace are gone
+        a.partial = (double*)ws;
+    }
+    return BSC_OK;
+}
+
+// 16 draws per accumulator chunk: launch(NC) with NC = 1, 2 or 4 chunks as std::integral_constant (S in 33 .. 48 runs
+// four, one of them empty).
+template <class F>
+void predict_launch_chunks(int S, F launch) {
+    if (S <= 16) launch(std::integral_constant<int, 1>{});
+    else if (S <= 32) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 4>{});
 }
 
 }  // namespace

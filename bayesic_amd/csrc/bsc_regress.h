@@ -1,5 +1,7 @@
 // Scaffolding shared by the regression SVI passes and their finishes: csrc/bsc_blr.hip, bsc_glm.hip, bsc_softmax.hip,
-// bsc_predict.hip and the two full-covariance finishes (csrc/bsc_fullrank.h).  Header-only, internal linkage: every
+// bsc_predict.hip, the two full-covariance finishes (csrc/bsc_fullrank.h) and the two-launch mean-field finishes
+// (csrc/bsc_meanfield.h).  The host side ends with what every finishing entry point checks and does alike
+// (check_meanfield_update, next_draw_noise).  Header-only, internal linkage: every
 // .hip is compiled on its own without relocatable device code, so each gets its own copy and the named kernels stay
 // in their files.  What lives here has to give the same bits wherever it is used (the mean-field and full-covariance
 // finishes are compared bit for bit, the slab reduction promises the same bytes run to run), hence one definition.
@@ -239,7 +241,7 @@ __device__ __forceinline__ double bsc_adam_ascent(double lam, double g, double& 
     return lam + a.lr * mhat / (sqrt(vhat) + a.eps);
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------
+// ---- host side: the passes -----------------------------------------------------------------------------------------
 
 // Grid and per-wave trip count: fill the resident wave slots, then balance so
 // that every wave runs the same number of (almost all real) tiles.
@@ -287,6 +289,39 @@ inline int check_regress_args(const char* who, const float* X, int64_t ldx, int6
                               int32_t S, int max_s) {
     const int rc = check_regress_batch(who, X, B, W);
     return rc != BSC_OK ? rc : check_regress_shape(who, X, ldx, D, W, S, max_s);
+}
+
+// ---- host side: what the finishing entry points check and do alike ------------------------------------------------
+
+// The checks every mean-field finish makes of its state and its scalars, in the order they have always been made;
+// `pointers_set`: the caller's own list.  has_gamma: the model has a Gamma(a0, b0) prior on a scalar latent.  A check
+// of the model's own (stats, J) stays with the caller.
+inline int check_meanfield_update(const char* who, bool pointers_set, const double* lam_in, const double* lam_out,
+                                  int32_t D, int32_t S, int max_s, double prior_precision, bool has_gamma, double a0,
+                                  double b0, double scale, int64_t t) {
+    BSC_REQUIRE(pointers_set, "%s: null pointer", who);
+    BSC_REQUIRE(lam_in != lam_out, "%s: lam_in and lam_out must differ", who);
+    BSC_REQUIRE(D > 0 && S >= 1 && S <= max_s, "%s: D=%d S=%d (S<=%d)", who, D, S, max_s);
+    BSC_REQUIRE(prior_precision > 0.0, "%s: prior_precision=%g must be positive", who, prior_precision);
+    BSC_REQUIRE(!has_gamma || (a0 > 0.0 && b0 > 0.0), "%s: a0=%g b0=%g must be positive", who, a0, b0);
+    BSC_REQUIRE(scale > 0.0, "%s: scale=%g must be positive", who, scale);
+    BSC_REQUIRE(t >= 1, "%s: the Adam step count starts at 1", who);
+    return BSC_OK;
+}
+
+// The next-draw buffers (all set or all null, none of them its current twin; has_extra: the model has a latent besides
+// W with buffers of its own -- xi, Bz, logphi), then the next step's noise in bsc_blr_noise's layout, `noise_dim`
+// stream-0 columns, unless the caller has drawn it.
+inline int next_draw_noise(bsc_ctx* ctx, const char* who, bool has_extra, const double* eps, const float* W,
+                           const void* extra, double* eps_next, float* W_next, const void* extra_next,
+                           int32_t noise_dim, int32_t S, uint64_t seed, uint32_t next_step, int32_t eps_next_ready) {
+    const char* how_many = has_extra ? "all" : "both";
+    BSC_REQUIRE((eps_next && W_next && (extra_next || !has_extra)) || (!eps_next && !W_next && !extra_next),
+                "%s: next-draw buffers must be %s set or %s null", who, how_many, how_many);
+    BSC_REQUIRE(!eps_next || (eps_next != eps && W_next != W && (!has_extra || extra_next != extra)),
+                "%s: next-draw buffers must not alias the current draws", who);
+    if (eps_next && !eps_next_ready) return bsc_blr_noise(ctx, noise_dim, S, seed, next_step, 1, eps_next);
+    return BSC_OK;
 }
 
 }  // namespace

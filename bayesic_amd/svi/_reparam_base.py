@@ -1,4 +1,5 @@
-"""What the reparameterised regression drivers (svi/blr.py, svi/glm.py, svi/softmax.py, svi/hier_glm.py) share.
+"""What the reparameterised regression drivers (svi/blr.py, svi/glm.py, svi/softmax.py, svi/hier_glm.py, svi/glm_nb.py)
+share.
 
 A Gaussian guide over P flattened parameters: ``covariance="diag"`` lam = [m (P) | rho (P)], ``"full"`` lam =
 [mu (P) | L packed row-major, lower triangle incl. the diagonal, rho_i = log L_ii in the diagonal slots]
@@ -65,6 +66,24 @@ def first_draw(lam, eps, P, covariance):
         mu, L = unpack_full(lam, P)
         return mu[None, :] + eps @ L.T
     return lam[None, :P] + np.exp(lam[None, P:]) * eps
+
+
+def check_priors(prior_precision, a0, b0, gamma_of):
+    """prior_precision and the Gamma(a0, b0) prior of ``gamma_of`` (the message's noun)."""
+    if not float(prior_precision) > 0.0:
+        raise ValueError("prior_precision must be positive")
+    if not (float(a0) > 0.0 and float(b0) > 0.0):
+        raise ValueError("a0 and b0 (the Gamma prior of %s) must be positive" % gamma_of)
+
+
+def check_n_samples(n_samples):
+    if not 1 <= int(n_samples) <= 64:
+        raise ValueError("n_samples must be in [1, 64]")
+
+
+def check_lam0(lam0, P, layout):
+    if lam0 is not None and np.asarray(lam0).size != 2 * P:
+        raise ValueError("lam0 has %d entries; [m | rho] over [%s] needs %d" % (np.asarray(lam0).size, layout, 2 * P))
 
 
 def float_batch(ctx, X, y, need_y=True):
@@ -195,6 +214,22 @@ class ReparamDriver:
         eps = self._eps[step % self._ring].cpu().numpy().reshape(self.S, self._noise_dim + 1)[:, :self.P]
         return first_draw(self._lam[self.cur].cpu().numpy(), eps, self.P, self.covariance_kind)
 
+    def _store_W(self, z, cols):
+        """The first ``cols`` columns of a first draw z (float32 [S, P]) into the current W."""
+        import torch
+        self._W[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :cols]).reshape(-1)))
+
+    def _finish_latent(self, name, stats, extra, dims):
+        """_finish of a mean-field model with a Gamma(a0, b0) prior and one latent besides W, through entry point
+        ``name``; ``extra``: that latent's [2, .] double buffer, ``dims``: the sizes the call takes before S."""
+        c, n, t = self.cur, 1 - self.cur, self.t + 1
+        self._ensure_noise(t)
+        self.ctx.call(name, stats, self._lam[c], self._lam[n], self.m1, self.m2, self._eps[self.t % self._ring],
+                      self._W[c], extra[c], *dims, self.S, self.scale, self.prior_precision, self.a0, self.b0, t,
+                      self.lr, 0.9, 0.999, 1e-8, self.seed, t, self._eps[t % self._ring], 1, self._W[n], extra[n],
+                      self.elbo, self.grad)
+        self.t = t
+
     def all_reduce(self):
         self.exchange.all_reduce(self.stats)
 
@@ -214,9 +249,7 @@ class ReparamRegressionBase(ReparamDriver):
 
     def sample(self, step):
         """The first draw (first_draw), rounded to float32 as the finish rounds."""
-        import torch
-        W = self._first_draw(step).astype(np.float32)
-        self._W[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(W).reshape(-1)))
+        self._store_W(self._first_draw(step).astype(np.float32), self.P)
         self._drawn = True
 
     def _tail(self, t):

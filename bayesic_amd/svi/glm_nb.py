@@ -31,18 +31,14 @@ import math
 import numpy as np
 
 from ._obs import ObsBatch, batch_obs, check_link
-from ._reparam_base import ReparamDriver
+from ._reparam_base import ReparamDriver, check_lam0, check_n_samples, check_priors
 
 
 def check_arguments(prior_precision, a0, b0, n_samples, offset, exposure):
     """The constructor's checks that need no device."""
     check_link("poisson", offset, exposure)      # a count model: exposure is allowed, not together with offset
-    if not float(prior_precision) > 0.0:
-        raise ValueError("prior_precision must be positive")
-    if not (float(a0) > 0.0 and float(b0) > 0.0):
-        raise ValueError("a0 and b0 (the Gamma prior of the dispersion) must be positive")
-    if not 1 <= int(n_samples) <= 64:
-        raise ValueError("n_samples must be in [1, 64]")
+    check_priors(prior_precision, a0, b0, "the dispersion")
+    check_n_samples(n_samples)
 
 
 def check_counts(y):
@@ -82,8 +78,7 @@ class NegBinReparamSVI(ObsBatch, ReparamDriver):
         self.has_offset = self._oarg is not None      # predict() refuses to run without one
         D, S = self.D, int(n_samples)
         P = D + 1
-        if lam0 is not None and np.asarray(lam0).size != 2 * P:
-            raise ValueError("lam0 has %d entries; [m | rho] over [w (%d) | tau] needs %d" % (np.asarray(lam0).size, D, 2 * P))
+        check_lam0(lam0, P, "w (%d) | tau" % D)
         # stats = [ell | G | T]; the slab of the pass is 8 * 256 + 16 floats per workgroup
         self._init_state(P, lam0, n_total, S, seed, lr, group, noise_dim=D, w_cols=D, n_stats=S * (D + 2),
                          reserve_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 16) * 4)
@@ -109,10 +104,9 @@ class NegBinReparamSVI(ObsBatch, ReparamDriver):
     def sample(self, step):
         """The first draw (first_draw) of w and tau, rounded to float32 as the finish rounds."""
         import torch
-        c, D = self.cur, self.D
         z = self._first_draw(step).astype(np.float32)
-        self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :D]).reshape(-1)))
-        self._logphi[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, D])))
+        self._store_W(z, self.D)
+        self._logphi[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(z[:, self.D])))
         self._drawn = True
 
     def data_pass(self):
@@ -120,15 +114,7 @@ class NegBinReparamSVI(ObsBatch, ReparamDriver):
                       self.W, self.logphi, self.S, self.ell, self.G, self.T)
 
     def _finish(self, stats):
-        """Gradient + Adam + next draws from all-reduced statistics; flips the double buffer."""
-        c, n = self.cur, 1 - self.cur
-        t = self.t + 1
-        self._ensure_noise(t)
-        self.ctx.call("bsc_glm_nb_update", stats, self._lam[c], self._lam[n], self.m1, self.m2,
-                      self._eps[self.t % self._ring], self._W[c], self._logphi[c], self.D, self.S, self.scale,
-                      self.prior_precision, self.a0, self.b0, t, self.lr, 0.9, 0.999, 1e-8, self.seed, t,
-                      self._eps[t % self._ring], 1, self._W[n], self._logphi[n], self.elbo, self.grad)
-        self.t = t
+        self._finish_latent("bsc_glm_nb_update", stats, self._logphi, (self.D,))
 
     # -- posterior predictive (svi/predict.py: one bsc_nb_predict_pass over X for all draws) -----------------------
     def predict(self, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):

@@ -28,7 +28,7 @@ import ctypes
 import numpy as np
 
 from ._obs import LINKS, ObsBatch, batch_obs, check_link
-from ._reparam_base import ReparamDriver
+from ._reparam_base import ReparamDriver, check_lam0, check_n_samples, check_priors
 
 MAX_GROUPS = 65536          # include/bayesic_hip.h: BSC_GLM_GROUP_MAX_J
 
@@ -41,10 +41,7 @@ def check_arguments(link, n_groups, prior_precision, a0, b0, covariance, offset,
     check_link(link, offset, exposure)
     if int(n_groups) != n_groups or not 1 <= int(n_groups) <= MAX_GROUPS:
         raise ValueError("n_groups must be an integer in [1, %d], got %r" % (MAX_GROUPS, n_groups))
-    if not float(prior_precision) > 0.0:
-        raise ValueError("prior_precision must be positive")
-    if not (float(a0) > 0.0 and float(b0) > 0.0):
-        raise ValueError("a0 and b0 (the Gamma prior of the intercepts' precision) must be positive")
+    check_priors(prior_precision, a0, b0, "the intercepts' precision")
 
 
 class HierGLMReparamSVI(ObsBatch, ReparamDriver):
@@ -54,8 +51,7 @@ class HierGLMReparamSVI(ObsBatch, ReparamDriver):
         """``groups``: int32 [B], ids in [0, n_groups) (checked here and in set_batch, where the plan is built).
         ``group``: the torch.distributed process group of a data-parallel job, as in the other drivers."""
         check_arguments(link, n_groups, prior_precision, a0, b0, covariance, offset, exposure)
-        if not 1 <= int(n_samples) <= 64:
-            raise ValueError("n_samples must be in [1, 64]")
+        check_n_samples(n_samples)
         from ..device import default_context
         self.link, self._link = link, LINKS[link]
         self.covariance_kind = "diag"
@@ -67,9 +63,7 @@ class HierGLMReparamSVI(ObsBatch, ReparamDriver):
         groups = self._checked_groups(groups, self.B)
         D, J, S = self.D, self.J, int(n_samples)
         P = D + J + 1
-        if lam0 is not None and np.asarray(lam0).size != 2 * P:
-            raise ValueError("lam0 has %d entries; [m | rho] over [w (%d) | b (%d) | zeta] needs %d"
-                             % (np.asarray(lam0).size, D, J, 2 * P))
+        check_lam0(lam0, P, "w (%d) | b (%d) | zeta" % (D, J))
         import torch
         # stats = [ell | G | H]; the pass's workspace is reserved with the plan (_build_plan)
         self._init_state(P, lam0, n_total, S, seed, lr, group, noise_dim=D + J, w_cols=D, n_stats=S * (1 + D + J))
@@ -151,10 +145,9 @@ class HierGLMReparamSVI(ObsBatch, ReparamDriver):
         """The first draw (first_draw) of w and b, rounded to float32 as the finish rounds.  zeta is drawn where it is
         used."""
         import torch
-        c, D, J = self.cur, self.D, self.J
         z = self._first_draw(step).astype(np.float32)
-        self._W[c].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :D]).reshape(-1)))
-        self._Bz[c].copy_(torch.from_numpy(self.chunked(z[:, D:D + J])))
+        self._store_W(z, self.D)
+        self._Bz[self.cur].copy_(torch.from_numpy(self.chunked(z[:, self.D:self.D + self.J])))
         self._drawn = True
 
     def data_pass(self):
@@ -162,15 +155,7 @@ class HierGLMReparamSVI(ObsBatch, ReparamDriver):
                       self._garg, self.plan, self.B, self.D, self.J, self.W, self.Bz, self.S, self.ell, self.G, self.H)
 
     def _finish(self, stats):
-        """Gradient + Adam + next draws from all-reduced statistics; flips the double buffer."""
-        c, n = self.cur, 1 - self.cur
-        t = self.t + 1
-        self._ensure_noise(t)
-        self.ctx.call("bsc_glm_hier_update", stats, self._lam[c], self._lam[n], self.m1, self.m2,
-                      self._eps[self.t % self._ring], self._W[c], self._Bz[c], self.D, self.J, self.S, self.scale,
-                      self.prior_precision, self.a0, self.b0, t, self.lr, 0.9, 0.999, 1e-8, self.seed, t,
-                      self._eps[t % self._ring], 1, self._W[n], self._Bz[n], self.elbo, self.grad)
-        self.t = t
+        self._finish_latent("bsc_glm_hier_update", stats, self._Bz, (self.D, self.J))
 
     # -- what this version does not do ----------------------------------------------------------------------------
     def predict(self, *args, **kwargs):

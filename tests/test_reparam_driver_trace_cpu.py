@@ -1,12 +1,13 @@
-"""The C-ABI calls of the four reparameterised drivers, written down by tests/_trace_ctx.TraceContext and compared with
-tests/golden/reparam_driver_traces.json: for every case the names, scalar arguments, buffers (and which half of each
+"""The C-ABI calls of the five reparameterised drivers, written down by tests/_trace_ctx.TraceContext and compared with
+tests/golden/reparam_driver_traces.json (the negative-binomial cases: reparam_driver_traces_negbin.json): for every
+case the names, scalar arguments, buffers (and which half of each
 double buffer) and reserve sizes of construction, posterior_draws, three steps, set_batch with tensors, a step,
-set_batch with raw pointers and one more step; with SHA-256 digests of the start lam, of the first draw (W, and xi or
-Bz where the driver has them) and of the predictive draws, all of which the drivers compute on the host.  Equality,
-not closeness: the drivers' numerics are pinned on the device by the GPU tests, and this shows that the same calls
-reach the library.
+set_batch with raw pointers and one more step; with SHA-256 digests of the start lam, of the first draw (W, and xi, Bz
+or logphi where the driver has them) and of the predictive draws, all of which the drivers compute on the host.
+Equality, not closeness: the drivers' numerics are pinned on the device by the GPU tests, and this shows that the same
+calls reach the library.
 
-``python tests/test_reparam_driver_trace_cpu.py`` writes the golden file from the tree it runs in.
+``python tests/test_reparam_driver_trace_cpu.py`` writes the golden files from the tree it runs in.
 """
 import json
 import os
@@ -18,6 +19,8 @@ import torch
 from _trace_ctx import TraceContext
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reparam_driver_traces.json")
+# the negative-binomial cases came later and have a file of their own: the first one stays as it was, byte for byte
+GOLDEN_NEGBIN = GOLDEN[:-5] + "_negbin.json"
 B, D, J, K, B2, LD2 = 40, 12, 5, 3, 24, 16
 RAW = dict(X=0x10000, y=0x20000, offset=0x30000, weights=0x40000, groups=0x50000)
 
@@ -58,6 +61,11 @@ def _hier(obs=(), **kw):
     return HierGLMReparamSVI, ("X", "y", "groups"), dict(kw, n_groups=J), obs
 
 
+def _negbin(obs=(), **kw):
+    from bayesic_amd.svi import NegBinReparamSVI
+    return NegBinReparamSVI, ("X", "y"), kw, obs
+
+
 CASES = {
     "blr-diag-S8": lambda: _blr(n_samples=8),
     "blr-diag-S16": lambda: _blr(n_samples=16),
@@ -75,6 +83,9 @@ CASES = {
     "hier-S8": lambda: _hier(n_samples=8),
     "hier-S12": lambda: _hier(n_samples=12),
     "hier-offset-weights": lambda: _hier(("offset", "weights")),
+    "negbin-S8": lambda: _negbin(n_samples=8),
+    "negbin-S12": lambda: _negbin(n_samples=12),
+    "negbin-exposure-weights": lambda: _negbin(("exposure", "weights")),
 }
 
 
@@ -96,7 +107,7 @@ def record(case):
         ctx.bind(model)
     model.step()
     ctx.bind(model)
-    for attr in ("_W", "_xi", "_Bz"):
+    for attr in ("_W", "_xi", "_Bz", "_logphi"):
         if hasattr(model, attr):
             ctx.digest(attr, getattr(model, attr))
     model.step()
@@ -117,8 +128,11 @@ def record(case):
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(GOLDEN) as f:
-        return json.load(f)
+    traces = {}
+    for path in (GOLDEN, GOLDEN_NEGBIN):
+        with open(path) as f:
+            traces.update(json.load(f))
+    return traces
 
 
 def test_every_case_has_a_recorded_trace(golden):
@@ -136,6 +150,8 @@ def test_driver_makes_the_recorded_calls(case, golden):
 if __name__ == "__main__":
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    with open(GOLDEN, "w") as f:
-        json.dump({case: record(case) for case in sorted(CASES)}, f, separators=(",", ":"), sort_keys=True)
-        f.write("\n")
+    for path in (GOLDEN, GOLDEN_NEGBIN):
+        mine = [case for case in sorted(CASES) if case.startswith("negbin-") == (path == GOLDEN_NEGBIN)]
+        with open(path, "w") as f:
+            json.dump({case: record(case) for case in mine}, f, separators=(",", ":"), sort_keys=True)
+            f.write("\n")
