@@ -139,6 +139,10 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_nb_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_predict_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                        c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "bsc_group_ids_check": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32]),
     "bsc_softmax_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_int32, c_void_p, c_void_p]),
     "bsc_softmax_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,

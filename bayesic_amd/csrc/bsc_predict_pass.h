@@ -2,8 +2,11 @@
 // one compile-time flag so that two translation units can instantiate it: OFFS = false is predict_kernel of
 // csrc/bsc_predict.hip, unchanged; OFFS = true is predict_offset_kernel of csrc/bsc_predict_offset.hip, which adds a
 // per-row offset o_n to l_ns = x_n . w_s before the link (logistic and Poisson families: log E[y_n] = x_n . w +
-// log exposure_n).  The host side at the end is the envelope of the entry points (predict_check_batch, predict_setup,
-// predict_launch_chunks), shared by csrc/bsc_predict.hip and csrc/bsc_glm_nb.hip.  Header-only, internal linkage, like
+// log exposure_n).  GRP = true (always with OFFS) is predict_group_kernel of csrc/bsc_predict_group.hip: a per-draw,
+// per-group intercept b_s[g_n] joins o_n, gathered from a table Bt [J + 1][ldb] by the row's group id (PredictGroups
+// below).  With GRP off nothing of it is compiled: the shipped instantiations keep their code.  The host side at the end
+// is the envelope of the entry points (predict_check_batch, predict_setup, predict_launch_chunks), shared by
+// csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like
 // csrc/bsc_regress.h.
 #pragma once
 
@@ -77,6 +80,42 @@ __device__ __forceinline__ float load_offset(const float* __restrict__ offset, i
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(os, 4 * i16, 0, 0));
 }
 
+// GRP: the group ids of the rows, g [B] (int32; -1 = a group not seen in training), and the intercept draws
+// Bt [J + 1][ldb] (float32, draws contiguous: Bt[j][s] = b_s[j], row J the unseen group's draws).
+struct PredictGroups {
+    const int32_t* g = nullptr;
+    const float* Bt = nullptr;
+    int J = 0;
+    int ldb = 0;
+};
+constexpr int P_MAX_LDB = 8192;   // (J + 2) ldb 4 stays below 2^32 at J = BSC_GLM_GROUP_MAX_J
+
+// The tile's sixteen ids, loaded like y; rows past B read id 0 (their results are never stored).
+__device__ __forceinline__ int load_group(const int32_t* __restrict__ g, int64_t B, int64_t row0, int i16) {
+    auto gs = bsc_vec_rsrc(g, B, row0);
+    return (int)__builtin_amdgcn_raw_buffer_load_b32(gs, 4 * i16, 0, 0);
+}
+
+// The intercepts of lane (i16, kq): draws 16 c + 4 kq .. + 3 of the row's group, one 16-byte load per chunk through a
+// descriptor of exactly (J + 1) ldb 4 bytes.  Id -1 is row J; every other id outside [0, J) goes to row J + 1, which
+// is past the descriptor and reads zeros.  The whole offset is in the per-lane operand, the one the range check
+// covers.  Columns from ldb on are the next row's bytes (or past the table: zeros): they are draws >= S, which `valid`
+// masks by a select, and nothing is done to the loaded registers here -- a select at this point would make the
+// compiler wait for the gather where it is issued.
+template <int NC>
+__device__ __forceinline__ void load_intercepts(p_f32x4 (&bt)[NC], const PredictGroups& gr, int id, int kq) {
+    auto bs = __builtin_amdgcn_make_buffer_rsrc((void*)gr.Bt, 0, (unsigned)(gr.J + 1) * (unsigned)gr.ldb * 4u,
+                                                0x00020000);
+    unsigned row = id == -1 ? (unsigned)gr.J : (unsigned)id;
+    row = row < (unsigned)gr.J + 1u ? row : (unsigned)gr.J + 1u;
+    const int base = (int)(row * (unsigned)gr.ldb * 4u) + 16 * kq;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        auto v = __builtin_amdgcn_raw_buffer_load_b128(bs, base + 64 * c, 0, 0);
+        bt[c] = p_f32x4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
+    }
+}
+
 // mu, v and log p(y | l) of one draw.  p4 = (logvar, exp(logvar), exp(-logvar)) for the Gaussian family.
 // Logistic: csrc/bsc_glm.hip's stable forms from e = exp(-|l|) <= 1 -- sigmoid = 1 / (1 + e) or e / (1 + e),
 // v = mu (1 - mu) = e / (1 + e)^2 without the cancellation, softplus = max(l, 0) + log1p(e) with log1p(e) =
@@ -123,8 +162,12 @@ __device__ __forceinline__ void predict_link(float l, float yv, float lv, float 
 
 // FULL: D == 256 (two strips, 32 columns per lane group, everything unrolled).
 // OFFS: `offset` [B] (not null) is loaded like y and added to every draw's l of its row before the link.
-template <int FAM, int NC, bool FULL, bool OFFS>
-__device__ __forceinline__ void predict_body(PredictArgs a, const float* offset) {
+// GRP (with OFFS; a null offset reads 0): the tile's ids are loaded with its y and offset, at `last` of the tile before;
+// its intercepts are requested at the top of its first strip, ahead of that strip's LDS store, and land behind the
+// tile's MFMAs.  Both loads are unconditional within their (wave-uniform) branch, so the X prefetch stays in flight.
+template <int FAM, int NC, bool FULL, bool OFFS, bool GRP = false>
+__device__ __forceinline__ void predict_body(PredictArgs a, const float* offset, PredictGroups gr = PredictGroups{}) {
+    static_assert(!GRP || OFFS, "the grouped body adds its intercept next to the offset");
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
     constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || FAM == PREDICT_NEGBIN;   // a scalar rides with every draw
@@ -172,10 +215,20 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
     load_strip(t, a, row0_of(0), 0, lane);
     float y_cur = load_y(a, row0_of(0), i16);
     float o_cur = 0.f;
-    [[maybe_unused]] const int64_t o_rows = (FAM == PREDICT_NEGBIN && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
+    [[maybe_unused]] const int64_t o_rows = ((FAM == PREDICT_NEGBIN || GRP) && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
     if constexpr (OFFS) o_cur = load_offset(offset, o_rows, row0_of(0), i16);
+    [[maybe_unused]] int g_cur = 0;
+    [[maybe_unused]] p_f32x4 bt[NC];
+    if constexpr (GRP) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) bt[c] = p_f32x4{0.f, 0.f, 0.f, 0.f};
+        g_cur = load_group(gr.g, a.B, row0_of(0), i16);
+    }
     int p = 0, h = 0;
     while (p < n_iter) {
+        if constexpr (GRP) {
+            if (h == 0) load_intercepts<NC>(bt, gr, g_cur, kq);   // this tile's, ahead of its first LDS store
+        }
         // the strip to LDS (row stride 130 floats: 8-byte aligned), its registers take the next strip
         {
             float* dst = xl + (lane >> 5) * XS + 4 * (lane & 31);
@@ -197,6 +250,9 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
         float o_next = 0.f;
         if constexpr (OFFS) {
             if (last) o_next = load_offset(offset, o_rows, row0_of(pn), i16);
+        }
+        if constexpr (GRP) {
+            if (last) g_cur = load_group(gr.g, a.B, row0_of(pn), i16);   // consumed by the gather above, next iteration
         }
         wave_lds_sync();
 
@@ -247,6 +303,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset)
                 for (int r = 0; r < 4; ++r) {
                     float l = acc[c][0][r] + acc[c][1][r];
                     if constexpr (OFFS) l += o_cur;
+                    if constexpr (GRP) l += bt[c][r];
                     const float lv = r == 0 ? lv4.x : r == 1 ? lv4.y : r == 2 ? lv4.z : lv4.w;
                     const float ev = r == 0 ? ev4.x : r == 1 ? ev4.y : r == 2 ? ev4.z : ev4.w;
                     const float iv = r == 0 ? iv4.x : r == 1 ? iv4.y : r == 2 ? iv4.z : iv4.w;

@@ -54,7 +54,10 @@ is BASELINE config 5's hierarchical logistic regression in any parameterisation 
 recogniser ``ScoreFunctionVI`` asks) are stepped by ``svi/hier_glm.py``: the grouped pass (csrc/bsc_glm_group.hip) and
 ``bsc_glm_hier_update``, with the one-hot group matrix turned into an index vector and scale, a0, b0 read off the
 plan.  ``route="auto"`` takes it (no model of three latent blocks had a fused or pass route before, and none is
-pinned to the general route by a test); the guide is mean-field, ``set_data`` and ``predict`` are refused there.
+pinned to the general route by a test); the guide is mean-field and ``set_data`` is refused there.  ``predict`` takes
+the new rows' group ids as ``groups=`` (int32, one per row, -1 for a group that was not seen in training) and hands
+them to the driver (csrc/bsc_predict_group.hip); without them it is refused, and on every other route ``groups=`` is
+a ValueError.
 
 **The pass route.**  When the data term is recognised but the parameter-sized remainder is NOT of that family
 (a known noise variance, another prior, more latents), the step still needs the data only through
@@ -458,7 +461,7 @@ class ReparamVI(object):
         self._fused = HierGLMReparamSVI(X, y, g, J, link="logistic", n_total=plan.scale * N, n_samples=self.S,
                                         seed=self.seed, lr=self.lr, prior_precision=1.0, a0=plan.a0, b0=plan.b0,
                                         ctx=self.backend.ctx, lam0=self._lam)
-        # (predict: the driver's own refusal says what is missing)
+        # (predict: with groups= the driver's grouped predictive; without, its own refusal says what to pass)
         self._fused_info = _NO_DRIVER._replace(
             elbo_offset=plan.offset, predict=True,
             set_data_refusal="set_data on the random-intercept route: build a new engine for another mini-batch (the "
@@ -720,13 +723,24 @@ class ReparamVI(object):
         grad = np.concatenate([g.mean(axis=0), (g * eps).mean(axis=0) * sigma + 1.0])
         return elbo, grad
 
-    def predict(self, X, y=None, n_samples=64, seed=None, draws=None, offset=None, weights=None):
+    def predict(self, X, y=None, n_samples=64, seed=None, draws=None, offset=None, weights=None, groups=None):
         """Posterior predictive for new rows (svi/predict.py): on a fused regression route the driver's own
         ``predict``; every other route has no likelihood the engine could name, and refuses.  ``offset`` /
-        ``weights``: for the new rows, on the fused GLM route (a model with an offset needs one to predict)."""
+        ``weights``: for the new rows, on the fused GLM route (a model with an offset needs one to predict).
+        ``groups``: the new rows' group ids on the fused random-intercept route (required there; -1 = a group not seen
+        in training), a ValueError on every other route."""
+        hierarchy = hasattr(self._fused, "_checked_groups")
+        if groups is not None and not hierarchy:
+            raise ValueError("predict: groups= belongs to the fused random-intercept route; this engine runs on route %r"
+                             % (self.route,))
         if not self._fused_info.predict:
             raise NotImplementedError("predict needs a fused regression route (fused: bsc_blr... / bsc_glm...); this "
                                       "engine runs on route %r" % (self.route,))
+        if hierarchy:           # (without groups: the driver's own refusal says what to pass)
+            if offset is not None or weights is not None:
+                raise ValueError("predict: offset and weights belong to the fused GLM route; this engine runs on "
+                                 "route %r" % (self.route,))
+            return self._fused.predict(X, y, groups=groups, n_samples=n_samples, seed=seed, draws=draws)
         if offset is None and weights is None:
             return self._fused.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
         if not self._fused_info.predict_obs:

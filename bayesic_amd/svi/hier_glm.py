@@ -18,10 +18,14 @@ double-buffered; the noise comes a block ahead from bsc_blr_noise with D + J str
 one; the first draw is made on the host.  The state, the first draw and step() are ReparamDriver's
 (svi/_reparam_base.py); offsets, exposure and row weights are svi/glm.py's (svi/_obs.py).
 
+predict() / heldout_lpd() (svi/predict.py; csrc/bsc_predict_group.hip, bsc_predict_pass_groups) take the rows' ids as
+``groups=``: the predictive needs a per-draw, per-group term in the logit, so a call without them is refused rather
+than read as "every row is a new group".  An id of -1 marks a group that was not seen in training: its intercept is
+integrated over N(0, e^{-zeta}) under q(zeta).  The ids are range-checked once per call (bsc_group_ids_check).
+
 Limits, by design of this version: the guide is mean-field (``covariance="full"`` is refused: P = D + J + 1 is past the
-full finish's 256 columns), and there is no predict() / heldout_lpd(): the predictive needs a per-draw, per-group
-term in the logit that bsc_predict_pass_offset's one offset per row cannot carry.  The multi-rank branch is wired like
-the other drivers' (every rank builds the plan of its own rows) and has been exercised at world size 1 only.
+full finish's 256 columns).  The multi-rank branch is wired like the other drivers' (every rank builds the plan of its
+own rows) and has been exercised at world size 1 only; prediction is single-rank.
 """
 import ctypes
 
@@ -44,6 +48,32 @@ def check_arguments(link, n_groups, prior_precision, a0, b0, covariance, offset,
     check_priors(prior_precision, a0, b0, "the intercepts' precision")
 
 
+NO_GROUPS = ("the predictive of a random-intercept model needs a per-draw, per-group term in the logit: pass groups= "
+             "(one int32 id per row, -1 for a group not seen in training)")
+
+
+def check_predict_groups(groups, B):
+    """The checks of predict()'s ``groups=`` that need no device: it is there (NotImplementedError otherwise: rows
+    without ids are not silently read as new groups), a tensor is int32, a host array holds integers, and either is a
+    contiguous [B].  A raw device pointer (an int) is taken as it is."""
+    if groups is None:
+        raise NotImplementedError(NO_GROUPS)
+    if isinstance(groups, (int, np.integer)):
+        return
+    import torch
+    if isinstance(groups, torch.Tensor):
+        if groups.dtype != torch.int32:
+            raise TypeError("groups must be int32")
+        shape, unit = tuple(groups.shape), groups.dim() != 1 or groups.shape[0] <= 1 or groups.stride(0) == 1
+    else:
+        a = np.asarray(groups)
+        if a.dtype.kind not in "iu":
+            raise TypeError("groups must hold integers (it is uploaded as int32), got dtype %s" % a.dtype)
+        shape, unit = a.shape, True
+    if len(shape) != 1 or shape[0] != B or not unit:
+        raise ValueError("groups must be a contiguous [%d], one id per row of X" % B)
+
+
 class HierGLMReparamSVI(ObsBatch, ReparamDriver):
     def __init__(self, X, y, groups, n_groups, link="logistic", n_total=None, n_samples=8, seed=1234, lr=1e-2,
                  prior_precision=1.0, a0=1.0, b0=1.0, offset=None, weights=None, exposure=None, ctx=None, group=None,
@@ -60,6 +90,7 @@ class HierGLMReparamSVI(ObsBatch, ReparamDriver):
         self.ctx = ctx or default_context()
         self._float_batch(X, y)
         self._set_obs(*batch_obs(self.ctx, self.B, offset, weights, exposure))
+        self.has_offset = self._oarg is not None      # predict() refuses to run without one
         groups = self._checked_groups(groups, self.B)
         D, J, S = self.D, self.J, int(n_samples)
         P = D + J + 1
@@ -157,15 +188,22 @@ class HierGLMReparamSVI(ObsBatch, ReparamDriver):
     def _finish(self, stats):
         self._finish_latent("bsc_glm_hier_update", stats, self._Bz, (self.D, self.J))
 
-    # -- what this version does not do ----------------------------------------------------------------------------
-    def predict(self, *args, **kwargs):
-        raise NotImplementedError("HierGLMReparamSVI has no predict(): the predictive of a random-intercept model needs "
-                                  "a per-draw, per-group term in the logit, which bsc_predict_pass_offset (one offset "
-                                  "per row) cannot carry; a grouped predictive pass is not part of this driver yet")
+    # -- the predictive --------------------------------------------------------------------------------------------
+    def predict(self, X, y=None, groups=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None,
+                weights=None):
+        """svi/predict.py's predict with the rows' ids (required; -1 = a group not seen in training)."""
+        check_predict_groups(groups, int(X.shape[0]))
+        from . import predict as P
+        return P.predict(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, exposure=exposure,
+                         weights=weights, groups=groups)
 
-    def heldout_lpd(self, *args, **kwargs):
-        raise NotImplementedError("HierGLMReparamSVI has no heldout_lpd(): it needs the grouped predictive pass that "
-                                  "predict() is waiting for (a per-draw, per-group term in the logit)")
+    def heldout_lpd(self, X, y, groups=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None,
+                    weights=None):
+        """svi/predict.py's heldout_lpd with the rows' ids (required, as in predict)."""
+        check_predict_groups(groups, int(X.shape[0]))
+        from . import predict as P
+        return P.heldout_lpd(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, exposure=exposure,
+                             weights=weights, groups=groups)
 
     # -- host views -----------------------------------------------------------------------------------------------
     def params(self):

@@ -19,6 +19,10 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
                                       (predict() below hands over to its predict(): bsc_softmax_predict_pass)
     NegBinReparamSVI                  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  tau = m_tau + e^{rho_tau} eps[:, D]
                                       (lam is already [m | rho] over z = [w | tau]; bsc_nb_predict_pass)
+    HierGLMReparamSVI                 eps [S, D + J + 2]:  z = m + e^rho eps[:, :D + J + 1] over z = [w | b | zeta], and
+                                      b_new = e^{-zeta / 2} eps[:, D + J + 1], the intercept of a group that was not
+                                      seen in training; returned as (W [S, D], Bt [J + 1, ldb]) with Bt[j, s] = b_s[j],
+                                      row J = b_new, ldb = 16 ceil(S / 16), padding zero (bsc_predict_pass_groups)
 xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass); tau = log phi is the log-dispersion
 of the negative binomial and travels in the same slot of the returned pair.
 
@@ -26,6 +30,14 @@ Offsets and weights (logistic, Poisson and negative-binomial models): ``offset``
 linear predictor in the pass (bsc_predict_pass_offset), so a Poisson ``mean`` is the expected count at that exposure.
 A model fitted with an offset refuses to predict without one.  ``weights`` leave every per-row output alone and make
 ``lpd_sum`` the weighted sum_n v_n lpd_n (float64, on the device, from the lpd vector).
+
+Groups (HierGLMReparamSVI): ``groups`` is one int32 id per row, in [0, J) for a group of the training data or -1 for a
+group that was not seen in training; the ids are range-checked once per call (bsc_group_ids_check, one
+synchronisation) and the pass adds b_s[g_n] to the linear predictor.  A row with id -1 has its intercept integrated
+over N(0, e^{-zeta}) under q(zeta): one draw b_new,s per posterior draw, SHARED by all such rows of the call.  Each
+row's ``mean``, ``var`` and ``lpd`` are correct Monte-Carlo estimates of its marginal predictive; JOINT statements about
+two rows of the same new group are not (one call cannot tell two new groups apart, and ``lpd_sum`` adds the rows'
+marginal log densities, as it does for every model here).  offset, exposure and weights behave as for GLMReparamSVI.
 """
 import numpy as np
 import torch
@@ -42,8 +54,8 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 
 
 def family_of(model):
-    """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI), "softmax" for
-    SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
+    """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI; HierGLMReparamSVI's link too --
+    ``grouped`` tells that model apart), "softmax" for SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
     if getattr(model, "n_classes", None) is not None:
         return "softmax"
     link = getattr(model, "link", None)
@@ -55,6 +67,25 @@ def family_of(model):
             "the log-joint do not identify the likelihood precision (s_q and k_w mix it with the prior's), so the "
             "predictive distribution is not defined by them")
     return "gaussian"
+
+
+def grouped(model):
+    """Whether the model is the random-intercept one (svi/hier_glm.py): its predictive takes ``groups=``."""
+    return getattr(model, "J", None) is not None and hasattr(model, "_checked_groups")
+
+
+def table_ld(S):
+    """Leading dimension of the intercept table Bt for S draws: whole accumulator chunks of sixteen."""
+    return 16 * ((int(S) + 15) // 16)
+
+
+def intercept_table(b, b_new):
+    """Bt float32 [J + 1, ldb] (host) from b [S, J] and b_new [S]: Bt[j, s] = b[s, j], row J = b_new, padding zero."""
+    S, J = b.shape
+    Bt = np.zeros((J + 1, table_ld(S)), np.float32)
+    Bt[:J, :S] = b.T
+    Bt[J, :S] = b_new
+    return Bt
 
 
 def _check_samples(n_samples):
@@ -69,10 +100,22 @@ def _check_samples(n_samples):
 def posterior_draws(model, n_samples=64, seed=None):
     """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q; W is [S, K, D] for
     SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d); for NegBinReparamSVI the second
-    entry is logphi float32 [S]."""
+    entry is logphi float32 [S]; for HierGLMReparamSVI it is the intercept table Bt float32 [J + 1, ldb] (module
+    docstring)."""
     S = _check_samples(n_samples)
     family = family_of(model)
     ctx, D = model.ctx, model.D
+    if grouped(model):
+        J = model.J
+        P = D + J + 1
+        seed = model.seed if seed is None else int(seed)
+        eps_d = torch.zeros((S, P + 1), dtype=torch.float64, device=ctx.device)
+        ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P + 1, eps_d)
+        eps = eps_d.cpu().numpy()
+        z = first_draw(model.lam.cpu().numpy(), eps[:, :P], P, "diag")
+        b_new = np.exp(-0.5 * z[:, P - 1]) * eps[:, P]
+        W = ctx.to_device(np.ascontiguousarray(z[:, :D], np.float32))
+        return W, ctx.to_device(intercept_table(z[:, D:D + J].astype(np.float32), b_new.astype(np.float32)))
     if family == "softmax":
         D = model.n_classes * model.D          # the guide's width; the transforms below are the GLM ones
     seed = model.seed if seed is None else int(seed)
@@ -118,15 +161,36 @@ def _obs(model, family, B, offset, exposure, weights):
     return batch_obs(model.ctx, B, offset, weights, exposure)
 
 
-def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):
+def _groups(model, groups, B):
+    """The checked ids of a batch of B rows (a device tensor or a raw pointer), or None for a model without groups."""
+    if not grouped(model):
+        if groups is not None:
+            raise ValueError("predict: groups= belongs to the random-intercept model (HierGLMReparamSVI)")
+        return None
+    from .hier_glm import check_predict_groups
+    check_predict_groups(groups, B)
+    g = model._checked_groups(groups, B)
+    model.ctx.call("bsc_group_ids_check", g, B, model.J, 1)      # [-1, J): one synchronisation per call
+    return g
+
+
+def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None,
+            groups=None):
     """Posterior predictive of ``model`` for the rows of X: a dict of device tensors ``mean`` and ``var`` (float32
     [B]) and, with y, ``lpd`` (float32 [B]) and ``lpd_sum`` (float64 [1]).  ``draws`` = (W, logvar) reuses draws of
     ``posterior_draws``; otherwise n_samples (at most 64) are drawn with ``seed`` (default: the model's).
     ``offset`` / ``exposure`` / ``weights``: float32 [B] (module docstring); with weights ``lpd_sum`` is the weighted
-    sum and ``weight_sum`` (float64 [1]) is sum_n v_n."""
+    sum and ``weight_sum`` (float64 [1]) is sum_n v_n.
+    ``groups`` (HierGLMReparamSVI, required there): int32 [B] -- a device tensor, a host array (uploaded) or a raw
+    device pointer -- with -1 for a group that was not seen in training.  Such a row's intercept is integrated over
+    N(0, e^{-zeta}) with ONE draw per posterior draw that all -1 rows of the call share: per-row ``mean``, ``var`` and
+    ``lpd`` are correct Monte-Carlo estimates, joint statements about two rows of the same new group are not."""
     family = family_of(model)
     if family == "softmax":      # its own pass and outputs (prob [B, K] instead of mean and var)
+        if groups is not None:
+            raise ValueError("predict: groups= belongs to the random-intercept model (HierGLMReparamSVI)")
         return model.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
+    groups = _groups(model, groups, int(X.shape[0]))
     offset, weights = _obs(model, family, int(X.shape[0]), offset, exposure, weights)
     if draws is None:
         draws = posterior_draws(model, n_samples, seed)
@@ -143,7 +207,14 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
         out["lpd"] = torch.empty(B, dtype=torch.float32, device=dev)
         if weights is None:        # (the weighted sum is formed from the lpd vector below)
             out["lpd_sum"] = torch.zeros(1, dtype=torch.float64, device=dev)
-    if family == "negbin":       # its own entry point; the offset may be None
+    if groups is not None:       # the random-intercept model: `logvar` is the intercept table; the offset may be None
+        Bt = logvar
+        if Bt.dim() != 2 or Bt.shape[0] != model.J + 1 or Bt.stride(1) != 1 or Bt.dtype != torch.float32:
+            raise ValueError("draws of the random-intercept model are (W [S, D], Bt float32 [J + 1, ldb]) as "
+                             "posterior_draws returns them")
+        ctx.call("bsc_predict_pass_groups", FAMILIES[family], X, ldx, y, offset, groups, B, model.D, model.J, W, Bt,
+                 int(Bt.stride(0)), S, out["mean"], out["var"], out.get("lpd"), out.get("lpd_sum"))
+    elif family == "negbin":       # its own entry point; the offset may be None
         ctx.call("bsc_nb_predict_pass", X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"],
                  out.get("lpd"), out.get("lpd_sum"))
     elif offset is None:
@@ -159,11 +230,12 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     return out
 
 
-def heldout_lpd(model, X, y, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None):
+def heldout_lpd(model, X, y, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None,
+                groups=None):
     """Mean log predictive density per row of the held-out (X, y): lpd_sum / B, a host float (synchronises).  With
-    weights: sum_n v_n lpd_n / sum_n v_n."""
+    weights: sum_n v_n lpd_n / sum_n v_n.  ``groups``: as in ``predict``."""
     out = predict(model, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, exposure=exposure,
-                  weights=weights)
+                  weights=weights, groups=groups)
     if "weight_sum" in out:
         return float(out["lpd_sum"].item()) / float(out["weight_sum"].item())
     return float(out["lpd_sum"].item()) / max(int(out["lpd"].shape[0]), 1)

@@ -620,6 +620,35 @@ int bsc_nb_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* 
                         int32_t D, const float* W, const float* logphi, int32_t S, float* mean, float* var, float* lpd,
                         double* lpd_sum);
 
+/* The predictive of the random-intercept model (csrc/bsc_predict_group.hip: bsc_predict_pass_offset's kernel with a
+ * per-draw, per-group intercept; bsc_glm_data_pass_groups is its training pass):
+ *      l[n,s] = sum_d X[n,d] W[s,d] + Bt[row(groups[n]), s] + o[n]          (offset may be NULL: o = 0)
+ * family BSC_PREDICT_LOGISTIC or BSC_PREDICT_POISSON, everything after l as bsc_predict_pass.  groups int32 [B],
+ * contiguous, any 4-byte alignment.  Bt float32 [J + 1][ldb], the draws CONTIGUOUS: Bt[j, s] = b_s[j] for the J groups
+ * of training, and row J the draws of a group that was NOT seen in training, b_new,s ~ N(0, e^{-zeta_s}), which the id
+ * -1 selects: row(-1) = J, row(j) = j.  (bsc_glm_data_pass_groups' Bz [chunk][J][8] is the same numbers in the
+ * training pass's order.)  Columns S .. ldb - 1 are not used.
+ * IDS ARE TRUSTED HERE -- bsc_group_ids_check is the range check, once per batch.  They cannot touch memory all the
+ * same: the gather goes through a descriptor of exactly (J + 1) ldb 4 bytes, and an id outside [-1, J) reads an
+ * intercept of 0 for every draw.
+ * Argument errors (BSC_ERR_INVALID) as bsc_predict_pass.  Outside the envelope (BSC_ERR_UNSUPPORTED, nothing is
+ * launched, outputs untouched): bsc_predict_pass's, and a family other than the two above, groups or Bt NULL, J outside
+ * [1, BSC_GLM_GROUP_MAX_J], ldb < S, ldb % 4 != 0, ldb > 8192, Bt not 16-byte aligned, groups or offset not 4-byte
+ * aligned.  Asynchronous and allocation-free once the workspace holds lpd_sum's block partials (bsc_ctx_reserve).
+ * Deterministic like bsc_predict_pass: no float atomics.  With Bt = 0 every output is bit-identical to
+ * bsc_predict_pass_offset on the same inputs. */
+int bsc_predict_pass_groups(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, const float* y,
+                            const float* offset, const int32_t* groups, int64_t B, int32_t D, int32_t J, const float* W,
+                            const float* Bt, int32_t ldb, int32_t S, float* mean, float* var, float* lpd,
+                            double* lpd_sum);
+
+/* The range check of a predictive batch's ids: every groups[n] in [0, J), or in [-1, J) with allow_new != 0.  One small
+ * kernel finds the first offending row; the call then SYNCHRONISES (like bsc_glm_group_plan, which checks the ids of a
+ * training batch) -- call it once per batch, never inside an update.  BSC_ERR_INVALID with
+ * "row <n> has group id <id> outside [-1,<J>)" (or "[0,<J>)").  Uses 8 bytes of the workspace (pending pass partials of
+ * bsc_blr_data_pass_partial are dropped). */
+int bsc_group_ids_check(bsc_ctx* ctx, const int32_t* groups, int64_t B, int32_t J, int32_t allow_new);
+
 /* ---- multi-class softmax regression (csrc/bsc_softmax.hip; ABSENT in the reference) ------------------------
  *
  * Labels y[n] in {0 .. K-1} (int32), weights W[S,K,D] (S draws of a K x D matrix, flattened parameter p = k D + d)
