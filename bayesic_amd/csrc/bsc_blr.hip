@@ -26,6 +26,44 @@ namespace {
 constexpr int SLAB_G = REG_SLAB_G;            // slab[b][d*8 + s], then Q at [SLAB_G + s]
 constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
 
+// ---- block epilogue of the eight-draw passes: the four waves' partials summed in wave order, one slab row out -------
+//
+// In slab order [d * 8 + s] a lane's 32 accumulators (columns 4 lane .. 4 lane + 3, eight draws) are 128 contiguous
+// bytes of the row: its 16-byte chunk j = 2 q + sb is column 4 lane + q, draws 4 sb .. 4 sb + 3, chunk 8 lane + j of the
+// row.  So the transposition happens in registers while WRITING: each wave puts its chunks into its [SLAB_STRIDE] LDS
+// region, and the sum over the waves reads whole chunks, consecutive threads consecutive chunks, and stores 16 bytes.
+// Chunk c sits at chunk position slab_chunk_pos(c) -- its index within the lane's eight XORed with lane % 8 -- which
+// keeps both sides conflict-free: the eight contiguous lanes of a ds_write_b128 group then cover eight different 16-byte
+// slots of the 128-byte bank row, and the XOR maps aligned runs of four chunks onto aligned runs of four, so the
+// sixteen lanes of a ds_read_b128 group still cover sixteen different slots of the 256-byte one.
+__device__ __forceinline__ int slab_chunk_pos(int c) { return (c & ~7) | ((c & 7) ^ ((c >> 3) & 7)); }
+
+template <typename V>
+__device__ __forceinline__ void slab_chunk_put(float* __restrict__ ep, int lane, int j, const V& v) {
+    static_assert(sizeof(V) == 16, "one 16-byte chunk");
+    *reinterpret_cast<V*>(ep + 4 * slab_chunk_pos(8 * lane + j)) = v;
+}
+
+// `lds`: PASS_WAVES regions of SLAB_STRIDE floats (chunks as above, then the eight scalars); out: the slab row.
+__device__ __forceinline__ void slab_row_out(const float* __restrict__ lds, float* __restrict__ out, int tid) {
+    for (int c = tid; c < SLAB_G / 4; c += PASS_BLOCK) {
+        const int p = 4 * slab_chunk_pos(c);
+        float4 v = *reinterpret_cast<const float4*>(lds + p);
+#pragma unroll
+        for (int k = 1; k < PASS_WAVES; ++k) {
+            const float4 u = *reinterpret_cast<const float4*>(lds + k * SLAB_STRIDE + p);
+            v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+        }
+        *reinterpret_cast<float4*>(out + 4 * c) = v;
+    }
+    if (tid < SG) {
+        float v = lds[SLAB_G + tid];
+#pragma unroll
+        for (int k = 1; k < PASS_WAVES; ++k) v += lds[k * SLAB_STRIDE + SLAB_G + tid];
+        out[SLAB_G + tid] = v;
+    }
+}
+
 // One tile = ROWS rows starting at row0, through buffer loads: the descriptor
 // (SGPRs) covers exactly the rows [row0, B), so rows past the end -- and whole
 // tiles past the end -- read as zeros without touching memory.  No ragged-tail
@@ -173,8 +211,13 @@ __global__ __launch_bounds__(PASS_BLOCK, Geo<ROWS>::OCC) void blr_pass_kernel(
     __syncthreads();  // every wave is done with its private region
     float* ep = lds + wave * SLAB_STRIDE;
 #pragma unroll
-    for (int s = 0; s < SG; ++s)
-        *reinterpret_cast<float4*>(ep + s * GCOLS + 4 * lane) = acc[s];
+    for (int sb = 0; sb < 2; ++sb) {
+        const float4 &a0 = acc[4 * sb], &a1 = acc[4 * sb + 1], &a2 = acc[4 * sb + 2], &a3 = acc[4 * sb + 3];
+        slab_chunk_put(ep, lane, 0 + sb, make_float4(a0.x, a1.x, a2.x, a3.x));
+        slab_chunk_put(ep, lane, 2 + sb, make_float4(a0.y, a1.y, a2.y, a3.y));
+        slab_chunk_put(ep, lane, 4 + sb, make_float4(a0.z, a1.z, a2.z, a3.z));
+        slab_chunk_put(ep, lane, 6 + sb, make_float4(a0.w, a1.w, a2.w, a3.w));
+    }
     // qacc of lane k belongs to sample lane_value(k)&7; fold the tile rows (lane bits 1..)
     // -- with ROWS == 4 lanes k and k^8 carry the same residuals, hence the 0.5
     float qv = qacc;
@@ -184,15 +227,8 @@ __global__ __launch_bounds__(PASS_BLOCK, Geo<ROWS>::OCC) void blr_pass_kernel(
     if (ROWS == 4) qv *= 0.5f;
     if ((lane & 14) == 0) ep[SLAB_G + (lane_value<ROWS>(lane) & 7)] = qv;
     __syncthreads();
-    float* out = slab + (int64_t)blockIdx.x * SLAB_STRIDE;
-    for (int i = tid; i < SLAB_STRIDE; i += PASS_BLOCK) {
-        // slab order is [d][s] so that a finisher reads 8 columns x 8 samples as one 256-B run
-        const int src = i < SLAB_G ? (i & 7) * GCOLS + (i >> 3) : i;
-        float v = lds[src];
-#pragma unroll
-        for (int k = 1; k < PASS_WAVES; ++k) v += lds[k * SLAB_STRIDE + src];
-        out[i] = v;
-    }
+    // slab order is [d][s] so that a finisher reads 8 columns x 8 samples as one 256-B run
+    slab_row_out(lds, slab + (int64_t)blockIdx.x * SLAB_STRIDE, tid);
 }
 
 // ---- 16-row tiles for the kernels that contract on the MFMA pipe (D == 256) -----------------
@@ -475,22 +511,13 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void blr_pass_q_kernel(
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            *reinterpret_cast<float4*>(ep + (4 * sb + i) * GCOLS + 4 * lane) =
-                make_float4(acc[sb][0][i], acc[sb][1][i], acc[sb][2][i], acc[sb][3][i]);
+        for (int q = 0; q < 4; ++q) slab_chunk_put(ep, lane, 2 * q + sb, acc[sb][q]);   // an accumulator IS a chunk
     float qv = (lane & 8) ? 0.f : qacc;        // lane (draw lane % 8, kq): rows 4 kq .. of that draw; lanes l ^ 8 repeat them
     qv += __shfl_xor(qv, 16);
     qv += __shfl_xor(qv, 32);
     if (lane < SG) ep[SLAB_G + lane] = qv;
     __syncthreads();
-    float* out = slab + (int64_t)blockIdx.x * SLAB_STRIDE;
-    for (int i = tid; i < SLAB_STRIDE; i += PASS_BLOCK) {
-        const int src = i < SLAB_G ? (i & 7) * GCOLS + (i >> 3) : i;
-        float v = lds[src];
-#pragma unroll
-        for (int kk = 1; kk < PASS_WAVES; ++kk) v += lds[kk * SLAB_STRIDE + src];
-        out[i] = v;
-    }
+    slab_row_out(lds, slab + (int64_t)blockIdx.x * SLAB_STRIDE, tid);
     if (stamps) {
         // measurement aid (option blr_stamps): when did this workgroup start and end, and on which XCD did it run
         // (words 4-7 of a row are unused)
@@ -909,16 +936,84 @@ struct FusedArgs {
     bsc_adam adam;
     uint64_t seed;
     uint32_t next_step;
+    unsigned long long* stamps;   // option blr_finish_stamps: FIN_STAMPS words per workgroup, else nullptr
 };
+
+// Stage stamps of the finish (measurement aid, option blr_finish_stamps; the STAMP instantiations only, so the kernel
+// that ships carries none of it).  Thread 0 of a workgroup keeps one s_memrealtime per stage and writes them at its end:
+//   0 wave start | 1 small operands landed | 2 slab landed and summed | 3 after the workgroup barrier |
+//   4, 5 scalar workgroup: per-draw terms handed over through LDS / their fixed-order sums done |
+//   6 Adam done | 7 stores issued | 8 end
+// A stage a workgroup does not have repeats the stage before it.
+constexpr int FIN_STAMPS = 16;           // words per workgroup (two 64-byte rows of bsc_blr_read_stamps)
+constexpr int FIN_STAMP_WGS = 64;        // workgroups that fit the stamp buffer behind the pass's rows
+
+template <bool STAMP>
+struct FinStamps {
+    unsigned long long t[9];
+    __device__ __forceinline__ void at(int k) {
+        if (STAMP) t[k] = __builtin_amdgcn_s_memrealtime();
+    }
+    // every load issued before the last `behind` ones has landed (loads return in order)
+    template <int BEHIND>
+    __device__ __forceinline__ void landed(int k) {
+        if (STAMP) {
+            __builtin_amdgcn_s_waitcnt(bsc_vmcnt_only(BEHIND));
+            asm volatile("" ::: "memory");
+            at(k);
+        }
+    }
+    __device__ __forceinline__ void skip(int k) {
+        if (STAMP) t[k] = t[k - 1];
+    }
+    __device__ __forceinline__ void write(unsigned long long* stamps) {
+        if (STAMP && threadIdx.x == 0 && (int)blockIdx.x < FIN_STAMP_WGS) {
+            at(8);
+            unsigned long long* st = stamps + FIN_STAMPS * (int64_t)blockIdx.x;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) st[k] = t[k];
+        }
+    }
+};
+
+// slab_column_sum (csrc/bsc_regress.h) of slab column `col` with a hook and without branches: `between` runs once, after
+// the first batch of loads has been issued and before it is consumed, and the loads are buffer loads whose descriptor
+// ends with the slab -- a row past n_rows reads as zero, where the guarded load of slab_column_sum is a branch that waits
+// for its load (eight round trips in a row).  The same values and the same order of additions.
+template <int STRIDE, int BATCH, typename F>
+__device__ __forceinline__ double slab_column_sum_between(const float* __restrict__ slab, int col, int first, int step,
+                                                          int n_rows, F between) {
+    const uint64_t slab_bytes = (uint64_t)n_rows * STRIDE * 4u;
+    auto rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)slab, 0, slab_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)slab_bytes, 0x00020000);
+    double sum = 0.0;
+    bool pending = true;
+    for (int b0 = first; b0 < n_rows; b0 += step * BATCH) {
+        float v[BATCH];
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j)
+            v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, ((b0 + j * step) * STRIDE + col) * 4, 0, 0));
+        if (pending) { between(); pending = false; }
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j) sum += (double)v[j];
+    }
+    if (pending) between();
+    return sum;
+}
 
 // BLOCK threads per workgroup (1024 = 16 waves: 32 slab rows per wave at 512 partials; fewer waves
 // launch sooner -- BSC_BLR_FINISH_BLOCK, A/B in tools/ab_pass.py)
-template <int FUSED_BLOCK>
+template <int FUSED_BLOCK, bool STAMP>
 __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs a) {
     constexpr int FUSED_WAVES = FUSED_BLOCK / BSC_WAVE;
+    constexpr int SLAB_JJ = FUSED_WAVES >= 16 ? 8 : 32;      // slab loads a lane has in flight (slab_run_sum)
+    constexpr int Q_BATCH = FUSED_BLOCK >= 1024 ? 8 : 16;    // the same for the scalar workgroup's column of Q
     __shared__ double red[FUSED_WAVES][BSC_WAVE];
     __shared__ double sh[2 * FIN_MAX_S + 16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: branches on it are scalar
+    FinStamps<STAMP> stamp;
+    stamp.at(0);
     const int D = a.D, S = a.S;
     const int n_chunks = (D + 7) / 8;
     const int chunk = (int)blockIdx.x;   // == n_chunks: the scalar workgroup
@@ -931,52 +1026,64 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
         const int d = d0 + dl;
         double gm = 0.0, gr = 0.0;
         // every small operand of wave 0 is requested before the slab so that the whole
-        // workgroup pays one memory round trip, not one per dependent stage
+        // workgroup pays one memory round trip, not one per dependent stage.  The loads are
+        // UNCONDITIONAL, from clamped indices: a load under a lane condition is waited for
+        // (s_waitcnt vmcnt(0)) where its branch ends, so every such block was a round trip of
+        // its own and the slab was asked for last.  A lane outside the condition reads a
+        // neighbour's value and never uses it.
         double p_m = 0.0, p_rho = 0.0, p_m1 = 0.0, p_m2 = 0.0, p_r1 = 0.0, p_r2 = 0.0;
         double e_next = 0.0, e_rho = 0.0;   // e_rho = exp(rho), set before it is used on either path
         const bool pre_noise = a.eps_next && a.eps_next_ready;
+        const int dc = d < D ? d : D - 1, sc = sl < S ? sl : S - 1;
         if (wave == 0) {
-            if (sl == 0 && d < D) {
-                p_m = a.lam_in[d]; p_rho = a.lam_in[D + d];
-                p_m1 = a.m1[d]; p_m2 = a.m2[d];
-                p_r1 = a.m1[D + d]; p_r2 = a.m2[D + d];
-            }
-            if (pre_noise && sl < S && d < D) e_next = a.eps_next[(int64_t)sl * (D + 1) + d];
+            p_m = a.lam_in[dc]; p_rho = a.lam_in[D + dc];
+            p_m1 = a.m1[dc]; p_m2 = a.m2[dc];
+            p_r1 = a.m1[D + dc]; p_r2 = a.m2[D + dc];
+            if (pre_noise) e_next = a.eps_next[(int64_t)sc * (D + 1) + dc];
         }
         if (a.slab) {  // S <= 8: lane <-> (column dl, sample sl) of one 256-B slab run
             const bool live = sl < S && d < D;
-            double wv = 0.0, xs = 0.0, ev = 0.0;
-            if (wave == 0 && live) {
-                wv = (double)a.W[(int64_t)sl * D + d];
-                xs = a.xi[sl];
-                ev = a.eps[(int64_t)sl * (D + 1) + d];
+            float wf = 0.f;   // (widened where it is used: a conversion here would wait for the load)
+            double xs = 0.0, ev = 0.0;
+            if (wave == 0) {
+                wf = a.W[(int64_t)sc * D + dc];
+                xs = a.xi[sc];
+                ev = a.eps[(int64_t)sc * (D + 1) + dc];
             }
             // this wave's share of the slab (rows wave + 16 k, the workgroup's 64-float run); the
             // float64 exponentials that do not depend on it run while it is in flight
             double s4[4];
             double e_mxs = 0.0;
-            slab_run_sum<SLAB_STRIDE, FUSED_WAVES, (FUSED_WAVES >= 16 ? 8 : 32)>(a.slab, a.n_slab, 64 * chunk, wave, lane, s4, [&] {
+            slab_run_sum<SLAB_STRIDE, FUSED_WAVES, SLAB_JJ>(a.slab, a.n_slab, 64 * chunk, wave, lane, s4, [&] {
+                stamp.template landed<SLAB_JJ>(1);
                 if (wave == 0) {
                     e_mxs = exp(-xs);
                     e_rho = exp(p_rho);
                 }
             });
+            stamp.at(2);
             if (lane < 16) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) red[wave][4 * lane + i] = s4[i];
             }
             __syncthreads();
             if (wave != 0) return;
+            stamp.at(3);
             double g = red[0][lane];
 #pragma unroll
             for (int k = 1; k < FUSED_WAVES; ++k) g += red[k][lane];
             if (live) {
+                asm volatile("" : "+v"(wf));   // (keeps the compiler from hoisting the conversion back to the load)
+                const double wv = (double)wf;
                 const double dw = e_mxs * (a.s_q * g - a.k_w * wv);
                 gm = dw;
                 gr = dw * ev;
             }
         } else {
             if (wave != 0) return;
+            stamp.template landed<0>(1);
+            stamp.skip(2);
+            stamp.skip(3);
             e_rho = exp(p_rho);
             for (int s = sl; s < S; s += 8) {
                 if (d < D) {
@@ -996,23 +1103,24 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
         }
         double* new_m = sh;        // [8]
         double* new_rho = sh + 8;  // [8]
-        if (sl == 0 && d < D) {
-            const double rho = p_rho;
+        // the two Adam steps of a column side by side: lane sl = 0 steps m, lane sl = 1 steps rho (every lane of the
+        // column holds both gradients after the fold and, the loads being unconditional, both parameters' state)
+        if (sl < 2 && d < D) {
+            const bool r = sl == 1;
             const double g_m = gm * inv_S;
             const double g_r = gr * inv_S * e_rho + 1.0;
-            a.grad[d] = g_m;
-            a.grad[D + d] = g_r;
-            double m1 = p_m1, m2 = p_m2;
-            const double nm = bsc_adam_ascent(p_m, g_m, m1, m2, a.adam);
-            a.m1[d] = m1; a.m2[d] = m2;
-            double r1 = p_r1, r2 = p_r2;
-            const double nr = bsc_adam_ascent(rho, g_r, r1, r2, a.adam);
-            a.m1[D + d] = r1; a.m2[D + d] = r2;
-            a.lam_out[d] = nm;
-            a.lam_out[D + d] = nr;
-            new_m[dl] = nm;
-            new_rho[dl] = nr;
+            const double g = r ? g_r : g_m;
+            double m1 = r ? p_r1 : p_m1, m2 = r ? p_r2 : p_m2;
+            const double np = bsc_adam_ascent(r ? p_rho : p_m, g, m1, m2, a.adam);
+            const int at = r ? D + d : d;
+            a.grad[at] = g;
+            a.m1[at] = m1; a.m2[at] = m2;
+            a.lam_out[at] = np;
+            (r ? new_rho : new_m)[dl] = np;
         }
+        stamp.skip(4);
+        stamp.skip(5);
+        stamp.at(6);
         wave_lds_sync();
         if (pre_noise) {
             // noise precomputed: w = m + e^rho * eps for this lane's (column, sample)
@@ -1031,49 +1139,67 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
                                    a.eps_next, a.W_next);
             }
         }
+        stamp.at(7);
+        stamp.write(a.stamps);
         return;
     }
 
     // ---------------------------- scalar workgroup ----------------------------
     double* Qs = sh;                    // [S]
     double* wsq = sh + FIN_MAX_S;       // [S]
-    double* misc = sh + 2 * FIN_MAX_S;  // [1]=new a [2]=new b
+    double* misc = sh + 2 * FIN_MAX_S;  // [0]=sum of rho
     __shared__ double terms[3 * FIN_MAX_S];
     const bool pre_noise = a.eps_next && a.eps_next_ready;
-    // request every small operand first (one memory round trip for the workgroup)
-    double x_s = 0.0, e_sD = 0.0, e_next = 0.0;           // thread s < S
-    if (tid < S) {
-        x_s = a.xi[tid];
-        e_sD = a.eps[(int64_t)tid * (D + 1) + D];
-        if (pre_noise) e_next = a.eps_next[(int64_t)tid * (D + 1) + D];
-    }
-    double av = 0.0, bv = 0.0, am1 = 0.0, am2 = 0.0, bm1 = 0.0, bm2 = 0.0;  // thread 0
-    if (tid == 0) {
-        av = a.lam_in[2 * D]; bv = a.lam_in[2 * D + 1];
-        am1 = a.m1[2 * D]; am2 = a.m2[2 * D];
-        bm1 = a.m1[2 * D + 1]; bm2 = a.m2[2 * D + 1];
-    }
-    double rho_part = 0.0;
-    for (int d = tid; d < D; d += FUSED_BLOCK) rho_part += a.lam_in[D + d];
+    // request every small operand first (one memory round trip for the workgroup): unconditional loads from clamped
+    // indices, as in the column workgroups -- a thread past the range reads a neighbour's value and never uses it
+    const int sc = tid < S ? tid : S - 1;                 // thread s < S
+    const double x_s = a.xi[sc];
+    const double e_sD = a.eps[(int64_t)sc * (D + 1) + D];
+    double e_next = 0.0;
+    if (pre_noise) e_next = a.eps_next[(int64_t)sc * (D + 1) + D];
+    // the two scalar parameters, one lane each: thread 0 owns a, thread 1 owns b (value and Adam moments); thread 2,
+    // which writes the ELBO, needs b as well
+    const int pc = tid < 1 ? 0 : 1;
+    double p_v = a.lam_in[2 * D + pc], p_1 = a.m1[2 * D + pc], p_2 = a.m2[2 * D + pc];
+    const double bv = a.lam_in[2 * D + 1];
+    // the float64 exponentials that depend on the small operands alone run while the slab is in flight
+    double e_mx = 0.0, e_pv = 0.0;                         // exp(-xi_s) (thread s < S), exp(b) (thread 1)
+    auto early_exps = [&] {
+        if (wave == 0) {
+            e_mx = exp(-x_s);
+            e_pv = exp(p_v);
+        }
+    };
+    // the sum of rho: this thread's first term is requested here and added behind the slab loads -- a loop that adds
+    // as it loads waits for memory before the slab has even been asked for (a second round trip on the chain)
+    const double rho_pre = a.lam_in[D + (tid < D ? tid : D - 1)];
     // |w_s|^2: wave-per-sample, fixed order (first 4 loads of each lane issued here)
-    float wpre[4] = {0.f, 0.f, 0.f, 0.f};
-    if (wave < S) {
+    float wpre[4];
+    {
+        const int ws = wave < S ? wave : S - 1;    // (used where wave < S and d < D)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int d = lane + BSC_WAVE * j;
-            if (d < D) wpre[j] = a.W[(int64_t)wave * D + d];
+            wpre[j] = a.W[(int64_t)ws * D + (d < D ? d : D - 1)];
         }
     }
     if (a.slab) {  // S <= 8: thread -> (sample tid&7, slab-row group tid>>3)
-        double part = slab_column_sum<SLAB_STRIDE, (FUSED_BLOCK >= 1024 ? 8 : 16)>(a.slab + SLAB_G + (tid & 7), tid >> 3, FUSED_BLOCK / 8,
-                                                                       a.n_slab);
+        double part = slab_column_sum_between<SLAB_STRIDE, Q_BATCH>(a.slab, SLAB_G + (tid & 7), tid >> 3, FUSED_BLOCK / 8,
+                                                                    a.n_slab, [&] {
+                                                                        stamp.template landed<Q_BATCH>(1);
+                                                                        early_exps();
+                                                                    });
         // fold the 8 row groups of this wave (lane bits 3-5), then the 16 waves
         part += __shfl_xor(part, 8);
         part += __shfl_xor(part, 16);
         part += __shfl_xor(part, 32);
         if (lane < 8) red[wave][lane] = part;
+        stamp.at(2);
     } else {
         for (int s = tid; s < S; s += FUSED_BLOCK) Qs[s] = a.stats[s];
+        stamp.template landed<0>(1);
+        stamp.skip(2);
+        early_exps();
     }
     for (int s = wave; s < S; s += FUSED_WAVES) {
         double part = 0.0;
@@ -1092,59 +1218,66 @@ __global__ __launch_bounds__(FUSED_BLOCK) void blr_fused_update_kernel(FusedArgs
         part = wave_allsum_f64(part);
         if (lane == 0) wsq[s] = part;
     }
+    double rho_part = 0.0;
+    if (tid < D) rho_part += rho_pre;          // the same terms in the same ascending order
+    for (int d = tid + FUSED_BLOCK; d < D; d += FUSED_BLOCK) rho_part += a.lam_in[D + d];
     rho_part = wave_allsum_f64(rho_part);
     if (lane == 0) red[wave][32] = rho_part;  // column 32: clear of the Q staging columns
     __syncthreads();
-    if (a.slab && tid < 8) {
-        double t = 0.0;
-        for (int k = 0; k < FUSED_WAVES; ++k) t += red[k][tid];
-        Qs[tid] = t;
-    }
-    // per-sample terms in parallel (one thread per sample; thread s wrote Qs[s] itself),
-    // then a fixed-order sum
+    // What is left is one wave's work: the other waves are done, and wave 0 hands its values from lane to lane through
+    // LDS behind wave-level fences -- no second or third workgroup barrier on the chain.
+    if (wave != 0) return;
+    stamp.at(3);
+    // lane l adds column l of the staging rows in wave order: lanes 0-7 end with Q, lane 32 with the sum of rho (the
+    // other columns are not read again)
+    double colsum = 0.0;
+    for (int k = 0; k < FUSED_WAVES; ++k) colsum += red[k][lane];
+    if (lane == 32) misc[0] = colsum;
+    // per-sample terms in parallel (one lane per sample), then fixed-order sums
     double* t_dxi = terms;              // [S]
     double* t_dxe = t_dxi + FIN_MAX_S;  // [S]
     double* t_f = t_dxe + FIN_MAX_S;    // [S]
-    if (tid < S) {
-        const int s = tid;
-        const double x = x_s, e = exp(-x);
-        const double inner = 0.5 * a.s_q * Qs[s] + 0.5 * a.k_w * wsq[s] + a.beta;
+    if (lane < S) {
+        const int s = lane;
+        const double Qv = a.slab ? colsum : Qs[s];
+        const double x = x_s, e = e_mx;
+        const double inner = 0.5 * a.s_q * Qv + 0.5 * a.k_w * wsq[s] + a.beta;
         const double dxi = a.c_xi + e * inner;
         t_dxi[s] = dxi;
         t_dxe[s] = dxi * e_sD;
         t_f[s] = a.c0 + a.c_xi * x - e * inner;
     }
-    __syncthreads();
-    if (tid == 0) {
-        double sum_rho = 0.0;
-        for (int k = 0; k < FUSED_WAVES; ++k) sum_rho += red[k][32];
-        double fa = 0.0, fb = 0.0, fsum = 0.0;
-        for (int s = 0; s < S; ++s) {
-            fa += t_dxi[s];
-            fb += t_dxe[s];
-            fsum += t_f[s];
-        }
-        const double g_a = fa * inv_S;
-        const double g_b = fb * inv_S * exp(bv) + 1.0;
-        a.grad[2 * D] = g_a;
-        a.grad[2 * D + 1] = g_b;
-        a.elbo[0] = fsum * inv_S + sum_rho + bv + 0.5 * (double)(D + 1) * (1.0 + BSC_LOG_2PI);
-        const double na = bsc_adam_ascent(av, g_a, am1, am2, a.adam);
-        a.m1[2 * D] = am1; a.m2[2 * D] = am2;
-        const double nb = bsc_adam_ascent(bv, g_b, bm1, bm2, a.adam);
-        a.m1[2 * D + 1] = bm1; a.m2[2 * D + 1] = bm2;
-        a.lam_out[2 * D] = na;
-        a.lam_out[2 * D + 1] = nb;
-        misc[1] = na;
-        misc[2] = nb;
+    wave_lds_sync();
+    stamp.at(4);
+    // lane 0: sum of dxi (the gradient of a), lane 1: sum of dxi * eps (of b), lane 2: sum of f (the ELBO) -- each
+    // from s = 0 upwards, as one thread used to add all three
+    double f = 0.0;
+    if (lane < 3) {
+        const double* t = terms + lane * FIN_MAX_S;
+        for (int s = 0; s < S; ++s) f += t[s];
     }
-    __syncthreads();
+    stamp.at(5);
+    double np_v = 0.0;                  // lane 0: new a, lane 1: new b
+    if (lane == 2) a.elbo[0] = f * inv_S + misc[0] + bv + 0.5 * (double)(D + 1) * (1.0 + BSC_LOG_2PI);
+    if (lane < 2) {
+        double g = f * inv_S;
+        if (lane == 1) g = g * e_pv + 1.0;
+        a.grad[2 * D + lane] = g;
+        np_v = bsc_adam_ascent(p_v, g, p_1, p_2, a.adam);
+        a.m1[2 * D + lane] = p_1;
+        a.m2[2 * D + lane] = p_2;
+        a.lam_out[2 * D + lane] = np_v;
+    }
+    stamp.at(6);
+    // the next xi in the lanes that hold its noise
+    const double na = __shfl(np_v, 0), nb = __shfl(np_v, 1);
     if (pre_noise) {
-        if (tid < S) a.xi_next[tid] = misc[1] + exp(misc[2]) * e_next;
+        if (lane < S) a.xi_next[lane] = na + exp(nb) * e_next;
     } else if (a.eps_next) {
-        for (int s = tid; s < S; s += FUSED_BLOCK)
-            blr_draw_scale(misc[1], misc[2], D, s, a.seed, a.next_step, a.eps_next, a.xi_next);
+        if (lane < S) blr_draw_scale(na, nb, D, lane, a.seed, a.next_step, a.eps_next, a.xi_next);
     }
+    stamp.at(7);
+    stamp.write(a.stamps);
 }
 
 // Tile height of the variant that will run: 16 = forward on the MFMA pipe (needs the full
@@ -1163,6 +1296,13 @@ PassGrid blr_pass_grid(const bsc_ctx* ctx, int64_t B, int rows) {
 }
 
 constexpr int MAX_SLAB_ROWS = 4 * 256 + 64;  // workspace sizing hint for callers
+
+// The stamp buffer of options blr_stamps / blr_finish_stamps: 64 bytes per pass workgroup, then the finish's rows.
+bool stamp_buffer(bsc_ctx* ctx) {
+    constexpr size_t bytes = ((size_t)MAX_SLAB_ROWS + (size_t)FIN_STAMP_WGS * (FIN_STAMPS / 8)) * 64;
+    if (!ctx->stamps && hipMalloc(&ctx->stamps, bytes) != hipSuccess) ctx->stamps = nullptr;
+    return ctx->stamps != nullptr;
+}
 
 // Every pass entry point reports under the name of bsc_blr_data_pass.
 int check_pass_args(const float* X, int64_t ldx, const float* y, int64_t B, int32_t D,
@@ -1213,7 +1353,7 @@ void launch_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, int6
         // both contractions on v_mfma_f32_4x4x1, the tile by LDS-DMA
         unsigned long long* stamps = nullptr;
         if (ctx->blr_stamps && !ctx->capturing) {
-            if (!ctx->stamps && hipMalloc(&ctx->stamps, (size_t)MAX_SLAB_ROWS * 64) != hipSuccess) ctx->stamps = nullptr;
+            (void)stamp_buffer(ctx);
             stamps = (unsigned long long*)ctx->stamps;
             ctx->stamp_rows = g.n_blocks <= MAX_SLAB_ROWS ? g.n_blocks : 0;
             if (!ctx->stamp_rows) stamps = nullptr;
@@ -1321,7 +1461,13 @@ int bsc_blr_read_stamps(bsc_ctx* ctx, uint64_t* host_stamps, int32_t capacity_ro
     BSC_HIP(hipStreamSynchronize(ctx->stream));
     const int n = ctx->stamps ? (ctx->stamp_rows < capacity_rows ? ctx->stamp_rows : capacity_rows) : 0;
     if (n > 0) BSC_HIP(hipMemcpy(host_stamps, ctx->stamps, (size_t)n * 64, hipMemcpyDeviceToHost));
-    *host_rows = n;
+    // the last stamped finish (option blr_finish_stamps) follows the pass's rows
+    int nf = ctx->stamps ? ctx->fin_stamp_rows : 0;
+    if (nf > capacity_rows - n) nf = capacity_rows - n;
+    if (nf > 0)
+        BSC_HIP(hipMemcpy(host_stamps + 8 * (size_t)n, (const char*)ctx->stamps + (size_t)MAX_SLAB_ROWS * 64, (size_t)nf * 64,
+                          hipMemcpyDeviceToHost));
+    *host_rows = n + nf;
     return BSC_OK;
 }
 
@@ -1436,15 +1582,26 @@ int fused_update_impl(bsc_ctx* ctx, const char* who, const double* stats, const 
     a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
     a.seed = seed;
     a.next_step = next_step;
+    a.stamps = nullptr;
+    const dim3 fgrid((D + 7) / 8 + 1);
+    ctx->fin_stamp_rows = 0;
+    if (ctx->blr_finish_stamps && !ctx->capturing && stamp_buffer(ctx)) {
+        // behind the pass's rows: a pass stamped by blr_stamps in the same update keeps its own
+        a.stamps = (unsigned long long*)ctx->stamps + 8 * (size_t)MAX_SLAB_ROWS;
+        const int wgs = (int)fgrid.x < FIN_STAMP_WGS ? (int)fgrid.x : FIN_STAMP_WGS;
+        ctx->fin_stamp_rows = wgs * (FIN_STAMPS / 8);
+    }
     {
         bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish kernel, timed apart from the pass
-        const dim3 fgrid((D + 7) / 8 + 1);
-        if (ctx->blr_finish_block == 256)
-            hipLaunchKernelGGL(blr_fused_update_kernel<256>, fgrid, dim3(256), 0, ctx->stream, a);
-        else if (ctx->blr_finish_block == 512)
-            hipLaunchKernelGGL(blr_fused_update_kernel<512>, fgrid, dim3(512), 0, ctx->stream, a);
-        else
-            hipLaunchKernelGGL(blr_fused_update_kernel<1024>, fgrid, dim3(1024), 0, ctx->stream, a);
+#define BSC_FINISH(BLOCK_)                                                                                         \
+    do {                                                                                                           \
+        if (a.stamps) hipLaunchKernelGGL((blr_fused_update_kernel<BLOCK_, true>), fgrid, dim3(BLOCK_), 0, ctx->stream, a);  \
+        else hipLaunchKernelGGL((blr_fused_update_kernel<BLOCK_, false>), fgrid, dim3(BLOCK_), 0, ctx->stream, a); \
+    } while (0)
+        if (ctx->blr_finish_block == 256) BSC_FINISH(256);
+        else if (ctx->blr_finish_block == 512) BSC_FINISH(512);
+        else BSC_FINISH(1024);
+#undef BSC_FINISH
     }
     BSC_LAUNCH_CHECK();
     return BSC_OK;

@@ -54,6 +54,8 @@ struct bsc_ctx {
     int blr_stamps = 0;          // blr_pass_q_kernel: every workgroup leaves start / end s_memrealtime stamps and its XCD (bsc_blr_read_stamps)
     void* stamps = nullptr;      // 64 bytes per workgroup (words 0-3 used), allocated when blr_stamps is first used
     int stamp_rows = 0;          // workgroups of the last stamped launch
+    int blr_finish_stamps = 0;   // blr_fused_update_kernel: thread 0 of every workgroup leaves one s_memrealtime stamp per stage
+    int fin_stamp_rows = 0;      // 64-byte rows the last finish stamped (two per workgroup), behind the pass's in `stamps`
     int profiling_builds = 0;    // 1: the deletion builds (options marked dbg) may be selected -- WRONG results, timing only
     int blr_finish_block = 1024; // threads per workgroup of blr_fused_update_kernel (BSC_BLR_FINISH_BLOCK = 256 | 512 | 1024)
     int blr_nt_loads = 1;        // non-temporal loads of X (read once per pass): +9% measured

@@ -139,7 +139,8 @@ class Context:
 
     def read_stamps(self):
         """Option blr_stamps: (rows, 8) uint64 array {start tick, end tick, XCD, HW_ID, four unused words} per workgroup
-        of the last D = 256, S <= 8 pass (100 MHz ticks); syncs."""
+        of the last D = 256, S <= 8 pass (100 MHz ticks); syncs.  Option blr_finish_stamps: followed by two rows per
+        workgroup of the last stamped finish, nine stage stamps and seven unused words (include/bayesic_hip.h)."""
         import numpy as np
         buf = np.zeros((2048, 8), np.uint64)
         n = ctypes.c_int32()

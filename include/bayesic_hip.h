@@ -264,7 +264,13 @@ int bsc_blr_data_pass_partial_sweep(bsc_ctx* ctx, const float* X, int64_t ldx, c
 /* Measurement aid (option "blr_stamps" = 1): the D = 256, S <= 8 pass leaves per workgroup
  * {start, end} in s_memrealtime ticks (100 MHz), the XCD it ran on and its HW_ID; this copies the
  * stamps of the LAST such launch to host_stamps[8 * rows] (synchronises; entries 4..7 of a row are unused).
- * Shows how evenly a static partition of the mini-batch finishes (tools/ab_q.py). */
+ * Shows how evenly a static partition of the mini-batch finishes (tools/ab_q.py).
+ * Option "blr_finish_stamps" = 1: the fused finish (bsc_blr_fused_update*, bsc_blr_pass_update*) leaves, per
+ * workgroup (the column workgroups, then the scalar one), nine stage stamps in two rows of eight words
+ * {wave start, small operands landed, slab summed, after the workgroup barrier, the scalar workgroup's
+ * per-draw terms handed over and their sums done, Adam done, stores issued, end, seven unused}; a stage a workgroup does not have repeats the one
+ * before it.  The rows of the LAST stamped finish follow the pass's rows (none when blr_stamps is off).  Nothing is
+ * stamped while capturing. */
 int bsc_blr_read_stamps(bsc_ctx* ctx, uint64_t* host_stamps, int32_t capacity_rows, int32_t* host_rows);
 
 /* How many launches of the pass kernel bsc_blr_data_pass[_sweep] makes for S draws (eight per pass, or
