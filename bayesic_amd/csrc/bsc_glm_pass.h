@@ -30,6 +30,9 @@
 //                 more lane accumulator next to ell.  The slab has no room for it, so these kernels write block
 //                 partials of NB_SLAB_STRIDE = REG_SLAB_G + 16 floats: ell at [SLAB_G + s], T at [SLAB_G + 8 + s].
 //                 Everything of it is behind `if constexpr (DSP)`; the flag defaults to off.
+//                 csrc/bsc_glm_gamma.hip (LINK = GLM_GAMMA) runs the same flag with a shape alpha_s = exp(tau_s) in the
+//                 place of phi_s: the four registers are tau_s, alpha_s and the two per-draw constants of the Gamma
+//                 density (glm_link below), T[s] and the slab are the same.
 //
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
@@ -43,20 +46,29 @@ constexpr int SLAB_G = REG_SLAB_G;            // slab[b][d*8 + s], then ell at [
 constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
 constexpr int NB_SLAB_STRIDE = REG_SLAB_G + 2 * SG;   // DSP: ell at [SLAB_G + s], T at [SLAB_G + 8 + s]
 constexpr int GLM_NEGBIN = 2;                 // the third link; internal: the BSC_GLM_* entry points refuse it
+constexpr int GLM_GAMMA = 3;                  // the fourth, internal as well: csrc/bsc_glm_gamma.hip
 
-// DSP: what a lane keeps of its draw's dispersion.
+// DSP: what a lane keeps of its draw's dispersion (GLM_GAMMA: of its draw's shape alpha_s).
 struct GlmDisp {
     float tau, phi;     // log phi_s as the pass read it, exp(tau)
-    float lg, psi;      // lnGamma(phi), psi(phi)
+    float lg, psi;      // lnGamma(phi), psi(phi); GLM_GAMMA: c_a = alpha log alpha - lnGamma(alpha),
+                        // c_1 = log alpha + 1 - psi(alpha)
 };
 
 // Draw s of this launch's chunk (s >= S: a dead slot, phi = 1).  The special values in float64, once per launch.
+template <int LINK = GLM_NEGBIN>
 __device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi, int s, int S) {
     GlmDisp d;
     d.tau = s < S ? logphi[s] : 0.0f;
     d.phi = expf(d.tau);
-    d.lg = (float)bsc_lgamma_f64((double)d.phi);
-    d.psi = (float)bsc_digamma_f64((double)d.phi);
+    if constexpr (LINK == GLM_GAMMA) {
+        const double a = (double)d.phi, la = log(a);
+        d.lg = (float)(a * la - bsc_lgamma_f64(a));
+        d.psi = (float)(la + 1.0 - bsc_digamma_f64(a));
+    } else {
+        d.lg = (float)bsc_lgamma_f64((double)d.phi);
+        d.psi = (float)bsc_digamma_f64((double)d.phi);
+    }
     return d;
 }
 
@@ -72,6 +84,12 @@ __device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi,
 //     resid = v [ y - z sigmoid(u) ]                                                           (= d / d l)
 //     T    += v [ phi dpsi(y, phi) - phi softplus(u) ] - resid       dpsi = psi(z) - psi(phi)   (= d / d tau)
 // finite for every finite l; both differences are exactly 0 at y = 0 (csrc/bsc_special_f32.h: an empty product).
+// GLM_GAMMA (always OBS; dp and T set): y > 0, alpha = e^tau, ly = log y, q = y e^{-l}, and dp's c_a, c_1:
+//     ell  += v [ c_a + alpha (ly - l - q) - ly ]                    (the full density, nothing left out)
+//     resid = v alpha (q - 1)                                                                  (= d / d l)
+//     T    += v alpha (c_1 + ly - l - q)                                                       (= d / d tau)
+// NOT clamped, like the Poisson link: finite while e^{-l} and y e^{-l} are below the float32 maximum (l > -88 at
+// y = 1).  One exp and one log per (row, draw), both at full float32 accuracy: ly enters ell multiplied by alpha.
 template <int LINK, bool OBS = false>
 __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv = 1.0f,
                                           const GlmDisp* dp = nullptr, float* T = nullptr) {
@@ -100,6 +118,22 @@ __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, floa
         ell = fmaf(vq, dlg + fmaf(yq, u, -z * sp), ell);
         *T = fmaf(vq, fmaf(dp->phi, dps - sp, -res), *T);
         return vq * res;
+    }
+    if constexpr (LINK == GLM_GAMMA) {
+        // The selects sit on the INPUTS, for the reason given above: a dropped row is evaluated at y = 1, l = 0 -- every
+        // term finite, log 0 never formed -- and multiplied by an exact 0.
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const float yq = keep ? yv : 1.0f;
+        const float lq = keep ? l : 0.0f;
+        const float ly = logf(yq);
+        // y e^{-l} as a product: expf(ly - l) would round its argument, 4e-6 of the result at |l| = 80.  The difference
+        // ly - l is used in the linear term alone.
+        const float q = yq * expf(-lq);
+        const float d = (ly - lq) - q;
+        ell = fmaf(vq, fmaf(dp->phi, d, dp->lg) - ly, ell);
+        *T = fmaf(vq, dp->phi * (dp->psi + d), *T);
+        return vq * (dp->phi * (q - 1.0f));
     }
     float a, da;
     if (LINK == BSC_GLM_LOGISTIC) {
@@ -293,7 +327,8 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
                                               int n_iter, const GlmGroupArgs* ga = nullptr,
                                               const float* logphi = nullptr) {
-    static_assert(!DSP || (OBS && !GRP && LINK == GLM_NEGBIN), "the dispersion rides with OBS and its own link");
+    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA)),
+                  "the dispersion (the shape) rides with OBS and its own link");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > STRIDE ? G8::WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -304,7 +339,7 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     const bool has_v = OBS && v_ != nullptr;
     GlmDisp dp;
     float tacc = 0.f;
-    if constexpr (DSP) dp = glm_disp_of(logphi, lane_value<ROWS>(lane) & 7, S);   // before anything fills the file
+    if constexpr (DSP) dp = glm_disp_of<LINK>(logphi, lane_value<ROWS>(lane) & 7, S);   // before anything fills the file
 
     float4 w[SG], acc[SG];
 #pragma unroll
@@ -437,7 +472,8 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
                                                    int n_iter, const GlmGroupArgs* ga = nullptr,
                                                    const float* logphi = nullptr) {
-    static_assert(!DSP || (OBS && !GRP && LINK == GLM_NEGBIN), "the dispersion rides with OBS and its own link");
+    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA)),
+                  "the dispersion (the shape) rides with OBS and its own link");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > STRIDE ? MT_WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -450,7 +486,7 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     const bool has_v = OBS && v_ != nullptr;
     GlmDisp dp;
     float tacc = 0.f;
-    if constexpr (DSP) dp = glm_disp_of(logphi, i16, S);   // lane (i16, kq) owns draw i16 (live lanes: i16 < 8)
+    if constexpr (DSP) dp = glm_disp_of<LINK>(logphi, i16, S);   // lane (i16, kq) owns draw i16 (live lanes: i16 < 8)
 
     // forward B operand: W[draw i16][64 kq + 4 j + c]; MFMA columns 8 .. 15 and draws >= S are zero.  Lane group
     // kq contracts columns 64 kq .. 64 kq + 63, which keeps the 16-byte A reads of a lane group conflict-free.
@@ -653,6 +689,46 @@ int for_draw_chunks(bsc_ctx* ctx, int S, Pass pass, Reduce reduce, Tail tail) {
 template <class Pass, class Reduce>
 int for_draw_chunks(bsc_ctx* ctx, int S, Pass pass, Reduce reduce) {
     return for_draw_chunks(ctx, S, pass, reduce, [](int) { return (int)BSC_OK; });
+}
+
+// The data pass of a DSP route (csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip) through the calling translation unit's own
+// kernels: the 16-row MFMA kernel, the 8-row kernel with D == 256 and with any D, and the reduction of the
+// NB_SLAB_STRIDE slab.  `logphi` [S] is the per-draw scalar under the name `what`.
+template <class Mfma, class Rows8Full, class Rows8, class Reduce>
+int dsp_data_pass(bsc_ctx* ctx, const char* who, const char* what, Mfma mfma_kernel, Rows8Full rows8_full_kernel,
+                  Rows8 rows8_kernel, Reduce reduce_kernel, int max_s, const float* X, int64_t ldx, const float* y,
+                  const float* offset, const float* weight, int64_t B, int32_t D, const float* W, const float* logphi,
+                  int32_t S, double* ell, double* G, double* T) {
+    const int rc0 = check_glm_obs_args(who, BSC_GLM_LOGISTIC, X, ldx, y, offset, weight, B, D, W, S, max_s);
+    if (rc0 != BSC_OK) return rc0;
+    BSC_REQUIRE(logphi, "%s: %s is null", who, what);
+    BSC_REQUIRE((((uintptr_t)logphi) & 3) == 0, "%s: %s must be 4-byte aligned", who, what);
+    BSC_REQUIRE(ell && G && T, "%s: null output", who);
+
+    const int rows = pass_rows(D, y, offset, weight);
+    const PassGrid g = pass_grid(ctx, B, rows);
+    void* ws = nullptr;
+    const int rc = bsc_workspace(ctx, (size_t)g.n_blocks * NB_SLAB_STRIDE * sizeof(float), &ws);
+    if (rc != BSC_OK) return rc;
+    ctx->slab_rows = 0;  // the slab is consumed here
+    float* slab = (float*)ws;
+    const dim3 rgrid((NB_SLAB_STRIDE + BSC_WAVE - 1) / BSC_WAVE);
+    const auto go = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y, offset, weight, B,
+                           tail...);
+    };
+    return for_draw_chunks(
+        ctx, S,
+        [&](int s0, int sg) {   // each launch with its chunk of the scalar
+            const float *Ws = W + (int64_t)s0 * D, *lp = logphi + s0;
+            if (rows == MT_ROWS) go(mfma_kernel, Ws, lp, sg, slab, g.n_iter);
+            else if (D == GCOLS) go(rows8_full_kernel, (int)D, Ws, lp, sg, slab, g.n_iter);
+            else go(rows8_kernel, (int)D, Ws, lp, sg, slab, g.n_iter);
+        },
+        [&](int s0) {
+            hipLaunchKernelGGL(reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, (const float*)slab, g.n_blocks,
+                               (int)D, (int)S, s0, ell, G, T);
+        });
 }
 
 }  // namespace

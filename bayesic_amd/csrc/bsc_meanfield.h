@@ -124,4 +124,74 @@ __device__ __forceinline__ void meanfield_coord_body(const Model& a) {
     }
 }
 
+// ---- the model with ONE scalar behind the weights whose exponential has a Gamma(a0, b0) prior ------------------------
+//
+// z = [w (D) | tau]: the negative binomial's dispersion phi = e^tau (csrc/bsc_glm_nb.hip) and the Gamma likelihood's
+// shape alpha = e^tau (csrc/bsc_glm_gamma.hip).  The likelihood enters through ell_s, G_s and T_s = d ell_s / d tau_s
+// alone, so the finish is the same for both and each translation unit instantiates the bodies above with this model.
+// scal = [g_tau (64) | f (64) | sum rho]; c0 = D/2 log(prec / 2 pi) + a0 log b0 - lnGamma(a0).
+struct NbModel : MeanfieldArgs {
+    const float* logphi;     // [S]
+    float* logphi_next;
+
+    static constexpr int N_SLOTS = 2;
+    static constexpr bool LAST_HAS_NEXT = true;
+
+    static __device__ __forceinline__ double extra_sq(const NbModel&, int, double*) { return 0.0; }
+
+    // g_tau and f_s = scale ell_s + log p(z_s) with tau_s the float32 value the pass read; T sits behind G in stats
+    static __device__ __forceinline__ void draw_scalars(const NbModel& a, int s, double wsq, double) {
+        const int D = a.D, S = a.S;
+        const double tau = (double)a.logphi[s];
+        const double phi = exp(tau);
+        const double T = a.stats[S + (int64_t)S * D + s];
+        a.scal[s] = a.scale * T + a.a0 - a.b0 * phi;
+        a.scal[MF_MAX_S + s] = a.scale * a.stats[s] + a.c0 - 0.5 * a.prec * wsq + a.a0 * tau - a.b0 * phi;
+    }
+
+    static __device__ __forceinline__ double grad_term(const NbModel& a, int, int s) { return a.scal[s]; }
+
+    static __device__ __forceinline__ void store_next(const NbModel& a, int i, double nm, double sd) {
+        const int S = a.S, P = a.P;
+        for (int s = 0; s < S; ++s) a.logphi_next[s] = (float)(nm + sd * a.eps_next[(int64_t)s * P + i]);
+    }
+};
+
+// Host side of that finish: the checks, the next step's noise, the arguments and the two launches, through the calling
+// translation unit's own kernels (`scalars` runs meanfield_scalars_body, `coord` meanfield_coord_body on NbModel).
+template <class Scalars, class Coord>
+int nb_model_update(bsc_ctx* ctx, const char* who, Scalars scalars, Coord coord, const double* stats,
+                    const double* lam_in, double* lam_out, double* m1, double* m2, const double* eps, const float* W,
+                    const float* logphi, int32_t D, int32_t S, double scale, double prior_precision, double a0,
+                    double b0, int64_t t, double lr, double beta1, double beta2, double adam_eps, uint64_t seed,
+                    uint32_t next_step, double* eps_next, int32_t eps_next_ready, float* W_next, float* logphi_next,
+                    double* elbo, double* grad) {
+    BSC_REQUIRE(stats, "%s: stats is null (pending pass partials are not read: pass [ell | G | T])", who);
+    int rc = check_meanfield_update(who, lam_in && lam_out && m1 && m2 && eps && W && logphi && elbo && grad, lam_in,
+                                    lam_out, D, S, MF_MAX_S, prior_precision, /*has_gamma=*/true, a0, b0, scale, t);
+    if (rc != BSC_OK) return rc;
+    rc = next_draw_noise(ctx, who, /*has_extra=*/true, eps, W, logphi, eps_next, W_next, logphi_next, D, S, seed,
+                         next_step, eps_next_ready);
+    if (rc != BSC_OK) return rc;
+    void* ws = nullptr;
+    rc = bsc_workspace(ctx, (NbModel::N_SLOTS * MF_MAX_S + 8) * sizeof(double), &ws);
+    if (rc != BSC_OK) return rc;
+    NbModel a;
+    a.stats = stats; a.lam_in = lam_in; a.lam_out = lam_out; a.m1 = m1; a.m2 = m2;
+    a.eps = eps; a.W = W; a.logphi = logphi; a.eps_next = eps_next; a.W_next = W_next; a.logphi_next = logphi_next;
+    a.scal = (double*)ws; a.elbo = elbo; a.grad = grad;
+    a.D = D; a.S = S; a.P = D + 1;
+    a.scale = scale; a.prec = prior_precision; a.a0 = a0; a.b0 = b0;
+    a.c0 = 0.5 * (double)D * (log(prior_precision) - BSC_LOG_2PI) + a0 * log(b0) - lgamma(a0);
+    a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
+    ctx->slab_rows = 0;   // the workspace is this finish's now
+    {
+        bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish, timed apart from the pass
+        hipLaunchKernelGGL(scalars, dim3(S + 1), dim3(MF_BLOCK), 0, ctx->stream, a);
+        hipLaunchKernelGGL(coord, dim3((a.P + MF_BLOCK - 1) / MF_BLOCK), dim3(MF_BLOCK), 0, ctx->stream, a);
+    }
+    BSC_LAUNCH_CHECK();
+    return BSC_OK;
+}
+
 }  // namespace

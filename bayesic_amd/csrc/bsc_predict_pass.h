@@ -6,7 +6,7 @@
 // per-group intercept b_s[g_n] joins o_n, gathered from a table Bt [J + 1][ldb] by the row's group id (PredictGroups
 // below).  With GRP off nothing of it is compiled: the shipped instantiations keep their code.  The host side at the end
 // is the envelope of the entry points (predict_check_batch, predict_setup, predict_launch_chunks), shared by
-// csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like
+// csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like
 // csrc/bsc_regress.h.
 #pragma once
 
@@ -19,6 +19,9 @@ namespace {
 // bsc_predict_pass_offset refuse it.  Always with OFFS (a null offset reads 0 through an empty descriptor); `logvar`
 // carries tau_s = log phi_s.
 constexpr int PREDICT_NEGBIN = 3;
+// The fifth, internal as well: csrc/bsc_glm_gamma.hip's predict_gamma_kernel (bsc_gamma_predict_pass), the Gamma
+// likelihood with a per-draw shape; `logvar` carries tau_s = log alpha_s.  Always with OFFS, the offset may be null.
+constexpr int PREDICT_GAMMA = 4;
 
 constexpr int P_BLOCK = 512;
 constexpr int P_WAVES = P_BLOCK / BSC_WAVE;
@@ -38,7 +41,7 @@ struct PredictArgs {
     const float* y;          // may be null
     int64_t B;
     const float* W;
-    const float* logvar;     // Gaussian: log s2 per draw; PREDICT_NEGBIN: log phi per draw
+    const float* logvar;     // Gaussian: log s2 per draw; PREDICT_NEGBIN: log phi per draw; PREDICT_GAMMA: log alpha
     float* mean;             // outputs, each may be null
     float* var;
     float* lpd;
@@ -125,6 +128,9 @@ __device__ __forceinline__ void load_intercepts(p_f32x4 (&bt)[NC], const Predict
 // v = mu + mu^2 / phi; log p from the logistic forms at u = l - tau, finite for every finite l:
 // lnGamma(y + phi) - lnGamma(phi) + y u - (y + phi) softplus(u), the difference exactly 0 at y = 0; the row
 // constant lnGamma(y + 1) is taken off after the log-mean-exp.
+// PREDICT_GAMMA: p4 = (tau, alpha = exp(tau), 1 / alpha) and lgp = c_a = alpha log alpha - lnGamma(alpha).
+// mu = exp(l) (not clamped), v = mu^2 / alpha; log p = c_a + alpha (log y - l - y e^{-l}) - log y, the full density
+// (csrc/bsc_glm_pass.h's forms: the exponential as the product y e^{-l}); y > 0 is the caller's to see to.
 template <int FAM>
 __device__ __forceinline__ void predict_link(float l, float yv, float lv, float ev, float iv, float& mu, float& v,
                                              float& lp, float lgp = 0.0f) {
@@ -138,6 +144,13 @@ __device__ __forceinline__ void predict_link(float l, float yv, float lv, float 
         float dlg, dps;
         bsc_dlgamma_dpsi_f32(yv, ev, lgp, 0.0f, dlg, dps);      // (dpsi is not used and folds away)
         lp = dlg + fmaf(yv, u, -(yv + ev) * (fmaxf(u, 0.0f) + l1p));
+        return;
+    }
+    if constexpr (FAM == PREDICT_GAMMA) {
+        mu = expf(l);
+        v = mu * iv * mu;
+        const float ly = logf(yv);
+        lp = fmaf(ev, (ly - l) - yv * expf(-l), lgp) - ly;
         return;
     }
     if (FAM == BSC_PREDICT_GAUSSIAN) {
@@ -170,8 +183,9 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     static_assert(!GRP || OFFS, "the grouped body adds its intercept next to the offset");
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
-    constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || FAM == PREDICT_NEGBIN;   // a scalar rides with every draw
-    constexpr int GP_SLOTS = FAM == PREDICT_NEGBIN ? 4 : 3;                           // ... and lnGamma(phi)
+    constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA;   // families with a fourth per-draw value
+    constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || OWN4;        // a scalar rides with every draw
+    constexpr int GP_SLOTS = OWN4 ? 4 : 3;                                 // ... and lnGamma(phi), or c_a
     __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + GP_SLOTS * P_MAX_S];
     __shared__ double red[P_WAVES];
     const int tid = threadIdx.x;
@@ -192,6 +206,10 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
         gp[P_MAX_S + tid] = expf(lv);
         gp[2 * P_MAX_S + tid] = expf(-lv);
         if constexpr (FAM == PREDICT_NEGBIN) gp[3 * P_MAX_S + tid] = (float)bsc_lgamma_f64((double)expf(lv));
+        if constexpr (FAM == PREDICT_GAMMA) {
+            const double al = (double)expf(lv);
+            gp[3 * P_MAX_S + tid] = (float)(al * log(al) - bsc_lgamma_f64(al));
+        }
     }
     __syncthreads();
 
@@ -215,7 +233,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     load_strip(t, a, row0_of(0), 0, lane);
     float y_cur = load_y(a, row0_of(0), i16);
     float o_cur = 0.f;
-    [[maybe_unused]] const int64_t o_rows = ((FAM == PREDICT_NEGBIN || GRP) && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
+    [[maybe_unused]] const int64_t o_rows = ((OWN4 || GRP) && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
     if constexpr (OFFS) o_cur = load_offset(offset, o_rows, row0_of(0), i16);
     [[maybe_unused]] int g_cur = 0;
     [[maybe_unused]] p_f32x4 bt[NC];
@@ -298,7 +316,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
                     ev4 = *reinterpret_cast<const float4*>(gp + P_MAX_S + d0);
                     iv4 = *reinterpret_cast<const float4*>(gp + 2 * P_MAX_S + d0);
                 }
-                if constexpr (FAM == PREDICT_NEGBIN) lg4 = *reinterpret_cast<const float4*>(gp + 3 * P_MAX_S + d0);
+                if constexpr (OWN4) lg4 = *reinterpret_cast<const float4*>(gp + 3 * P_MAX_S + d0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float l = acc[c][0][r] + acc[c][1][r];
@@ -308,7 +326,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
                     const float ev = r == 0 ? ev4.x : r == 1 ? ev4.y : r == 2 ? ev4.z : ev4.w;
                     const float iv = r == 0 ? iv4.x : r == 1 ? iv4.y : r == 2 ? iv4.z : iv4.w;
                     float m_i, v_i, lp_i;
-                    if constexpr (FAM == PREDICT_NEGBIN)
+                    if constexpr (OWN4)
                         predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i,
                                           r == 0 ? lg4.x : r == 1 ? lg4.y : r == 2 ? lg4.z : lg4.w);
                     else
@@ -442,6 +460,35 @@ void predict_launch_chunks(int S, F launch) {
     if (S <= 16) launch(std::integral_constant<int, 1>{});
     else if (S <= 32) launch(std::integral_constant<int, 2>{});
     else launch(std::integral_constant<int, 4>{});
+}
+
+// The entry point of a family with a per-draw scalar of its own (`logphi` [S], named `what` in the messages) and an
+// offset that may be null: csrc/bsc_glm_nb.hip and csrc/bsc_glm_gamma.hip.  launch(NC, args, n_blocks) launches the
+// calling translation unit's kernel for NC chunks of draws, sum_kernel is its block_partial_sum.
+template <class Launch, class Sum>
+int scalar_predict_pass(bsc_ctx* ctx, const char* who, const char* what, Launch launch, Sum sum_kernel, const float* X,
+                        int64_t ldx, const float* y, const float* offset, int64_t B, int32_t D, const float* W,
+                        const float* logphi, int32_t S, float* mean, float* var, float* lpd, double* lpd_sum) {
+    int rc = predict_check_batch(who, X, y, B, W, mean, var, lpd, lpd_sum);
+    if (rc != BSC_OK) return rc;
+    BSC_REQUIRE(logphi, "%s: %s is null", who, what);
+    BSC_REQUIRE((((uintptr_t)offset) & 3) == 0 && (((uintptr_t)logphi) & 3) == 0,
+                "%s: offset and %s must be 4-byte aligned", who, what);
+    PredictArgs a;
+    int n_blocks = 0;
+    rc = predict_setup(ctx, who, X, ldx, y, B, D, W, logphi, S, mean, var, lpd, lpd_sum, &a, &n_blocks);
+    if (rc != BSC_OK || n_blocks == 0) return rc;
+    {
+        bsc_prof_scope prof(ctx);
+        predict_launch_chunks(S, [&](auto nc) { launch(nc, a, n_blocks); });
+    }
+    BSC_LAUNCH_CHECK();
+    if (lpd_sum) {
+        hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(BSC_WAVE), 0, ctx->stream, (const double*)a.partial, n_blocks,
+                           lpd_sum);
+        BSC_LAUNCH_CHECK();
+    }
+    return BSC_OK;
 }
 
 }  // namespace

@@ -547,6 +547,51 @@ int bsc_glm_nb_update(bsc_ctx* ctx, const double* stats, const double* lam_in, d
                       double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
                       float* W_next, float* logphi_next, double* elbo, double* grad);
 
+/* ---- Gamma regression (log link) with a learned shape on the same pass (csrc/bsc_glm_gamma.hip) --------------------
+ *
+ *      y_n ~ Gamma(shape alpha, rate alpha / mu_n),   y_n > 0,   E y_n = mu_n = exp(l_n),   Var y_n = mu_n^2 / alpha
+ *      l[n,s] = sum_d X[n,d] W[s,d] + o[n],   w ~ N(0, I / prior_precision),   alpha = e^tau ~ Gamma(a0, b0)
+ * The latent is z = [w (D) | tau], P = D + 1, the guide mean-field: lam = [m (P) | rho (P)].  One shape draw rides with
+ * every weight draw: logshape[s] = tau_s, float32 [S], any 4-byte alignment; alpha_s = e^{tau_s} (float32 expf of the
+ * value read).  With ly = log y, c_a(alpha) = alpha log alpha - lnGamma(alpha), c_1(alpha) = log alpha + 1 - psi(alpha)
+ * (both made once per launch in float64 from alpha_s and rounded to float32):
+ *      log p(y | l, alpha) = c_a + alpha (ly - l - y e^{-l}) - ly             (the FULL density: nothing is left out)
+ *      ell[s]  = sum_n v[n] log p(y[n] | l[n,s], alpha_s)
+ *      G[s,d]  = sum_n r[n,s] X[n,d]             r[n,s] = v[n] alpha_s ( y[n] e^{-l[n,s]} - 1 )               (= d / d l)
+ *      T[s]    = sum_n v[n] alpha_s ( c_1 + ly[n] - l[n,s] - y[n] e^{-l[n,s]} )                  (= d ell[s] / d tau_s)
+ * Outputs float64: ell [S], G [S, D], T [S].  offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0,
+ * v = 1; a row with v[n] = 0 adds EXACTLY nothing to ell, G and T, by a select on the link's inputs: it is evaluated at
+ * y = 1, l = 0 whatever it held, as the rows past B are, and log 0 is never formed).  The exponential is taken as the
+ * product y e^{-l}, exp and log at full float32 accuracy.
+ * y IS NOT CHECKED ON THE DEVICE: a kept row with y <= 0 or a non-finite y makes ell and T of every draw NaN or
+ * infinite (bayesic_amd/svi/glm_gamma.py checks y where a batch is set).
+ * OVERFLOW: exp is NOT clamped, as for the Poisson link (a clamp would change the gradient silently): the outputs are
+ * finite while e^{-l} and y e^{-l} stay below the float32 maximum (l > -88 at y = 1).
+ * ACCURACY ENVELOPE: tau in [-2.5, 5] (alpha in [0.08, 148]); there a plain float32 evaluation stays within 1e-6 of
+ * sum_n v ( |c_a| + alpha (|ly - l| + y e^{-l}) + |ly| + 1 ) for ell, of sum_n v ( alpha (|c_1| + |ly - l| + y e^{-l}) + 1 )
+ * for T and of max |G|.  Above it c_1 -> 1 + 1 / (2 alpha) and T's terms cancel beyond what float32 holds.
+ * The envelope and its refusals are bsc_glm_nb_data_pass's (D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 with eight draws
+ * and their eight tau per launch, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26); logshape == NULL is
+ * refused.  The 16-row MFMA kernel (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned,
+ * else the 8-row kernel.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block partials of
+ * 8 * 256 + 16 floats (ell and T behind G), fixed-order float64 finish, no float atomics. */
+int bsc_glm_gamma_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                            const float* weight, int64_t B, int32_t D, const float* W, const float* logshape,
+                            int32_t S, double* ell, double* G, double* T);
+
+/* The finish: bsc_glm_nb_update with logshape in the place of logphi -- the prior on e^tau has the same form, the
+ * likelihood enters through ell, G and T alone, and both entry points run one body (csrc/bsc_meanfield.h), so the same
+ * arguments give the same bits:
+ *     g_w = scale G_s - prior_precision w_s,     g_tau = scale T_s + a0 - b0 e^{tau_s}
+ *     ELBO = mean_s [ scale ell_s - prior_precision/2 |w_s|^2 + log p(tau_s) ] + D/2 log(prior_precision / 2 pi)
+ *            + sum rho + P/2 (1 + log 2 pi)
+ * stats = [ell (S) | G (S*D) | T (S)]; checks, next draws and requirements as there. */
+int bsc_glm_gamma_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                         double* m2, const double* eps, const float* W, const float* logshape, int32_t D, int32_t S,
+                         double scale, double prior_precision, double a0, double b0, int64_t t, double lr, double beta1,
+                         double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
+                         int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo, double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
@@ -625,6 +670,19 @@ int bsc_predict_pass_offset(bsc_ctx* ctx, int32_t family, const float* X, int64_
 int bsc_nb_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                         int32_t D, const float* W, const float* logphi, int32_t S, float* mean, float* var, float* lpd,
                         double* lpd_sum);
+
+/* The predictive of the Gamma model (csrc/bsc_glm_gamma.hip: bsc_predict_pass's kernel with a fifth family that only
+ * this entry point reaches).  Per draw, with alpha_s = exp(logshape[s]) and l[n,s] = sum_d X[n,d] W[s,d] + o[n] (offset
+ * may be NULL):
+ *      mu = exp(l)    v = mu^2 / alpha_s    log p(y | l, alpha_s) = c_a + alpha_s (log y - l - y e^{-l}) - log y
+ *      mean[n] = 1/S sum_s mu,     var[n] = 1/S sum_s mu^2 / alpha_s + 1/S sum_s (mu - mean[n])^2
+ *      lpd[n]  = logsumexp_s log p(y[n] | l[n,s], alpha_s) - log S,     lpd_sum = sum_n lpd[n]     (float64 [1])
+ * The density is bsc_glm_gamma_data_pass's, complete.  exp is NOT clamped: mean stops being finite at l > 88, var at
+ * l > 44, lpd where y e^{-l} overflows; y > 0 is not checked here.  Outputs, refusals, envelope and determinism are
+ * bsc_nb_predict_pass's; logshape == NULL is BSC_ERR_INVALID.  Accuracy envelope of lpd: logshape in [-2.5, 5]. */
+int bsc_gamma_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
+                           int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
+                           float* lpd, double* lpd_sum);
 
 /* The predictive of the random-intercept model (csrc/bsc_predict_group.hip: bsc_predict_pass_offset's kernel with a
  * per-draw, per-group intercept; bsc_glm_data_pass_groups is its training pass):
