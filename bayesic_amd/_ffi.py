@@ -136,6 +136,12 @@ SIGNATURES = {
                                      c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
                                      c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_weibull_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_weibull_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
+                                       c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_glm_fullrank_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_int32, c_double, c_double, c_int64, c_double, c_double, c_double,
                                         c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -147,6 +153,8 @@ SIGNATURES = {
                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_gamma_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                        c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_weibull_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                         c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_predict_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                         c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),

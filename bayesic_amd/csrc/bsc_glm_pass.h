@@ -33,6 +33,9 @@
 //                 csrc/bsc_glm_gamma.hip (LINK = GLM_GAMMA) runs the same flag with a shape alpha_s = exp(tau_s) in the
 //                 place of phi_s: the four registers are tau_s, alpha_s and the two per-draw constants of the Gamma
 //                 density (glm_link below), T[s] and the slab are the same.
+//                 csrc/bsc_glm_weibull.hip (LINK = GLM_WEIBULL) runs it with the Weibull shape k_s = exp(tau_s): only
+//                 tau_s and k_s are kept (the density has no per-draw constant), and the censoring flag of a row is
+//                 the sign of its y, so the tiles carry nothing new.
 //
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
@@ -47,12 +50,13 @@ constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
 constexpr int NB_SLAB_STRIDE = REG_SLAB_G + 2 * SG;   // DSP: ell at [SLAB_G + s], T at [SLAB_G + 8 + s]
 constexpr int GLM_NEGBIN = 2;                 // the third link; internal: the BSC_GLM_* entry points refuse it
 constexpr int GLM_GAMMA = 3;                  // the fourth, internal as well: csrc/bsc_glm_gamma.hip
+constexpr int GLM_WEIBULL = 4;                // the fifth, internal as well: csrc/bsc_glm_weibull.hip
 
-// DSP: what a lane keeps of its draw's dispersion (GLM_GAMMA: of its draw's shape alpha_s).
+// DSP: what a lane keeps of its draw's dispersion (GLM_GAMMA: of its draw's shape alpha_s; GLM_WEIBULL: of k_s).
 struct GlmDisp {
     float tau, phi;     // log phi_s as the pass read it, exp(tau)
     float lg, psi;      // lnGamma(phi), psi(phi); GLM_GAMMA: c_a = alpha log alpha - lnGamma(alpha),
-                        // c_1 = log alpha + 1 - psi(alpha)
+                        // c_1 = log alpha + 1 - psi(alpha); GLM_WEIBULL: not used (0)
 };
 
 // Draw s of this launch's chunk (s >= S: a dead slot, phi = 1).  The special values in float64, once per launch.
@@ -61,7 +65,9 @@ __device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi,
     GlmDisp d;
     d.tau = s < S ? logphi[s] : 0.0f;
     d.phi = expf(d.tau);
-    if constexpr (LINK == GLM_GAMMA) {
+    if constexpr (LINK == GLM_WEIBULL) {
+        d.lg = d.psi = 0.0f;       // tau and k alone: the Weibull density has no special function in it
+    } else if constexpr (LINK == GLM_GAMMA) {
         const double a = (double)d.phi, la = log(a);
         d.lg = (float)(a * la - bsc_lgamma_f64(a));
         d.psi = (float)(la + 1.0 - bsc_digamma_f64(a));
@@ -90,6 +96,15 @@ __device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi,
 //     T    += v alpha (c_1 + ly - l - q)                                                       (= d / d tau)
 // NOT clamped, like the Poisson link: finite while e^{-l} and y e^{-l} are below the float32 maximum (l > -88 at
 // y = 1).  One exp and one log per (row, draw), both at full float32 accuracy: ly enters ell multiplied by alpha.
+// GLM_WEIBULL (always OBS; dp and T set): the sign of y is the censoring flag -- y > 0 an event at y, y < 0 right-censored
+// at -y -- so delta = (y > 0), t = |y|; k = e^tau, ly = log t, z = k (ly - l), l the log SCALE:
+//     ell  += v [ delta (tau + z - ly) - e^z ]            (log f = tau + z - ly - e^z, log S = -e^z: nothing left out)
+//     resid = v k (e^z - delta)                                                                (= d / d l)
+//     T    += v [ delta (1 + z) - z e^z ]                                                      (= d / d tau)
+// NOT clamped, like the Poisson and Gamma links: finite while z stays below about 88 (e^z and z e^z below the float32
+// maximum).  One log and one exp per (row, draw) at full float32 accuracy; z is rounded before the exponential, which
+// costs |z| eps of e^z (the tests' bounds count (1 + |z|) e^z per row).  y = 0 or a non-finite y on a kept row is the
+// caller's to keep out.
 template <int LINK, bool OBS = false>
 __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv = 1.0f,
                                           const GlmDisp* dp = nullptr, float* T = nullptr) {
@@ -134,6 +149,21 @@ __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, floa
         ell = fmaf(vq, fmaf(dp->phi, d, dp->lg) - ly, ell);
         *T = fmaf(vq, dp->phi * (dp->psi + d), *T);
         return vq * (dp->phi * (q - 1.0f));
+    }
+    if constexpr (LINK == GLM_WEIBULL) {
+        // The selects sit on the INPUTS, for the reason given above: a dropped row is evaluated at t = 1, l = 0,
+        // delta = 0 -- z = 0, every term finite whatever y held (0 and NaN included) -- and multiplied by an exact 0.
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const float tq = keep ? fabsf(yv) : 1.0f;
+        const float dl = (keep && yv > 0.0f) ? 1.0f : 0.0f;
+        const float lq = keep ? l : 0.0f;
+        const float ly = logf(tq);
+        const float z = dp->phi * (ly - lq);
+        const float ez = expf(z);
+        ell = fmaf(vq, fmaf(dl, (dp->tau + z) - ly, -ez), ell);
+        *T = fmaf(vq, fmaf(dl, 1.0f + z, -z * ez), *T);
+        return vq * (dp->phi * (ez - dl));
     }
     float a, da;
     if (LINK == BSC_GLM_LOGISTIC) {
@@ -327,7 +357,7 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
                                               int n_iter, const GlmGroupArgs* ga = nullptr,
                                               const float* logphi = nullptr) {
-    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA)),
+    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
                   "the dispersion (the shape) rides with OBS and its own link");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > STRIDE ? G8::WAVE_LDS : STRIDE);
@@ -472,7 +502,7 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
                                                    int n_iter, const GlmGroupArgs* ga = nullptr,
                                                    const float* logphi = nullptr) {
-    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA)),
+    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
                   "the dispersion (the shape) rides with OBS and its own link");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > STRIDE ? MT_WAVE_LDS : STRIDE);
@@ -691,9 +721,9 @@ int for_draw_chunks(bsc_ctx* ctx, int S, Pass pass, Reduce reduce) {
     return for_draw_chunks(ctx, S, pass, reduce, [](int) { return (int)BSC_OK; });
 }
 
-// The data pass of a DSP route (csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip) through the calling translation unit's own
-// kernels: the 16-row MFMA kernel, the 8-row kernel with D == 256 and with any D, and the reduction of the
-// NB_SLAB_STRIDE slab.  `logphi` [S] is the per-draw scalar under the name `what`.
+// The data pass of a DSP route (csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip) through the
+// calling translation unit's own kernels: the 16-row MFMA kernel, the 8-row kernel with D == 256 and with any D, and the
+// reduction of the NB_SLAB_STRIDE slab.  `logphi` [S] is the per-draw scalar under the name `what`.
 template <class Mfma, class Rows8Full, class Rows8, class Reduce>
 int dsp_data_pass(bsc_ctx* ctx, const char* who, const char* what, Mfma mfma_kernel, Rows8Full rows8_full_kernel,
                   Rows8 rows8_kernel, Reduce reduce_kernel, int max_s, const float* X, int64_t ldx, const float* y,

@@ -6,8 +6,8 @@
 // per-group intercept b_s[g_n] joins o_n, gathered from a table Bt [J + 1][ldb] by the row's group id (PredictGroups
 // below).  With GRP off nothing of it is compiled: the shipped instantiations keep their code.  The host side at the end
 // is the envelope of the entry points (predict_check_batch, predict_setup, predict_launch_chunks), shared by
-// csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like
-// csrc/bsc_regress.h.
+// csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip and
+// csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
 #include "bsc_regress.h"
@@ -22,6 +22,10 @@ constexpr int PREDICT_NEGBIN = 3;
 // The fifth, internal as well: csrc/bsc_glm_gamma.hip's predict_gamma_kernel (bsc_gamma_predict_pass), the Gamma
 // likelihood with a per-draw shape; `logvar` carries tau_s = log alpha_s.  Always with OFFS, the offset may be null.
 constexpr int PREDICT_GAMMA = 4;
+// The sixth, internal as well: csrc/bsc_glm_weibull.hip's predict_weibull_kernel (bsc_weibull_predict_pass), the Weibull
+// likelihood with a per-draw shape and right censoring in the sign of y; `logvar` carries tau_s = log k_s.  Always with
+// OFFS, the offset may be null.
+constexpr int PREDICT_WEIBULL = 5;
 
 constexpr int P_BLOCK = 512;
 constexpr int P_WAVES = P_BLOCK / BSC_WAVE;
@@ -41,7 +45,8 @@ struct PredictArgs {
     const float* y;          // may be null
     int64_t B;
     const float* W;
-    const float* logvar;     // Gaussian: log s2 per draw; PREDICT_NEGBIN: log phi per draw; PREDICT_GAMMA: log alpha
+    const float* logvar;     // Gaussian: log s2 per draw; PREDICT_NEGBIN: log phi per draw; PREDICT_GAMMA: log alpha;
+                             // PREDICT_WEIBULL: log k
     float* mean;             // outputs, each may be null
     float* var;
     float* lpd;
@@ -131,6 +136,13 @@ __device__ __forceinline__ void load_intercepts(p_f32x4 (&bt)[NC], const Predict
 // PREDICT_GAMMA: p4 = (tau, alpha = exp(tau), 1 / alpha) and lgp = c_a = alpha log alpha - lnGamma(alpha).
 // mu = exp(l) (not clamped), v = mu^2 / alpha; log p = c_a + alpha (log y - l - y e^{-l}) - log y, the full density
 // (csrc/bsc_glm_pass.h's forms: the exponential as the product y e^{-l}); y > 0 is the caller's to see to.
+// PREDICT_WEIBULL: p4 = (tau, k = exp(tau), g1 = Gamma(1 + 1/k)) and lgp = g2 = Gamma(1 + 2/k) - Gamma(1 + 1/k)^2, both
+// made once per launch in float64 (the exp(-logvar) slot is not needed and carries g1).  l is the log SCALE:
+// mu = e^l g1, v = e^{2l} g2 (not clamped); with t = |y|, z = k (log t - l):  log p = tau + z - log t - e^z for y > 0 (an
+// event at y), log p = -e^z for y < 0 (right-censored at -y: the log survival), so the lpd of a censored row is the log of
+// the posterior-predictive survival probability.  y = 0 is the caller's to keep out.
+// FLOAT32 ENVELOPE OF THE MOMENTS: Gamma(1 + 2/k) overflows float32 near k = 0.06 (tau = -2.8); accuracy envelope tau in
+// [-2, 4].  g2 is a difference of float64 values, 5e-4 at tau = 4: no digit of the float32 result is lost to it.
 template <int FAM>
 __device__ __forceinline__ void predict_link(float l, float yv, float lv, float ev, float iv, float& mu, float& v,
                                              float& lp, float lgp = 0.0f) {
@@ -151,6 +163,16 @@ __device__ __forceinline__ void predict_link(float l, float yv, float lv, float 
         v = mu * iv * mu;
         const float ly = logf(yv);
         lp = fmaf(ev, (ly - l) - yv * expf(-l), lgp) - ly;
+        return;
+    }
+    if constexpr (FAM == PREDICT_WEIBULL) {
+        const float el = expf(l);
+        mu = el * iv;
+        v = el * lgp * el;
+        const float ly = logf(fabsf(yv));
+        const float z = ev * (ly - l);
+        const float ez = expf(z);
+        lp = yv > 0.0f ? ((lv + z) - ly) - ez : -ez;
         return;
     }
     if (FAM == BSC_PREDICT_GAUSSIAN) {
@@ -183,7 +205,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     static_assert(!GRP || OFFS, "the grouped body adds its intercept next to the offset");
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
-    constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA;   // families with a fourth per-draw value
+    constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA || FAM == PREDICT_WEIBULL;   // a fourth value
     constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || OWN4;        // a scalar rides with every draw
     constexpr int GP_SLOTS = OWN4 ? 4 : 3;                                 // ... and lnGamma(phi), or c_a
     __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + GP_SLOTS * P_MAX_S];
@@ -209,6 +231,12 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
         if constexpr (FAM == PREDICT_GAMMA) {
             const double al = (double)expf(lv);
             gp[3 * P_MAX_S + tid] = (float)(al * log(al) - bsc_lgamma_f64(al));
+        }
+        if constexpr (FAM == PREDICT_WEIBULL) {   // Gamma(1 + 1/k) in the exp(-logvar) slot, the variance factor behind
+            const double ik = 1.0 / (double)expf(lv);
+            const double g1 = exp(bsc_lgamma_f64(1.0 + ik));
+            gp[2 * P_MAX_S + tid] = (float)g1;
+            gp[3 * P_MAX_S + tid] = (float)(exp(bsc_lgamma_f64(1.0 + 2.0 * ik)) - g1 * g1);
         }
     }
     __syncthreads();
@@ -463,8 +491,8 @@ void predict_launch_chunks(int S, F launch) {
 }
 
 // The entry point of a family with a per-draw scalar of its own (`logphi` [S], named `what` in the messages) and an
-// offset that may be null: csrc/bsc_glm_nb.hip and csrc/bsc_glm_gamma.hip.  launch(NC, args, n_blocks) launches the
-// calling translation unit's kernel for NC chunks of draws, sum_kernel is its block_partial_sum.
+// offset that may be null: csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip.  launch(NC, args,
+// n_blocks) launches the calling translation unit's kernel for NC chunks of draws, sum_kernel is its block_partial_sum.
 template <class Launch, class Sum>
 int scalar_predict_pass(bsc_ctx* ctx, const char* who, const char* what, Launch launch, Sum sum_kernel, const float* X,
                         int64_t ldx, const float* y, const float* offset, int64_t B, int32_t D, const float* W,

@@ -1,5 +1,5 @@
 """What the reparameterised regression drivers (svi/blr.py, svi/glm.py, svi/softmax.py, svi/hier_glm.py, svi/glm_nb.py,
-svi/glm_gamma.py) share.
+svi/glm_gamma.py, svi/glm_weibull.py) share.
 
 A Gaussian guide over P flattened parameters: ``covariance="diag"`` lam = [m (P) | rho (P)], ``"full"`` lam =
 [mu (P) | L packed row-major, lower triangle incl. the diagonal, rho_i = log L_ii in the diagonal slots]

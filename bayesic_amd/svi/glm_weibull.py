@@ -1,0 +1,205 @@
+"""Weibull survival regression (accelerated failure time) with right censoring and a learned shape by
+reparameterised-ELBO SVI on the fused pass.
+
+Host-side driver of csrc/bsc_glm_weibull.hip; every numeric step is a C-ABI call into libbayesic_hip.so.
+
+Model:  t_n ~ Weibull(shape k, scale e^{l_n}),   l_n = x_n . w + o_n,   w ~ N(0, I / prior_precision),
+        k = e^tau ~ Gamma(a0, b0);   delta_n = 1: the event was seen at t_n,  delta_n = 0: right-censored, the event is
+        later than t_n.
+q:      z = [w (D) | tau] ~ N(m, diag e^{2 rho}),  lam = [m (P) | rho (P)],  P = D + 1.
+
+The model for a duration that is only partly observed (time to failure, length of stay, time to churn): the rows that
+are still running when the data are cut enter through their survival probability, log S(t) = -e^z, the others through
+the density, log f(t) = tau + z - log t - e^z, with z = k (log t - l).  Dropping the censored rows, or treating the
+cut-off as the failure time (what a GammaReparamSVI fit of the same data has to do), biases the scale and the shape.
+l is the log SCALE, not the log mean: E t = e^l Gamma(1 + 1/k), Var t = e^{2l} (Gamma(1 + 2/k) - Gamma(1 + 1/k)^2).
+At k = 1 with every row an event this is the Gamma model at alpha = 1, the exponential distribution.
+
+The censoring flag costs nothing on the device: the driver keeps ONE float32 vector y = where(event, time, -time) --
+y_n > 0 is an event at y_n, y_n < 0 is censored at -y_n; a duration is positive, so the sign is free -- and that vector is
+what the pass reads (include/bayesic_hip.h, bsc_glm_weibull_data_pass).  With raw device pointers the caller passes the
+signed vector.  The data enter one update through ell_s, G_s (svi/glm.py) and T_s = d ell_s / d tau_s, all from ONE
+streaming pass over X; the shape draw tau_s rides with the weight draw w_s exactly as NegBinReparamSVI's dispersion and
+GammaReparamSVI's shape do, and the finish is theirs (the prior on e^tau has the same form).  step() = pass ->
+all-reduce of [ell | G | T] -> bsc_glm_weibull_update; the state, the first draw and step() are ReparamDriver's
+(svi/_reparam_base.py), offsets and row weights svi/glm.py's (svi/_obs.py).  There is no ``exposure``: a multiplier on
+the scale has no established meaning here, and ``offset`` covers it.
+
+``time`` must be finite and strictly positive, ``event`` a bool or 0/1 array of length B (None: every row is an event).
+Both are checked where a batch is set -- the constructor and set_batch, on the host before a device is asked for when
+they are host arrays -- and never in step(); raw device pointers are taken as they are.  The pass does not clamp: it is
+finite while z = k (log t - l) stays below about 88.
+
+Accuracy envelope: tau in [-2, 4] (k from 0.14 to 55); below it the predictive moments leave float32 (Gamma(1 + 2/k)
+overflows near k = 0.06).
+
+Out of scope, by design of this version: left and interval censoring (one bit per row says right-censored or not); the
+full-covariance guide (the guide is mean-field); groups together with the shape; recognition by ReparamVI (it does not
+recognise a Weibull log-joint); MiniBatchLoader (it does not carry offset and weights).  There is no one-call (pass +
+finish) form, so every update is pass -> all-reduce -> finish.  The multi-rank branch is wired like the other drivers'
+and has been exercised at world size 1 only.
+"""
+import math
+
+import numpy as np
+
+from ._obs import ObsBatch, batch_obs
+from ._reparam_base import ReparamDriver, check_lam0, check_n_samples, check_priors
+
+TIME_MSG = "time must be finite and > 0 (a duration; censoring is given by event=, not by a sign)"
+EVENT_MSG = "event must be a bool or 0/1 array of length %d, one entry per row (None: every row is an event)"
+
+
+def check_arguments(prior_precision, a0, b0, n_samples):
+    """The constructor's checks that need no device."""
+    check_priors(prior_precision, a0, b0, "the shape")
+    check_n_samples(n_samples)
+
+
+def pack_response(time, event=None):
+    """The signed float32 response the pass reads, where(event, time, -time), after the checks of ``time`` (finite and
+    > 0 as float32) and ``event`` (bool or 0/1, length B).  Host arrays give a host array; a tensor ``time`` gives a
+    tensor on its device (one synchronisation, so it sits outside step())."""
+    import torch
+    if isinstance(time, torch.Tensor):
+        if time.dim() != 1 or not bool((torch.isfinite(time) & (time > 0)).all()):
+            raise ValueError(TIME_MSG)
+        if event is None:
+            return time
+        ev = event if isinstance(event, torch.Tensor) else torch.as_tensor(np.asarray(event))
+        if ev.dim() != 1 or ev.shape[0] != time.shape[0]:
+            raise ValueError(EVENT_MSG % time.shape[0])
+        if ev.dtype != torch.bool:
+            if not bool(((ev == 0) | (ev == 1)).all()):
+                raise ValueError(EVENT_MSG % time.shape[0])
+            ev = ev != 0
+        return torch.where(ev.to(time.device), time, -time)
+    with np.errstate(over="ignore"):
+        t = np.asarray(time, np.float32)
+    if t.ndim != 1 or not (np.isfinite(t).all() and (t > 0).all()):
+        raise ValueError(TIME_MSG)
+    if event is None:
+        return t
+    if isinstance(event, torch.Tensor):
+        event = event.cpu().numpy()
+    ev = np.asarray(event)
+    if ev.ndim != 1 or ev.shape[0] != t.shape[0]:
+        raise ValueError(EVENT_MSG % t.shape[0])
+    if ev.dtype != np.bool_:
+        if ev.dtype.kind not in "iuf" or not ((ev == 0) | (ev == 1)).all():
+            raise ValueError(EVENT_MSG % t.shape[0])
+        ev = ev != 0
+    return np.where(ev, t, -t).astype(np.float32)
+
+
+class WeibullReparamSVI(ObsBatch, ReparamDriver):
+    link = "weibull"         # svi/predict.py: family_of
+
+    def __init__(self, X, time, event=None, n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0, a0=1.0,
+                 b0=0.1, ctx=None, group=None, lam0=None, *, offset=None, weights=None):
+        """``time`` [B] finite and > 0; ``event`` [B] bool or 0/1, None = every row an event.  ``a0``, ``b0``: the
+        Gamma(shape, rate) prior of the Weibull shape k (default: mean 10, wide).  ``lam0``: [m | rho] over
+        [w (D) | tau] (default m = 0 -- tau starts at 0, k at 1, the exponential distribution -- and every rho = log 0.1).
+        ``offset`` / ``weights``: float32 [B], as in GLMReparamSVI.  time, event and the weights are checked here (one
+        synchronisation), never in step()."""
+        check_arguments(prior_precision, a0, b0, n_samples)
+        import torch
+        host = not isinstance(time, torch.Tensor)
+        if host:
+            y = pack_response(time, event)        # before a device is asked for
+        shape = getattr(X, "shape", ())
+        if len(shape) == 2:                       # an array or a tensor: lam0 too is checked before a device is asked for
+            check_lam0(lam0, int(shape[1]) + 1, "w (%d) | tau" % int(shape[1]))
+        from ..device import default_context
+        self.covariance_kind = "diag"
+        self.prior_precision, self.a0, self.b0 = float(prior_precision), float(a0), float(b0)
+        self.ctx = ctx or default_context()
+        if not host:
+            y = pack_response(time, event)
+        self._float_batch(X, y)
+        self._set_obs(*batch_obs(self.ctx, self.B, offset, weights))
+        self.has_offset = self._oarg is not None      # predict() refuses to run without one
+        D, S = self.D, int(n_samples)
+        P = D + 1
+        check_lam0(lam0, P, "w (%d) | tau" % D)
+        # stats = [ell | G | T]; the slab of the pass is 8 * 256 + 16 floats per workgroup
+        self._init_state(P, lam0, n_total, S, seed, lr, group, noise_dim=D, w_cols=D, n_stats=S * (D + 2),
+                         reserve_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 16) * 4)
+        self.T = self.stats[S + S * D:]
+        self._logshape = torch.zeros((2, S), dtype=torch.float32, device=self.ctx.device)
+
+    def set_batch(self, X, time, event=None, rows=None, ldx=None, offset=None, weights=None):
+        """ReparamDriver.set_batch with the batch's censoring flags, offset and weights: tensors (time checked finite and
+        > 0, event bool or 0/1, the weights finite and >= 0; y = where(event, time, -time) is what the driver keeps)
+        with tensor X and time; raw device pointers (unchecked) with raw ones, ``time`` then being the signed vector and
+        ``event`` not allowed.  None drops offset or weights for this batch."""
+        import torch
+        if isinstance(X, torch.Tensor):
+            time = pack_response(time, event)
+            offset, weights = batch_obs(self.ctx, X.shape[0], offset, weights)
+        elif event is not None:
+            raise ValueError("with raw device pointers pass the signed vector where(event, time, -time) as time; "
+                             "event= is for tensors")
+        super().set_batch(X, time, rows=rows, ldx=ldx)
+        self._set_obs(offset, weights)
+
+    @property
+    def logshape(self):
+        return self._logshape[self.cur]
+
+    # -- phases -------------------------------------------------------------------------------------------------
+    def sample(self, step):
+        """The first draw (first_draw) of w and tau, rounded to float32 as the finish rounds."""
+        import torch
+        z = self._first_draw(step).astype(np.float32)
+        self._store_W(z, self.D)
+        self._logshape[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(z[:, self.D])))
+        self._drawn = True
+
+    def data_pass(self):
+        self.ctx.call("bsc_glm_weibull_data_pass", self._Xarg, self._ldx, self._yarg, self._oarg, self._varg, self.B,
+                      self.D, self.W, self.logshape, self.S, self.ell, self.G, self.T)
+
+    def _finish(self, stats):
+        self._finish_latent("bsc_glm_weibull_update", stats, self._logshape, (self.D,))
+
+    # -- posterior predictive (svi/predict.py: one bsc_weibull_predict_pass over X for all draws) -------------------
+    def _signed(self, time, event):
+        """The signed response of held-out rows (on the context's device), or None without ``time``."""
+        if time is None:
+            if event is not None:
+                raise ValueError("event= needs time=")
+            return None
+        return pack_response(time, event)
+
+    def predict(self, X, time=None, event=None, n_samples=64, seed=None, draws=None, offset=None, weights=None):
+        """``mean`` = E t and ``var`` = Var t per row under the posterior predictive and, with ``time``, ``lpd`` and
+        ``lpd_sum``: the log predictive density at an event, the log predictive SURVIVAL probability at a censored
+        time."""
+        from .predict import predict
+        return predict(self, X, self._signed(time, event), n_samples=n_samples, seed=seed, draws=draws, offset=offset,
+                       weights=weights)
+
+    def heldout_lpd(self, X, time, event=None, n_samples=64, seed=None, draws=None, offset=None, weights=None):
+        """Mean log predictive density per held-out row (a host float); with weights sum v lpd / sum v."""
+        from .predict import heldout_lpd
+        return heldout_lpd(self, X, self._signed(time, event), n_samples=n_samples, seed=seed, draws=draws,
+                           offset=offset, weights=weights)
+
+    def survival(self, X, t, n_samples=64, seed=None, draws=None, offset=None):
+        """S(t_n | x_n) = P(T_n > t_n) under the posterior predictive, float32 [B] on the device: one predictive pass with
+        every row censored at t_n (its lpd is the log of the draw average of e^{-e^z}), exponentiated."""
+        import torch
+        from .predict import predict
+        y = -pack_response(t)                     # t checked like a duration, every row censored
+        return torch.exp(predict(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset)["lpd"])
+
+    # -- host views -----------------------------------------------------------------------------------------------
+    def params(self):
+        """m and rho (host float64) whole and split -- w [D] and tau (scalars), each as (mean, rho) -- and
+        shape_mean = E_q[k] = exp(m_tau + e^{2 rho_tau} / 2)."""
+        lam = self.lam.cpu().numpy()
+        D, P = self.D, self.P
+        m, rho = lam[:P], lam[P:]
+        return dict(m=m, rho=rho, w=(m[:D], rho[:D]), tau=(m[D], rho[D]),
+                    shape_mean=math.exp(m[D] + 0.5 * math.exp(2.0 * rho[D])))

@@ -20,6 +20,9 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
     NegBinReparamSVI                  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  tau = m_tau + e^{rho_tau} eps[:, D]
                                       (lam is already [m | rho] over z = [w | tau]; bsc_nb_predict_pass)
     GammaReparamSVI                   eps [S, D + 1]:  the same transform, tau = log alpha (bsc_gamma_predict_pass)
+    WeibullReparamSVI                 eps [S, D + 1]:  the same transform, tau = log k (bsc_weibull_predict_pass; y is
+                                      the signed response of svi/glm_weibull.py, negative = right-censored, and the
+                                      lpd of such a row is its log predictive survival probability)
     HierGLMReparamSVI                 eps [S, D + J + 2]:  z = m + e^rho eps[:, :D + J + 1] over z = [w | b | zeta], and
                                       b_new = e^{-zeta / 2} eps[:, D + J + 1], the intercept of a group that was not
                                       seen in training; returned as (W [S, D], Bt [J + 1, ldb]) with Bt[j, s] = b_s[j],
@@ -27,7 +30,7 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
 xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass); tau = log phi is the log-dispersion
 of the negative binomial, or the log-shape of the Gamma model, and travels in the same slot of the returned pair.
 
-Offsets and weights (logistic, Poisson, negative-binomial and Gamma models): ``offset`` (or, with a log link, ``exposure`` = e^offset) is added to the
+Offsets and weights (logistic, Poisson, negative-binomial, Gamma and Weibull models): ``offset`` (or, with a log link, ``exposure`` = e^offset) is added to the
 linear predictor in the pass (bsc_predict_pass_offset), so a Poisson ``mean`` is the expected count at that exposure.
 A model fitted with an offset refuses to predict without one.  ``weights`` leave every per-row output alone and make
 ``lpd_sum`` the weighted sum_n v_n lpd_n (float64, on the device, from the lpd vector).
@@ -49,7 +52,8 @@ from ._reparam_base import first_draw, float_batch
 # include/bayesic_hip.h: BSC_PREDICT_*
 FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
 # families with an entry point of their own: a per-draw log-scalar behind the weights, the offset may be None
-SCALAR_PASSES = {"negbin": "bsc_nb_predict_pass", "gamma": "bsc_gamma_predict_pass"}
+SCALAR_PASSES = {"negbin": "bsc_nb_predict_pass", "gamma": "bsc_gamma_predict_pass",
+                 "weibull": "bsc_weibull_predict_pass"}
 PREDICT_STREAM = 2     # Philox stream of the predictive draws
 MAX_SAMPLES = 64       # draws per bsc_predict_pass call
 
@@ -57,8 +61,8 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 
 
 def family_of(model):
-    """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI, "gamma" for GammaReparamSVI;
-    HierGLMReparamSVI's link too --
+    """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI, "gamma" for GammaReparamSVI,
+    "weibull" for WeibullReparamSVI; HierGLMReparamSVI's link too --
     ``grouped`` tells that model apart), "softmax" for SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
     if getattr(model, "n_classes", None) is not None:
         return "softmax"
@@ -104,7 +108,7 @@ def _check_samples(n_samples):
 def posterior_draws(model, n_samples=64, seed=None):
     """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q; W is [S, K, D] for
     SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d); for NegBinReparamSVI the second
-    entry is logphi float32 [S], for GammaReparamSVI logshape float32 [S]; for HierGLMReparamSVI it is the intercept table Bt float32 [J + 1, ldb] (module
+    entry is logphi float32 [S], for GammaReparamSVI and WeibullReparamSVI logshape float32 [S]; for HierGLMReparamSVI it is the intercept table Bt float32 [J + 1, ldb] (module
     docstring)."""
     S = _check_samples(n_samples)
     family = family_of(model)
@@ -123,7 +127,7 @@ def posterior_draws(model, n_samples=64, seed=None):
     if family == "softmax":
         D = model.n_classes * model.D          # the guide's width; the transforms below are the GLM ones
     seed = model.seed if seed is None else int(seed)
-    scalar = family in ("gaussian", "negbin", "gamma")  # a scalar latent rides behind the weights
+    scalar = family == "gaussian" or family in SCALAR_PASSES   # a scalar latent rides behind the weights
     P = D + 1 if scalar else D
     eps_d = torch.zeros((S, P), dtype=torch.float64, device=ctx.device)
     ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P, eps_d)
@@ -159,7 +163,7 @@ def _obs(model, family, B, offset, exposure, weights):
                          "counts")
     if offset is None and exposure is None and weights is None:
         return None, None
-    if family not in ("logistic", "poisson", "negbin", "gamma"):
+    if family not in ("logistic", "poisson") and family not in SCALAR_PASSES:
         raise ValueError("predict: offset, exposure and weights are for the logistic and Poisson models, not %s" % family)
     check_link("poisson" if family in SCALAR_PASSES else family, offset, exposure, kept="means")   # a log link's rules
     return batch_obs(model.ctx, B, offset, weights, exposure)

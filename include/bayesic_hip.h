@@ -592,6 +592,54 @@ int bsc_glm_gamma_update(bsc_ctx* ctx, const double* stats, const double* lam_in
                          double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
                          int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo, double* grad);
 
+/* ---- Weibull survival regression with right censoring and a learned shape on the same pass (csrc/bsc_glm_weibull.hip)
+ *
+ *      t_n ~ Weibull(shape k, scale e^{l_n}),   l[n,s] = sum_d X[n,d] W[s,d] + o[n]   (accelerated failure time)
+ *      w ~ N(0, I / prior_precision),   k = e^tau ~ Gamma(a0, b0)
+ * The latent is z = [w (D) | tau], P = D + 1, the guide mean-field: lam = [m (P) | rho (P)].  One shape draw rides with
+ * every weight draw: logshape[s] = tau_s, float32 [S], any 4-byte alignment; k_s = e^{tau_s} (float32 expf of the value
+ * read).  l is the log SCALE, not the log mean: E t = e^l Gamma(1 + 1/k), Var t = e^{2l} (Gamma(1 + 2/k) -
+ * Gamma(1 + 1/k)^2).
+ * ENCODING: the censoring flag of a row is the SIGN of y (a duration is positive, so the sign is free and the pass reads
+ * no new vector):  y[n] > 0 is an event seen at y[n];  y[n] < 0 is right-censored at -y[n] (the event is later);
+ * 0, NaN and +-infinity are invalid.  With delta = (y > 0), t = |y|, ly = log t and z = k (ly - l):
+ *      log f(t) = tau + z - ly - e^z        log S(t) = -e^z              (the FULL density: nothing is left out)
+ *      ell[s]  = sum_n v[n] ( delta[n] (tau_s + z[n,s] - ly[n]) - e^{z[n,s]} )
+ *      G[s,d]  = sum_n r[n,s] X[n,d]             r[n,s] = v[n] k_s ( e^{z[n,s]} - delta[n] )                   (= d / d l)
+ *      T[s]    = sum_n v[n] ( delta[n] (1 + z[n,s]) - z[n,s] e^{z[n,s]} )                        (= d ell[s] / d tau_s)
+ * At k = 1 with every row an event ell and G are bsc_glm_gamma_data_pass's at alpha = 1 (T is not).
+ * Outputs float64: ell [S], G [S, D], T [S].  offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0,
+ * v = 1; a row with v[n] = 0 adds EXACTLY nothing to ell, G and T, by a select on the link's inputs: it is evaluated at
+ * t = 1, l = 0, delta = 0 whatever it held -- 0 and NaN included -- as the rows past B are).
+ * y IS NOT CHECKED ON THE DEVICE: a kept row with y = 0 or a non-finite y makes ell and T of every draw NaN or infinite
+ * (bayesic_amd/svi/glm_weibull.py checks time and event where a batch is set).
+ * OVERFLOW: exp is NOT clamped, as for the Poisson and Gamma links (a clamp would change the gradient silently): the
+ * outputs are finite while z = k (log t - l) stays below about 88 (e^z and z e^z below the float32 maximum).
+ * ACCURACY ENVELOPE: tau in [-2, 4] (k in [0.14, 55]).  z is rounded to float32 before the exponential, which costs
+ * |z| eps of e^z, and z inherits the rounding of k, ly and l: with c = |z| + k (|ly| + sum_d |x_d w_d| + |o|) a plain
+ * float32 evaluation stays within 1e-6 of sum_n v ( delta (|tau| + |z| + |ly| + c) + (1 + c) e^z + 1 ) for ell, of
+ * sum_n v ( delta (1 + |z| + c) + (|z| + (1 + |z|) c) e^z + 1 ) for T and of sum_n v k ( (1 + c) e^z + delta ) |x_d| for
+ * G[., d].
+ * The envelope and its refusals are bsc_glm_nb_data_pass's (D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 with eight draws
+ * and their eight tau per launch, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26); logshape == NULL is
+ * refused.  The 16-row MFMA kernel (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned,
+ * else the 8-row kernel.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block partials of
+ * 8 * 256 + 16 floats (ell and T behind G), fixed-order float64 finish, no float atomics. */
+int bsc_glm_weibull_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                              const float* weight, int64_t B, int32_t D, const float* W, const float* logshape,
+                              int32_t S, double* ell, double* G, double* T);
+
+/* The finish: bsc_glm_nb_update with logshape in the place of logphi -- the prior on e^tau has the same form, the
+ * likelihood enters through ell, G and T alone, and the entry points run one body (csrc/bsc_meanfield.h), so the same
+ * arguments give the same bits as bsc_glm_nb_update and bsc_glm_gamma_update.  stats = [ell (S) | G (S*D) | T (S)];
+ * checks, next draws and requirements as there. */
+int bsc_glm_weibull_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                           double* m2, const double* eps, const float* W, const float* logshape, int32_t D, int32_t S,
+                           double scale, double prior_precision, double a0, double b0, int64_t t, double lr,
+                           double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
+                           double* eps_next, int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo,
+                           double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
@@ -683,6 +731,24 @@ int bsc_nb_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* 
 int bsc_gamma_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                            int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
                            float* lpd, double* lpd_sum);
+
+/* The predictive of the Weibull survival model (csrc/bsc_glm_weibull.hip: bsc_predict_pass's kernel with a sixth family
+ * that only this entry point reaches).  y carries bsc_glm_weibull_data_pass's encoding: y[n] > 0 an event at y[n],
+ * y[n] < 0 right-censored at -y[n].  Per draw, with k_s = exp(logshape[s]), l[n,s] = sum_d X[n,d] W[s,d] + o[n] (offset
+ * may be NULL), t = |y| and z = k_s (log t - l):
+ *      mu = e^l Gamma(1 + 1/k_s)        v = e^{2l} ( Gamma(1 + 2/k_s) - Gamma(1 + 1/k_s)^2 )
+ *      log p(y | l, k_s) = tau_s + z - log t - e^z   (y > 0: the density)        = -e^z   (y < 0: the log survival)
+ *      mean[n] = 1/S sum_s mu,     var[n] = 1/S sum_s v + 1/S sum_s (mu - mean[n])^2
+ *      lpd[n]  = logsumexp_s log p(y[n] | l[n,s], k_s) - log S,     lpd_sum = sum_n lpd[n]     (float64 [1])
+ * The lpd of a censored row is therefore the log of the posterior-predictive survival probability at that time, and a
+ * batch with every row censored at t_n gives log S(t_n | x_n).  Both special values are made once per launch in float64
+ * and rounded.  exp is NOT clamped: mean stops being finite at l > 88, var at l > 44, lpd where z > 88; y = 0 is not
+ * checked here.  FLOAT32 ENVELOPE OF THE MOMENTS: Gamma(1 + 2/k) overflows float32 near k = 0.06; accuracy envelope
+ * logshape in [-2, 4].  Outputs, refusals, envelope and determinism are bsc_nb_predict_pass's; logshape == NULL is
+ * BSC_ERR_INVALID. */
+int bsc_weibull_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
+                             int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
+                             float* lpd, double* lpd_sum);
 
 /* The predictive of the random-intercept model (csrc/bsc_predict_group.hip: bsc_predict_pass_offset's kernel with a
  * per-draw, per-group intercept; bsc_glm_data_pass_groups is its training pass):
