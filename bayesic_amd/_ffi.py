@@ -145,6 +145,10 @@ SIGNATURES = {
     "bsc_glm_fullrank_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_int32, c_double, c_double, c_int64, c_double, c_double, c_double,
                                         c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_scalar_fullrank_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int32, c_int32, c_double, c_double, c_double,
+                                               c_double, c_int64, c_double, c_double, c_double, c_double, c_uint64,
+                                               c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_predict_pass": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                  c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_predict_pass_offset": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32,

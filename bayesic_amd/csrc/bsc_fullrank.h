@@ -1,8 +1,9 @@
-// The body the two full-covariance finishes share (blr_fullrank_update_kernel in csrc/bsc_blr_full.hip,
-// glm_fullrank_update_kernel in csrc/bsc_glm_full.hip): q = N(mu, L L^T) over P parameters, lam = [mu (P) | L packed
+// The body the full-covariance finishes share (blr_fullrank_update_kernel in csrc/bsc_blr_full.hip,
+// glm_fullrank_update_kernel in csrc/bsc_glm_full.hip, glm_scalar_fullrank_update_kernel in
+// csrc/bsc_glm_scalar_full.hip): q = N(mu, L L^T) over P parameters, lam = [mu (P) | L packed
 // row-major, lower triangle incl. the diagonal], row i at P + i(i+1)/2 with rho_i = log L_ii in its diagonal slot.
 // Workgroup k owns rows k and P-1-k of L (k + 1 and P - k entries: equal work); once a kernel's own prologue has put
-// g_{s,i} = d f / d z_i at draw s of its rows into LDS, everything below is the same for both models: the gradient
+// g_{s,i} = d f / d z_i at draw s of its rows into LDS, everything below is the same for every model: the gradient
 // of mu_i and of the row's entries, Adam on each, and the rows' share of the next draw z' = mu' + L' eps'.  Every sum
 // runs in a fixed order and nothing is contracted into FMAs, so that with a diagonal L this is the mean-field
 // finish's arithmetic.  Header-only, internal linkage (csrc/bsc_regress.h says why).
@@ -85,7 +86,7 @@ __device__ __forceinline__ void fr_next_draw(const fr_rows& rp, int E, int S, co
     }
 }
 
-// ---- host side: what the two entry points check and do alike ------------------------------------------------------
+// ---- host side: what the entry points check and do alike ----------------------------------------------------------
 
 // The state and size checks (the next-draw buffers and the noise: next_draw_noise, csrc/bsc_regress.h);
 // `stats_layout` names the data pass's statistics ("Q | G", "ell | G").

@@ -3,7 +3,8 @@ svi/glm_gamma.py, svi/glm_weibull.py) share.
 
 A Gaussian guide over P flattened parameters: ``covariance="diag"`` lam = [m (P) | rho (P)], ``"full"`` lam =
 [mu (P) | L packed row-major, lower triangle incl. the diagonal, rho_i = log L_ii in the diagonal slots]
-(include/bayesic_hip.h, bsc_glm_fullrank_update).  lam and the draws are double-buffered (index t & 1 is current at the
+(include/bayesic_hip.h, bsc_glm_fullrank_update; with a scalar latent behind the weights bsc_blr_fullrank_update and
+bsc_glm_scalar_fullrank_update).  lam and the draws are double-buffered (index t & 1 is current at the
 start of step t + 1) and the noise is drawn NOISE_BLOCK steps ahead by bsc_blr_noise into a ring of two blocks, in its
 [S, noise width + 1] layout (the last column belongs to a scalar latent: BLR's xi, the hierarchy's zeta).
 
@@ -81,9 +82,52 @@ def check_n_samples(n_samples):
         raise ValueError("n_samples must be in [1, 64]")
 
 
-def check_lam0(lam0, P, layout):
-    if lam0 is not None and np.asarray(lam0).size != 2 * P:
+def check_covariance(covariance):
+    if covariance not in ("diag", "full"):
+        raise ValueError("covariance must be 'diag' or 'full', got %r" % (covariance,))
+
+
+def check_lam0(lam0, P, layout, covariance="diag"):
+    if lam0 is None:
+        return
+    if covariance == "full":
+        if np.asarray(lam0).size != full_size(P):
+            raise ValueError("lam0 has %d entries; covariance='full' ([mu | packed L]) over [%s] needs %d"
+                             % (np.asarray(lam0).size, layout, full_size(P)))
+    elif np.asarray(lam0).size != 2 * P:
         raise ValueError("lam0 has %d entries; [m | rho] over [%s] needs %d" % (np.asarray(lam0).size, layout, 2 * P))
+
+
+def scalar_latent_params(lam, D, covariance, mean_key):
+    """The host views of a guide over z = [w (D) | tau] whose e^tau is a dispersion or a shape (svi/glm_nb.py,
+    svi/glm_gamma.py, svi/glm_weibull.py): m and rho whole and split -- w [D] and tau (scalars), each as (mean, rho) --,
+    with ``covariance="full"`` the dense lower-triangular L [P, P] as well, and ``mean_key`` = E_q[e^tau] =
+    exp(m_tau + Var_q(tau) / 2).  Var_q(tau) is e^{2 rho_tau} under the mean-field guide and the squared norm of the
+    WHOLE last row of L under the full one (tau is correlated with w through that row's off-diagonal entries)."""
+    lam = np.asarray(lam, np.float64)
+    P = D + 1
+    if covariance == "full":
+        m, L = unpack_full(lam, P)
+        rho = rho_of_full(lam, P)
+        out = dict(m=m, L=L, rho=rho)
+        var_tau = float((L[D] * L[D]).sum())
+    else:
+        m, rho = lam[:P], lam[P:]
+        out = dict(m=m, rho=rho)
+        var_tau = math.exp(2.0 * rho[D])
+    out.update(w=(m[:D], rho[:D]), tau=(m[D], rho[D]))
+    out[mean_key] = math.exp(m[D] + 0.5 * var_tau)
+    return out
+
+
+def scalar_latent_covariance(lam, D, covariance):
+    """Cov_q over z = [w (D) | tau] (P x P, host float64): L L^T of the full guide, diag(e^{2 rho}) of the mean-field
+    one."""
+    P = D + 1
+    if covariance == "full":
+        L = unpack_full(np.asarray(lam, np.float64), P)[1]
+        return L @ L.T
+    return np.diag(np.exp(2.0 * np.asarray(lam, np.float64)[P:]))
 
 
 def float_batch(ctx, X, y, need_y=True):
@@ -220,8 +264,9 @@ class ReparamDriver:
         self._W[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(z[:, :cols]).reshape(-1)))
 
     def _finish_latent(self, name, stats, extra, dims):
-        """_finish of a mean-field model with a Gamma(a0, b0) prior and one latent besides W, through entry point
-        ``name``; ``extra``: that latent's [2, .] double buffer, ``dims``: the sizes the call takes before S."""
+        """_finish of a model with a Gamma(a0, b0) prior and one latent besides W, through entry point ``name`` (a
+        mean-field finish, or bsc_glm_scalar_fullrank_update, which takes the same arguments); ``extra``: that latent's
+        [2, .] double buffer, ``dims``: the sizes the call takes before S."""
         c, n, t = self.cur, 1 - self.cur, self.t + 1
         self._ensure_noise(t)
         self.ctx.call(name, stats, self._lam[c], self._lam[n], self.m1, self.m2, self._eps[self.t % self._ring],

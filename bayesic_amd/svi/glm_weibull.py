@@ -6,7 +6,8 @@ Host-side driver of csrc/bsc_glm_weibull.hip; every numeric step is a C-ABI call
 Model:  t_n ~ Weibull(shape k, scale e^{l_n}),   l_n = x_n . w + o_n,   w ~ N(0, I / prior_precision),
         k = e^tau ~ Gamma(a0, b0);   delta_n = 1: the event was seen at t_n,  delta_n = 0: right-censored, the event is
         later than t_n.
-q:      z = [w (D) | tau] ~ N(m, diag e^{2 rho}),  lam = [m (P) | rho (P)],  P = D + 1.
+q:      z = [w (D) | tau] ~ N(m, diag e^{2 rho}),  lam = [m (P) | rho (P)],  P = D + 1    (covariance="diag", default)
+        z ~ N(mu, L L^T),  lam = [mu (P) | packed L]                                   (covariance="full", below).
 
 The model for a duration that is only partly observed (time to failure, length of stay, time to churn): the rows that
 are still running when the data are cut enter through their survival probability, log S(t) = -e^z, the others through
@@ -33,18 +34,22 @@ finite while z = k (log t - l) stays below about 88.
 Accuracy envelope: tau in [-2, 4] (k from 0.14 to 55); below it the predictive moments leave float32 (Gamma(1 + 2/k)
 overflows near k = 0.06).
 
-Out of scope, by design of this version: left and interval censoring (one bit per row says right-censored or not); the
-full-covariance guide (the guide is mean-field); groups together with the shape; recognition by ReparamVI (it does not
-recognise a Weibull log-joint); MiniBatchLoader (it does not carry offset and weights).  There is no one-call (pass +
+``covariance="full"``: q(z) = N(mu, L L^T) over z = [w (D) | tau] in the full layout of svi/_reparam_base.py, first draw
+mu + L eps, finish bsc_glm_scalar_fullrank_update (svi/glm_nb.py says more).  With censoring the shape is correlated a
+posteriori with the intercept and with every coefficient that moves the scale; a diagonal q reports it too narrow, and
+that width is what predict, heldout_lpd and survival carry on.
+
+Out of scope, by design of this version: left and interval censoring (one bit per row says right-censored or not);
+groups together with the shape; recognition by ReparamVI (it does not recognise a Weibull log-joint); MiniBatchLoader
+(it does not carry offset and weights).  There is no one-call (pass +
 finish) form, so every update is pass -> all-reduce -> finish.  The multi-rank branch is wired like the other drivers'
 and has been exercised at world size 1 only.
 """
-import math
-
 import numpy as np
 
 from ._obs import ObsBatch, batch_obs
-from ._reparam_base import ReparamDriver, check_lam0, check_n_samples, check_priors
+from ._reparam_base import (ReparamDriver, check_covariance, check_lam0, check_n_samples, check_priors,
+                            scalar_latent_covariance, scalar_latent_params)
 
 TIME_MSG = "time must be finite and > 0 (a duration; censoring is given by event=, not by a sign)"
 EVENT_MSG = "event must be a bool or 0/1 array of length %d, one entry per row (None: every row is an event)"
@@ -96,22 +101,24 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
     link = "weibull"         # svi/predict.py: family_of
 
     def __init__(self, X, time, event=None, n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0, a0=1.0,
-                 b0=0.1, ctx=None, group=None, lam0=None, *, offset=None, weights=None):
+                 b0=0.1, ctx=None, group=None, lam0=None, *, offset=None, weights=None, covariance="diag"):
         """``time`` [B] finite and > 0; ``event`` [B] bool or 0/1, None = every row an event.  ``a0``, ``b0``: the
         Gamma(shape, rate) prior of the Weibull shape k (default: mean 10, wide).  ``lam0``: [m | rho] over
         [w (D) | tau] (default m = 0 -- tau starts at 0, k at 1, the exponential distribution -- and every rho = log 0.1).
-        ``offset`` / ``weights``: float32 [B], as in GLMReparamSVI.  time, event and the weights are checked here (one
-        synchronisation), never in step()."""
+        ``covariance``: "diag" (the mean-field guide, default) or "full" (module docstring; ``lam0`` then in the full
+        layout, default the same start with no off-diagonal entries).  ``offset`` / ``weights``: float32 [B], as in
+        GLMReparamSVI.  time, event and the weights are checked here (one synchronisation), never in step()."""
         check_arguments(prior_precision, a0, b0, n_samples)
+        check_covariance(covariance)
         import torch
         host = not isinstance(time, torch.Tensor)
         if host:
             y = pack_response(time, event)        # before a device is asked for
         shape = getattr(X, "shape", ())
         if len(shape) == 2:                       # an array or a tensor: lam0 too is checked before a device is asked for
-            check_lam0(lam0, int(shape[1]) + 1, "w (%d) | tau" % int(shape[1]))
+            check_lam0(lam0, int(shape[1]) + 1, "w (%d) | tau" % int(shape[1]), covariance)
         from ..device import default_context
-        self.covariance_kind = "diag"
+        self.covariance_kind = covariance
         self.prior_precision, self.a0, self.b0 = float(prior_precision), float(a0), float(b0)
         self.ctx = ctx or default_context()
         if not host:
@@ -121,7 +128,7 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         self.has_offset = self._oarg is not None      # predict() refuses to run without one
         D, S = self.D, int(n_samples)
         P = D + 1
-        check_lam0(lam0, P, "w (%d) | tau" % D)
+        check_lam0(lam0, P, "w (%d) | tau" % D, covariance)
         # stats = [ell | G | T]; the slab of the pass is 8 * 256 + 16 floats per workgroup
         self._init_state(P, lam0, n_total, S, seed, lr, group, noise_dim=D, w_cols=D, n_stats=S * (D + 2),
                          reserve_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 16) * 4)
@@ -161,7 +168,8 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
                       self.D, self.W, self.logshape, self.S, self.ell, self.G, self.T)
 
     def _finish(self, stats):
-        self._finish_latent("bsc_glm_weibull_update", stats, self._logshape, (self.D,))
+        name = "bsc_glm_scalar_fullrank_update" if self.covariance_kind == "full" else "bsc_glm_weibull_update"
+        self._finish_latent(name, stats, self._logshape, (self.D,))
 
     # -- posterior predictive (svi/predict.py: one bsc_weibull_predict_pass over X for all draws) -------------------
     def _signed(self, time, event):
@@ -196,10 +204,12 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
 
     # -- host views -----------------------------------------------------------------------------------------------
     def params(self):
-        """m and rho (host float64) whole and split -- w [D] and tau (scalars), each as (mean, rho) -- and
-        shape_mean = E_q[k] = exp(m_tau + e^{2 rho_tau} / 2)."""
-        lam = self.lam.cpu().numpy()
-        D, P = self.D, self.P
-        m, rho = lam[:P], lam[P:]
-        return dict(m=m, rho=rho, w=(m[:D], rho[:D]), tau=(m[D], rho[D]),
-                    shape_mean=math.exp(m[D] + 0.5 * math.exp(2.0 * rho[D])))
+        """m and rho (host float64) whole and split -- w [D] and tau (scalars), each as (mean, rho) --, the dense
+        lower-triangular L [P, P] of a full guide, and shape_mean = E_q[k] = exp(m_tau + Var_q(tau) / 2) with
+        Var_q(tau) = e^{2 rho_tau} (mean-field) or the squared norm of the last row of L (full)."""
+        return scalar_latent_params(self.lam.cpu().numpy(), self.D, self.covariance_kind, "shape_mean")
+
+    def covariance(self):
+        """Cov_q over z = [w (D) | tau] (P x P, host float64): L L^T of the full guide, diag(e^{2 rho}) of the
+        mean-field one."""
+        return scalar_latent_covariance(self.lam.cpu().numpy(), self.D, self.covariance_kind)

@@ -19,6 +19,8 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
                                       (predict() below hands over to its predict(): bsc_softmax_predict_pass)
     NegBinReparamSVI                  eps [S, D + 1]:  w = m + e^rho eps[:, :D],  tau = m_tau + e^{rho_tau} eps[:, D]
                                       (lam is already [m | rho] over z = [w | tau]; bsc_nb_predict_pass)
+      ... (covariance="full")         eps [S, D + 1]:  z = mu + L eps over z = [w | tau], so that tau_s = mu_tau +
+                                      sum_j L_Dj eps_sj is correlated with w_s; the same for the two models below
     GammaReparamSVI                   eps [S, D + 1]:  the same transform, tau = log alpha (bsc_gamma_predict_pass)
     WeibullReparamSVI                 eps [S, D + 1]:  the same transform, tau = log k (bsc_weibull_predict_pass; y is
                                       the signed response of svi/glm_weibull.py, negative = right-censored, and the

@@ -666,6 +666,36 @@ int bsc_glm_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam
                             uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready, float* W_next,
                             double* elbo, double* grad);
 
+/* The finish of bsc_glm_nb_update / bsc_glm_gamma_update / bsc_glm_weibull_update for a FULL-COVARIANCE Gaussian guide
+ * (csrc/bsc_glm_scalar_full.hip): q(z) = N(mu, L L^T) over z = [w (D) | tau], P = D + 1, L lower-triangular with
+ * L_ii = e^{rho_i}.
+ *     lam = [mu (P) | L packed row-major, lower triangle incl. the diagonal (P(P+1)/2)]
+ * row i of L starts at lam[P + i(i+1)/2] and its diagonal slot holds rho_i (33 410 doubles at D = 256): the layout of
+ * bsc_blr_fullrank_update; m1, m2 and grad have lam's layout.  ONE entry point for the three families: the likelihood
+ * enters through stats = [ell (S) | G (S*D) | T (S)] alone (NULL is refused), as the pass of any of them and the
+ * all-reduce leave them.  Arguments and their order are bsc_glm_nb_update's; logscalar [S] is the float32 tau_s the
+ * pass read (logphi, logshape), eps in bsc_blr_noise's [S, D+1] layout with EVERY column read, W the float32 draws:
+ *     g_si = scale G_si - prior_precision W_si  (i < D),     g_sD = scale T_s + a0 - b0 e^{tau_s}
+ *     ELBO = mean_s [ scale ell_s - prior_precision/2 |w_s|^2 + a0 tau_s - b0 e^{tau_s} ]
+ *            + D/2 log(prior_precision / 2 pi) + a0 log b0 - lnGamma(a0) + sum_i rho_i + P/2 (1 + log 2 pi)
+ *            (the mean-field finishes' quantity)
+ *     d / d mu = mean_s g_s,   d / d L_ij = mean_s g_si eps_sj (j < i),
+ *     d / d rho_i = mean_s g_si eps_si e^{rho_i} + 1
+ * then Adam ascent on every entry (lam_in is not modified, m1 and m2 in place) and, when the *_next buffers are set
+ * (all or none), the next draw z'_s = mu' + L' eps'_s rounded to float32 into W_next [S, D] and logscalar_next [S].
+ * eps_next_ready = 0: the noise of next_step is drawn into eps_next first (one bsc_blr_noise launch).  With every
+ * off-diagonal entry zero the ELBO, the mu / rho gradients and their Adam step equal bsc_glm_nb_update's on the same
+ * stats and noise (rtol 1e-12: two sums run in another order).
+ * One launch of D / 2 + 1 workgroups, workgroup k owning rows k and D - k of L (row D / 2 alone); fixed-order sums, no
+ * atomics: reproducible bit for bit.  lam_in != lam_out, and *_next must not alias eps / W / logscalar.
+ * Requires D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64, t >= 1 and prior_precision, a0, b0, scale > 0. */
+int bsc_glm_scalar_fullrank_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                                   double* m2, const double* eps, const float* W, const float* logscalar, int32_t D,
+                                   int32_t S, double scale, double prior_precision, double a0, double b0, int64_t t,
+                                   double lr, double beta1, double beta2, double adam_eps, uint64_t seed,
+                                   uint32_t next_step, double* eps_next, int32_t eps_next_ready, float* W_next,
+                                   float* logscalar_next, double* elbo, double* grad);
+
 /* ---- posterior predictive and held-out log density (csrc/bsc_predict.hip; ABSENT in the reference) ---------
  *
  * One streaming pass over X[B,D] (row-major, leading dimension ldx floats) for S draws W[S,D] of a fitted q.  With
