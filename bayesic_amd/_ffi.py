@@ -138,6 +138,9 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_glm_weibull_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                           c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_weibull_data_pass_interval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                                   c_void_p]),
     "bsc_glm_weibull_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
                                        c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
@@ -159,6 +162,9 @@ SIGNATURES = {
                                        c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_weibull_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                          c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_weibull_predict_pass_interval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                  c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
     "bsc_predict_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                         c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),

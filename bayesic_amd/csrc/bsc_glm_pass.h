@@ -36,6 +36,10 @@
 //                 csrc/bsc_glm_weibull.hip (LINK = GLM_WEIBULL) runs it with the Weibull shape k_s = exp(tau_s): only
 //                 tau_s and k_s are kept (the density has no per-draw constant), and the censoring flag of a row is
 //                 the sign of its y, so the tiles carry nothing new.
+//   ITV = true    csrc/bsc_glm_weibull_interval.hip (always with DSP and LINK = GLM_WEIBULL): interval and left
+//                 censoring.  One more per-row vector, `upper` [B] float32, rides in the tiles next to y and is loaded
+//                 the way y is (rows past B read 0); glm_link says how it is read.  Everything of it is behind
+//                 `if constexpr (ITV)`; the flag defaults to off and every other kernel compiles as it did.
 //
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
@@ -105,9 +109,53 @@ __device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi,
 // maximum).  One log and one exp per (row, draw) at full float32 accuracy; z is rounded before the exponential, which
 // costs |z| eps of e^z (the tests' bounds count (1 + |z|) e^z per row).  y = 0 or a non-finite y on a kept row is the
 // caller's to keep out.
-template <int LINK, bool OBS = false>
+// GLM_WEIBULL with ITV (csrc/bsc_glm_weibull_interval.hip): `uv` is the row's entry of the vector `upper` -- 0: the row is
+// what y says, as above; uv > 0 (with y < 0): interval-censored on (a, b] = (-y, uv]; uv < 0: left-censored at b = -uv,
+// the magnitude of y not read.  With z = k (log a - l), E = e^z, d = log b - log a and Delta = E expm1(k d) = E_b - E_a
+// (a left-censored row: z = k (log b - l), Delta = E, and E_a = 0 in what follows), e = e^{-Delta}, p = -expm1(-Delta):
+// (d through log1p((b - a) / a) where b < 2 a: the difference of two rounded logarithms would lose a narrow interval)
+//     ell  += v [ -E_a + log p ]                                       (= log(S(a) - S(b)): nothing left out)
+//     resid = v k ( E_a - Delta e / p )                                (Delta e / p = Delta / expm1(Delta), in (0, 1))
+//     T    += v [ -z E_a + (z Delta + k d E_b) e / p ]                 E_b = E_a + Delta
+// all three in ONE form with the rows above: an indicator `ic` (1 on such a row, else 0) multiplies the new terms, which
+// a row without an upper end evaluates at Delta = 1, k d = 0.  OVERFLOW: where Delta >= ITV_BIG -- e^{-Delta} is zero in
+// float32 (csrc/bsc_special_f32.h), or the upper end is so far out that e^{k d} or Delta is infinite (upper = 1e30 for "no bound") -- the row is
+// the right-censored one at a (the left-censored one adds nothing: its probability is 1), by the same select on the
+// inputs; a NaN Delta (0 times infinity) goes the same way.  Seven transcendentals per (row, draw) for two.
+
+template <int LINK, bool OBS = false, bool ITV = false>
 __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv = 1.0f,
-                                          const GlmDisp* dp = nullptr, float* T = nullptr) {
+                                          const GlmDisp* dp = nullptr, float* T = nullptr, float uv = 0.0f) {
+    static_assert(!ITV || LINK == GLM_WEIBULL, "the upper end belongs to the Weibull link");
+    if constexpr (LINK == GLM_WEIBULL && ITV) {
+        // The selects sit on the INPUTS, as below: a dropped row is evaluated at a = b = 1, l = 0, delta = 0, ic = 0.
+        // Each select is flat, between values at hand: a nested one (keep ? (left ? .. : ..) : ..) comes out as a branch
+        // that the logit's last additions sink into, which splits the loop body and spills 150 bytes per lane.
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const bool left = keep && uv < 0.0f;
+        const bool itv = keep && uv > 0.0f;
+        const float tq = keep ? fabsf(uv < 0.0f ? uv : yv) : 1.0f;     // one select after the other, not nested
+        const float bq = itv ? uv : tq;
+        const float dl = (keep && uv == 0.0f && yv > 0.0f) ? 1.0f : 0.0f;
+        const float lq = keep ? l : 0.0f;
+        const float ly = logf(tq);
+        const float z = dp->phi * (ly - lq);
+        const float ez = expf(z);
+        const float kd = dp->phi * bsc_logratio_f32(bq, tq, ly);   // exactly 0 unless the row is an interval
+        const float dlt = ez * (bsc_expm1_f32(kd) + (left ? 1.0f : 0.0f));   // expm1(0) = 0 on a left-censored row
+        const bool on = (left || itv) && dlt < ITV_BIG;      // false for a NaN as well
+        const float ic = on ? 1.0f : 0.0f;
+        const float dq = on ? dlt : 1.0f;
+        const float kq = on ? kd : 0.0f;
+        const float ea = left ? 0.0f : ez;
+        const float p = -bsc_expm1_f32(-dq);
+        const float q = expf(-dq) * __builtin_amdgcn_rcpf(p);                      // 1 / expm1(Delta), never through an infinite expm1
+        const float eb = ea + dq;
+        ell = fmaf(vq, fmaf(dl, (dp->tau + z) - ly, fmaf(ic, logf(p), -ea)), ell);
+        *T = fmaf(vq, fmaf(dl, 1.0f + z, fmaf(ic * q, fmaf(z, dq, kq * eb), -z * ea)), *T);
+        return vq * (dp->phi * (ea - fmaf(ic * q, dq, dl)));
+    }
     if constexpr (LINK == GLM_NEGBIN) {
         // The selects sit on the INPUTS: a dropped row (weight 0, or past B) is evaluated at y = 0, u = 0 -- finite
         // whatever it held -- and its terms are multiplied by an exact 0.  A select on the results turns into a
@@ -192,14 +240,19 @@ __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, floa
 constexpr int ROWS = 8;
 using G8 = Geo<ROWS>;
 
-template <bool OBS, bool GRP = false>
+template <bool OBS, bool GRP = false, bool ITV = false>
 struct GlmTile : RowTile<ROWS> {};
 template <>
-struct GlmTile<true, false> : RowTile<ROWS> {
+struct GlmTile<true, false, false> : RowTile<ROWS> {
     float ov, vv;   // offset and weight of row lane_value(lane) >> 3, as yv
 };
 template <>
-struct GlmTile<true, true> : RowTile<ROWS> {
+struct GlmTile<true, false, true> : RowTile<ROWS> {
+    float ov, vv;
+    float uv;       // ITV: the upper end of the same row (glm_link says how it is read)
+};
+template <>
+struct GlmTile<true, true, false> : RowTile<ROWS> {
     float ov, vv;
     int gv;         // group id of the same row
     float bz;       // Bz[gv][lane_value(lane) & 7], gathered by gather_tile
@@ -222,11 +275,12 @@ __device__ __forceinline__ auto glm_bz_rsrc(const GlmGroupArgs& ga) {
 }
 
 // One tile = ROWS rows from row0 on, through descriptors that cover exactly the rows [row0, B).
-template <bool FULL, bool OBS, bool GRP = false>
-__device__ __forceinline__ void load_tile(GlmTile<OBS, GRP>& t, const float* __restrict__ X, int64_t ldx,
+template <bool FULL, bool OBS, bool GRP = false, bool ITV = false>
+__device__ __forceinline__ void load_tile(GlmTile<OBS, GRP, ITV>& t, const float* __restrict__ X, int64_t ldx,
                                           const float* __restrict__ y, const float* __restrict__ o,
                                           const float* __restrict__ v_, int64_t row0, int64_t B, int D, int lane,
-                                          const int* __restrict__ g_ = nullptr) {
+                                          const int* __restrict__ g_ = nullptr,
+                                          const float* __restrict__ u_ = nullptr) {
     auto xs = bsc_rows_rsrc(X, ldx, D, B, row0);
     auto ys = bsc_vec_rsrc(y, B, row0);
     const int lane_off = 16 * lane;
@@ -250,6 +304,10 @@ __device__ __forceinline__ void load_tile(GlmTile<OBS, GRP>& t, const float* __r
         auto gs = bsc_vec_rsrc(g_, B, row0);
         t.gv = (int)__builtin_amdgcn_raw_buffer_load_b32(gs, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0);
     }
+    if constexpr (ITV) {   // rows past B read 0: what y says, and y is dropped there
+        auto us = bsc_vec_rsrc(u_, B, row0);
+        t.uv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(us, 4 * (lane_value<ROWS>(lane) >> 3), 0, 0));
+    }
 }
 
 // GRP: the intercept of this lane's (row, draw), requested before the next tile's loads are issued.
@@ -262,8 +320,8 @@ __device__ __forceinline__ void gather_tile(GlmTile<true, true>& t, const GlmGro
 // are set (uniform; without them every row weighs 1.0f and real_row alone masks the rows past B).
 // GRP: `row0` is the tile's first row (a multiple of 8), its residuals also go to ga.R.
 // DSP: `dp` is the dispersion of this lane's draw, `T` its accumulator.
-template <int LINK, bool OBS, bool GRP = false, bool DSP = false>
-__device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP>& t, const float4 (&w)[SG], float4 (&acc)[SG],
+template <int LINK, bool OBS, bool GRP = false, bool DSP = false, bool ITV = false>
+__device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP, ITV>& t, const float4 (&w)[SG], float4 (&acc)[SG],
                                              float& ell, float* wl, int lane, int64_t rows_left, bool has_v,
                                              const GlmGroupArgs* ga = nullptr, int64_t row0 = 0,
                                              const GlmDisp* dp = nullptr, float* T = nullptr) {
@@ -313,7 +371,10 @@ __device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP>& t, const f
         auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(resid), rs,
                                               4 * ((val & 7) * 16 + (int)(row0 & 8) + (val >> 3)), 0, 0);
-    } else if constexpr (DSP)
+    } else if constexpr (ITV)
+        resid = glm_link<LINK, true, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell,
+                                           has_v ? t.vv : 1.0f, dp, T, t.uv);
+    else if constexpr (DSP)
         resid = glm_link<LINK, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell, has_v ? t.vv : 1.0f,
                                      dp, T);
     else if constexpr (OBS)
@@ -352,13 +413,15 @@ __device__ __forceinline__ void write_block_partial(const float* lds, float* __r
 // FULL: D == 256.  n_iter: tiles per wave (the same for every wave; tiles past the end read zeros).
 // o, v_: the offset and the weight, each may be null; read only where OBS.
 // DSP: logphi [S] (this launch's chunk of the dispersion draws); the slab is NB_SLAB_STRIDE floats per block.
-template <int LINK, bool FULL, bool OBS, bool GRP = false, bool DSP = false>
+// ITV (with DSP and LINK = GLM_WEIBULL): `upper` [B], not null, rides in the tiles next to y.
+template <int LINK, bool FULL, bool OBS, bool GRP = false, bool DSP = false, bool ITV = false>
 __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const float* y, const float* o,
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
                                               int n_iter, const GlmGroupArgs* ga = nullptr,
-                                              const float* logphi = nullptr) {
+                                              const float* logphi = nullptr, const float* upper = nullptr) {
     static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
                   "the dispersion (the shape) rides with OBS and its own link");
+    static_assert(!ITV || (DSP && LINK == GLM_WEIBULL), "the upper end rides with the Weibull shape");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > STRIDE ? G8::WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -403,13 +466,13 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
             compute_tile<LINK, OBS, GRP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS);
         }
     } else {   // (dp and tacc: untouched without DSP)
-        GlmTile<OBS> ta, tb;
-        load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane);
+        GlmTile<OBS, false, ITV> ta, tb;
+        load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane, nullptr, upper);
         for (int k = 0; k + 1 < n_iter; k += 2) {
-            load_tile<FULL, OBS>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane);
+            load_tile<FULL, OBS>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane, nullptr, upper);
             compute_tile<LINK, OBS, false, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, nullptr, 0, &dp,
                                                 &tacc);
-            load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane);
+            load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane, nullptr, upper);
             compute_tile<LINK, OBS, false, DSP>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, nullptr,
                                                 0, &dp, &tacc);
             tile += 2 * stride;
@@ -451,14 +514,19 @@ struct MTileXY {
     float4 x[MT_ROWS];
     float4 yv;     // y[row0 + 4 kq .. + 3]: the rows of this lane's forward result registers
 };
-template <bool OBS, bool GRP = false>
+template <bool OBS, bool GRP = false, bool ITV = false>
 struct MTile : MTileXY {};
 template <>
-struct MTile<true, false> : MTileXY {
+struct MTile<true, false, false> : MTileXY {
     float4 ov, vv;   // offset and weight of the same four rows
 };
 template <>
-struct MTile<true, true> : MTileXY {
+struct MTile<true, false, true> : MTileXY {
+    float4 ov, vv;
+    float4 uv;       // ITV: the upper ends of the same four rows
+};
+template <>
+struct MTile<true, true, false> : MTileXY {
     float4 ov, vv;
     int4 gv;         // group ids of the same four rows
 };
@@ -469,11 +537,12 @@ __device__ __forceinline__ float4 load_rows4(const float* __restrict__ p, int64_
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
 }
 
-template <bool OBS, bool GRP = false>
-__device__ __forceinline__ void load_mtile(MTile<OBS, GRP>& t, const float* __restrict__ X, int64_t ldx,
+template <bool OBS, bool GRP = false, bool ITV = false>
+__device__ __forceinline__ void load_mtile(MTile<OBS, GRP, ITV>& t, const float* __restrict__ X, int64_t ldx,
                                            const float* __restrict__ y, const float* __restrict__ o,
                                            const float* __restrict__ v_, int64_t row0, int64_t B, int lane,
-                                           const int* __restrict__ g_ = nullptr) {
+                                           const int* __restrict__ g_ = nullptr,
+                                           const float* __restrict__ u_ = nullptr) {
     auto xs = bsc_rows_rsrc(X, ldx, GCOLS, B, row0);
     auto ys = bsc_vec_rsrc(y, B, row0);
     const int lane_off = 16 * lane;
@@ -495,15 +564,17 @@ __device__ __forceinline__ void load_mtile(MTile<OBS, GRP>& t, const float* __re
         auto gi = __builtin_amdgcn_raw_buffer_load_b128(gs, 16 * (lane >> 4), 0, 0);
         t.gv = make_int4((int)gi[0], (int)gi[1], (int)gi[2], (int)gi[3]);
     }
+    if constexpr (ITV) t.uv = load_rows4(u_, B, row0, lane);
 }
 
-template <int LINK, bool OBS, bool GRP = false, bool DSP = false>
+template <int LINK, bool OBS, bool GRP = false, bool DSP = false, bool ITV = false>
 __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, const float* y, const float* o,
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
                                                    int n_iter, const GlmGroupArgs* ga = nullptr,
-                                                   const float* logphi = nullptr) {
+                                                   const float* logphi = nullptr, const float* upper = nullptr) {
     static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
                   "the dispersion (the shape) rides with OBS and its own link");
+    static_assert(!ITV || (DSP && LINK == GLM_WEIBULL), "the upper end rides with the Weibull shape");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > STRIDE ? MT_WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -543,8 +614,8 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
 
     const int* g_ = nullptr;
     if constexpr (GRP) g_ = ga->g;
-    MTile<OBS, GRP> t;
-    load_mtile<OBS, GRP>(t, X, ldx, y, o, v_, row0_of(0), B, lane, g_);
+    MTile<OBS, GRP, ITV> t;
+    load_mtile<OBS, GRP>(t, X, ldx, y, o, v_, row0_of(0), B, lane, g_, upper);
     for (int p = 0; p < n_iter; ++p) {
         // the tile to LDS, its registers take the next window's tile
 #pragma unroll
@@ -555,6 +626,8 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
             ov = t.ov;
             if (has_v) vv = t.vv;
         }
+        [[maybe_unused]] float4 uv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (ITV) uv = t.uv;
         const int64_t rows_left = B - row0_of(p) - 4 * kq;     // rows 4 kq + reg < rows_left are real
         float4 bz = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (GRP) {   // the intercepts of this lane's four rows, ahead of the prefetch and of the forward
@@ -565,7 +638,7 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
             bz.z = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bs, 32 * t.gv.z + so, 0, 0));
             bz.w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bs, 32 * t.gv.w + so, 0, 0));
         }
-        load_mtile<OBS, GRP>(t, X, ldx, y, o, v_, row0_of(p + 1), B, lane, g_);
+        load_mtile<OBS, GRP>(t, X, ldx, y, o, v_, row0_of(p + 1), B, lane, g_, upper);
         wave_lds_sync();
 
         // forward on v_mfma_f32_16x16x4_f32 (two accumulators: no MFMA waits on its predecessor)
@@ -600,6 +673,11 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
                 __builtin_amdgcn_raw_buffer_store_b128(
                     u32x4{__float_as_uint(r0), __float_as_uint(r1), __float_as_uint(r2), __float_as_uint(r3)}, rs,
                     4 * (i16 * MT_ROWS + 4 * kq), 0, 0);
+            } else if constexpr (ITV) {
+                r0 = glm_link<LINK, true, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x, &dp, &tacc, uv.x);
+                r1 = glm_link<LINK, true, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y, &dp, &tacc, uv.y);
+                r2 = glm_link<LINK, true, true>(d0[2] + d1[2] + ov.z, yv.z, rows_left > 2, ell, vv.z, &dp, &tacc, uv.z);
+                r3 = glm_link<LINK, true, true>(d0[3] + d1[3] + ov.w, yv.w, rows_left > 3, ell, vv.w, &dp, &tacc, uv.w);
             } else if constexpr (DSP) {
                 r0 = glm_link<LINK, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x, &dp, &tacc);
                 r1 = glm_link<LINK, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y, &dp, &tacc);
@@ -670,11 +748,12 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-// 16 = the MFMA kernel (needs the full 256-column layout and 16-byte aligned y, offset, weight and group ids -- null
-// ones count as aligned), else 8-row tiles.
+// 16 = the MFMA kernel (needs the full 256-column layout and 16-byte aligned y, offset, weight, group ids and upper
+// ends -- null ones count as aligned), else 8-row tiles.
 inline int pass_rows(int D, const float* y, const float* o = nullptr, const float* v = nullptr,
-                     const int32_t* g = nullptr) {
-    return (D == GCOLS && aligned16(y) && aligned16(o) && aligned16(v) && aligned16(g)) ? MT_ROWS : ROWS;
+                     const int32_t* g = nullptr, const float* u = nullptr) {
+    return (D == GCOLS && aligned16(y) && aligned16(o) && aligned16(v) && aligned16(g) && aligned16(u)) ? MT_ROWS
+                                                                                                         : ROWS;
 }
 
 // The envelope of the entry points that take an offset and a weight: y by name, the vectors' alignment.

@@ -6,8 +6,8 @@
 // per-group intercept b_s[g_n] joins o_n, gathered from a table Bt [J + 1][ldb] by the row's group id (PredictGroups
 // below).  With GRP off nothing of it is compiled: the shipped instantiations keep their code.  The host side at the end
 // is the envelope of the entry points (predict_check_batch, predict_setup, predict_launch_chunks), shared by
-// csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip and
-// csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
+// csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip,
+// csrc/bsc_glm_weibull_interval.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
 #include "bsc_regress.h"
@@ -195,14 +195,42 @@ __device__ __forceinline__ void predict_link(float l, float yv, float lv, float 
     }
 }
 
+// PREDICT_WEIBULL with interval and left censoring (csrc/bsc_glm_weibull_interval.hip): `uv` is the row's entry of
+// `upper`, read as csrc/bsc_glm_pass.h's glm_link reads it (0: what y says; > 0: the interval (-y, uv]; < 0: left-censored
+// at -uv), the same forms and the same overflow rule: log p = -E_a + log(-expm1(-Delta)), the log of the row's
+// probability, so its lpd is the log of the draw average of that probability.  mu and v do not depend on the row's kind.
+__device__ __forceinline__ void predict_link_weibull_itv(float l, float yv, float uv, float lv, float ev, float iv,
+                                                         float& mu, float& v, float& lp, float lgp) {
+    const float el = expf(l);
+    mu = el * iv;
+    v = el * lgp * el;
+    const bool left = uv < 0.0f, itv = uv > 0.0f;
+    const float tq = fabsf(left ? uv : yv);
+    const float bq = itv ? uv : tq;
+    const float ly = logf(tq);
+    const float z = ev * (ly - l);
+    const float ez = expf(z);
+    const float kd = ev * bsc_logratio_f32(bq, tq, ly);    // exactly 0 unless the row is an interval
+    const float dlt = ez * (bsc_expm1_f32(kd) + (left ? 1.0f : 0.0f));   // expm1(0) = 0 on a left-censored row
+    const bool on = (left || itv) && dlt < ITV_BIG;         // false for a NaN as well
+    const float dq = on ? dlt : 1.0f;
+    const float ea = left ? 0.0f : ez;
+    const float lpc = fmaf(on ? 1.0f : 0.0f, logf(-bsc_expm1_f32(-dq)), -ea);
+    lp = (uv == 0.0f && yv > 0.0f) ? ((lv + z) - ly) - ez : lpc;
+}
+
 // FULL: D == 256 (two strips, 32 columns per lane group, everything unrolled).
 // OFFS: `offset` [B] (not null) is loaded like y and added to every draw's l of its row before the link.
 // GRP (with OFFS; a null offset reads 0): the tile's ids are loaded with its y and offset, at `last` of the tile before;
 // its intercepts are requested at the top of its first strip, ahead of that strip's LDS store, and land behind the
 // tile's MFMAs.  Both loads are unconditional within their (wave-uniform) branch, so the X prefetch stays in flight.
-template <int FAM, int NC, bool FULL, bool OFFS, bool GRP = false>
-__device__ __forceinline__ void predict_body(PredictArgs a, const float* offset, PredictGroups gr = PredictGroups{}) {
+// ITV (PREDICT_WEIBULL with OFFS): `upper` [B] (not null) is loaded like y and the offset; with the flag off nothing of
+// it is compiled.
+template <int FAM, int NC, bool FULL, bool OFFS, bool GRP = false, bool ITV = false>
+__device__ __forceinline__ void predict_body(PredictArgs a, const float* offset, PredictGroups gr = PredictGroups{},
+                                             const float* upper = nullptr) {
     static_assert(!GRP || OFFS, "the grouped body adds its intercept next to the offset");
+    static_assert(!ITV || (FAM == PREDICT_WEIBULL && OFFS && !GRP), "the upper end belongs to the Weibull family");
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
     constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA || FAM == PREDICT_WEIBULL;   // a fourth value
@@ -263,6 +291,8 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     float o_cur = 0.f;
     [[maybe_unused]] const int64_t o_rows = ((OWN4 || GRP) && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
     if constexpr (OFFS) o_cur = load_offset(offset, o_rows, row0_of(0), i16);
+    [[maybe_unused]] float u_cur = 0.f;
+    if constexpr (ITV) u_cur = load_offset(upper, a.B, row0_of(0), i16);
     [[maybe_unused]] int g_cur = 0;
     [[maybe_unused]] p_f32x4 bt[NC];
     if constexpr (GRP) {
@@ -299,6 +329,10 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
         }
         if constexpr (GRP) {
             if (last) g_cur = load_group(gr.g, a.B, row0_of(pn), i16);   // consumed by the gather above, next iteration
+        }
+        [[maybe_unused]] float u_next = 0.f;
+        if constexpr (ITV) {
+            if (last) u_next = load_offset(upper, a.B, row0_of(pn), i16);
         }
         wave_lds_sync();
 
@@ -354,7 +388,10 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
                     const float ev = r == 0 ? ev4.x : r == 1 ? ev4.y : r == 2 ? ev4.z : ev4.w;
                     const float iv = r == 0 ? iv4.x : r == 1 ? iv4.y : r == 2 ? iv4.z : iv4.w;
                     float m_i, v_i, lp_i;
-                    if constexpr (OWN4)
+                    if constexpr (ITV)
+                        predict_link_weibull_itv(l, yv, u_cur, lv, ev, iv, m_i, v_i, lp_i,
+                                                 r == 0 ? lg4.x : r == 1 ? lg4.y : r == 2 ? lg4.z : lg4.w);
+                    else if constexpr (OWN4)
                         predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i,
                                           r == 0 ? lg4.x : r == 1 ? lg4.y : r == 2 ? lg4.z : lg4.w);
                     else
@@ -405,6 +442,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
             }
             y_cur = y_next;
             if constexpr (OFFS) o_cur = o_next;
+            if constexpr (ITV) u_cur = u_next;
         }
         h = hn;
         p = pn;

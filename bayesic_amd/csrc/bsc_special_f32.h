@@ -46,4 +46,32 @@ __device__ __forceinline__ void bsc_dlgamma_dpsi_f32(float y, float phi, float l
     dps = fmaf(on, asym - ps0, sgn * q);
 }
 
+// Interval censoring (csrc/bsc_glm_pass.h's glm_link and csrc/bsc_predict_pass.h's predict_link_weibull_itv, ONE value for
+// the training pass and the predictive): from Delta = ITV_BIG on the upper end of a row is read as absent.
+constexpr float ITV_BIG = 103.0f;              // e^{-103} = 1.8e-45: at most one denormal step from 1 - e^{-Delta} = 1
+
+// expm1 from the full-accuracy exp and log: u - 1 with u = e^x where that does not cancel (|x| > 1/2), else Kahan's
+// (u - 1) x / log u, which undoes the rounding of u (u - 1 is exact there), and x itself where u == 1.  The selects sit
+// on the inputs of the quotient (a select on its result turns into a branch around it); e^x infinite gives infinity.
+__device__ __forceinline__ float bsc_expm1_f32(float x) {
+    const float u = expf(x);
+    const bool far = fabsf(x) > 0.5f, one = u == 1.0f;
+    const float lu = logf(one ? 2.0f : u);                       // never 0 where it divides
+    return fmaf(u - 1.0f, (far ? 1.0f : x) * __builtin_amdgcn_rcpf(far ? 1.0f : lu), one ? x : 0.0f);
+}
+
+// log(b / a) for b >= a > 0, la = log a at hand.  b < 2 a: b - a is exact and log1p((b - a) / a) keeps every digit of a
+// narrow ratio (the difference of two rounded logarithms loses |log a| eps of it) -- log1p(r) = log(w) r / (w - 1) with
+// w = 1 + r, the quotient undoing the rounding of w, and r itself where w == 1; else log b - la.  ONE logarithm, the
+// selects on its input and between values at hand; exactly 0 at b == a.
+__device__ __forceinline__ float bsc_logratio_f32(float b, float a, float la) {
+    const bool near = b < 2.0f * a;
+    const float r = (near ? b - a : 0.0f) * __builtin_amdgcn_rcpf(a);
+    const float w = 1.0f + r;
+    const bool one = w == 1.0f;
+    const float lg = logf(near ? w : b);
+    const float ratio = near ? r * __builtin_amdgcn_rcpf(one ? 1.0f : w - 1.0f) : 1.0f;
+    return fmaf(lg, ratio, one ? r : 0.0f) - (near ? 0.0f : la);
+}
+
 }  // namespace

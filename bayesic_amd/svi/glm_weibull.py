@@ -39,7 +39,23 @@ mu + L eps, finish bsc_glm_scalar_fullrank_update (svi/glm_nb.py says more).  Wi
 posteriori with the intercept and with every coefficient that moves the scale; a diagonal q reports it too narrow, and
 that width is what predict, heldout_lpd and survival carry on.
 
-Out of scope, by design of this version: left and interval censoring (one bit per row says right-censored or not);
+Interval and left censoring (``upper=``, keyword-only, on the constructor, set_batch, predict and heldout_lpd): a
+float [B] vector of upper ends next to ``time``.  ``inf`` says the row has no upper end and is whatever ``event`` says;
+a finite value greater than ``time`` says the event lies in (time, upper] -- found failed at an inspection, known to
+the day -- and a finite value on a row with ``time == 0`` says it had already happened when the row was first looked at
+(left-censored at ``upper``; only such a row may have ``time == 0``).  With ``event=None`` a row with a finite upper end
+is censored and every other row is an event.  Such a row enters through its probability, log(S(a) - S(b)) =
+-E_a + log(-expm1(-Delta)) with Delta = E_a expm1(k d) (include/bayesic_hip.h, bsc_glm_weibull_data_pass_interval, has
+the forms, the derivatives and the overflow rule: an upper end so far out that the row's upper survival is 0 in float32,
+``upper=1e30`` say, is read as absent).  Taking the midpoint or the upper end as the event time biases the shape,
+calling the row right-censored at ``time`` throws the upper end away.  On the device it is ONE more float32 vector
+(``pack_censored``): 0 = the row is what y says, > 0 = the interval's upper end (y = -time), < 0 = left-censored at its
+magnitude (y holds the same value).  The pass with it is the new entry point, and only when an ``upper`` is set: with
+``upper=None`` every check, message, call and bit is what it was.  The finishes see [ell | G | T] alone, so
+``covariance="full"`` needs nothing new; ``survival`` is unchanged.  With raw device pointers ``upper`` is a raw pointer to
+the device encoding.
+
+Out of scope, by design of this version: left truncation (delayed entry);
 groups together with the shape; recognition by ReparamVI (it does not recognise a Weibull log-joint); MiniBatchLoader
 (it does not carry offset and weights).  There is no one-call (pass +
 finish) form, so every update is pass -> all-reduce -> finish.  The multi-rank branch is wired like the other drivers'
@@ -47,12 +63,21 @@ and has been exercised at world size 1 only.
 """
 import numpy as np
 
-from ._obs import ObsBatch, batch_obs
+from ._obs import ObsBatch, batch_obs, obs_vector
 from ._reparam_base import (ReparamDriver, check_covariance, check_lam0, check_n_samples, check_priors,
                             scalar_latent_covariance, scalar_latent_params)
 
 TIME_MSG = "time must be finite and > 0 (a duration; censoring is given by event=, not by a sign)"
 EVENT_MSG = "event must be a bool or 0/1 array of length %d, one entry per row (None: every row is an event)"
+UPPER_SHAPE_MSG = "upper must be a float array of length %d, one entry per row (inf: no upper end)"
+UPPER_NAN_MSG = "upper must not be NaN (inf says that a row has no upper end)"
+UPPER_NEG_MSG = "upper must not be negative: it is the upper end of a censoring interval (the device encoding's sign " \
+                "is pack_censored's to set)"
+UPPER_EVENT_MSG = "an event row (event = 1) cannot have a finite upper: an event seen at time has no interval; pass " \
+                  "event = 0 or upper = inf there"
+UPPER_INTERVAL_MSG = "an interval-censored row needs upper > time (as float32): the event lies in (time, upper]"
+UPPER_LEFT_MSG = "a left-censored row (time == 0) needs a finite upper > 0"
+TIME_UPPER_MSG = TIME_MSG + "; only a left-censored row (a finite upper) may have time == 0"
 
 
 def check_arguments(prior_precision, a0, b0, n_samples):
@@ -97,23 +122,103 @@ def pack_response(time, event=None):
     return np.where(ev, t, -t).astype(np.float32)
 
 
+def _event_mask(event, B, xp, like):
+    """``event`` as a bool mask of length B in ``xp`` (numpy or torch; on ``like``'s device), with pack_response's checks."""
+    import torch
+    if xp is np:
+        if isinstance(event, torch.Tensor):
+            event = event.cpu().numpy()
+        ev = np.asarray(event)
+        if ev.ndim != 1 or ev.shape[0] != B:
+            raise ValueError(EVENT_MSG % B)
+        if ev.dtype != np.bool_:
+            if ev.dtype.kind not in "iuf" or not ((ev == 0) | (ev == 1)).all():
+                raise ValueError(EVENT_MSG % B)
+            ev = ev != 0
+        return ev
+    ev = event if isinstance(event, torch.Tensor) else torch.as_tensor(np.asarray(event))
+    if ev.dim() != 1 or ev.shape[0] != B:
+        raise ValueError(EVENT_MSG % B)
+    if ev.dtype != torch.bool:
+        if not bool(((ev == 0) | (ev == 1)).all()):
+            raise ValueError(EVENT_MSG % B)
+        ev = ev != 0
+    return ev.to(like.device)
+
+
+def pack_censored(time, event=None, upper=None):
+    """The pair (y, upper) in the device encoding of bsc_glm_weibull_data_pass_interval, after the checks of the module
+    docstring (each refusal names the row kind): y = where(event, time, -time) and upper = 0 on a row without an upper
+    end; y = -time and upper = the upper end on an interval row; y = upper = -(the upper end) on a left-censored row.
+    Host arrays give host arrays, a tensor ``time`` gives tensors on its device (one synchronisation).  ``upper=None``:
+    (pack_response(time, event), None)."""
+    if upper is None:
+        return pack_response(time, event), None
+    import torch
+    if isinstance(time, torch.Tensor):
+        xp, t = torch, time
+        u = upper if isinstance(upper, torch.Tensor) else torch.as_tensor(np.asarray(upper))
+        if t.dim() != 1:
+            raise ValueError(TIME_UPPER_MSG)
+        if u.dim() != 1 or u.shape[0] != t.shape[0] or not u.dtype.is_floating_point:
+            raise ValueError(UPPER_SHAPE_MSG % t.shape[0])
+        if not t.dtype.is_floating_point:
+            raise ValueError(TIME_UPPER_MSG)
+        t = t.to(torch.float32)                   # the comparisons below are made on what the device reads
+        u = u.to(device=t.device, dtype=torch.float32)
+    else:
+        xp = np
+        if isinstance(upper, torch.Tensor):
+            upper = upper.cpu().numpy()
+        with np.errstate(over="ignore"):
+            t = np.asarray(time, np.float32)
+            if t.ndim != 1:
+                raise ValueError(TIME_UPPER_MSG)
+            u = np.asarray(upper)
+            if u.ndim != 1 or u.shape[0] != t.shape[0] or u.dtype.kind != "f":
+                raise ValueError(UPPER_SHAPE_MSG % t.shape[0])
+            u = u.astype(np.float32)
+    B = int(t.shape[0])
+    if bool(xp.isnan(u).any()):
+        raise ValueError(UPPER_NAN_MSG)
+    if bool((u < 0).any()):
+        raise ValueError(UPPER_NEG_MSG)
+    fin = xp.isfinite(u)
+    left = fin & (t == 0)
+    if not bool((xp.isfinite(t) & ((t > 0) | left)).all()):
+        raise ValueError(TIME_UPPER_MSG)
+    ev = ~fin if event is None else _event_mask(event, B, xp, t)
+    if bool((ev & fin).any()):
+        raise ValueError(UPPER_EVENT_MSG)
+    if bool((left & ~(u > 0)).any()):
+        raise ValueError(UPPER_LEFT_MSG)
+    itv = fin & ~left
+    if bool((itv & ~(u > t)).any()):
+        raise ValueError(UPPER_INTERVAL_MSG)
+    zero = xp.zeros_like(t)
+    y = xp.where(left, -u, xp.where(ev, t, -t))
+    ud = xp.where(itv, u, xp.where(left, -u, zero))
+    return y, ud
+
+
 class WeibullReparamSVI(ObsBatch, ReparamDriver):
     link = "weibull"         # svi/predict.py: family_of
 
     def __init__(self, X, time, event=None, n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0, a0=1.0,
-                 b0=0.1, ctx=None, group=None, lam0=None, *, offset=None, weights=None, covariance="diag"):
+                 b0=0.1, ctx=None, group=None, lam0=None, *, upper=None, offset=None, weights=None, covariance="diag"):
         """``time`` [B] finite and > 0; ``event`` [B] bool or 0/1, None = every row an event.  ``a0``, ``b0``: the
         Gamma(shape, rate) prior of the Weibull shape k (default: mean 10, wide).  ``lam0``: [m | rho] over
         [w (D) | tau] (default m = 0 -- tau starts at 0, k at 1, the exponential distribution -- and every rho = log 0.1).
         ``covariance``: "diag" (the mean-field guide, default) or "full" (module docstring; ``lam0`` then in the full
         layout, default the same start with no off-diagonal entries).  ``offset`` / ``weights``: float32 [B], as in
-        GLMReparamSVI.  time, event and the weights are checked here (one synchronisation), never in step()."""
+        GLMReparamSVI.  ``upper``: float [B] upper ends (module docstring; inf = none), None = the model without them.
+        time, event, upper and the weights are checked here (one synchronisation), never in step()."""
         check_arguments(prior_precision, a0, b0, n_samples)
         check_covariance(covariance)
         import torch
         host = not isinstance(time, torch.Tensor)
         if host:
-            y = pack_response(time, event)        # before a device is asked for
+            y, u = pack_censored(time, event, upper)      # before a device is asked for
         shape = getattr(X, "shape", ())
         if len(shape) == 2:                       # an array or a tensor: lam0 too is checked before a device is asked for
             check_lam0(lam0, int(shape[1]) + 1, "w (%d) | tau" % int(shape[1]), covariance)
@@ -122,8 +227,9 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         self.prior_precision, self.a0, self.b0 = float(prior_precision), float(a0), float(b0)
         self.ctx = ctx or default_context()
         if not host:
-            y = pack_response(time, event)
+            y, u = pack_censored(time, event, upper)
         self._float_batch(X, y)
+        self._set_upper(None if u is None else obs_vector(self.ctx, "upper", u, self.B))
         self._set_obs(*batch_obs(self.ctx, self.B, offset, weights))
         self.has_offset = self._oarg is not None      # predict() refuses to run without one
         D, S = self.D, int(n_samples)
@@ -135,20 +241,30 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         self.T = self.stats[S + S * D:]
         self._logshape = torch.zeros((2, S), dtype=torch.float32, device=self.ctx.device)
 
-    def set_batch(self, X, time, event=None, rows=None, ldx=None, offset=None, weights=None):
+    def _set_upper(self, upper):
+        """The upper ends of the current batch in the device encoding: a tensor, a raw device pointer or None."""
+        import torch
+        self.upper = upper if isinstance(upper, torch.Tensor) else None
+        self._uarg = upper if upper is None or isinstance(upper, torch.Tensor) else int(upper)
+
+    def set_batch(self, X, time, event=None, rows=None, ldx=None, offset=None, weights=None, *, upper=None):
         """ReparamDriver.set_batch with the batch's censoring flags, offset and weights: tensors (time checked finite and
         > 0, event bool or 0/1, the weights finite and >= 0; y = where(event, time, -time) is what the driver keeps)
         with tensor X and time; raw device pointers (unchecked) with raw ones, ``time`` then being the signed vector and
-        ``event`` not allowed.  None drops offset or weights for this batch."""
+        ``event`` not allowed.  ``upper``: the batch's upper ends (inf = none) with tensors; with raw pointers a raw pointer
+        to the device encoding (pack_censored).  None drops offset, weights or upper for this batch."""
         import torch
         if isinstance(X, torch.Tensor):
-            time = pack_response(time, event)
+            time, upper = pack_censored(time, event, upper)
+            if upper is not None:
+                upper = obs_vector(self.ctx, "upper", upper, X.shape[0])
             offset, weights = batch_obs(self.ctx, X.shape[0], offset, weights)
         elif event is not None:
             raise ValueError("with raw device pointers pass the signed vector where(event, time, -time) as time; "
                              "event= is for tensors")
         super().set_batch(X, time, rows=rows, ldx=ldx)
         self._set_obs(offset, weights)
+        self._set_upper(upper)
 
     @property
     def logshape(self):
@@ -164,6 +280,10 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         self._drawn = True
 
     def data_pass(self):
+        if getattr(self, "_uarg", None) is not None:      # only a batch with upper ends takes the interval pass
+            self.ctx.call("bsc_glm_weibull_data_pass_interval", self._Xarg, self._ldx, self._yarg, self._uarg,
+                          self._oarg, self._varg, self.B, self.D, self.W, self.logshape, self.S, self.ell, self.G, self.T)
+            return
         self.ctx.call("bsc_glm_weibull_data_pass", self._Xarg, self._ldx, self._yarg, self._oarg, self._varg, self.B,
                       self.D, self.W, self.logshape, self.S, self.ell, self.G, self.T)
 
@@ -172,27 +292,33 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         self._finish_latent(name, stats, self._logshape, (self.D,))
 
     # -- posterior predictive (svi/predict.py: one bsc_weibull_predict_pass over X for all draws) -------------------
-    def _signed(self, time, event):
-        """The signed response of held-out rows (on the context's device), or None without ``time``."""
+    def _signed(self, time, event, upper=None):
+        """The signed response of held-out rows and their upper ends in the device encoding (None without ``upper``), or
+        (None, None) without ``time``."""
         if time is None:
             if event is not None:
                 raise ValueError("event= needs time=")
-            return None
-        return pack_response(time, event)
+            if upper is not None:
+                raise ValueError("upper= needs time=")
+            return None, None
+        return pack_censored(time, event, upper)
 
-    def predict(self, X, time=None, event=None, n_samples=64, seed=None, draws=None, offset=None, weights=None):
+    def predict(self, X, time=None, event=None, n_samples=64, seed=None, draws=None, offset=None, weights=None, *,
+                upper=None):
         """``mean`` = E t and ``var`` = Var t per row under the posterior predictive and, with ``time``, ``lpd`` and
         ``lpd_sum``: the log predictive density at an event, the log predictive SURVIVAL probability at a censored
-        time."""
+        time and, with ``upper``, the log predictive PROBABILITY of an interval or left-censored row."""
         from .predict import predict
-        return predict(self, X, self._signed(time, event), n_samples=n_samples, seed=seed, draws=draws, offset=offset,
-                       weights=weights)
+        y, u = self._signed(time, event, upper)
+        return predict(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, weights=weights, upper=u)
 
-    def heldout_lpd(self, X, time, event=None, n_samples=64, seed=None, draws=None, offset=None, weights=None):
+    def heldout_lpd(self, X, time, event=None, n_samples=64, seed=None, draws=None, offset=None, weights=None, *,
+                    upper=None):
         """Mean log predictive density per held-out row (a host float); with weights sum v lpd / sum v."""
         from .predict import heldout_lpd
-        return heldout_lpd(self, X, self._signed(time, event), n_samples=n_samples, seed=seed, draws=draws,
-                           offset=offset, weights=weights)
+        y, u = self._signed(time, event, upper)
+        return heldout_lpd(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, weights=weights,
+                           upper=u)
 
     def survival(self, X, t, n_samples=64, seed=None, draws=None, offset=None):
         """S(t_n | x_n) = P(T_n > t_n) under the posterior predictive, float32 [B] on the device: one predictive pass with

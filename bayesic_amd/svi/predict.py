@@ -24,7 +24,8 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
     GammaReparamSVI                   eps [S, D + 1]:  the same transform, tau = log alpha (bsc_gamma_predict_pass)
     WeibullReparamSVI                 eps [S, D + 1]:  the same transform, tau = log k (bsc_weibull_predict_pass; y is
                                       the signed response of svi/glm_weibull.py, negative = right-censored, and the
-                                      lpd of such a row is its log predictive survival probability)
+                                      lpd of such a row is its log predictive survival probability; with ``upper``,
+                                      bsc_weibull_predict_pass_interval and the log probability of the interval)
     HierGLMReparamSVI                 eps [S, D + J + 2]:  z = m + e^rho eps[:, :D + J + 1] over z = [w | b | zeta], and
                                       b_new = e^{-zeta / 2} eps[:, D + J + 1], the intercept of a group that was not
                                       seen in training; returned as (W [S, D], Bt [J + 1, ldb]) with Bt[j, s] = b_s[j],
@@ -185,7 +186,7 @@ def _groups(model, groups, B):
 
 
 def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None,
-            groups=None):
+            groups=None, upper=None):
     """Posterior predictive of ``model`` for the rows of X: a dict of device tensors ``mean`` and ``var`` (float32
     [B]) and, with y, ``lpd`` (float32 [B]) and ``lpd_sum`` (float64 [1]).  ``draws`` = (W, logvar) reuses draws of
     ``posterior_draws``; otherwise n_samples (at most 64) are drawn with ``seed`` (default: the model's).
@@ -194,8 +195,13 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     ``groups`` (HierGLMReparamSVI, required there): int32 [B] -- a device tensor, a host array (uploaded) or a raw
     device pointer -- with -1 for a group that was not seen in training.  Such a row's intercept is integrated over
     N(0, e^{-zeta}) with ONE draw per posterior draw that all -1 rows of the call share: per-row ``mean``, ``var`` and
-    ``lpd`` are correct Monte-Carlo estimates, joint statements about two rows of the same new group are not."""
+    ``lpd`` are correct Monte-Carlo estimates, joint statements about two rows of the same new group are not.
+    ``upper`` (WeibullReparamSVI only): the rows' upper ends in the DEVICE encoding of svi/glm_weibull.pack_censored,
+    float32 [B] next to the signed y -- the driver's own predict() takes the plain ones and packs them; ``lpd`` of an
+    interval or left-censored row is the log of its predictive probability (bsc_weibull_predict_pass_interval)."""
     family = family_of(model)
+    if upper is not None and family != "weibull":
+        raise ValueError("predict: upper= (interval and left censoring) belongs to the Weibull model, not %s" % family)
     if family == "softmax":      # its own pass and outputs (prob [B, K] instead of mean and var)
         if groups is not None:
             raise ValueError("predict: groups= belongs to the random-intercept model (HierGLMReparamSVI)")
@@ -209,6 +215,11 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     X, y = _data(model, X, y)
     ctx = model.ctx
     B = int(X.shape[0])
+    if upper is not None:
+        if y is None:
+            raise ValueError("predict: upper= needs y")
+        from ._obs import obs_vector
+        upper = obs_vector(ctx, "upper", upper, B)
     ldx = int(X.stride(0)) if B > 1 else max(int(X.stride(0)), model.D)
     dev = ctx.device
     out = {"mean": torch.empty(B, dtype=torch.float32, device=dev),
@@ -224,6 +235,9 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
                              "posterior_draws returns them")
         ctx.call("bsc_predict_pass_groups", FAMILIES[family], X, ldx, y, offset, groups, B, model.D, model.J, W, Bt,
                  int(Bt.stride(0)), S, out["mean"], out["var"], out.get("lpd"), out.get("lpd_sum"))
+    elif upper is not None:        # the Weibull model with interval and left censoring; the offset may be None
+        ctx.call("bsc_weibull_predict_pass_interval", X, ldx, y, upper, offset, B, model.D, W, logvar, S, out["mean"],
+                 out["var"], out.get("lpd"), out.get("lpd_sum"))
     elif family in SCALAR_PASSES:  # its own entry point; the offset may be None
         ctx.call(SCALAR_PASSES[family], X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"],
                  out.get("lpd"), out.get("lpd_sum"))
@@ -241,11 +255,11 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
 
 
 def heldout_lpd(model, X, y, n_samples=64, seed=None, draws=None, offset=None, exposure=None, weights=None,
-                groups=None):
+                groups=None, upper=None):
     """Mean log predictive density per row of the held-out (X, y): lpd_sum / B, a host float (synchronises).  With
-    weights: sum_n v_n lpd_n / sum_n v_n.  ``groups``: as in ``predict``."""
+    weights: sum_n v_n lpd_n / sum_n v_n.  ``groups`` and ``upper``: as in ``predict``."""
     out = predict(model, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, exposure=exposure,
-                  weights=weights, groups=groups)
+                  weights=weights, groups=groups, upper=upper)
     if "weight_sum" in out:
         return float(out["lpd_sum"].item()) / float(out["weight_sum"].item())
     return float(out["lpd_sum"].item()) / max(int(out["lpd"].shape[0]), 1)

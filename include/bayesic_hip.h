@@ -629,6 +629,44 @@ int bsc_glm_weibull_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const f
                               const float* weight, int64_t B, int32_t D, const float* W, const float* logshape,
                               int32_t S, double* ell, double* G, double* T);
 
+/* bsc_glm_weibull_data_pass with INTERVAL and LEFT censoring (csrc/bsc_glm_weibull_interval.hip): one more per-row
+ * vector, upper [B] float32 (contiguous, 4-byte aligned), next to the signed y.
+ * ENCODING:  upper[n] == 0              the row is exactly what y[n] says above (an event, or right-censored)
+ *            upper[n] >  0, y[n] < 0    interval-censored: the event lies in (a, b] = (-y[n], upper[n]];  b > a is required
+ *            upper[n] <  0              left-censored: the event is at or before b = -upper[n]; the magnitude of y[n] is
+ *                                       NOT read on such a row (bayesic_amd/svi/glm_weibull.py stores y[n] = upper[n])
+ * so a vector of zeros is bsc_glm_weibull_data_pass's model, and the rows past B read upper = 0 through the descriptor.
+ * With la = log a, d = log b - la, z_a = k (la - l), E_a = e^{z_a}, Delta = E_b - E_a formed as E_a expm1(k d) (a narrow
+ * interval does not cancel) and E_b = E_a + Delta, an interval row adds, times v[n],
+ *      ell:  log P = -E_a + log(-expm1(-Delta))                       (= log(S(a) - S(b)): nothing is left out)
+ *      r:    k ( E_a - Delta / expm1(Delta) )                         (= d / d l;  Delta / expm1(Delta) lies in (0, 1))
+ *      T:    -z_a E_a + ( z_a Delta + k d E_b ) / expm1(Delta)         (= d / d tau)
+ * and a left-censored row the same with E_a = 0, z_a E_a = 0 and Delta = E_b = e^{k (log b - l)}:
+ *      ell:  log(-expm1(-E_b))        r:  -k E_b / expm1(E_b)        T:  z_b E_b / expm1(E_b)
+ * Event rows and right-censored rows keep the expressions above.  1 / expm1(Delta) is formed as e^{-Delta} / (1 -
+ * e^{-Delta}), expm1 from the full-accuracy exp and log (Kahan's quotient below 1/2): seven transcendentals per (row,
+ * draw) where the pass above has two.
+ * OVERFLOW RULE: where Delta >= 103 -- e^{-Delta} is zero in float32 (103 is one denormal step short of it) -- or where
+ * e^{k d} or Delta is infinite in float32, the upper end is taken as ABSENT: the row adds the right-censored row's values
+ * at a, finite (a left-censored row adds nothing: its probability is 1), by a select on the link's inputs.  upper = 1e30
+ * is therefore a valid way to write "no bound".  An interval with k d > 88 is always read this way, whatever z_a.  Apart
+ * from that exp is NOT clamped: finite while z_a stays below about 88.  A kept row whose Delta underflows to 0 (z_a below
+ * -103) has probability 0 in float32: ell = -infinity, and G and T of that draw are NaN (1 / expm1(0) times 0); such a
+ * row is the caller's to keep out, like y = 0 above.
+ * A row with v[n] = 0, and every row past B, is evaluated at a = b = 1, l = 0 as an uncensored row of weight 0, whatever y
+ * and upper hold there (0, NaN and infinity included), and adds EXACTLY nothing.  y and upper ARE NOT CHECKED ON THE
+ * DEVICE (bayesic_amd/svi/glm_weibull.py checks them where a batch is set).
+ * ACCURACY ENVELOPE: tau in [-2, 4], as above.  A plain float32 evaluation stays within 1e-6 of the sums of the
+ * magnitudes of the terms with the conditioning of z_a, k d and Delta on their rounded inputs (spelled out in
+ * tests/_glm_weibull_interval_ref.py), the device within 2e-5.  d = log b - log a is formed as log1p((b - a) / a) where
+ * b < 2 a (b - a is exact there), so that a narrow interval keeps its digits.
+ * upper == NULL: the kernels of bsc_glm_weibull_data_pass, bit for bit.  The envelope and the refusals are that entry
+ * point's; upper must be 4-byte aligned, and counts among the vectors whose 16-byte alignment decides the MFMA route.
+ * Outputs, determinism and the slab as there; the finishes are shared (they see ell, G and T alone). */
+int bsc_glm_weibull_data_pass_interval(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* upper,
+                                       const float* offset, const float* weight, int64_t B, int32_t D, const float* W,
+                                       const float* logshape, int32_t S, double* ell, double* G, double* T);
+
 /* The finish: bsc_glm_nb_update with logshape in the place of logphi -- the prior on e^tau has the same form, the
  * likelihood enters through ell, G and T alone, and the entry points run one body (csrc/bsc_meanfield.h), so the same
  * arguments give the same bits as bsc_glm_nb_update and bsc_glm_gamma_update.  stats = [ell (S) | G (S*D) | T (S)];
@@ -779,6 +817,15 @@ int bsc_gamma_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const floa
 int bsc_weibull_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                              int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
                              float* lpd, double* lpd_sum);
+
+/* bsc_weibull_predict_pass with bsc_glm_weibull_data_pass_interval's upper [B] (csrc/bsc_glm_weibull_interval.hip): the
+ * same encoding, forms and overflow rule.  mean and var do not depend on the row's kind.  For an interval or left-censored
+ * row log p(y | l, k_s) = -E_a + log(-expm1(-Delta)) is the log of the row's PROBABILITY under draw s, so lpd[n] is the log
+ * of the draw average of that probability (the same log-mean-exp).  upper == NULL: bsc_weibull_predict_pass, bit for bit.
+ * upper must be 4-byte aligned; everything else as there. */
+int bsc_weibull_predict_pass_interval(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* upper,
+                                      const float* offset, int64_t B, int32_t D, const float* W, const float* logshape,
+                                      int32_t S, float* mean, float* var, float* lpd, double* lpd_sum);
 
 /* The predictive of the random-intercept model (csrc/bsc_predict_group.hip: bsc_predict_pass_offset's kernel with a
  * per-draw, per-group intercept; bsc_glm_data_pass_groups is its training pass):
