@@ -173,6 +173,10 @@ SIGNATURES = {
                                       c_int32, c_void_p, c_void_p]),
     "bsc_softmax_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                          c_int32, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_ordinal_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                          c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "bsc_ordinal_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                         c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "bsc_blr_noise": (c_int, [c_void_p, c_int32, c_int32, c_uint64, c_uint32, c_int32, c_void_p]),
     "bsc_blr_elbo_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int32, c_int32, c_double, c_double, c_double,

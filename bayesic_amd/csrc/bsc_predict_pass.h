@@ -7,7 +7,7 @@
 // below).  With GRP off nothing of it is compiled: the shipped instantiations keep their code.  The host side at the end
 // is the envelope of the entry points (predict_check_batch, predict_setup, predict_launch_chunks), shared by
 // csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip,
-// csrc/bsc_glm_weibull_interval.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
+// csrc/bsc_glm_weibull_interval.hip, csrc/bsc_glm_ordinal.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
 #include "bsc_regress.h"
@@ -26,6 +26,11 @@ constexpr int PREDICT_GAMMA = 4;
 // likelihood with a per-draw shape and right censoring in the sign of y; `logvar` carries tau_s = log k_s.  Always with
 // OFFS, the offset may be null.
 constexpr int PREDICT_WEIBULL = 5;
+// The seventh, internal as well: csrc/bsc_glm_ordinal.hip's predict_ordinal_kernel (bsc_ordinal_predict_pass), the
+// cumulative-logit likelihood with K - 1 cutpoints per draw.  Always with OFFS, the offset may be null; y holds the bits of
+// int32 labels; the outputs are prob [B, K] (PredictOrdinal below) and lpd, no mean and no var.
+constexpr int PREDICT_ORDINAL = 6;
+constexpr int P_ORD_K = 8;                     // classes at most
 
 constexpr int P_BLOCK = 512;
 constexpr int P_WAVES = P_BLOCK / BSC_WAVE;
@@ -219,7 +224,63 @@ __device__ __forceinline__ void predict_link_weibull_itv(float l, float yv, floa
     lp = (uv == 0.0f && yv > 0.0f) ? ((lv + z) - ly) - ez : lpc;
 }
 
+// PREDICT_ORDINAL: what the family needs besides PredictArgs.  The draws are a.W = Z [S, ldz] with the weights in
+// columns 0 .. D-1 and theta_0 = c_0, theta_j = log(c_j - c_{j-1}) behind them (4-byte aligned).
+struct PredictOrdinal {
+    float* prob = nullptr;   // [B, K], may be null
+    int64_t ldz = 0;
+    int K = 0;
+};
+
+// The two tables of the ordinal family, [draw][class] each, by thread (draw tid / 8, class tid % 8) of the 512: the
+// cutpoints c_k (k < K - 1; +infinity from there on, so that sigmoid(c_k - l) = 1) as the float32 roundings of the
+// float64 cumulative sum of the float32 theta, and log(-expm1(-g_k)) of the float32 gap g_k = c_k - c_{k-1} of an inner
+// class (0 for the two end classes), made in float64 and rounded: csrc/bsc_glm_ordinal.hip's constants.
+__device__ __forceinline__ void predict_ordinal_tables(float* ct, float* lt, const PredictArgs& a,
+                                                       const PredictOrdinal& od, int tid) {
+    const int s = tid >> 3, k = tid & 7, K = od.K;
+    double c = 0.0;
+    float lo = 0.f, hi = INFINITY;
+    for (int j = 0; j < K - 1; ++j) {
+        const float th = s < a.S ? a.W[(int64_t)s * od.ldz + a.D + j] : 0.0f;
+        c = j == 0 ? (double)th : c + exp((double)th);
+        if (j == k - 1) lo = (float)c;
+        if (j == k) hi = (float)c;
+    }
+    const bool mid = k >= 1 && k <= K - 2;
+    ct[tid] = hi;
+    lt[tid] = mid ? (float)log(-expm1(-(double)(hi - lo))) : 0.0f;
+}
+
+// One (row, draw) of the ordinal family: pk[k] += P(y = k | l, c) for a valid draw, as the differences of the cumulative
+// sigmoid(c_k - l) -- they telescope, so the K probabilities of a draw add up to 1 to rounding -- and the return value is
+// log p(yq | l, c) in csrc/bsc_glm_ordinal.hip's form, -U sp(-b) - L sp(a) + log(-expm1(-g)), which does not cancel.
+// cut: the draw's eight table entries; lg: the table's log(-expm1(-g)) at the row's class yq.
+__device__ __forceinline__ float predict_link_ordinal(float l, const float (&cut)[P_ORD_K], float lg, int yq, bool U,
+                                                      bool L, bool valid, float (&pk)[P_ORD_K]) {
+    float prev = 0.0f, a_ = 0.0f, b_ = 0.0f;
+#pragma unroll
+    for (int k = 0; k < P_ORD_K; ++k) {
+        const float x = cut[k] - l;
+        const float e = expf(-fabsf(x));
+        const float r = 1.0f / (1.0f + e);
+        const float cum = x >= 0.0f ? r : e * r;
+        pk[k] += valid ? cum - prev : 0.0f;
+        prev = cum;
+        b_ = yq == k ? x : b_;                 // flat selects: c_y - l and c_{y-1} - l
+        a_ = yq == k + 1 ? x : a_;
+    }
+    const float xb = U ? -b_ : 0.0f, xa = L ? a_ : 0.0f;       // an end class: its missing side is evaluated at 0, unused
+    const float eb = expf(-fabsf(xb)), ea = expf(-fabsf(xa));
+    const float tb = 1.0f + eb, ta = 1.0f + ea;
+    const float spb = fmaxf(xb, 0.0f) + (tb == 1.0f ? eb : logf(tb) * eb / (tb - 1.0f));
+    const float spa = fmaxf(xa, 0.0f) + (ta == 1.0f ? ea : logf(ta) * ea / (ta - 1.0f));
+    return lg - ((U ? spb : 0.0f) + (L ? spa : 0.0f));
+}
+
 // FULL: D == 256 (two strips, 32 columns per lane group, everything unrolled).
+// PREDICT_ORDINAL (with OFFS; a null offset reads 0): `od` says where prob goes and how the draws are laid out; everything
+// of it is behind `if constexpr`, and with another family nothing of it is compiled.
 // OFFS: `offset` [B] (not null) is loaded like y and added to every draw's l of its row before the link.
 // GRP (with OFFS; a null offset reads 0): the tile's ids are loaded with its y and offset, at `last` of the tile before;
 // its intercepts are requested at the top of its first strip, ahead of that strip's LDS store, and land behind the
@@ -228,15 +289,18 @@ __device__ __forceinline__ void predict_link_weibull_itv(float l, float yv, floa
 // it is compiled.
 template <int FAM, int NC, bool FULL, bool OFFS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset, PredictGroups gr = PredictGroups{},
-                                             const float* upper = nullptr) {
+                                             const float* upper = nullptr, PredictOrdinal od = PredictOrdinal{}) {
     static_assert(!GRP || OFFS, "the grouped body adds its intercept next to the offset");
     static_assert(!ITV || (FAM == PREDICT_WEIBULL && OFFS && !GRP), "the upper end belongs to the Weibull family");
+    constexpr bool ORD = FAM == PREDICT_ORDINAL;
+    static_assert(!ORD || (OFFS && !GRP && !ITV), "the ordinal family takes an offset and nothing else");
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
     constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA || FAM == PREDICT_WEIBULL;   // a fourth value
     constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || OWN4;        // a scalar rides with every draw
     constexpr int GP_SLOTS = OWN4 ? 4 : 3;                                 // ... and lnGamma(phi), or c_a
-    __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + GP_SLOTS * P_MAX_S];
+    constexpr int ORD_FLOATS = ORD ? 2 * P_ORD_K * P_MAX_S : 0;           // the cutpoints and log(-expm1(-g)), [draw][class]
+    __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + GP_SLOTS * P_MAX_S + ORD_FLOATS];
     __shared__ double red[P_WAVES];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -245,11 +309,14 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     float* wl = lds;                                    // draws [16 NC][WS], zero-padded
     float* xl = lds + W_FLOATS + wave * (T_ROWS * XS);  // this wave's strip [16][XS]
     float* gp = lds + W_FLOATS + X_FLOATS;              // logvar | exp(logvar) | exp(-logvar), [64] each
+    [[maybe_unused]] float* ct = gp + GP_SLOTS * P_MAX_S;   // ORD: c_k, [64][8]
+    [[maybe_unused]] float* lt = ct + P_ORD_K * P_MAX_S;    // ORD: log(-expm1(-g_k)), [64][8]
     const int S = a.S, D = a.D;
 
     for (int row = wave; row < NC * 16; row += P_WAVES)
         for (int col = lane; col < WS; col += BSC_WAVE)
-            wl[row * WS + col] = (row < S && col < D) ? a.W[(int64_t)row * D + col] : 0.f;
+            wl[row * WS + col] = (row < S && col < D) ? a.W[(int64_t)row * (ORD ? od.ldz : (int64_t)D) + col] : 0.f;
+    if constexpr (ORD) predict_ordinal_tables(ct, lt, a, od, tid);
     if (tid < P_MAX_S) {
         const float lv = (PER_DRAW && tid < S) ? a.logvar[tid] : 0.f;
         gp[tid] = lv;
@@ -289,7 +356,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     load_strip(t, a, row0_of(0), 0, lane);
     float y_cur = load_y(a, row0_of(0), i16);
     float o_cur = 0.f;
-    [[maybe_unused]] const int64_t o_rows = ((OWN4 || GRP) && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
+    [[maybe_unused]] const int64_t o_rows = ((OWN4 || GRP || ORD) && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
     if constexpr (OFFS) o_cur = load_offset(offset, o_rows, row0_of(0), i16);
     [[maybe_unused]] float u_cur = 0.f;
     if constexpr (ITV) u_cur = load_offset(upper, a.B, row0_of(0), i16);
@@ -363,7 +430,71 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
         }
         wave_lds_sync();   // the next iteration overwrites the strip
 
-        if (last) {
+        if constexpr (ORD) {
+            if (last) {
+                // ---- the row's draws, as in the branch below; the label's bits ride in y_cur ----
+                const int K = od.K;
+                const int yi = (int)__float_as_uint(y_cur);
+                const bool y_ok = (unsigned)yi < (unsigned)K;      // a label outside [0, K): the row scores 0
+                const int yq = y_ok ? yi : 0;                       // what indexes the table is inside it
+                const bool U = yq < K - 1, L = yq > 0;
+                // The draws run in a LOOP, one after the other, with this lane's 4 NC linear predictors -- and then their
+                // log p -- staged in the wave's strip buffer, which the MFMAs above are done with ([draw][lane]: no bank
+                // conflicts, and only the lane itself reads what it wrote).  Unrolled, the sixteen draws' eight cumulative
+                // terms apiece spill at NC = 4 and the code is ten exponentials per draw long.
+                float* ls = xl + lane;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ls[(4 * c + r) * BSC_WAVE] = acc[c][0][r] + acc[c][1][r] + o_cur;
+                    acc[c][0] = acc[c][1] = p_f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                float pk[P_ORD_K];
+#pragma unroll
+                for (int k = 0; k < P_ORD_K; ++k) pk[k] = 0.f;
+                float mx = -INFINITY;
+#pragma unroll 1
+                for (int i = 0; i < 4 * NC; ++i) {
+                    const int d = 16 * (i >> 2) + 4 * kq + (i & 3);
+                    const float4 c0 = *reinterpret_cast<const float4*>(ct + P_ORD_K * d);
+                    const float4 c1 = *reinterpret_cast<const float4*>(ct + P_ORD_K * d + 4);
+                    const float cut[P_ORD_K] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+                    const bool valid = d < S;
+                    const float lp_i = predict_link_ordinal(ls[i * BSC_WAVE], cut, lt[P_ORD_K * d + yq], yq, U, L, valid,
+                                                            pk);
+                    const float lpv = valid ? lp_i : -INFINITY;
+                    ls[i * BSC_WAVE] = lpv;
+                    mx = fmaxf(mx, lpv);
+                }
+#pragma unroll
+                for (int k = 0; k < P_ORD_K; ++k) pk[k] = fold4_sum(pk[k]) * inv_S;
+                float lpd = 0.f;
+                if (a.do_lp) {
+                    mx = fold4_max(mx);
+                    const float ms = mx == -INFINITY ? 0.f : mx;   // every draw at -inf: lpd = -inf, not NaN
+                    float se = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 4 * NC; ++i) se += __expf(ls[i * BSC_WAVE] - ms);
+                    se = fold4_sum(se);
+                    lpd = y_ok ? ms + logf(se) - log_S : 0.f;
+                }
+                wave_lds_sync();   // the next strip overwrites the buffer
+                const int64_t row = row0_of(p) + i16;
+                if (kq == 0 && row < B) {     // lanes 0 .. 15: one row each
+                    if (od.prob) {
+#pragma unroll
+                        for (int k = 0; k < P_ORD_K; ++k)
+                            if (k < K) od.prob[row * K + k] = pk[k];
+                    }
+                    if (a.do_lp) {
+                        if (a.lpd) a.lpd[row] = lpd;
+                        lsum += (double)lpd;
+                    }
+                }
+                y_cur = y_next;
+                o_cur = o_next;
+            }
+        } else if (last) {
             // ---- the row's draws: register i = 4 c + reg of lane (i16, kq) is draw 16 c + 4 kq + reg ----
             const float yv = y_cur;
             float mu[4 * NC], lp[4 * NC];
@@ -478,15 +609,18 @@ inline int predict_check_batch(const char* who, const float* X, const float* y, 
 }
 
 // The shapes the kernels take, the grid, the arguments and the workspace of lpd_sum's block partials.  *n_blocks = 0:
-// an empty batch, lpd_sum is zeroed and there is nothing to launch.
+// an empty batch, lpd_sum is zeroed and there is nothing to launch.  w_mask: the alignment asked of the draws (3: the
+// ordinal family, which reads them with 4-byte loads).
 inline int predict_setup(bsc_ctx* ctx, const char* who, const float* X, int64_t ldx, const float* y, int64_t B,
                          int32_t D, const float* W, const float* logvar, int32_t S, float* mean, float* var, float* lpd,
-                         double* lpd_sum, PredictArgs* args, int* n_blocks) {
+                         double* lpd_sum, PredictArgs* args, int* n_blocks, unsigned w_mask = 15) {
     PREDICT_UNSUPPORTED(D > 0 && D <= WCOLS && D % 4 == 0, "%s: D=%d must be a multiple of 4 in [4,%d]", who, D, WCOLS);
     PREDICT_UNSUPPORTED(S >= 1 && S <= P_MAX_S, "%s: S=%d must be in [1,%d]", who, S, P_MAX_S);
     PREDICT_UNSUPPORTED(ldx >= D && ldx % 4 == 0 && ldx < ((int64_t)1 << 26),
                         "%s: ldx=%lld must be >= D, %% 4 == 0 and < 2^26", who, (long long)ldx);
-    PREDICT_UNSUPPORTED(((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: X and W must be 16-byte aligned",
+    PREDICT_UNSUPPORTED(((uintptr_t)X & 15) == 0 && ((uintptr_t)W & w_mask) == 0,
+                        w_mask == 15 ? "%s: X and W must be 16-byte aligned"
+                                     : "%s: X must be 16-byte aligned and the draws 4-byte aligned",
                         who);
     *n_blocks = 0;
     if (B == 0) {

@@ -30,6 +30,9 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
                                       b_new = e^{-zeta / 2} eps[:, D + J + 1], the intercept of a group that was not
                                       seen in training; returned as (W [S, D], Bt [J + 1, ldb]) with Bt[j, s] = b_s[j],
                                       row J = b_new, ldb = 16 ceil(S / 16), padding zero (bsc_predict_pass_groups)
+    OrdinalReparamSVI                 eps [S, D + K - 1]:  the two GLM transforms at width P = D + K - 1 over
+                                      z = [w | theta], returned whole as Z [S, P] (predict() below hands over to its
+                                      predict(): bsc_ordinal_predict_pass, prob [B, K] instead of mean and var)
 xi = log s2 is the log-variance of the Gaussian likelihood (``logvar`` of the pass); tau = log phi is the log-dispersion
 of the negative binomial, or the log-shape of the Gamma model, and travels in the same slot of the returned pair.
 
@@ -65,7 +68,7 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 
 def family_of(model):
     """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI, "gamma" for GammaReparamSVI,
-    "weibull" for WeibullReparamSVI; HierGLMReparamSVI's link too --
+    "weibull" for WeibullReparamSVI, "ordinal" for OrdinalReparamSVI; HierGLMReparamSVI's link too --
     ``grouped`` tells that model apart), "softmax" for SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
     if getattr(model, "n_classes", None) is not None:
         return "softmax"
@@ -110,7 +113,8 @@ def _check_samples(n_samples):
 
 def posterior_draws(model, n_samples=64, seed=None):
     """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q; W is [S, K, D] for
-    SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d); for NegBinReparamSVI the second
+    SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d) and Z [S, D + K - 1] = [w | theta] for
+    OrdinalReparamSVI; for NegBinReparamSVI the second
     entry is logphi float32 [S], for GammaReparamSVI and WeibullReparamSVI logshape float32 [S]; for HierGLMReparamSVI it is the intercept table Bt float32 [J + 1, ldb] (module
     docstring)."""
     S = _check_samples(n_samples)
@@ -129,6 +133,8 @@ def posterior_draws(model, n_samples=64, seed=None):
         return W, ctx.to_device(intercept_table(z[:, D:D + J].astype(np.float32), b_new.astype(np.float32)))
     if family == "softmax":
         D = model.n_classes * model.D          # the guide's width; the transforms below are the GLM ones
+    elif family == "ordinal":
+        D = model.P                            # z = [w | theta], returned whole: the pass reads both from Z [S, P]
     seed = model.seed if seed is None else int(seed)
     scalar = family == "gaussian" or family in SCALAR_PASSES   # a scalar latent rides behind the weights
     P = D + 1 if scalar else D
@@ -206,6 +212,12 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
         if groups is not None:
             raise ValueError("predict: groups= belongs to the random-intercept model (HierGLMReparamSVI)")
         return model.predict(X, y, n_samples=n_samples, seed=seed, draws=draws)
+    if family == "ordinal":      # its own pass and outputs as well; offset and weights are its predict()'s
+        if groups is not None:
+            raise ValueError("predict: groups= belongs to the random-intercept model (HierGLMReparamSVI)")
+        if exposure is not None:
+            raise ValueError("predict: exposure belongs to the Poisson rate model; the ordinal model takes offset=")
+        return model.predict(X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset, weights=weights)
     groups = _groups(model, groups, int(X.shape[0]))
     offset, weights = _obs(model, family, int(X.shape[0]), offset, exposure, weights)
     if draws is None:

@@ -887,6 +887,57 @@ int bsc_softmax_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const int32
 int bsc_softmax_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const int32_t* y, int64_t B, int32_t D,
                              int32_t K, const float* W, int32_t S, float* prob, float* lpd, double* lpd_sum);
 
+/* ---- ordinal (cumulative-logit, proportional-odds) regression with learned cutpoints (csrc/bsc_glm_ordinal.hip;
+ *      ABSENT in the reference) ---------------------------------------------------------------------------------
+ *
+ * Labels y[n] in {0 .. K-1} (int32), 2 <= K <= 8, in their ORDER.  eta[n,s] = sum_d X[n,d] w[s,d] + o[n], cutpoints
+ * c_0 < .. < c_{K-2} per draw:
+ *      P(y <= k) = sigmoid(c_k - eta),     P(y = k) = sigmoid(c_k - eta) - sigmoid(c_{k-1} - eta)   (c_{-1} = -inf,
+ *      c_{K-1} = +inf)
+ * in the unconstrained coordinates theta_0 = c_0, theta_j = log(c_j - c_{j-1}) (j >= 1), so every draw is ordered.  The
+ * latent is z = [w (D) | theta (K - 1)], P = D + K - 1, under z ~ N(0, I / prior_precision); there is no intercept: the
+ * cutpoints are the intercepts.
+ * Z: the draws, float32 [S, ldz] with ldz >= P, weights in columns 0 .. D-1 and theta in columns D .. P-1, 4-BYTE
+ * aligned (bsc_glm_update's W_next [S, P] as it stands; the kernels read the draws once per launch with 4-byte loads).
+ * With a = c_{y-1} - eta, b = c_y - eta, U = [y < K-1], L = [y > 0], g = c_y - c_{y-1}, sp the stable softplus:
+ *      log p            = -U sp(-b) - L sp(a) + U L log(-expm1(-g))
+ *      r = d log p / d eta  = L sigmoid(a) - U sigmoid(-b)
+ *      d log p / d c_y      = U (sigmoid(-b) + L / expm1(g)),      d log p / d c_{y-1} = -L (sigmoid(a) + U / expm1(g))
+ *      ell[s]       = sum_n v[n] log p                              (float64 out, [S])
+ *      G[s,d]       = sum_n v[n] r[n,s] X[n,d]      (d < D)         (float64 out, [S, P])
+ *      G[s,D]       = sum_j H_j[s],   G[s,D+i] = e^{theta_i} sum_{j >= i} H_j[s]  (i >= 1),   H_j = d ell[s] / d c_j
+ * [ell | G] is the stats vector of bsc_glm_update / bsc_glm_fullrank_update called with D := P.  The cutpoints are the
+ * float32 roundings of the float64 cumulative sum of the float32 theta read, g the float32 difference of those;
+ * log(-expm1(-g)) and 1 / expm1(g) are made once per launch in float64 and rounded.  ACCURACY ENVELOPE: theta_j in
+ * [-3, 1.5] for j >= 1 (gaps 0.05 .. 4.5), |eta - c| <= 30.
+ * offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0, v = 1).  A row is dropped -- adds EXACTLY
+ * nothing -- when v[n] = 0 or y[n] is outside [0, K), by a select on the link's inputs; the label that indexes the
+ * (draw, class) table is inside it for every int32 value.
+ * Envelope (BSC_ERR_INVALID with a message naming the quantity, outputs untouched): 2 <= K <= 8, D % 4 == 0,
+ * 4 <= D <= 256, 1 <= S <= 64 (eight draws per launch), X 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26,
+ * ldz >= D + K - 1, ldz < 2^26, y, offset, weight and Z 4-byte aligned, non-NULL ell and G.  The 16-row MFMA kernel
+ * (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned, else the 8-row kernel.  B = 0 gives
+ * zeros.  Deterministic: fixed partition, float32 block partials of 8 * 256 + 8 + 7 * 8 floats (ell and the H_j behind
+ * G), fixed-order float64 finish, no float atomics. */
+int bsc_glm_ordinal_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const int32_t* y, const float* offset,
+                              const float* weight, int64_t B, int32_t D, int32_t K, const float* Z, int64_t ldz,
+                              int32_t S, double* ell, double* G);
+
+/* The predictive of the ordinal model (csrc/bsc_glm_ordinal.hip: bsc_predict_pass's kernel with a seventh family that
+ * only this entry point reaches) for S <= 64 draws Z [S, ldz] as above; offset may be NULL.  Per row (each output may be
+ * NULL)
+ *      prob[n,k] = 1/S sum_s P(y = k | eta[n,s], c_s)                                     (float32 [B, K])
+ *      lpd[n]    = logsumexp_s log p(y[n] | eta[n,s], c_s) - log S                        (float32 [B]; needs y)
+ *      lpd_sum   = sum_n lpd[n]                                                           (float64 [1]; needs y)
+ * prob comes from the differences of the cumulative sigmoids, which telescope (the K entries of a row add up to 1 to
+ * rounding); log p from the form above, which does not cancel.  A row whose label is outside [0, K) gets lpd[n] = 0 and
+ * adds nothing to lpd_sum; prob is written for every row.  Refusals: K, Z's alignment, ldz, null pointers, no output
+ * requested and lpd or lpd_sum without y are BSC_ERR_INVALID; D, S, ldx and X's alignment are bsc_predict_pass's
+ * (BSC_ERR_UNSUPPORTED).  B = 0 writes lpd_sum = 0 and nothing else.  Deterministic as bsc_predict_pass. */
+int bsc_ordinal_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const int32_t* y, const float* offset,
+                             int64_t B, int32_t D, int32_t K, const float* Z, int64_t ldz, int32_t S, float* prob,
+                             float* lpd, double* lpd_sum);
+
 /* ---- parameter updates --------------------------------------------------- */
 
 /* Adam ascent on a flat float64 vector; t is the 1-based step count. */
