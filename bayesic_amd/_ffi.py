@@ -18,6 +18,23 @@ class BayesicHipError(RuntimeError):
     """A libbayesic_hip.so call returned a non-zero status."""
 
 
+# The argument types of the three entry points of a family with a learned log-scalar behind the weights
+# (csrc/bsc_scalar_family.h): the negative-binomial, Gamma and Weibull routes have the same signatures, the interval pair
+# one more pointer behind y.  Tuples: every entry of SIGNATURES gets a list of its own (_scalar).
+_SCALAR_DATA_PASS = (c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                     c_int32, c_void_p, c_void_p, c_void_p)
+_SCALAR_UPDATE = (c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                  c_int32, c_double, c_double, c_double, c_double, c_int64, c_double, c_double, c_double, c_double,
+                  c_uint64, c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p)
+_SCALAR_PREDICT_PASS = (c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32,
+                        c_void_p, c_void_p, c_void_p, c_void_p)
+
+
+def _scalar(argtypes, upper=False):
+    """The entry of SIGNATURES; ``upper``: (ctx, X, ldx, y, ...) -> (ctx, X, ldx, y, upper, ...)."""
+    return c_int, list(argtypes[:4] + (c_void_p,) + argtypes[4:] if upper else argtypes)
+
+
 # name -> (restype, argtypes); every symbol declared in include/bayesic_hip.h.
 SIGNATURES = {
     "bsc_ctx_create": (c_int, [c_int, c_void_p, POINTER(c_void_p)]),
@@ -124,27 +141,13 @@ SIGNATURES = {
                                     c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
                                     c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
-    "bsc_glm_nb_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
-                                     c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
-    "bsc_glm_nb_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64, c_double,
-                                  c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p,
-                                  c_void_p, c_void_p, c_void_p]),
-    "bsc_glm_gamma_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
-                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
-    "bsc_glm_gamma_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
-                                     c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
-                                     c_void_p, c_void_p, c_void_p, c_void_p]),
-    "bsc_glm_weibull_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
-                                          c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
-    "bsc_glm_weibull_data_pass_interval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                   c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
-                                                   c_void_p]),
-    "bsc_glm_weibull_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int64,
-                                       c_double, c_double, c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32,
-                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_nb_data_pass": _scalar(_SCALAR_DATA_PASS),
+    "bsc_glm_nb_update": _scalar(_SCALAR_UPDATE),
+    "bsc_glm_gamma_data_pass": _scalar(_SCALAR_DATA_PASS),
+    "bsc_glm_gamma_update": _scalar(_SCALAR_UPDATE),
+    "bsc_glm_weibull_data_pass": _scalar(_SCALAR_DATA_PASS),
+    "bsc_glm_weibull_data_pass_interval": _scalar(_SCALAR_DATA_PASS, upper=True),
+    "bsc_glm_weibull_update": _scalar(_SCALAR_UPDATE),
     "bsc_glm_fullrank_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_int32, c_double, c_double, c_int64, c_double, c_double, c_double,
                                         c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -156,15 +159,10 @@ SIGNATURES = {
                                  c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_predict_pass_offset": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32,
                                         c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "bsc_nb_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
-                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "bsc_gamma_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
-                                       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "bsc_weibull_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
-                                         c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "bsc_weibull_predict_pass_interval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                                  c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
-                                                  c_void_p]),
+    "bsc_nb_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
+    "bsc_gamma_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
+    "bsc_weibull_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
+    "bsc_weibull_predict_pass_interval": _scalar(_SCALAR_PREDICT_PASS, upper=True),
     "bsc_predict_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                         c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),

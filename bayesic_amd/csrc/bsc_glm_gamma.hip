@@ -1,7 +1,8 @@
 // Gamma regression (log link) with a learned shape on the fused pathwise pass: csrc/bsc_glm_pass.h's OBS bodies with the
 // per-draw scalar flag on and the fourth link, their slab reduction, the finish for the latent z = [w (D) | tau]
 // (csrc/bsc_meanfield.h's bodies with NbModel -- the prior on the scalar has the negative binomial's form, so the finish
-// is the same), and the predictive (csrc/bsc_predict_pass.h's body and envelope with its fifth family).
+// is the same), and the predictive (csrc/bsc_predict_pass.h's body and envelope with its fifth family).  The kernels and
+// the host side of the three entry points are csrc/bsc_scalar_family.h's, with GLM_GAMMA and PREDICT_GAMMA.
 //
 //     y_n ~ Gamma(shape alpha, rate alpha / mu_n),  y_n > 0,  E y_n = mu_n = exp(l_n),  Var y_n = mu_n^2 / alpha
 //     l[n,s] = x_n . w_s + o_n,   w ~ N(0, I / prior_precision),   alpha = e^tau ~ Gamma(a0, b0)
@@ -17,67 +18,7 @@
 // anywhere: the same bits run to run.  NOT clamped: finite while y e^{-l} is below the float32 maximum.
 //
 // A translation unit of its own so that every other one keeps its kernels, their names, their count and their code.
-#include "bsc_glm_pass.h"
-#include "bsc_meanfield.h"
-#include "bsc_predict_pass.h"
-
-namespace {
-
-constexpr int MAX_S = 64;
-static_assert(MAX_S == MF_MAX_S, "the pass and the finish take the same number of draws");
-
-// ---- the pass ---------------------------------------------------------------------------------------------------------
-
-template <bool FULL>
-__global__ __launch_bounds__(PASS_BLOCK, 2) void glm_gamma_pass_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
-    const float* __restrict__ v, int64_t B, int D, const float* __restrict__ W, const float* __restrict__ logshape,
-    int S, float* __restrict__ slab, int n_iter) {
-    glm_pass_body<GLM_GAMMA, FULL, true, false, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, nullptr, logshape);
-}
-
-__global__ __launch_bounds__(PASS_BLOCK, 2) void glm_gamma_pass_mfma_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
-    const float* __restrict__ v, int64_t B, const float* __restrict__ W, const float* __restrict__ logshape, int S,
-    float* __restrict__ slab, int n_iter) {
-    glm_pass_mfma_body<GLM_GAMMA, true, false, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, nullptr, logshape);
-}
-
-__global__ __launch_bounds__(RED_BLOCK) void glm_gamma_slab_reduce_kernel(const float* __restrict__ slab, int n_blocks,
-                                                                          int D, int S, int s_base,
-                                                                          double* __restrict__ ell,
-                                                                          double* __restrict__ G,
-                                                                          double* __restrict__ T) {
-    regress_slab_reduce<NB_SLAB_STRIDE>(slab, n_blocks, D, S, s_base, ell, G, T);
-}
-
-// ---- the finish: NbModel of csrc/bsc_meanfield.h with the log-shape in the place of the log-dispersion ------------------
-
-__global__ __launch_bounds__(MF_BLOCK) void glm_gamma_scalars_kernel(NbModel a) { meanfield_scalars_body(a); }
-
-__global__ __launch_bounds__(MF_BLOCK) void glm_gamma_coord_kernel(NbModel a) { meanfield_coord_body(a); }
-
-// ---- the predictive ---------------------------------------------------------------------------------------------------
-
-// FULL: D == 256.  offset may be null.
-template <int NC, bool FULL>
-__global__ __launch_bounds__(P_BLOCK, 2) void predict_gamma_kernel(PredictArgs a, const float* __restrict__ offset) {
-    predict_body<PREDICT_GAMMA, NC, FULL, true>(a, offset);
-}
-
-__global__ __launch_bounds__(BSC_WAVE) void predict_gamma_sum_kernel(const double* __restrict__ partial, int n,
-                                                                     double* __restrict__ out) {
-    block_partial_sum(partial, n, out);
-}
-
-template <int NC>
-void launch_predict_gamma_nc(bsc_ctx* ctx, const PredictArgs& a, const float* offset, int n_blocks) {
-    const dim3 grid(n_blocks), block(P_BLOCK);
-    if (a.D == WCOLS) hipLaunchKernelGGL((predict_gamma_kernel<NC, true>), grid, block, 0, ctx->stream, a, offset);
-    else hipLaunchKernelGGL((predict_gamma_kernel<NC, false>), grid, block, 0, ctx->stream, a, offset);
-}
-
-}  // namespace
+#include "bsc_scalar_family.h"
 
 extern "C" {
 
@@ -85,9 +26,8 @@ int bsc_glm_gamma_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const flo
                             const float* weight, int64_t B, int32_t D, const float* W, const float* logshape,
                             int32_t S, double* ell, double* G, double* T) {
     BSC_CHECK_CTX(ctx);
-    return dsp_data_pass(ctx, "bsc_glm_gamma_data_pass", "logshape", glm_gamma_pass_mfma_kernel,
-                         glm_gamma_pass_kernel<true>, glm_gamma_pass_kernel<false>, glm_gamma_slab_reduce_kernel, MAX_S,
-                         X, ldx, y, offset, weight, B, D, W, logshape, S, ell, G, T);
+    return scalar_family_data_pass<GLM_GAMMA>(ctx, "bsc_glm_gamma_data_pass", "logshape", X, ldx, y, nullptr, offset,
+                                              weight, B, D, W, logshape, S, ell, G, T);
 }
 
 int bsc_glm_gamma_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
@@ -96,21 +36,18 @@ int bsc_glm_gamma_update(bsc_ctx* ctx, const double* stats, const double* lam_in
                          double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
                          int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo, double* grad) {
     BSC_CHECK_CTX(ctx);
-    return nb_model_update(ctx, "bsc_glm_gamma_update", glm_gamma_scalars_kernel, glm_gamma_coord_kernel, stats, lam_in,
-                           lam_out, m1, m2, eps, W, logshape, D, S, scale, prior_precision, a0, b0, t, lr, beta1, beta2,
-                           adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, logshape_next, elbo, grad);
+    return scalar_family_update<GLM_GAMMA>(ctx, "bsc_glm_gamma_update", stats, lam_in, lam_out, m1, m2, eps, W,
+                                           logshape, D, S, scale, prior_precision, a0, b0, t, lr, beta1, beta2,
+                                           adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, logshape_next,
+                                           elbo, grad);
 }
 
 int bsc_gamma_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                            int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
                            float* lpd, double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
-    return scalar_predict_pass(
-        ctx, "bsc_gamma_predict_pass", "logshape",
-        [&](auto nc, const PredictArgs& a, int n_blocks) {
-            launch_predict_gamma_nc<decltype(nc)::value>(ctx, a, offset, n_blocks);
-        },
-        predict_gamma_sum_kernel, X, ldx, y, offset, B, D, W, logshape, S, mean, var, lpd, lpd_sum);
+    return scalar_family_predict_pass<PREDICT_GAMMA>(ctx, "bsc_gamma_predict_pass", "logshape", X, ldx, y, nullptr,
+                                                     offset, B, D, W, logshape, S, mean, var, lpd, lpd_sum);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Negative-binomial regression with a learned dispersion on the fused pathwise pass: csrc/bsc_glm_pass.h's OBS bodies
 // with the dispersion flag on, their slab reduction, the finish for the latent z = [w (D) | tau] (csrc/bsc_meanfield.h's
-// bodies with NbModel below), and the predictive (csrc/bsc_predict_pass.h's body and envelope with its fourth family).
+// bodies with NbModel), and the predictive (csrc/bsc_predict_pass.h's body and envelope with its fourth family).  The
+// kernels and the host side of the three entry points are csrc/bsc_scalar_family.h's, with GLM_NEGBIN and PREDICT_NEGBIN.
 //
 //     y_n ~ NegBin(mean exp(l_n), dispersion phi),  Var y_n = mu_n + mu_n^2 / phi,   l[n,s] = x_n . w_s + o_n
 //     w ~ N(0, I / prior_precision),   phi = e^tau ~ Gamma(a0, b0)
@@ -17,66 +18,7 @@
 //
 // A translation unit of its own so that the kernels of csrc/bsc_glm.hip, bsc_glm_obs.hip, bsc_glm_group.hip,
 // bsc_predict.hip and bsc_predict_offset.hip keep their names, their count and their code.
-#include "bsc_glm_pass.h"
-#include "bsc_meanfield.h"
-#include "bsc_predict_pass.h"
-
-namespace {
-
-constexpr int MAX_S = 64;
-
-// ---- the pass ---------------------------------------------------------------------------------------------------------
-
-template <bool FULL>
-__global__ __launch_bounds__(PASS_BLOCK, 2) void glm_nb_pass_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
-    const float* __restrict__ v, int64_t B, int D, const float* __restrict__ W, const float* __restrict__ logphi, int S,
-    float* __restrict__ slab, int n_iter) {
-    glm_pass_body<GLM_NEGBIN, FULL, true, false, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, nullptr, logphi);
-}
-
-__global__ __launch_bounds__(PASS_BLOCK, 2) void glm_nb_pass_mfma_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
-    const float* __restrict__ v, int64_t B, const float* __restrict__ W, const float* __restrict__ logphi, int S,
-    float* __restrict__ slab, int n_iter) {
-    glm_pass_mfma_body<GLM_NEGBIN, true, false, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, nullptr, logphi);
-}
-
-__global__ __launch_bounds__(RED_BLOCK) void glm_nb_slab_reduce_kernel(const float* __restrict__ slab, int n_blocks,
-                                                                       int D, int S, int s_base,
-                                                                       double* __restrict__ ell, double* __restrict__ G,
-                                                                       double* __restrict__ T) {
-    regress_slab_reduce<NB_SLAB_STRIDE>(slab, n_blocks, D, S, s_base, ell, G, T);
-}
-
-// ---- the finish -------------------------------------------------------------------------------------------------------
-
-// z = [w (D) | tau]: NbModel of csrc/bsc_meanfield.h, which csrc/bsc_glm_gamma.hip instantiates as well.
-__global__ __launch_bounds__(MF_BLOCK) void glm_nb_scalars_kernel(NbModel a) { meanfield_scalars_body(a); }
-
-__global__ __launch_bounds__(MF_BLOCK) void glm_nb_coord_kernel(NbModel a) { meanfield_coord_body(a); }
-
-// ---- the predictive ---------------------------------------------------------------------------------------------------
-
-// FULL: D == 256.  offset may be null.
-template <int NC, bool FULL>
-__global__ __launch_bounds__(P_BLOCK, 2) void predict_nb_kernel(PredictArgs a, const float* __restrict__ offset) {
-    predict_body<PREDICT_NEGBIN, NC, FULL, true>(a, offset);
-}
-
-__global__ __launch_bounds__(BSC_WAVE) void predict_nb_sum_kernel(const double* __restrict__ partial, int n,
-                                                                  double* __restrict__ out) {
-    block_partial_sum(partial, n, out);
-}
-
-template <int NC>
-void launch_predict_nb_nc(bsc_ctx* ctx, const PredictArgs& a, const float* offset, int n_blocks) {
-    const dim3 grid(n_blocks), block(P_BLOCK);
-    if (a.D == WCOLS) hipLaunchKernelGGL((predict_nb_kernel<NC, true>), grid, block, 0, ctx->stream, a, offset);
-    else hipLaunchKernelGGL((predict_nb_kernel<NC, false>), grid, block, 0, ctx->stream, a, offset);
-}
-
-}  // namespace
+#include "bsc_scalar_family.h"
 
 extern "C" {
 
@@ -84,9 +26,8 @@ int bsc_glm_nb_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float*
                          const float* weight, int64_t B, int32_t D, const float* W, const float* logphi, int32_t S,
                          double* ell, double* G, double* T) {
     BSC_CHECK_CTX(ctx);
-    return dsp_data_pass(ctx, "bsc_glm_nb_data_pass", "logphi", glm_nb_pass_mfma_kernel, glm_nb_pass_kernel<true>,
-                         glm_nb_pass_kernel<false>, glm_nb_slab_reduce_kernel, MAX_S, X, ldx, y, offset, weight, B, D, W,
-                         logphi, S, ell, G, T);
+    return scalar_family_data_pass<GLM_NEGBIN>(ctx, "bsc_glm_nb_data_pass", "logphi", X, ldx, y, nullptr, offset,
+                                               weight, B, D, W, logphi, S, ell, G, T);
 }
 
 int bsc_glm_nb_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1, double* m2,
@@ -95,22 +36,17 @@ int bsc_glm_nb_update(bsc_ctx* ctx, const double* stats, const double* lam_in, d
                       double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
                       float* W_next, float* logphi_next, double* elbo, double* grad) {
     BSC_CHECK_CTX(ctx);
-    static_assert(MAX_S == MF_MAX_S, "the pass and the finish take the same number of draws");
-    return nb_model_update(ctx, "bsc_glm_nb_update", glm_nb_scalars_kernel, glm_nb_coord_kernel, stats, lam_in, lam_out,
-                           m1, m2, eps, W, logphi, D, S, scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps,
-                           seed, next_step, eps_next, eps_next_ready, W_next, logphi_next, elbo, grad);
+    return scalar_family_update<GLM_NEGBIN>(ctx, "bsc_glm_nb_update", stats, lam_in, lam_out, m1, m2, eps, W, logphi, D,
+                                            S, scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps, seed,
+                                            next_step, eps_next, eps_next_ready, W_next, logphi_next, elbo, grad);
 }
 
 int bsc_nb_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                         int32_t D, const float* W, const float* logphi, int32_t S, float* mean, float* var, float* lpd,
                         double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
-    return scalar_predict_pass(
-        ctx, "bsc_nb_predict_pass", "logphi",
-        [&](auto nc, const PredictArgs& a, int n_blocks) {
-            launch_predict_nb_nc<decltype(nc)::value>(ctx, a, offset, n_blocks);
-        },
-        predict_nb_sum_kernel, X, ldx, y, offset, B, D, W, logphi, S, mean, var, lpd, lpd_sum);
+    return scalar_family_predict_pass<PREDICT_NEGBIN>(ctx, "bsc_nb_predict_pass", "logphi", X, ldx, y, nullptr, offset,
+                                                      B, D, W, logphi, S, mean, var, lpd, lpd_sum);
 }
 
 }  // extern "C"

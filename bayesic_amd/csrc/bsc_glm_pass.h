@@ -800,45 +800,7 @@ int for_draw_chunks(bsc_ctx* ctx, int S, Pass pass, Reduce reduce) {
     return for_draw_chunks(ctx, S, pass, reduce, [](int) { return (int)BSC_OK; });
 }
 
-// The data pass of a DSP route (csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip) through the
-// calling translation unit's own kernels: the 16-row MFMA kernel, the 8-row kernel with D == 256 and with any D, and the
-// reduction of the NB_SLAB_STRIDE slab.  `logphi` [S] is the per-draw scalar under the name `what`.
-template <class Mfma, class Rows8Full, class Rows8, class Reduce>
-int dsp_data_pass(bsc_ctx* ctx, const char* who, const char* what, Mfma mfma_kernel, Rows8Full rows8_full_kernel,
-                  Rows8 rows8_kernel, Reduce reduce_kernel, int max_s, const float* X, int64_t ldx, const float* y,
-                  const float* offset, const float* weight, int64_t B, int32_t D, const float* W, const float* logphi,
-                  int32_t S, double* ell, double* G, double* T) {
-    const int rc0 = check_glm_obs_args(who, BSC_GLM_LOGISTIC, X, ldx, y, offset, weight, B, D, W, S, max_s);
-    if (rc0 != BSC_OK) return rc0;
-    BSC_REQUIRE(logphi, "%s: %s is null", who, what);
-    BSC_REQUIRE((((uintptr_t)logphi) & 3) == 0, "%s: %s must be 4-byte aligned", who, what);
-    BSC_REQUIRE(ell && G && T, "%s: null output", who);
-
-    const int rows = pass_rows(D, y, offset, weight);
-    const PassGrid g = pass_grid(ctx, B, rows);
-    void* ws = nullptr;
-    const int rc = bsc_workspace(ctx, (size_t)g.n_blocks * NB_SLAB_STRIDE * sizeof(float), &ws);
-    if (rc != BSC_OK) return rc;
-    ctx->slab_rows = 0;  // the slab is consumed here
-    float* slab = (float*)ws;
-    const dim3 rgrid((NB_SLAB_STRIDE + BSC_WAVE - 1) / BSC_WAVE);
-    const auto go = [&](auto kernel, auto... tail) {
-        hipLaunchKernelGGL(kernel, dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y, offset, weight, B,
-                           tail...);
-    };
-    return for_draw_chunks(
-        ctx, S,
-        [&](int s0, int sg) {   // each launch with its chunk of the scalar
-            const float *Ws = W + (int64_t)s0 * D, *lp = logphi + s0;
-            if (rows == MT_ROWS) go(mfma_kernel, Ws, lp, sg, slab, g.n_iter);
-            else if (D == GCOLS) go(rows8_full_kernel, (int)D, Ws, lp, sg, slab, g.n_iter);
-            else go(rows8_kernel, (int)D, Ws, lp, sg, slab, g.n_iter);
-        },
-        [&](int s0) {
-            hipLaunchKernelGGL(reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream, (const float*)slab, g.n_blocks,
-                               (int)D, (int)S, s0, ell, G, T);
-        });
-}
+// (The data pass of the DSP routes, kernels and host side: csrc/bsc_scalar_family.h.)
 
 }  // namespace
 

@@ -1,6 +1,6 @@
 // The two-launch mean-field finish of the models whose latent is z = [w (D) | the model's own coordinates]: the bodies
-// of glm_hier_scalars_kernel / glm_hier_coord_kernel (csrc/bsc_glm_group.hip) and glm_nb_scalars_kernel /
-// glm_nb_coord_kernel (csrc/bsc_glm_nb.hip).  q = N(m, diag e^{2 rho}), lam = [m (P) | rho (P)], eps [S, P].
+// of glm_hier_scalars_kernel / glm_hier_coord_kernel (csrc/bsc_glm_group.hip) and scalar_mf_scalars_kernel /
+// scalar_mf_coord_kernel (csrc/bsc_scalar_family.h).  q = N(m, diag e^{2 rho}), lam = [m (P) | rho (P)], eps [S, P].
 //
 //   scalars  workgroup s < S: |w_s|^2 and what else the model keeps per draw, into scal; workgroup S: sum rho.
 //   coord    one thread per coordinate i of z: d f / d z_i over the draws in draw order, the entropy term, Adam on m_i
@@ -157,41 +157,6 @@ struct NbModel : MeanfieldArgs {
     }
 };
 
-// Host side of that finish: the checks, the next step's noise, the arguments and the two launches, through the calling
-// translation unit's own kernels (`scalars` runs meanfield_scalars_body, `coord` meanfield_coord_body on NbModel).
-template <class Scalars, class Coord>
-int nb_model_update(bsc_ctx* ctx, const char* who, Scalars scalars, Coord coord, const double* stats,
-                    const double* lam_in, double* lam_out, double* m1, double* m2, const double* eps, const float* W,
-                    const float* logphi, int32_t D, int32_t S, double scale, double prior_precision, double a0,
-                    double b0, int64_t t, double lr, double beta1, double beta2, double adam_eps, uint64_t seed,
-                    uint32_t next_step, double* eps_next, int32_t eps_next_ready, float* W_next, float* logphi_next,
-                    double* elbo, double* grad) {
-    BSC_REQUIRE(stats, "%s: stats is null (pending pass partials are not read: pass [ell | G | T])", who);
-    int rc = check_meanfield_update(who, lam_in && lam_out && m1 && m2 && eps && W && logphi && elbo && grad, lam_in,
-                                    lam_out, D, S, MF_MAX_S, prior_precision, /*has_gamma=*/true, a0, b0, scale, t);
-    if (rc != BSC_OK) return rc;
-    rc = next_draw_noise(ctx, who, /*has_extra=*/true, eps, W, logphi, eps_next, W_next, logphi_next, D, S, seed,
-                         next_step, eps_next_ready);
-    if (rc != BSC_OK) return rc;
-    void* ws = nullptr;
-    rc = bsc_workspace(ctx, (NbModel::N_SLOTS * MF_MAX_S + 8) * sizeof(double), &ws);
-    if (rc != BSC_OK) return rc;
-    NbModel a;
-    a.stats = stats; a.lam_in = lam_in; a.lam_out = lam_out; a.m1 = m1; a.m2 = m2;
-    a.eps = eps; a.W = W; a.logphi = logphi; a.eps_next = eps_next; a.W_next = W_next; a.logphi_next = logphi_next;
-    a.scal = (double*)ws; a.elbo = elbo; a.grad = grad;
-    a.D = D; a.S = S; a.P = D + 1;
-    a.scale = scale; a.prec = prior_precision; a.a0 = a0; a.b0 = b0;
-    a.c0 = 0.5 * (double)D * (log(prior_precision) - BSC_LOG_2PI) + a0 * log(b0) - lgamma(a0);
-    a.adam = bsc_adam_make(lr, beta1, beta2, adam_eps, t);
-    ctx->slab_rows = 0;   // the workspace is this finish's now
-    {
-        bsc_prof_scope prof(ctx, /*slot=*/2);  // the finish, timed apart from the pass
-        hipLaunchKernelGGL(scalars, dim3(S + 1), dim3(MF_BLOCK), 0, ctx->stream, a);
-        hipLaunchKernelGGL(coord, dim3((a.P + MF_BLOCK - 1) / MF_BLOCK), dim3(MF_BLOCK), 0, ctx->stream, a);
-    }
-    BSC_LAUNCH_CHECK();
-    return BSC_OK;
-}
+// (The kernels and the host side of that finish: csrc/bsc_scalar_family.h, scalar_family_update.)
 
 }  // namespace

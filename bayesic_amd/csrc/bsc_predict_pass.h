@@ -15,14 +15,14 @@
 
 namespace {
 
-// The fourth family, internal: csrc/bsc_glm_nb.hip's predict_nb_kernel (bsc_nb_predict_pass).  bsc_predict_pass and
+// The fourth family, internal: csrc/bsc_glm_nb.hip's scalar_predict_kernel (bsc_nb_predict_pass).  bsc_predict_pass and
 // bsc_predict_pass_offset refuse it.  Always with OFFS (a null offset reads 0 through an empty descriptor); `logvar`
 // carries tau_s = log phi_s.
 constexpr int PREDICT_NEGBIN = 3;
-// The fifth, internal as well: csrc/bsc_glm_gamma.hip's predict_gamma_kernel (bsc_gamma_predict_pass), the Gamma
+// The fifth, internal as well: csrc/bsc_glm_gamma.hip's scalar_predict_kernel (bsc_gamma_predict_pass), the Gamma
 // likelihood with a per-draw shape; `logvar` carries tau_s = log alpha_s.  Always with OFFS, the offset may be null.
 constexpr int PREDICT_GAMMA = 4;
-// The sixth, internal as well: csrc/bsc_glm_weibull.hip's predict_weibull_kernel (bsc_weibull_predict_pass), the Weibull
+// The sixth, internal as well: csrc/bsc_glm_weibull.hip's scalar_predict_kernel (bsc_weibull_predict_pass), the Weibull
 // likelihood with a per-draw shape and right censoring in the sign of y; `logvar` carries tau_s = log k_s.  Always with
 // OFFS, the offset may be null.
 constexpr int PREDICT_WEIBULL = 5;
@@ -662,34 +662,8 @@ void predict_launch_chunks(int S, F launch) {
     else launch(std::integral_constant<int, 4>{});
 }
 
-// The entry point of a family with a per-draw scalar of its own (`logphi` [S], named `what` in the messages) and an
-// offset that may be null: csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip.  launch(NC, args,
-// n_blocks) launches the calling translation unit's kernel for NC chunks of draws, sum_kernel is its block_partial_sum.
-template <class Launch, class Sum>
-int scalar_predict_pass(bsc_ctx* ctx, const char* who, const char* what, Launch launch, Sum sum_kernel, const float* X,
-                        int64_t ldx, const float* y, const float* offset, int64_t B, int32_t D, const float* W,
-                        const float* logphi, int32_t S, float* mean, float* var, float* lpd, double* lpd_sum) {
-    int rc = predict_check_batch(who, X, y, B, W, mean, var, lpd, lpd_sum);
-    if (rc != BSC_OK) return rc;
-    BSC_REQUIRE(logphi, "%s: %s is null", who, what);
-    BSC_REQUIRE((((uintptr_t)offset) & 3) == 0 && (((uintptr_t)logphi) & 3) == 0,
-                "%s: offset and %s must be 4-byte aligned", who, what);
-    PredictArgs a;
-    int n_blocks = 0;
-    rc = predict_setup(ctx, who, X, ldx, y, B, D, W, logphi, S, mean, var, lpd, lpd_sum, &a, &n_blocks);
-    if (rc != BSC_OK || n_blocks == 0) return rc;
-    {
-        bsc_prof_scope prof(ctx);
-        predict_launch_chunks(S, [&](auto nc) { launch(nc, a, n_blocks); });
-    }
-    BSC_LAUNCH_CHECK();
-    if (lpd_sum) {
-        hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(BSC_WAVE), 0, ctx->stream, (const double*)a.partial, n_blocks,
-                           lpd_sum);
-        BSC_LAUNCH_CHECK();
-    }
-    return BSC_OK;
-}
+// (The entry point of the families with a per-draw scalar of their own -- csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip,
+// csrc/bsc_glm_weibull.hip, csrc/bsc_glm_weibull_interval.hip -- with its kernels: csrc/bsc_scalar_family.h.)
 
 }  // namespace
 

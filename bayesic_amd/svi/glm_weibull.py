@@ -63,9 +63,9 @@ and has been exercised at world size 1 only.
 """
 import numpy as np
 
-from ._obs import ObsBatch, batch_obs, obs_vector
-from ._reparam_base import (ReparamDriver, check_covariance, check_lam0, check_n_samples, check_priors,
-                            scalar_latent_covariance, scalar_latent_params)
+from ._obs import batch_obs, obs_vector
+from ._reparam_base import ReparamDriver
+from ._scalar_latent import ScalarLatentDriver
 
 TIME_MSG = "time must be finite and > 0 (a duration; censoring is given by event=, not by a sign)"
 EVENT_MSG = "event must be a bool or 0/1 array of length %d, one entry per row (None: every row is an event)"
@@ -78,12 +78,6 @@ UPPER_EVENT_MSG = "an event row (event = 1) cannot have a finite upper: an event
 UPPER_INTERVAL_MSG = "an interval-censored row needs upper > time (as float32): the event lies in (time, upper]"
 UPPER_LEFT_MSG = "a left-censored row (time == 0) needs a finite upper > 0"
 TIME_UPPER_MSG = TIME_MSG + "; only a left-censored row (a finite upper) may have time == 0"
-
-
-def check_arguments(prior_precision, a0, b0, n_samples):
-    """The constructor's checks that need no device."""
-    check_priors(prior_precision, a0, b0, "the shape")
-    check_n_samples(n_samples)
 
 
 def pack_response(time, event=None):
@@ -201,8 +195,14 @@ def pack_censored(time, event=None, upper=None):
     return y, ud
 
 
-class WeibullReparamSVI(ObsBatch, ReparamDriver):
-    link = "weibull"         # svi/predict.py: family_of
+class WeibullReparamSVI(ScalarLatentDriver):
+    """ScalarLatentDriver (svi/_scalar_latent.py: the state, the phases and the host views) with the shape k = e^tau and a
+    response of three vectors -- time, event, upper -- packed into the signed y and the device encoding of the upper ends;
+    params() reports shape_mean = E_q[k]."""
+    link = "weibull"
+    pass_name, finish_name = "bsc_glm_weibull_data_pass", "bsc_glm_weibull_update"
+    scalar_attr, mean_key, prior_noun = "_logshape", "shape_mean", "the shape"
+    has_exposure = False
 
     def __init__(self, X, time, event=None, n_total=None, n_samples=8, seed=1234, lr=1e-2, prior_precision=1.0, a0=1.0,
                  b0=0.1, ctx=None, group=None, lam0=None, *, upper=None, offset=None, weights=None, covariance="diag"):
@@ -213,33 +213,16 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         layout, default the same start with no off-diagonal entries).  ``offset`` / ``weights``: float32 [B], as in
         GLMReparamSVI.  ``upper``: float [B] upper ends (module docstring; inf = none), None = the model without them.
         time, event, upper and the weights are checked here (one synchronisation), never in step()."""
-        check_arguments(prior_precision, a0, b0, n_samples)
-        check_covariance(covariance)
-        import torch
-        host = not isinstance(time, torch.Tensor)
-        if host:
-            y, u = pack_censored(time, event, upper)      # before a device is asked for
-        shape = getattr(X, "shape", ())
-        if len(shape) == 2:                       # an array or a tensor: lam0 too is checked before a device is asked for
-            check_lam0(lam0, int(shape[1]) + 1, "w (%d) | tau" % int(shape[1]), covariance)
-        from ..device import default_context
-        self.covariance_kind = covariance
-        self.prior_precision, self.a0, self.b0 = float(prior_precision), float(a0), float(b0)
-        self.ctx = ctx or default_context()
-        if not host:
-            y, u = pack_censored(time, event, upper)
+        self._construct(X, (time, event, upper), n_total, n_samples, seed, lr, prior_precision, a0, b0, ctx, group,
+                        lam0, offset, weights, None, covariance)
+
+    def _checked_response(self, time, event, upper):
+        return pack_censored(time, event, upper)
+
+    def _set_response(self, X, response, checked):
+        y, u = pack_censored(*response) if checked is None else checked
         self._float_batch(X, y)
         self._set_upper(None if u is None else obs_vector(self.ctx, "upper", u, self.B))
-        self._set_obs(*batch_obs(self.ctx, self.B, offset, weights))
-        self.has_offset = self._oarg is not None      # predict() refuses to run without one
-        D, S = self.D, int(n_samples)
-        P = D + 1
-        check_lam0(lam0, P, "w (%d) | tau" % D, covariance)
-        # stats = [ell | G | T]; the slab of the pass is 8 * 256 + 16 floats per workgroup
-        self._init_state(P, lam0, n_total, S, seed, lr, group, noise_dim=D, w_cols=D, n_stats=S * (D + 2),
-                         reserve_bytes=(4 * self.ctx.info()["cu_count"] + 8) * (8 * 256 + 16) * 4)
-        self.T = self.stats[S + S * D:]
-        self._logshape = torch.zeros((2, S), dtype=torch.float32, device=self.ctx.device)
 
     def _set_upper(self, upper):
         """The upper ends of the current batch in the device encoding: a tensor, a raw device pointer or None."""
@@ -262,7 +245,8 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         elif event is not None:
             raise ValueError("with raw device pointers pass the signed vector where(event, time, -time) as time; "
                              "event= is for tensors")
-        super().set_batch(X, time, rows=rows, ldx=ldx)
+        # (not ScalarLatentDriver.set_batch: that one checks a single y with check_response, which this family has not)
+        ReparamDriver.set_batch(self, X, time, rows=rows, ldx=ldx)
         self._set_obs(offset, weights)
         self._set_upper(upper)
 
@@ -271,25 +255,12 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         return self._logshape[self.cur]
 
     # -- phases -------------------------------------------------------------------------------------------------
-    def sample(self, step):
-        """The first draw (first_draw) of w and tau, rounded to float32 as the finish rounds."""
-        import torch
-        z = self._first_draw(step).astype(np.float32)
-        self._store_W(z, self.D)
-        self._logshape[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(z[:, self.D])))
-        self._drawn = True
-
     def data_pass(self):
-        if getattr(self, "_uarg", None) is not None:      # only a batch with upper ends takes the interval pass
-            self.ctx.call("bsc_glm_weibull_data_pass_interval", self._Xarg, self._ldx, self._yarg, self._uarg,
-                          self._oarg, self._varg, self.B, self.D, self.W, self.logshape, self.S, self.ell, self.G, self.T)
-            return
-        self.ctx.call("bsc_glm_weibull_data_pass", self._Xarg, self._ldx, self._yarg, self._oarg, self._varg, self.B,
-                      self.D, self.W, self.logshape, self.S, self.ell, self.G, self.T)
-
-    def _finish(self, stats):
-        name = "bsc_glm_scalar_fullrank_update" if self.covariance_kind == "full" else "bsc_glm_weibull_update"
-        self._finish_latent(name, stats, self._logshape, (self.D,))
+        if getattr(self, "_uarg", None) is None:
+            return super().data_pass()
+        # only a batch with upper ends takes the interval pass
+        self.ctx.call("bsc_glm_weibull_data_pass_interval", self._Xarg, self._ldx, self._yarg, self._uarg, self._oarg,
+                      self._varg, self.B, self.D, self.W, self.logshape, self.S, self.ell, self.G, self.T)
 
     # -- posterior predictive (svi/predict.py: one bsc_weibull_predict_pass over X for all draws) -------------------
     def _signed(self, time, event, upper=None):
@@ -328,14 +299,5 @@ class WeibullReparamSVI(ObsBatch, ReparamDriver):
         y = -pack_response(t)                     # t checked like a duration, every row censored
         return torch.exp(predict(self, X, y, n_samples=n_samples, seed=seed, draws=draws, offset=offset)["lpd"])
 
-    # -- host views -----------------------------------------------------------------------------------------------
-    def params(self):
-        """m and rho (host float64) whole and split -- w [D] and tau (scalars), each as (mean, rho) --, the dense
-        lower-triangular L [P, P] of a full guide, and shape_mean = E_q[k] = exp(m_tau + Var_q(tau) / 2) with
-        Var_q(tau) = e^{2 rho_tau} (mean-field) or the squared norm of the last row of L (full)."""
-        return scalar_latent_params(self.lam.cpu().numpy(), self.D, self.covariance_kind, "shape_mean")
 
-    def covariance(self):
-        """Cov_q over z = [w (D) | tau] (P x P, host float64): L L^T of the full guide, diag(e^{2 rho}) of the
-        mean-field one."""
-        return scalar_latent_covariance(self.lam.cpu().numpy(), self.D, self.covariance_kind)
+check_arguments = WeibullReparamSVI.check_arguments

@@ -1,5 +1,5 @@
 """Compile-time resource guard for the ordinal-regression kernels (csrc/bsc_glm_ordinal.hip), as
-tests/test_glm_weibull_kernel_resources.py keeps for the Weibull ones (no GPU needed: hipcc cross-compiles for gfx950;
+tests/test_scalar_family_kernel_resources.py keeps for the Weibull ones (no GPU needed: hipcc cross-compiles for gfx950;
 only the compiler's resource remarks are read).
 
 Measured from this compile (VGPRs, scratch bytes per lane, waves per SIMD):

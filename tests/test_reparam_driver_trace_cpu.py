@@ -1,9 +1,10 @@
-"""The C-ABI calls of the five reparameterised drivers, written down by tests/_trace_ctx.TraceContext and compared with
-tests/golden/reparam_driver_traces.json (the negative-binomial cases: reparam_driver_traces_negbin.json): for every
+"""The C-ABI calls of the seven reparameterised drivers, written down by tests/_trace_ctx.TraceContext and compared with
+tests/golden/reparam_driver_traces.json (the negative-binomial cases: reparam_driver_traces_negbin.json; the Gamma and
+Weibull drivers and the full guide of the three learned-scalar drivers: reparam_driver_traces_scalar.json): for every
 case the names, scalar arguments, buffers (and which half of each
 double buffer) and reserve sizes of construction, posterior_draws, three steps, set_batch with tensors, a step,
 set_batch with raw pointers and one more step; with SHA-256 digests of the start lam, of the first draw (W, and xi, Bz
-or logphi where the driver has them) and of the predictive draws, all of which the drivers compute on the host.
+logphi or logshape where the driver has them) and of the predictive draws, all of which the drivers compute on the host.
 Equality, not closeness: the drivers' numerics are pinned on the device by the GPU tests, and this shows that the same
 calls reach the library.
 
@@ -21,8 +22,10 @@ from _trace_ctx import TraceContext
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reparam_driver_traces.json")
 # the negative-binomial cases came later and have a file of their own: the first one stays as it was, byte for byte
 GOLDEN_NEGBIN = GOLDEN[:-5] + "_negbin.json"
+# ... and so have the cases that pin the three learned-scalar drivers as a group
+GOLDEN_SCALAR = GOLDEN[:-5] + "_scalar.json"
 B, D, J, K, B2, LD2 = 40, 12, 5, 3, 24, 16
-RAW = dict(X=0x10000, y=0x20000, offset=0x30000, weights=0x40000, groups=0x50000)
+RAW = dict(X=0x10000, y=0x20000, offset=0x30000, weights=0x40000, groups=0x50000, upper=0x60000)
 
 
 def _full_lam0(P, seed):
@@ -34,11 +37,20 @@ def _full_lam0(P, seed):
 def _batch(rows, seed, ld=D):
     rs = np.random.RandomState(seed)
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32))
-    return dict(X=f32(rs.standard_normal((rows, ld)))[:, :D], y=f32(rs.poisson(1.5, rows)),
-                labels=torch.from_numpy(rs.randint(K, size=rows).astype(np.int32)),
-                groups=torch.from_numpy(rs.randint(J, size=rows).astype(np.int32)),
-                offset=f32(0.1 * rs.standard_normal(rows)), exposure=f32(rs.uniform(0.5, 2.0, rows)),
-                weights=f32(rs.uniform(0.0, 3.0, rows)))
+    out = dict(X=f32(rs.standard_normal((rows, ld)))[:, :D], y=f32(rs.poisson(1.5, rows)),
+               labels=torch.from_numpy(rs.randint(K, size=rows).astype(np.int32)),
+               groups=torch.from_numpy(rs.randint(J, size=rows).astype(np.int32)),
+               offset=f32(0.1 * rs.standard_normal(rows)), exposure=f32(rs.uniform(0.5, 2.0, rows)),
+               weights=f32(rs.uniform(0.0, 3.0, rows)))
+    # the learned-scalar drivers' vectors, drawn after the ones above: a strictly positive response, the censoring flags,
+    # and upper ends of every kind (0: none, inf; 1: an interval above the time; 2: left-censored, the time is 0)
+    pos = rs.gamma(2.0, 1.0, rows) + 0.05
+    event = rs.randint(2, size=rows).astype(bool)
+    kind = rs.randint(3, size=rows)
+    kind[:3] = (0, 1, 2)
+    upper = np.where(kind == 0, np.inf, np.where(kind == 1, pos * rs.uniform(1.5, 3.0, rows), rs.uniform(0.5, 2.0, rows)))
+    out.update(ypos=f32(pos), event=torch.from_numpy(event), time0=f32(np.where(kind == 2, 0.0, pos)), upper=f32(upper))
+    return out
 
 
 def _blr(**kw):
@@ -66,6 +78,17 @@ def _negbin(obs=(), **kw):
     return NegBinReparamSVI, ("X", "y"), kw, obs
 
 
+def _gamma(obs=(), **kw):
+    from bayesic_amd.svi import GammaReparamSVI
+    return GammaReparamSVI, ("X", "ypos"), kw, obs
+
+
+def _weibull(obs=(), time="ypos", **kw):
+    """(X, time, event) are the constructor's first three; with ``upper`` the time has its zeros and event is None."""
+    from bayesic_amd.svi import WeibullReparamSVI
+    return WeibullReparamSVI, ("X", time) + (() if "upper" in obs else ("event",)), kw, obs
+
+
 CASES = {
     "blr-diag-S8": lambda: _blr(n_samples=8),
     "blr-diag-S16": lambda: _blr(n_samples=16),
@@ -87,6 +110,19 @@ CASES = {
     "negbin-S12": lambda: _negbin(n_samples=12),
     "negbin-exposure-weights": lambda: _negbin(("exposure", "weights")),
 }
+SCALAR_CASES = {
+    "gamma-S8": lambda: _gamma(n_samples=8),
+    "gamma-exposure-weights": lambda: _gamma(("exposure", "weights")),
+    "gamma-full": lambda: _gamma(covariance="full", lam0=_full_lam0(D + 1, 4)),
+    "negbin-full": lambda: _negbin(covariance="full", lam0=_full_lam0(D + 1, 5)),
+    "weibull-S8": lambda: _weibull(n_samples=8),
+    "weibull-S12": lambda: _weibull(n_samples=12),
+    "weibull-offset-weights": lambda: _weibull(("offset", "weights")),
+    "weibull-upper": lambda: _weibull(("upper",), time="time0"),
+    "weibull-upper-offset-weights": lambda: _weibull(("upper", "offset", "weights"), time="time0"),
+    "weibull-full": lambda: _weibull(covariance="full", lam0=_full_lam0(D + 1, 6)),
+}
+CASES.update(SCALAR_CASES)
 
 
 def record(case):
@@ -107,7 +143,7 @@ def record(case):
         ctx.bind(model)
     model.step()
     ctx.bind(model)
-    for attr in ("_W", "_xi", "_Bz", "_logphi"):
+    for attr in ("_W", "_xi", "_Bz", "_logphi", "_logshape"):
         if hasattr(model, attr):
             ctx.digest(attr, getattr(model, attr))
     model.step()
@@ -120,7 +156,8 @@ def record(case):
     model.step()
     ctx.bind(model)
     if not kw.get("reproducible"):          # (that mode cuts tensors into shards and refuses raw pointers)
-        model.set_batch(RAW["X"], RAW["y"], rows=B2, ldx=LD2, **{k: RAW[k] for k in extra})
+        # (Weibull: y is the signed vector and upper the device encoding; event= is for tensors)
+        model.set_batch(RAW["X"], RAW["y"], rows=B2, ldx=LD2, **{k: RAW[k] for k in extra if k != "event"})
         model.step()
         ctx.bind(model)
     return json.loads(json.dumps(ctx.trace))
@@ -129,7 +166,7 @@ def record(case):
 @pytest.fixture(scope="module")
 def golden():
     traces = {}
-    for path in (GOLDEN, GOLDEN_NEGBIN):
+    for path in (GOLDEN, GOLDEN_NEGBIN, GOLDEN_SCALAR):
         with open(path) as f:
             traces.update(json.load(f))
     return traces
@@ -150,8 +187,10 @@ def test_driver_makes_the_recorded_calls(case, golden):
 if __name__ == "__main__":
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    for path in (GOLDEN, GOLDEN_NEGBIN):
-        mine = [case for case in sorted(CASES) if case.startswith("negbin-") == (path == GOLDEN_NEGBIN)]
+    file_of = lambda case: GOLDEN_SCALAR if case in SCALAR_CASES else \
+        GOLDEN_NEGBIN if case.startswith("negbin-") else GOLDEN
+    for path in (GOLDEN, GOLDEN_NEGBIN, GOLDEN_SCALAR):
+        mine = [case for case in sorted(CASES) if file_of(case) == path]
         with open(path, "w") as f:
             json.dump({case: record(case) for case in mine}, f, separators=(",", ":"), sort_keys=True)
             f.write("\n")
