@@ -1196,7 +1196,8 @@ class DeviceBackend(Backend):
             if g is not None and self._keep is None:
                 xb, m, n, k, x, sxb, sxm, sxk, y, syb, syk, syn = g.gemm
                 if g.power == 1 and g.E is None and g.pre is None and xb == 1 and sxk == 1 and k % 8 == 0 \
-                        and k <= 64 and n <= 64 and n % 4 == 0 and sxm % 4 == 0 and x.data_ptr() % 16 == 0 \
+                        and k <= 64 and n <= 64 and n % 4 == 0 and sxm % 4 == 0 and sxm < 1 << 25 \
+                        and x.data_ptr() % 16 == 0 \
                         and g.dtype == torch.float32 and len(g.shape) == 2:
                     wkey = next((key for key, t in self._const_cache.items() if t is x and key[0] == "kcat"), None) \
                         if defer else None

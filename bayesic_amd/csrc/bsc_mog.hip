@@ -826,7 +826,10 @@ int bsc_mog_estep(bsc_ctx* ctx, const float* X, int64_t ldx, int64_t N, int32_t 
         return bsc_fail(BSC_ERR_UNSUPPORTED,
                         "bsc_mog_estep: D=%d K=%d outside the MFMA tile limits (D<=%d, K<=%d)", D,
                         K, MD, MK);
-    BSC_REQUIRE(ldx >= D && ldx < ((int64_t)1 << 26), "bsc_mog_estep: bad ldx=%lld", (long long)ldx);
+    // (load_rows addresses a tile's 32 rows through 32-bit byte offsets, (lane & 31) * ldx * 4: a leading dimension of
+    // 2^25 floats or more would wrap them for the rows past 2^32 / (4 ldx) and the lane would read another row's
+    // neighbourhood -- 31 * 2^27 < 2^32 holds below 2^25, as in csrc/bsc_gram.hip)
+    BSC_REQUIRE(ldx >= D && ldx < ((int64_t)1 << 25), "bsc_mog_estep: bad ldx=%lld", (long long)ldx);
     BSC_REQUIRE(((uintptr_t)X & 3) == 0, "bsc_mog_estep: X must be 4-byte aligned");
     const int64_t n_tiles = (N + MT - 1) / MT;
     const int64_t max_waves = 2 * 4 * (int64_t)ctx->cu_count;

@@ -518,7 +518,10 @@ int bsc_gemm_softmax_rows(bsc_ctx* ctx, const float* A, int64_t lda, int64_t row
     if (K > 2 * RS_KH || K % 8 != 0 || N > RS_N || N % 4 != 0)
         return bsc_fail(BSC_ERR_UNSUPPORTED,
                         "bsc_gemm_softmax_rows: K=%d (<= 64, multiple of 8) N=%d (<= 64, multiple of 4)", K, N);
-    BSC_REQUIRE(lda >= K && lda % 4 == 0 && lda < ((int64_t)1 << 26) && ldr >= N && ldr % 4 == 0,
+    // (rs_load addresses a tile's 32 rows through 32-bit byte offsets, (lane & 31) * lda * 4 plus the lane's columns:
+    // a leading dimension of 2^25 floats or more would wrap them -- (31 * (2^25 - 4) + 64) * 4 < 2^32 holds below it,
+    // as in csrc/bsc_gram.hip.  Callers take bsc_gemm_strided_batched + bsc_softmax_rows for such a view.)
+    BSC_REQUIRE(lda >= K && lda % 4 == 0 && lda < ((int64_t)1 << 25) && ldr >= N && ldr % 4 == 0,
                 "bsc_gemm_softmax_rows: lda=%lld ldr=%lld", (long long)lda, (long long)ldr);
     BSC_REQUIRE((((uintptr_t)A) & 15) == 0 && (((uintptr_t)R) & 15) == 0,
                 "bsc_gemm_softmax_rows: A and R must be 16-byte aligned");
@@ -558,7 +561,8 @@ int bsc_gemm_softmax_stats(bsc_ctx* ctx, const float* A, int64_t lda, int64_t ro
     if (K > 2 * RS_KH || K % 8 != 0 || N > RS_N || N % 4 != 0)
         return bsc_fail(BSC_ERR_UNSUPPORTED,
                         "bsc_gemm_softmax_stats: K=%d (<= 64, multiple of 8) N=%d (<= 64, multiple of 4)", K, N);
-    BSC_REQUIRE(lda >= K && lda % 4 == 0 && lda < ((int64_t)1 << 26) && ldst >= K + (bias ? 1 : 0),
+    // (lda < 2^25: the 32-bit lane offsets of rs_load, see bsc_gemm_softmax_rows)
+    BSC_REQUIRE(lda >= K && lda % 4 == 0 && lda < ((int64_t)1 << 25) && ldst >= K + (bias ? 1 : 0),
                 "bsc_gemm_softmax_stats: lda=%lld ldst=%lld", (long long)lda, (long long)ldst);
     if (bias && K > 56)
         return bsc_fail(BSC_ERR_UNSUPPORTED, "bsc_gemm_softmax_stats: a bias row needs K <= 56 (got %d)", K);

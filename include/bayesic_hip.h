@@ -975,8 +975,9 @@ int bsc_softmax_rows(bsc_ctx* ctx, const float* in, int64_t rows, int64_t cols, 
  * (README.md:43; alpha = the 1 / (N / B) of a local latent under mini-batch scaling, README.md:69-79).  One pass: A is read once and R written once; the logits never reach memory (as two
  * launches they are written, read and written again).  `cross` (may be NULL) is what the factor's
  * entropy sum_r (lse[r] - cross[r]) needs in place of the logits.  float32; K <= 64 and a multiple of
- * 8, N <= 64 and a multiple of 4, A and R 16-byte aligned, lda % 4 == ldr % 4 == 0; anything else is
- * BSC_ERR_UNSUPPORTED (callers then take bsc_gemm_strided_batched + bsc_softmax_rows). */
+ * 8, N <= 64 and a multiple of 4, A and R 16-byte aligned, lda % 4 == ldr % 4 == 0, lda < 2^25 (a tile's 32 rows
+ * are addressed through 32-bit byte offsets; BSC_ERR_INVALID beyond); a K or N outside these is
+ * BSC_ERR_UNSUPPORTED (callers then take bsc_gemm_strided_batched + bsc_softmax_rows, as they do for such a view). */
 int bsc_gemm_softmax_rows(bsc_ctx* ctx, const float* A, int64_t lda, int64_t rows, int32_t K,
                           const float* B, int64_t ldbk, int64_t ldbn, int32_t N, float alpha, float* R,
                           int64_t ldr, float* lse, float* cross);
@@ -1070,7 +1071,8 @@ int bsc_suffstats_normal(bsc_ctx* ctx, const float* x, int64_t n, double* stats)
  * and, summed over rows in float64 (fixed order):
  *     stats[k] = [sum r_k | sum r_k x (D) | sum r_k x^2 (D)]   ([K, 1+2D])
  *     lse[0]   = sum_n logsumexp_k(logit_nk)
- * Both contractions run on fp32 MFMA.  Limits: D <= 16, K <= 64 (one tile). */
+ * Both contractions run on fp32 MFMA.  Limits: D <= 16, K <= 64 (one tile); X 4-byte aligned, D <= ldx < 2^25
+ * (a tile's 32 rows are addressed through 32-bit byte offsets). */
 int bsc_mog_estep(bsc_ctx* ctx, const float* X, int64_t ldx, int64_t N, int32_t D, int32_t K,
                   const float* Wmat, const float* c, double* stats, double* lse);
 

@@ -53,8 +53,10 @@ ran follows from the dispatcher / kernel source at the place named and from the 
                                                         gemm_f32_* <- test_skinny[tn-big:ld+1], test_skinny[tn-ctl-skinny0]
   [K] bsc_skinny.hip bsc_gemm_skinny: TN, s * 15 + K    gemm_skinny_tn_kernel <- test_span_gates[skinny-tn-below]
                                                         gemm_f32_* <- test_span_gates[skinny-tn-above]
-  [-] bsc_skinny.hip small_span (ld < 2^26)             NOT crossed: the NT routes need >= 4096 rows at that stride (1 TiB), and for TN the
-                                                        s * 15 + K limit above binds first (s < 2^29 / 15)
+  [-] bsc_skinny.hip small_span (ld < 2^26)             the ld < 2^26 limit itself stays UNCROSSED: the NT routes need >= 4096 rows at that
+                                                        stride (1 TiB), and for TN the s * 15 + K limit above binds first (s < 2^29 / 15).
+                                                        Spans past 2^32 bytes BELOW it: test_span_routes_gpu.py test_below_gate[skinny-nt],
+                                                        [skinny-nt-swapped] (4100 rows, ld 327 680) and [skinny-tn] (K = 16 384, sb_k = 81 920)
   [K] bsc_fused.hip map_flat                            map_flat_f32_kernel <- test_map_family[map-64x64-ctl]
                                                         map_rows_f32_kernel / map_dense_f32_kernel (map_rows2d, map_is_dense) <-
                                                         test_map_family[map-64x64-ctl-flat0]; map_small_f32_kernel (map_small) <-
@@ -78,7 +80,9 @@ ran follows from the dispatcher / kernel source at the place named and from the 
                                                         (K = 96 has no stream kernel: lda_sstats_kernel always)
   [B] bsc_lda.hip csc: a.vec_th / csc_fast              lda_sstats_csc_kernel <- test_lda_sstats_csc[K64-ctl] (a.fast) vs [K64-th:off1], [K64-th:ld+1],
                                                         [K64-ctl-fast0] (general loads)
-  [-] bsc_mog.hip bsc_mog_estep (no gate: 4-byte loads) mog_estep_kernel, every layout
+  [-] bsc_mog.hip bsc_mog_estep (no ALIGNMENT gate:     mog_estep_kernel, every layout.  Its gate on the span, ldx < 2^25 (the 32-bit lane
+      4-byte loads)                                     offsets of a 32-row tile), is crossed in test_span_routes_gpu.py: test_below_gate[mog-D16],
+                                                        [mog-D5], [mog-bx-D16] at 2^25 - 4, test_refused[mog] at 2^25
 """
 import ctypes
 
