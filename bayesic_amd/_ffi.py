@@ -167,6 +167,18 @@ SIGNATURES = {
                                         c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),
     "bsc_group_ids_check": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32]),
+    "bsc_glm_scalar_group_workspace_bytes": (c_int64, [c_void_p, c_int64, c_int32]),
+    "bsc_glm_scalar_data_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                                c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_glm_scalar_hier_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_double,
+                                           c_double, c_double, c_double, c_double, c_int64, c_double, c_double,
+                                           c_double, c_double, c_uint64, c_uint32, c_void_p, c_int32, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsc_scalar_predict_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                               c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_softmax_data_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_int32, c_void_p, c_void_p]),
     "bsc_softmax_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,

@@ -23,6 +23,9 @@
 //                 past the batch and their stores do not land.  Everything of it is behind `if constexpr (GRP)`; the
 //                 flag defaults to off and the kernels of the two files above compile as they did without it.
 //
+//                 GRP with DSP (csrc/bsc_glm_scalar_group.hip): the link of the GRP branches also gets the draw's
+//                 dispersion and the T accumulator, the slab is DSP's; never with ITV.
+//
 //   DSP = true    csrc/bsc_glm_nb.hip (always with OBS and LINK = GLM_NEGBIN): the negative binomial with one
 //                 dispersion draw per weight draw, tau_s = log phi_s as float32 [S].  A lane owns ONE draw in both tile
 //                 shapes, so tau_s, phi_s = exp(tau_s), lnGamma(phi_s) and psi(phi_s) are made once per launch (the two
@@ -364,8 +367,9 @@ __device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP, ITV>& t, co
     const int val = lane_value<ROWS>(lane);
     float resid;
     if constexpr (GRP) {
+        // (dp and T are null without DSP, and a link without a dispersion never reads them)
         resid = glm_link<LINK, true>(logit + t.bz + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell,
-                                     has_v ? t.vv : 1.0f);
+                                     has_v ? t.vv : 1.0f, dp, T);
         // row row0 + (val >> 3) of block row0 >> 4, draw val & 7; nothing lands from the block r_blocks on
         const int64_t blk = row0 >> 4;
         auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);
@@ -419,9 +423,10 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
                                               int n_iter, const GlmGroupArgs* ga = nullptr,
                                               const float* logphi = nullptr, const float* upper = nullptr) {
-    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
+    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
                   "the dispersion (the shape) rides with OBS and its own link");
-    static_assert(!ITV || (DSP && LINK == GLM_WEIBULL), "the upper end rides with the Weibull shape");
+    static_assert(!ITV || (DSP && !GRP && LINK == GLM_WEIBULL),
+                  "the upper end rides with the Weibull shape, without groups");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > STRIDE ? G8::WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -449,21 +454,25 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     if constexpr (GRP) {
         // the same rotation; every tile's gather goes out before the loads of the tile after it
         const int* g_ = ga->g;
+        const GlmDisp* dq = DSP ? &dp : nullptr;   // (null without DSP, as the defaults of compute_tile are)
+        float* tq = DSP ? &tacc : nullptr;
         GlmTile<OBS, GRP> ta, tb;
         load_tile<FULL, OBS, GRP>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane, g_);
         for (int k = 0; k + 1 < n_iter; k += 2) {
             gather_tile(ta, *ga, lane);
             load_tile<FULL, OBS, GRP>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane, g_);
-            compute_tile<LINK, OBS, GRP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS);
+            compute_tile<LINK, OBS, GRP, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS, dq,
+                                              tq);
             gather_tile(tb, *ga, lane);
             load_tile<FULL, OBS, GRP>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane, g_);
-            compute_tile<LINK, OBS, GRP>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, ga,
-                                         (tile + stride) * ROWS);
+            compute_tile<LINK, OBS, GRP, DSP>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, ga,
+                                              (tile + stride) * ROWS, dq, tq);
             tile += 2 * stride;
         }
         if (n_iter & 1) {
             gather_tile(ta, *ga, lane);
-            compute_tile<LINK, OBS, GRP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS);
+            compute_tile<LINK, OBS, GRP, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS, dq,
+                                              tq);
         }
     } else {   // (dp and tacc: untouched without DSP)
         GlmTile<OBS, false, ITV> ta, tb;
@@ -572,9 +581,10 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
                                                    int n_iter, const GlmGroupArgs* ga = nullptr,
                                                    const float* logphi = nullptr, const float* upper = nullptr) {
-    static_assert(!DSP || (OBS && !GRP && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
+    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
                   "the dispersion (the shape) rides with OBS and its own link");
-    static_assert(!ITV || (DSP && LINK == GLM_WEIBULL), "the upper end rides with the Weibull shape");
+    static_assert(!ITV || (DSP && !GRP && LINK == GLM_WEIBULL),
+                  "the upper end rides with the Weibull shape, without groups");
     constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > STRIDE ? MT_WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -662,10 +672,12 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
         if (live) {
             float r0, r1, r2, r3;
             if constexpr (GRP) {
-                r0 = glm_link<LINK, true>(d0[0] + d1[0] + bz.x + ov.x, yv.x, rows_left > 0, ell, vv.x);
-                r1 = glm_link<LINK, true>(d0[1] + d1[1] + bz.y + ov.y, yv.y, rows_left > 1, ell, vv.y);
-                r2 = glm_link<LINK, true>(d0[2] + d1[2] + bz.z + ov.z, yv.z, rows_left > 2, ell, vv.z);
-                r3 = glm_link<LINK, true>(d0[3] + d1[3] + bz.w + ov.w, yv.w, rows_left > 3, ell, vv.w);
+                const GlmDisp* dq = DSP ? &dp : nullptr;   // (null without DSP, as the defaults of glm_link are)
+                float* tq = DSP ? &tacc : nullptr;
+                r0 = glm_link<LINK, true>(d0[0] + d1[0] + bz.x + ov.x, yv.x, rows_left > 0, ell, vv.x, dq, tq);
+                r1 = glm_link<LINK, true>(d0[1] + d1[1] + bz.y + ov.y, yv.y, rows_left > 1, ell, vv.y, dq, tq);
+                r2 = glm_link<LINK, true>(d0[2] + d1[2] + bz.z + ov.z, yv.z, rows_left > 2, ell, vv.z, dq, tq);
+                r3 = glm_link<LINK, true>(d0[3] + d1[3] + bz.w + ov.w, yv.w, rows_left > 3, ell, vv.w, dq, tq);
                 // block row0 / 16 of R, [draw][row]: nothing lands from the block r_blocks on
                 const int64_t blk = row0_of(p) >> 4;
                 auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);

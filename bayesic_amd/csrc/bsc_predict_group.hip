@@ -71,11 +71,8 @@ int bsc_predict_pass_groups(bsc_ctx* ctx, int32_t family, const float* X, int64_
                         "model has these two links", who, family);
     int rc = predict_check_batch(who, X, y, B, W, mean, var, lpd, lpd_sum);
     if (rc != BSC_OK) return rc;
-    PREDICT_UNSUPPORTED(groups && Bt, "%s: groups and Bt must not be null", who);
-    PREDICT_UNSUPPORTED(J >= 1 && J <= BSC_GLM_GROUP_MAX_J, "%s: J=%d must be in [1,%d]", who, J, BSC_GLM_GROUP_MAX_J);
-    PREDICT_UNSUPPORTED(ldb >= S && ldb % 4 == 0 && ldb <= P_MAX_LDB, "%s: ldb=%d must be >= S, %% 4 == 0 and <= %d",
-                        who, ldb, P_MAX_LDB);
-    PREDICT_UNSUPPORTED((((uintptr_t)Bt) & 15) == 0, "%s: Bt must be 16-byte aligned", who);
+    rc = predict_check_groups(who, groups, Bt, J, ldb, S);
+    if (rc != BSC_OK) return rc;
     PREDICT_UNSUPPORTED((((uintptr_t)groups) & 3) == 0 && (((uintptr_t)offset) & 3) == 0,
                         "%s: groups and offset must be 4-byte aligned", who);
     PredictArgs a;

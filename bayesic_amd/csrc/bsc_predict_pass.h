@@ -608,6 +608,18 @@ inline int predict_check_batch(const char* who, const float* X, const float* y, 
     return BSC_OK;
 }
 
+// What the entry points with a group table (csrc/bsc_predict_group.hip, csrc/bsc_predict_scalar_group.hip) ask of it;
+// the alignment of the ids and of the family's other vectors stays with the caller, which names them.
+inline int predict_check_groups(const char* who, const int32_t* groups, const float* Bt, int32_t J, int32_t ldb,
+                                int32_t S) {
+    PREDICT_UNSUPPORTED(groups && Bt, "%s: groups and Bt must not be null", who);
+    PREDICT_UNSUPPORTED(J >= 1 && J <= BSC_GLM_GROUP_MAX_J, "%s: J=%d must be in [1,%d]", who, J, BSC_GLM_GROUP_MAX_J);
+    PREDICT_UNSUPPORTED(ldb >= S && ldb % 4 == 0 && ldb <= P_MAX_LDB, "%s: ldb=%d must be >= S, %% 4 == 0 and <= %d",
+                        who, ldb, P_MAX_LDB);
+    PREDICT_UNSUPPORTED((((uintptr_t)Bt) & 15) == 0, "%s: Bt must be 16-byte aligned", who);
+    return BSC_OK;
+}
+
 // The shapes the kernels take, the grid, the arguments and the workspace of lpd_sum's block partials.  *n_blocks = 0:
 // an empty batch, lpd_sum is zeroed and there is nothing to launch.  w_mask: the alignment asked of the draws (3: the
 // ordinal family, which reads them with 4-byte loads).

@@ -6,10 +6,11 @@ from .glm_nb import NegBinReparamSVI  # noqa: E402,F401
 from .glm_ordinal import OrdinalReparamSVI  # noqa: E402,F401
 from .glm_weibull import WeibullReparamSVI  # noqa: E402,F401
 from .hier_glm import HierGLMReparamSVI  # noqa: E402,F401
+from .hier_scalar import HierGammaReparamSVI, HierNegBinReparamSVI, HierWeibullReparamSVI  # noqa: E402,F401
 from .softmax import SoftmaxReparamSVI  # noqa: E402,F401
 from . import predict  # noqa: E402,F401  (the module: predict.predict(model, X, ...))
 from .predict import heldout_lpd, posterior_draws  # noqa: E402,F401
 
-__all__ = ["GLMReparamSVI", "GammaReparamSVI", "HierGLMReparamSVI", "NegBinReparamSVI", "OrdinalReparamSVI",
-           "SoftmaxReparamSVI",
+__all__ = ["GLMReparamSVI", "GammaReparamSVI", "HierGLMReparamSVI", "HierGammaReparamSVI", "HierNegBinReparamSVI",
+           "HierWeibullReparamSVI", "NegBinReparamSVI", "OrdinalReparamSVI", "SoftmaxReparamSVI",
            "WeibullReparamSVI", "predict", "posterior_draws", "heldout_lpd"]

@@ -29,10 +29,11 @@ Accuracy envelope of the pass: tau in [-2.5, 5] (alpha from 0.08 to 148).
 mu + L eps, finish bsc_glm_scalar_fullrank_update (svi/glm_nb.py says more): the shape is correlated a posteriori with
 the intercept, and a diagonal q reports it too narrow.
 
-Limits, by design of this version: no groups together with the shape; ReparamVI does not recognise a Gamma log-joint;
-MiniBatchLoader does not carry offset and weights; there is no one-call (pass + finish) form, so every update is
-pass -> all-reduce -> finish.  The multi-rank branch is wired like the other drivers' and has been exercised at world
-size 1 only.
+Random intercepts per group together with the shape: HierGammaReparamSVI (svi/hier_scalar.py).
+
+Limits, by design of this version: ReparamVI does not recognise a Gamma log-joint; MiniBatchLoader does not carry
+offset and weights; there is no one-call (pass + finish) form, so every update is pass -> all-reduce -> finish.  The
+multi-rank branch is wired like the other drivers' and has been exercised at world size 1 only.
 """
 import numpy as np
 

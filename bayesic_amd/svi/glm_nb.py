@@ -28,10 +28,11 @@ scalar (it sees [ell | G | T], never the likelihood).  The dispersion is correla
 diagonal q reports it too narrow.  The pass, the all-reduce, set_batch, offsets and weights are the same for both
 guides.
 
-Limits, by design of this version: no groups together with the dispersion; ReparamVI does not recognise a
-negative-binomial log-joint; MiniBatchLoader does not carry offset and weights; there is no one-call (pass + finish)
-form, so every update is pass -> all-reduce -> finish.  The multi-rank branch is wired like the other drivers' and has
-been exercised at world size 1 only.
+Random intercepts per group together with the dispersion: HierNegBinReparamSVI (svi/hier_scalar.py).
+
+Limits, by design of this version: ReparamVI does not recognise a negative-binomial log-joint; MiniBatchLoader does
+not carry offset and weights; there is no one-call (pass + finish) form, so every update is pass -> all-reduce ->
+finish.  The multi-rank branch is wired like the other drivers' and has been exercised at world size 1 only.
 """
 import numpy as np
 

@@ -55,8 +55,11 @@ magnitude (y holds the same value).  The pass with it is the new entry point, an
 ``covariance="full"`` needs nothing new; ``survival`` is unchanged.  With raw device pointers ``upper`` is a raw pointer to
 the device encoding.
 
+Random intercepts per group together with the shape (a shared frailty; right censoring only): HierWeibullReparamSVI
+(svi/hier_scalar.py).
+
 Out of scope, by design of this version: left truncation (delayed entry);
-groups together with the shape; recognition by ReparamVI (it does not recognise a Weibull log-joint); MiniBatchLoader
+recognition by ReparamVI (it does not recognise a Weibull log-joint); MiniBatchLoader
 (it does not carry offset and weights).  There is no one-call (pass +
 finish) form, so every update is pass -> all-reduce -> finish.  The multi-rank branch is wired like the other drivers'
 and has been exercised at world size 1 only.

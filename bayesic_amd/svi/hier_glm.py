@@ -74,7 +74,86 @@ def check_predict_groups(groups, B):
         raise ValueError("groups must be a contiguous [%d], one id per row of X" % B)
 
 
-class HierGLMReparamSVI(ObsBatch, ReparamDriver):
+class GroupPlanBatch:
+    """The group ids of a driver's current batch and their plan: what HierGLMReparamSVI and the drivers of
+    svi/hier_scalar.py do alike.  The driver has ctx, J, B and _chunks, is an ObsBatch and a ReparamDriver, and names
+    the entry point that sizes its pass's workspace."""
+    workspace_name = "bsc_glm_group_workspace_bytes"
+
+    def _checked_groups(self, groups, B):
+        """The ids of a batch of B rows: a tensor or a host array (checked like y, uploaded as int32), or a raw device
+        pointer to B int32 (taken as it is)."""
+        import torch
+        if groups is None:
+            raise ValueError("groups is required: one int32 id in [0, %d) per row" % self.J)
+        if isinstance(groups, (int, np.integer)):
+            return int(groups)
+        g = groups if isinstance(groups, torch.Tensor) else self.ctx.to_device(np.asarray(groups), torch.int32)
+        if g.dtype != torch.int32:
+            raise TypeError("groups must be int32")
+        if g.dim() != 1 or g.shape[0] != B or (B > 1 and g.stride(0) != 1):
+            raise ValueError("groups must be a contiguous [%d], one id per row of X" % B)
+        return g
+
+    def _build_plan(self, garg, B):
+        """(plan, segment count) of B ids.  Synchronises (bsc_glm_group_plan: the ids' range is checked there) and
+        reserves the pass's workspace so that step() never allocates."""
+        import torch
+        lib = self.ctx.lib
+        n = int(lib.bsc_glm_group_plan_size(B, self.J))
+        if n < 0:
+            raise ValueError("a group plan holds at most 2^30 rows and %d groups (B = %d, J = %d)"
+                             % (MAX_GROUPS, B, self.J))
+        plan = torch.zeros(n, dtype=torch.int32, device=self.ctx.device)
+        n_seg = ctypes.c_int32(0)
+        self.ctx.call("bsc_glm_group_plan", garg, B, self.J, plan, ctypes.byref(n_seg))
+        self.ctx.reserve(int(getattr(lib, self.workspace_name)(self.ctx.handle, B, self.J)))
+        return plan, int(n_seg.value)
+
+    def build_plan(self, groups, rows):
+        """The group plan of ``rows`` ids, for ``set_batch(..., plan=)``: a loop over a fixed set of batches builds each
+        batch's plan once, outside the loop (this call synchronises and range-checks the ids), and set_batch then takes
+        it without rebuilding.  ``groups`` as in set_batch.  The pair belongs to these ids, this row count and this
+        model's n_groups: the pass does not read a plan whose header names another batch (H comes back NaN)."""
+        return self._build_plan(self._checked_groups(groups, int(rows)), int(rows))
+
+    def _set_groups(self, garg, built=None):
+        import torch
+        self.plan, self.n_segments = built if built is not None else self._build_plan(garg, self.B)
+        self.groups = garg if isinstance(garg, torch.Tensor) else None
+        self._garg = garg
+
+    def set_batch(self, X, y, rows=None, ldx=None, offset=None, weights=None, groups=None, plan=None):
+        """ReparamDriver.set_batch with the batch's group ids (required: the plan is rebuilt here, one
+        synchronisation) and its offset and weights as in GLMReparamSVI.set_batch.  ``plan``: what build_plan returned
+        for these ids; the plan is then not rebuilt (with raw device pointers the call does not synchronise)."""
+        import torch
+        if groups is None:
+            raise ValueError("set_batch needs groups=: the ids of the new rows (the group plan is rebuilt)")
+        if isinstance(X, torch.Tensor):
+            B = int(X.shape[0])
+            offset, weights = batch_obs(self.ctx, B, offset, weights)
+        elif rows is None:
+            raise ValueError("raw device pointers need `rows`")
+        else:
+            B = int(rows)
+        garg = self._checked_groups(groups, B)
+        # (a plan built here refuses bad ids before anything of the driver changes)
+        built = plan if plan is not None else self._build_plan(garg, B)
+        super().set_batch(X, y, rows=rows, ldx=ldx)
+        self._set_obs(offset, weights)
+        self._set_groups(garg, built)
+
+    def chunked(self, b):
+        """b [S, J] (host) -> the pass's float32 [ceil(S / 8)][J][8] layout, unused slots zero, flat."""
+        S, J = b.shape
+        out = np.zeros((self._chunks, J, 8), np.float32)
+        for s in range(S):
+            out[s // 8, :, s % 8] = b[s]
+        return out.reshape(-1)
+
+
+class HierGLMReparamSVI(GroupPlanBatch, ObsBatch, ReparamDriver):
     def __init__(self, X, y, groups, n_groups, link="logistic", n_total=None, n_samples=8, seed=1234, lr=1e-2,
                  prior_precision=1.0, a0=1.0, b0=1.0, offset=None, weights=None, exposure=None, ctx=None, group=None,
                  lam0=None, covariance="diag"):
@@ -103,75 +182,11 @@ class HierGLMReparamSVI(ObsBatch, ReparamDriver):
         self._Bz = torch.zeros((2, self._chunks * J * 8), dtype=torch.float32, device=self.ctx.device)
         self._set_groups(groups)
 
-    # -- the batch ----------------------------------------------------------------------------------------------
-    def _checked_groups(self, groups, B):
-        """The ids of a batch of B rows: a tensor or a host array (checked like y, uploaded as int32), or a raw device
-        pointer to B int32 (taken as it is)."""
-        import torch
-        if groups is None:
-            raise ValueError("groups is required: one int32 id in [0, %d) per row" % self.J)
-        if isinstance(groups, (int, np.integer)):
-            return int(groups)
-        g = groups if isinstance(groups, torch.Tensor) else self.ctx.to_device(np.asarray(groups), torch.int32)
-        if g.dtype != torch.int32:
-            raise TypeError("groups must be int32")
-        if g.dim() != 1 or g.shape[0] != B or (B > 1 and g.stride(0) != 1):
-            raise ValueError("groups must be a contiguous [%d], one id per row of X" % B)
-        return g
-
-    def _build_plan(self, garg, B):
-        """(plan, segment count) of B ids.  Synchronises (bsc_glm_group_plan: the ids' range is checked there) and
-        reserves the pass's workspace so that step() never allocates."""
-        import torch
-        lib = self.ctx.lib
-        n = int(lib.bsc_glm_group_plan_size(B, self.J))
-        if n < 0:
-            raise ValueError("a group plan holds at most 2^30 rows and %d groups (B = %d, J = %d)"
-                             % (MAX_GROUPS, B, self.J))
-        plan = torch.zeros(n, dtype=torch.int32, device=self.ctx.device)
-        n_seg = ctypes.c_int32(0)
-        self.ctx.call("bsc_glm_group_plan", garg, B, self.J, plan, ctypes.byref(n_seg))
-        self.ctx.reserve(int(lib.bsc_glm_group_workspace_bytes(self.ctx.handle, B, self.J)))
-        return plan, int(n_seg.value)
-
-    def _set_groups(self, garg, built=None):
-        import torch
-        self.plan, self.n_segments = built if built is not None else self._build_plan(garg, self.B)
-        self.groups = garg if isinstance(garg, torch.Tensor) else None
-        self._garg = garg
-
-    def set_batch(self, X, y, rows=None, ldx=None, offset=None, weights=None, groups=None):
-        """ReparamDriver.set_batch with the batch's group ids (required: the plan is rebuilt here, one
-        synchronisation) and its offset and weights as in GLMReparamSVI.set_batch."""
-        import torch
-        if groups is None:
-            raise ValueError("set_batch needs groups=: the ids of the new rows (the group plan is rebuilt)")
-        if isinstance(X, torch.Tensor):
-            B = int(X.shape[0])
-            offset, weights = batch_obs(self.ctx, B, offset, weights)
-        elif rows is None:
-            raise ValueError("raw device pointers need `rows`")
-        else:
-            B = int(rows)
-        garg = self._checked_groups(groups, B)
-        built = self._build_plan(garg, B)       # refuses bad ids before anything of the driver changes
-        super().set_batch(X, y, rows=rows, ldx=ldx)
-        self._set_obs(offset, weights)
-        self._set_groups(garg, built)
-
     @property
     def Bz(self):
         return self._Bz[self.cur]
 
     # -- phases -------------------------------------------------------------------------------------------------
-    def chunked(self, b):
-        """b [S, J] (host) -> the pass's float32 [ceil(S / 8)][J][8] layout, unused slots zero, flat."""
-        S, J = b.shape
-        out = np.zeros((self._chunks, J, 8), np.float32)
-        for s in range(S):
-            out[s // 8, :, s % 8] = b[s]
-        return out.reshape(-1)
-
     def sample(self, step):
         """The first draw (first_draw) of w and b, rounded to float32 as the finish rounds.  zeta is drawn where it is
         used."""

@@ -26,6 +26,9 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
                                       the signed response of svi/glm_weibull.py, negative = right-censored, and the
                                       lpd of such a row is its log predictive survival probability; with ``upper``,
                                       bsc_weibull_predict_pass_interval and the log probability of the interval)
+    HierNegBin/Gamma/WeibullReparamSVI  eps [S, D + J + 3]: the transform below over z = [w | b | zeta | tau], b_new
+                                      from the last column; returned as (W, Bt, logtau float32 [S])
+                                      (bsc_scalar_predict_pass_groups)
     HierGLMReparamSVI                 eps [S, D + J + 2]:  z = m + e^rho eps[:, :D + J + 1] over z = [w | b | zeta], and
                                       b_new = e^{-zeta / 2} eps[:, D + J + 1], the intercept of a group that was not
                                       seen in training; returned as (W [S, D], Bt [J + 1, ldb]) with Bt[j, s] = b_s[j],
@@ -60,6 +63,8 @@ FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
 # families with an entry point of their own: a per-draw log-scalar behind the weights, the offset may be None
 SCALAR_PASSES = {"negbin": "bsc_nb_predict_pass", "gamma": "bsc_gamma_predict_pass",
                  "weibull": "bsc_weibull_predict_pass"}
+# include/bayesic_hip.h: BSC_SCALAR_*, the same families with groups (svi/hier_scalar.py)
+SCALAR_FAMILIES = {"negbin": 0, "gamma": 1, "weibull": 2}
 PREDICT_STREAM = 2     # Philox stream of the predictive draws
 MAX_SAMPLES = 64       # draws per bsc_predict_pass call
 
@@ -116,21 +121,25 @@ def posterior_draws(model, n_samples=64, seed=None):
     SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d) and Z [S, D + K - 1] = [w | theta] for
     OrdinalReparamSVI; for NegBinReparamSVI the second
     entry is logphi float32 [S], for GammaReparamSVI and WeibullReparamSVI logshape float32 [S]; for HierGLMReparamSVI it is the intercept table Bt float32 [J + 1, ldb] (module
-    docstring)."""
+    docstring), and for the drivers of svi/hier_scalar.py the triple (W, Bt, logtau float32 [S])."""
     S = _check_samples(n_samples)
     family = family_of(model)
     ctx, D = model.ctx, model.D
     if grouped(model):
         J = model.J
-        P = D + J + 1
+        scalar = family in SCALAR_FAMILIES       # svi/hier_scalar.py: tau sits behind zeta
+        P = D + J + (2 if scalar else 1)
         seed = model.seed if seed is None else int(seed)
         eps_d = torch.zeros((S, P + 1), dtype=torch.float64, device=ctx.device)
         ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P + 1, eps_d)
         eps = eps_d.cpu().numpy()
         z = first_draw(model.lam.cpu().numpy(), eps[:, :P], P, "diag")
-        b_new = np.exp(-0.5 * z[:, P - 1]) * eps[:, P]
+        b_new = np.exp(-0.5 * z[:, D + J]) * eps[:, P]
         W = ctx.to_device(np.ascontiguousarray(z[:, :D], np.float32))
-        return W, ctx.to_device(intercept_table(z[:, D:D + J].astype(np.float32), b_new.astype(np.float32)))
+        Bt = ctx.to_device(intercept_table(z[:, D:D + J].astype(np.float32), b_new.astype(np.float32)))
+        if scalar:
+            return W, Bt, ctx.to_device(np.ascontiguousarray(z[:, P - 1], np.float32))
+        return W, Bt
     if family == "softmax":
         D = model.n_classes * model.D          # the guide's width; the transforms below are the GLM ones
     elif family == "ordinal":
@@ -206,6 +215,8 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     float32 [B] next to the signed y -- the driver's own predict() takes the plain ones and packs them; ``lpd`` of an
     interval or left-censored row is the log of its predictive probability (bsc_weibull_predict_pass_interval)."""
     family = family_of(model)
+    if upper is not None and grouped(model):
+        raise NotImplementedError("predict: upper= together with groups is not built (svi/hier_scalar.py)")
     if upper is not None and family != "weibull":
         raise ValueError("predict: upper= (interval and left censoring) belongs to the Weibull model, not %s" % family)
     if family == "softmax":      # its own pass and outputs (prob [B, K] instead of mean and var)
@@ -222,7 +233,14 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     offset, weights = _obs(model, family, int(X.shape[0]), offset, exposure, weights)
     if draws is None:
         draws = posterior_draws(model, n_samples, seed)
-    W, logvar = draws
+    logtau = None
+    if groups is not None and family in SCALAR_FAMILIES:     # svi/hier_scalar.py: (W, Bt, logtau [S])
+        if len(draws) != 3:
+            raise ValueError("draws of a random-intercept model with a learned scalar are (W [S, D], Bt float32 "
+                             "[J + 1, ldb], logtau float32 [S]) as posterior_draws returns them")
+        W, logvar, logtau = draws
+    else:
+        W, logvar = draws
     S = _check_samples(W.shape[0])
     X, y = _data(model, X, y)
     ctx = model.ctx
@@ -245,8 +263,13 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
         if Bt.dim() != 2 or Bt.shape[0] != model.J + 1 or Bt.stride(1) != 1 or Bt.dtype != torch.float32:
             raise ValueError("draws of the random-intercept model are (W [S, D], Bt float32 [J + 1, ldb]) as "
                              "posterior_draws returns them")
-        ctx.call("bsc_predict_pass_groups", FAMILIES[family], X, ldx, y, offset, groups, B, model.D, model.J, W, Bt,
-                 int(Bt.stride(0)), S, out["mean"], out["var"], out.get("lpd"), out.get("lpd_sum"))
+        if logtau is not None:
+            ctx.call("bsc_scalar_predict_pass_groups", SCALAR_FAMILIES[family], X, ldx, y, offset, groups, B, model.D,
+                     model.J, W, Bt, int(Bt.stride(0)), logtau, S, out["mean"], out["var"], out.get("lpd"),
+                     out.get("lpd_sum"))
+        else:
+            ctx.call("bsc_predict_pass_groups", FAMILIES[family], X, ldx, y, offset, groups, B, model.D, model.J, W,
+                     Bt, int(Bt.stride(0)), S, out["mean"], out["var"], out.get("lpd"), out.get("lpd_sum"))
     elif upper is not None:        # the Weibull model with interval and left censoring; the offset may be None
         ctx.call("bsc_weibull_predict_pass_interval", X, ldx, y, upper, offset, B, model.D, W, logvar, S, out["mean"],
                  out["var"], out.get("lpd"), out.get("lpd_sum"))

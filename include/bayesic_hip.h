@@ -856,6 +856,61 @@ int bsc_predict_pass_groups(bsc_ctx* ctx, int32_t family, const float* X, int64_
  * bsc_blr_data_pass_partial are dropped). */
 int bsc_group_ids_check(bsc_ctx* ctx, const int32_t* groups, int64_t B, int32_t J, int32_t allow_new);
 
+/* ---- random intercepts for the families with a learned scalar (csrc/bsc_glm_scalar_group.hip,
+ *      csrc/bsc_predict_scalar_group.hip; ABSENT in the reference) ------------------------------------------------------
+ *
+ * family F = BSC_SCALAR_NEGBIN (bsc_glm_nb_data_pass's density), BSC_SCALAR_GAMMA (bsc_glm_gamma_data_pass's) or
+ * BSC_SCALAR_WEIBULL (bsc_glm_weibull_data_pass's, right censoring in the sign of y), with its scalar e^tau:
+ *      l[n,s] = sum_d X[n,d] W[s,d] + Bz[g[n], s] + o[n]             y[n] ~ F(l[n,s], e^{tau_s})
+ *      w ~ N(0, I / prior_precision),  b_j | zeta ~ N(0, e^{-zeta}),  e^zeta ~ Gamma(group_a0, group_b0),
+ *      e^tau ~ Gamma(a0, b0)
+ * The latent is z = [w (D) | b (J) | zeta | tau], P = D + J + 2, the guide mean-field: lam = [m (P) | rho (P)].  The
+ * intercept enters through l alone: ell, the residual r = d ell / d l and T are the family's own forms at that l.
+ * From the data one update needs stats = [ell (S) | G (S*D) | H (S*J) | T (S)], H[s,j] = sum_{n : g[n] = j} r[n,s],
+ * T[s] = d ell[s] / d tau_s.
+ *
+ * The pass.  The plan is bsc_glm_group_plan's, Bz [ceil(S / 8)][J][8] and H bsc_glm_data_pass_groups', logtau [S] and T
+ * the family's pass's; every order of summation depends on the plan alone, no float atomics.  With Bz = 0, ell, G and T
+ * are bit-identical to the family's own pass on the same inputs.  The envelope and the refusals are
+ * bsc_glm_data_pass_groups' and the family's pass's, and a family outside the three codes is refused.  The 16-row MFMA
+ * kernel (D == 256) is taken when y, g and the set ones of offset and weight are 16-byte aligned, else the 8-row
+ * kernel.  The workspace (bsc_glm_scalar_group_workspace_bytes: the slab with T's eight floats per workgroup, residuals,
+ * segment sums) grows on demand -- synchronously; bsc_ctx_reserve it first. */
+#define BSC_SCALAR_NEGBIN 0
+#define BSC_SCALAR_GAMMA 1
+#define BSC_SCALAR_WEIBULL 2
+int64_t bsc_glm_scalar_group_workspace_bytes(bsc_ctx* ctx, int64_t B, int32_t J);
+int bsc_glm_scalar_data_pass_groups(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, const float* y,
+                                    const float* offset, const float* weight, const int32_t* g, const int32_t* plan,
+                                    int64_t B, int32_t D, int32_t J, const float* W, const float* Bz,
+                                    const float* logtau, int32_t S, double* ell, double* G, double* H, double* T);
+
+/* The finish of all three families (it sees the statistics, never the likelihood), two launches.  eps in
+ * bsc_blr_noise's [S, (P-1)+1] layout: columns 0 .. P-2 (w, b, zeta) from stream 0, column P-1 (tau) from stream 1.
+ * W, Bz and logtau are the float32 draws the pass read; zeta_s = m_zeta + e^{rho_zeta} eps_s,P-2 in float64:
+ *     log p(z) = c0 - prec/2 |w|^2 + J/2 zeta - e^zeta/2 |b|^2 + group_a0 zeta - group_b0 e^zeta + a0 tau - b0 e^tau
+ *     g_w    = scale G_s - prior_precision w_s            g_b   = scale H_s - e^{zeta_s} b_s
+ *     g_zeta = J/2 + group_a0 - e^{zeta_s} (group_b0 + 1/2 sum_j b_sj^2)       g_tau = scale T_s + a0 - b0 e^{tau_s}
+ * ELBO, d/d m, d/d rho and Adam as bsc_glm_hier_update.  When the *_next buffers are set (all or none), W_next,
+ * Bz_next (chunked, unused slots zeroed) and logtau_next [S] are made from eps_next; eps_next_ready = 0 draws the noise
+ * of next_step into eps_next first (bsc_blr_noise(P - 1)).  Requires 1 <= S <= 64, 1 <= J <= BSC_GLM_GROUP_MAX_J,
+ * t >= 1 and prior_precision, a0, b0, group_a0, group_b0, scale > 0.  Fixed-order sums, no atomics. */
+int bsc_glm_scalar_hier_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                               double* m2, const double* eps, const float* W, const float* Bz, const float* logtau,
+                               int32_t D, int32_t J, int32_t S, double scale, double prior_precision, double a0,
+                               double b0, double group_a0, double group_b0, int64_t t, double lr, double beta1,
+                               double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
+                               int32_t eps_next_ready, float* W_next, float* Bz_next, float* logtau_next, double* elbo,
+                               double* grad);
+
+/* The predictive: bsc_predict_pass_groups' table Bt [J + 1][ldb] (row J for id -1) and envelope, the family's
+ * bsc_nb_predict_pass / bsc_gamma_predict_pass / bsc_weibull_predict_pass link and per-draw scalar logtau [S] (not
+ * NULL, 4-byte aligned).  With Bt = 0 every output is bit-identical to the family's own predictive pass. */
+int bsc_scalar_predict_pass_groups(bsc_ctx* ctx, int32_t family, const float* X, int64_t ldx, const float* y,
+                                   const float* offset, const int32_t* groups, int64_t B, int32_t D, int32_t J,
+                                   const float* W, const float* Bt, int32_t ldb, const float* logtau, int32_t S,
+                                   float* mean, float* var, float* lpd, double* lpd_sum);
+
 /* ---- multi-class softmax regression (csrc/bsc_softmax.hip; ABSENT in the reference) ------------------------
  *
  * Labels y[n] in {0 .. K-1} (int32), weights W[S,K,D] (S draws of a K x D matrix, flattened parameter p = k D + d)
