@@ -39,6 +39,9 @@
 //                 csrc/bsc_glm_weibull.hip (LINK = GLM_WEIBULL) runs it with the Weibull shape k_s = exp(tau_s): only
 //                 tau_s and k_s are kept (the density has no per-draw constant), and the censoring flag of a row is
 //                 the sign of its y, so the tiles carry nothing new.
+//                 csrc/bsc_glm_beta.hip (LINK = GLM_BETA) runs it with the Beta precision phi_s = exp(tau_s): the four
+//                 registers are the negative binomial's (tau_s, phi_s, lnGamma(phi_s), psi(phi_s)); lnGamma and psi at
+//                 m phi and (1 - m) phi are float32, per (row, draw) (csrc/bsc_special_f32.h, bsc_lgamma_psi_f32).
 //   ITV = true    csrc/bsc_glm_weibull_interval.hip (always with DSP and LINK = GLM_WEIBULL): interval and left
 //                 censoring.  One more per-row vector, `upper` [B] float32, rides in the tiles next to y and is loaded
 //                 the way y is (rows past B read 0); glm_link says how it is read.  Everything of it is behind
@@ -58,12 +61,14 @@ constexpr int NB_SLAB_STRIDE = REG_SLAB_G + 2 * SG;   // DSP: ell at [SLAB_G + s
 constexpr int GLM_NEGBIN = 2;                 // the third link; internal: the BSC_GLM_* entry points refuse it
 constexpr int GLM_GAMMA = 3;                  // the fourth, internal as well: csrc/bsc_glm_gamma.hip
 constexpr int GLM_WEIBULL = 4;                // the fifth, internal as well: csrc/bsc_glm_weibull.hip
+constexpr int GLM_BETA = 5;                   // the sixth, internal as well: csrc/bsc_glm_beta.hip
 
-// DSP: what a lane keeps of its draw's dispersion (GLM_GAMMA: of its draw's shape alpha_s; GLM_WEIBULL: of k_s).
+// DSP: what a lane keeps of its draw's dispersion (GLM_GAMMA: of its draw's shape alpha_s; GLM_WEIBULL: of k_s;
+// GLM_BETA: of its draw's precision phi_s).
 struct GlmDisp {
     float tau, phi;     // log phi_s as the pass read it, exp(tau)
-    float lg, psi;      // lnGamma(phi), psi(phi); GLM_GAMMA: c_a = alpha log alpha - lnGamma(alpha),
-                        // c_1 = log alpha + 1 - psi(alpha); GLM_WEIBULL: not used (0)
+    float lg, psi;      // lnGamma(phi), psi(phi) (GLM_NEGBIN and GLM_BETA); GLM_GAMMA: c_a = alpha log alpha -
+                        // lnGamma(alpha), c_1 = log alpha + 1 - psi(alpha); GLM_WEIBULL: not used (0)
 };
 
 // Draw s of this launch's chunk (s >= S: a dead slot, phi = 1).  The special values in float64, once per launch.
@@ -78,7 +83,7 @@ __device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi,
         const double a = (double)d.phi, la = log(a);
         d.lg = (float)(a * la - bsc_lgamma_f64(a));
         d.psi = (float)(la + 1.0 - bsc_digamma_f64(a));
-    } else {
+    } else {                       // GLM_NEGBIN and GLM_BETA: lnGamma(phi) and psi(phi) themselves
         d.lg = (float)bsc_lgamma_f64((double)d.phi);
         d.psi = (float)bsc_digamma_f64((double)d.phi);
     }
@@ -112,6 +117,18 @@ __device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi,
 // maximum).  One log and one exp per (row, draw) at full float32 accuracy; z is rounded before the exponential, which
 // costs |z| eps of e^z (the tests' bounds count (1 + |z|) e^z per row).  y = 0 or a non-finite y on a kept row is the
 // caller's to keep out.
+// GLM_BETA (always OBS; dp and T set): 0 < y < 1, phi = e^tau, ly = log y, l1y = log1p(-y), m = sigmoid(l) and
+// 1 - m = sigmoid(-l) EACH from the stable logistic forms e / (1 + e), 1 / (1 + e) with e = exp(-|l|) (never 1 - m by
+// subtraction), a = m phi, b = (1 - m) phi, and dp's lnGamma(phi), psi(phi):
+//     ell  += v [ lnGamma(phi) - lnGamma(a) - lnGamma(b) + (a - 1) ly + (b - 1) l1y ]    (the full density, nothing left out)
+//     resid = v phi m (1 - m) [ (ly - l1y) - psi(a) + psi(b) ]                                (= d / d l)
+//     T    += v phi [ psi(phi) + m (ly - psi(a)) + (1 - m)(l1y - psi(b)) ]                     (= d / d tau)
+// lnGamma and psi of a and of b from csrc/bsc_special_f32.h's bsc_lgamma_psi_f32, one evaluation after the other: four
+// logs, four reciprocals and two shifted products per (row, draw) on top of the logistic link's exp.  l1y through
+// log(w) (-y) / (w - 1), w = 1 - y, which undoes the rounding of w (y = 1e-6: log(1 - y) alone is 6 % off).  NOT
+// clamped: finite while a, b and their reciprocals are normal float32 values -- |l| <= 80 at tau in [-2, 5], where
+// psi(a) ~ -1 / a reaches 4e35 and is multiplied by m before anything else.  y = 0, y = 1 or a non-finite y on a kept
+// row is the caller's to keep out.
 // GLM_WEIBULL with ITV (csrc/bsc_glm_weibull_interval.hip): `uv` is the row's entry of the vector `upper` -- 0: the row is
 // what y says, as above; uv > 0 (with y < 0): interval-censored on (a, b] = (-y, uv]; uv < 0: left-censored at b = -uv,
 // the magnitude of y not read.  With z = k (log a - l), E = e^z, d = log b - log a and Delta = E expm1(k d) = E_b - E_a
@@ -200,6 +217,30 @@ __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, floa
         ell = fmaf(vq, fmaf(dp->phi, d, dp->lg) - ly, ell);
         *T = fmaf(vq, dp->phi * (dp->psi + d), *T);
         return vq * (dp->phi * (q - 1.0f));
+    }
+    if constexpr (LINK == GLM_BETA) {
+        // The selects sit on the INPUTS, for the reason given above: a dropped row is evaluated at y = 1/2, l = 0 -- a = b
+        // = phi / 2, every term finite whatever y and l held -- and multiplied by an exact 0.  Each select is flat.
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const float yq = keep ? yv : 0.5f;
+        const float lq = keep ? l : 0.0f;
+        const float e = expf(-fabsf(lq));
+        const float r = __builtin_amdgcn_rcpf(1.0f + e);
+        const float er = e * r;
+        const bool pos = lq >= 0.0f;
+        const float m = pos ? r : er, m1 = pos ? er : r;         // sigmoid(l) and sigmoid(-l), neither by subtraction
+        const float ly = logf(yq);
+        const float w = 1.0f - yq;
+        const bool one = w == 1.0f;                              // (w - 1 is exact; w == 1: -y itself)
+        const float l1y = fmaf(logf(w), yq * __builtin_amdgcn_rcpf(one ? 1.0f : 1.0f - w), one ? -yq : 0.0f);
+        const float a = m * dp->phi, b = m1 * dp->phi;
+        float lga, psa, lgb, psb;
+        bsc_lgamma_psi_f32(a, lga, psa);
+        bsc_lgamma_psi_f32(b, lgb, psb);
+        ell = fmaf(vq, ((dp->lg - lga) - lgb) + fmaf(a - 1.0f, ly, (b - 1.0f) * l1y), ell);
+        *T = fmaf(vq, dp->phi * (dp->psi + fmaf(m, ly - psa, m1 * (l1y - psb))), *T);
+        return vq * ((dp->phi * (er * r)) * (((ly - l1y) - psa) + psb));
     }
     if constexpr (LINK == GLM_WEIBULL) {
         // The selects sit on the INPUTS, for the reason given above: a dropped row is evaluated at t = 1, l = 0,
@@ -423,7 +464,7 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
                                               int n_iter, const GlmGroupArgs* ga = nullptr,
                                               const float* logphi = nullptr, const float* upper = nullptr) {
-    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
+    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL || LINK == GLM_BETA)),
                   "the dispersion (the shape) rides with OBS and its own link");
     static_assert(!ITV || (DSP && !GRP && LINK == GLM_WEIBULL),
                   "the upper end rides with the Weibull shape, without groups");
@@ -581,7 +622,7 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
                                                    int n_iter, const GlmGroupArgs* ga = nullptr,
                                                    const float* logphi = nullptr, const float* upper = nullptr) {
-    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL)),
+    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL || LINK == GLM_BETA)),
                   "the dispersion (the shape) rides with OBS and its own link");
     static_assert(!ITV || (DSP && !GRP && LINK == GLM_WEIBULL),
                   "the upper end rides with the Weibull shape, without groups");

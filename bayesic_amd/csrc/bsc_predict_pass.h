@@ -7,7 +7,7 @@
 // below).  With GRP off nothing of it is compiled: the shipped instantiations keep their code.  The host side at the end
 // is the envelope of the entry points (predict_check_batch, predict_setup, predict_launch_chunks), shared by
 // csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip,
-// csrc/bsc_glm_weibull_interval.hip, csrc/bsc_glm_ordinal.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
+// csrc/bsc_glm_weibull_interval.hip, csrc/bsc_glm_beta.hip, csrc/bsc_glm_ordinal.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
 #include "bsc_regress.h"
@@ -31,6 +31,10 @@ constexpr int PREDICT_WEIBULL = 5;
 // int32 labels; the outputs are prob [B, K] (PredictOrdinal below) and lpd, no mean and no var.
 constexpr int PREDICT_ORDINAL = 6;
 constexpr int P_ORD_K = 8;                     // classes at most
+// The eighth, internal as well: csrc/bsc_glm_beta.hip's scalar_predict_kernel (bsc_beta_predict_pass), the Beta
+// likelihood in its mean / precision form with a per-draw precision; `logvar` carries tau_s = log phi_s.  Always with
+// OFFS, the offset may be null.
+constexpr int PREDICT_BETA = 7;
 
 constexpr int P_BLOCK = 512;
 constexpr int P_WAVES = P_BLOCK / BSC_WAVE;
@@ -51,8 +55,8 @@ struct PredictArgs {
     int64_t B;
     const float* W;
     const float* logvar;     // Gaussian: log s2 per draw; PREDICT_NEGBIN: log phi per draw; PREDICT_GAMMA: log alpha;
-                             // PREDICT_WEIBULL: log k
-    float* mean;             // outputs, each may be null
+                             // PREDICT_WEIBULL: log k; PREDICT_BETA: log phi
+    float* mean;            // outputs, each may be null
     float* var;
     float* lpd;
     double* partial;         // [gridDim.x] block sums of lpd
@@ -148,6 +152,11 @@ __device__ __forceinline__ void load_intercepts(p_f32x4 (&bt)[NC], const Predict
 // the posterior-predictive survival probability.  y = 0 is the caller's to keep out.
 // FLOAT32 ENVELOPE OF THE MOMENTS: Gamma(1 + 2/k) overflows float32 near k = 0.06 (tau = -2.8); accuracy envelope tau in
 // [-2, 4].  g2 is a difference of float64 values, 5e-4 at tau = 4: no digit of the float32 result is lost to it.
+// PREDICT_BETA: p4 = (tau, phi = exp(tau), 1 / (1 + phi)) and lgp = lnGamma(phi), both made once per launch in float64.
+// mu = m = sigmoid(l), v = m (1 - m) / (1 + phi) with m (1 - m) = e / (1 + e)^2; log p = lnGamma(phi) - lnGamma(a) -
+// lnGamma(b) + (a - 1) log y + (b - 1) log1p(-y), a = m phi, b = (1 - m) phi, the full density in csrc/bsc_glm_pass.h's
+// forms (m and 1 - m each from the stable logistic form, bsc_lgamma_psi_f32 whose psi half folds away); 0 < y < 1 is
+// the caller's to see to.
 template <int FAM>
 __device__ __forceinline__ void predict_link(float l, float yv, float lv, float ev, float iv, float& mu, float& v,
                                              float& lp, float lgp = 0.0f) {
@@ -178,6 +187,25 @@ __device__ __forceinline__ void predict_link(float l, float yv, float lv, float 
         const float z = ev * (ly - l);
         const float ez = expf(z);
         lp = yv > 0.0f ? ((lv + z) - ly) - ez : -ez;
+        return;
+    }
+    if constexpr (FAM == PREDICT_BETA) {
+        const float e = expf(-fabsf(l));
+        const float r = __builtin_amdgcn_rcpf(1.0f + e);
+        const float er = e * r;
+        const bool pos = l >= 0.0f;
+        const float m = pos ? r : er, m1 = pos ? er : r;
+        mu = m;
+        v = er * r * iv;
+        const float ly = logf(yv);
+        const float w = 1.0f - yv;
+        const bool one = w == 1.0f;
+        const float l1y = fmaf(logf(w), yv * __builtin_amdgcn_rcpf(one ? 1.0f : 1.0f - w), one ? -yv : 0.0f);
+        const float a = m * ev, b = m1 * ev;
+        float lga, psa, lgb, psb;                               // (psi is not used and folds away)
+        bsc_lgamma_psi_f32(a, lga, psa);
+        bsc_lgamma_psi_f32(b, lgb, psb);
+        lp = ((lgp - lga) - lgb) + fmaf(a - 1.0f, ly, (b - 1.0f) * l1y);
         return;
     }
     if (FAM == BSC_PREDICT_GAUSSIAN) {
@@ -296,7 +324,8 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     static_assert(!ORD || (OFFS && !GRP && !ITV), "the ordinal family takes an offset and nothing else");
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
-    constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA || FAM == PREDICT_WEIBULL;   // a fourth value
+    constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA || FAM == PREDICT_WEIBULL ||
+                          FAM == PREDICT_BETA;                                                        // a fourth value
     constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || OWN4;        // a scalar rides with every draw
     constexpr int GP_SLOTS = OWN4 ? 4 : 3;                                 // ... and lnGamma(phi), or c_a
     constexpr int ORD_FLOATS = ORD ? 2 * P_ORD_K * P_MAX_S : 0;           // the cutpoints and log(-expm1(-g)), [draw][class]
@@ -332,6 +361,11 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
             const double g1 = exp(bsc_lgamma_f64(1.0 + ik));
             gp[2 * P_MAX_S + tid] = (float)g1;
             gp[3 * P_MAX_S + tid] = (float)(exp(bsc_lgamma_f64(1.0 + 2.0 * ik)) - g1 * g1);
+        }
+        if constexpr (FAM == PREDICT_BETA) {      // 1 / (1 + phi) in the exp(-logvar) slot, the variance factor
+            const double ph = (double)expf(lv);
+            gp[2 * P_MAX_S + tid] = (float)(1.0 / (1.0 + ph));
+            gp[3 * P_MAX_S + tid] = (float)bsc_lgamma_f64(ph);
         }
     }
     __syncthreads();

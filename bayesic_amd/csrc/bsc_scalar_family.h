@@ -1,6 +1,7 @@
 // The kernels and the host envelopes of the regression families with ONE learned log-scalar behind the weights,
 // z = [w (D) | tau]: the negative binomial's dispersion (csrc/bsc_glm_nb.hip), the Gamma shape (csrc/bsc_glm_gamma.hip),
-// the Weibull shape (csrc/bsc_glm_weibull.hip) and the Weibull route with upper ends (csrc/bsc_glm_weibull_interval.hip).
+// the Weibull shape (csrc/bsc_glm_weibull.hip), the Weibull route with upper ends (csrc/bsc_glm_weibull_interval.hip)
+// and the Beta precision (csrc/bsc_glm_beta.hip).
 // A family is two constants -- its LINK of csrc/bsc_glm_pass.h and its FAMILY of csrc/bsc_predict_pass.h -- and the
 // bodies are those headers' and csrc/bsc_meanfield.h's; what is here is the shell the four units used to repeat:
 //

@@ -15,7 +15,8 @@
 // The route is chosen by selects on the INPUTS of the product; its two results are combined with factors 0 / 1 and
 // +1 / -1, all finite, so that the compiler has no expensive operand to branch around.
 // Callers state the range of phi over which the differences are good enough (include/bayesic_hip.h,
-// bsc_glm_nb_data_pass).  Device only, header-only, internal linkage.
+// bsc_glm_nb_data_pass).  bsc_lgamma_psi_f32 below is the pair itself, not a difference, for any positive argument (the
+// Beta link).  Device only, header-only, internal linkage.
 #pragma once
 
 namespace {
@@ -44,6 +45,35 @@ __device__ __forceinline__ void bsc_dlgamma_dpsi_f32(float y, float phi, float l
     const float on = count ? 0.0f : 1.0f, sgn = count ? 1.0f : -1.0f;
     dlg = fmaf(on, stirling - lg0, sgn * lP);
     dps = fmaf(on, asym - ps0, sgn * q);
+}
+
+// lnGamma(x) and psi(x) together for ANY float32 x > 0 (the Beta link, csrc/bsc_glm_beta.hip, whose two arguments
+// m phi and (1 - m) phi change with every (row, draw) and run towards 0 as the logit grows): the "otherwise" route above
+// without its subtraction.  n = the steps that shift x up to x + n >= 8 (none for x >= 8), ONE product P = prod_{i<n}
+// (x + i) of at most eight factors carried with P', three asymptotic terms at x + n:
+//     lnGamma = Stirling(x + n) - log P,     psi = asymptotic(x + n) - P' / P
+// Straight-line, the selects on the inputs of the product; two logs and two reciprocals.  Absolute error: a few ulps of
+// the largest term formed -- the shifted Stirling term (~10.6 at 8, (x - 1/2) log x above) or |log x| and 1 / x below 1,
+// where lnGamma ~ -log x and psi ~ -1 / x carry their own relative rounding and no more.  Finite while P and 1 / P are:
+// x > 1e-37 (P ~ 5040 x, P' / P ~ 1 / x).  The psi half folds away where it is not used.
+__device__ __forceinline__ void bsc_lgamma_psi_f32(float x, float& lg, float& ps) {
+    const float n = 8.0f - x;                      // factors x + i for i < n
+    float P = 1.0f, dP = 0.0f, zz = x;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const bool take = (float)i < n;
+        const float f = x + (float)i;
+        dP = take ? fmaf(dP, f, P) : dP;
+        P = take ? P * f : P;
+        zz = take ? f + 1.0f : zz;                 // the shifted argument
+    }
+    const float lz = logf(zz);
+    const float inv = __builtin_amdgcn_rcpf(zz), inv2 = inv * inv;
+    const float stirling = fmaf(zz - 0.5f, lz, -zz) + 0.91893853320467274f +
+                           inv * (1.0f / 12.0f - inv2 * (1.0f / 360.0f - inv2 * (1.0f / 1260.0f)));
+    const float asym = lz - 0.5f * inv - inv2 * (1.0f / 12.0f - inv2 * (1.0f / 120.0f - inv2 * (1.0f / 252.0f)));
+    lg = stirling - logf(P);
+    ps = fmaf(-dP, __builtin_amdgcn_rcpf(P), asym);
 }
 
 // Interval censoring (csrc/bsc_glm_pass.h's glm_link and csrc/bsc_predict_pass.h's predict_link_weibull_itv, ONE value for

@@ -1,6 +1,7 @@
 """Host-side drivers of the SVI inner loop (one class per BASELINE config)."""
 
 from .glm import GLMReparamSVI  # noqa: E402,F401
+from .glm_beta import BetaReparamSVI  # noqa: E402,F401
 from .glm_gamma import GammaReparamSVI  # noqa: E402,F401
 from .glm_nb import NegBinReparamSVI  # noqa: E402,F401
 from .glm_ordinal import OrdinalReparamSVI  # noqa: E402,F401
@@ -11,6 +12,6 @@ from .softmax import SoftmaxReparamSVI  # noqa: E402,F401
 from . import predict  # noqa: E402,F401  (the module: predict.predict(model, X, ...))
 from .predict import heldout_lpd, posterior_draws  # noqa: E402,F401
 
-__all__ = ["GLMReparamSVI", "GammaReparamSVI", "HierGLMReparamSVI", "HierGammaReparamSVI", "HierNegBinReparamSVI",
-           "HierWeibullReparamSVI", "NegBinReparamSVI", "OrdinalReparamSVI", "SoftmaxReparamSVI",
+__all__ = ["BetaReparamSVI", "GLMReparamSVI", "GammaReparamSVI", "HierGLMReparamSVI", "HierGammaReparamSVI",
+           "HierNegBinReparamSVI", "HierWeibullReparamSVI", "NegBinReparamSVI", "OrdinalReparamSVI", "SoftmaxReparamSVI",
            "WeibullReparamSVI", "predict", "posterior_draws", "heldout_lpd"]

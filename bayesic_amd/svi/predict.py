@@ -26,6 +26,8 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
                                       the signed response of svi/glm_weibull.py, negative = right-censored, and the
                                       lpd of such a row is its log predictive survival probability; with ``upper``,
                                       bsc_weibull_predict_pass_interval and the log probability of the interval)
+    BetaReparamSVI                    eps [S, D + 1]:  the same transform, tau = log phi, the precision
+                                      (bsc_beta_predict_pass; the link is a logit: offset allowed, exposure refused)
     HierNegBin/Gamma/WeibullReparamSVI  eps [S, D + J + 3]: the transform below over z = [w | b | zeta | tau], b_new
                                       from the last column; returned as (W, Bt, logtau float32 [S])
                                       (bsc_scalar_predict_pass_groups)
@@ -41,6 +43,7 @@ of the negative binomial, or the log-shape of the Gamma model, and travels in th
 
 Offsets and weights (logistic, Poisson, negative-binomial, Gamma and Weibull models): ``offset`` (or, with a log link, ``exposure`` = e^offset) is added to the
 linear predictor in the pass (bsc_predict_pass_offset), so a Poisson ``mean`` is the expected count at that exposure.
+The Beta model takes ``offset`` and ``weights`` the same way and, its link being a logit, no ``exposure``.
 A model fitted with an offset refuses to predict without one.  ``weights`` leave every per-row output alone and make
 ``lpd_sum`` the weighted sum_n v_n lpd_n (float64, on the device, from the lpd vector).
 
@@ -65,6 +68,9 @@ SCALAR_PASSES = {"negbin": "bsc_nb_predict_pass", "gamma": "bsc_gamma_predict_pa
                  "weibull": "bsc_weibull_predict_pass"}
 # include/bayesic_hip.h: BSC_SCALAR_*, the same families with groups (svi/hier_scalar.py)
 SCALAR_FAMILIES = {"negbin": 0, "gamma": 1, "weibull": 2}
+# the same kind of entry point behind a LOGIT link (the logistic model's rules: offset allowed, exposure refused); no
+# groups
+LOGIT_SCALAR_PASSES = {"beta": "bsc_beta_predict_pass"}
 PREDICT_STREAM = 2     # Philox stream of the predictive draws
 MAX_SAMPLES = 64       # draws per bsc_predict_pass call
 
@@ -73,8 +79,8 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 
 def family_of(model):
     """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI, "gamma" for GammaReparamSVI,
-    "weibull" for WeibullReparamSVI, "ordinal" for OrdinalReparamSVI; HierGLMReparamSVI's link too --
-    ``grouped`` tells that model apart), "softmax" for SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
+    "weibull" for WeibullReparamSVI, "beta" for BetaReparamSVI, "ordinal" for OrdinalReparamSVI; HierGLMReparamSVI's link
+    too -- ``grouped`` tells that model apart), "softmax" for SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
     if getattr(model, "n_classes", None) is not None:
         return "softmax"
     link = getattr(model, "link", None)
@@ -120,7 +126,8 @@ def posterior_draws(model, n_samples=64, seed=None):
     """(W float32 [S, D] on the device, logvar float32 [S] or None) from the model's current q; W is [S, K, D] for
     SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d) and Z [S, D + K - 1] = [w | theta] for
     OrdinalReparamSVI; for NegBinReparamSVI the second
-    entry is logphi float32 [S], for GammaReparamSVI and WeibullReparamSVI logshape float32 [S]; for HierGLMReparamSVI it is the intercept table Bt float32 [J + 1, ldb] (module
+    entry is logphi float32 [S], for GammaReparamSVI and WeibullReparamSVI logshape float32 [S], for BetaReparamSVI
+    logprec float32 [S]; for HierGLMReparamSVI it is the intercept table Bt float32 [J + 1, ldb] (module
     docstring), and for the drivers of svi/hier_scalar.py the triple (W, Bt, logtau float32 [S])."""
     S = _check_samples(n_samples)
     family = family_of(model)
@@ -145,7 +152,8 @@ def posterior_draws(model, n_samples=64, seed=None):
     elif family == "ordinal":
         D = model.P                            # z = [w | theta], returned whole: the pass reads both from Z [S, P]
     seed = model.seed if seed is None else int(seed)
-    scalar = family == "gaussian" or family in SCALAR_PASSES   # a scalar latent rides behind the weights
+    # a scalar latent rides behind the weights
+    scalar = family == "gaussian" or family in SCALAR_PASSES or family in LOGIT_SCALAR_PASSES
     P = D + 1 if scalar else D
     eps_d = torch.zeros((S, P), dtype=torch.float64, device=ctx.device)
     ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P, eps_d)
@@ -181,6 +189,10 @@ def _obs(model, family, B, offset, exposure, weights):
                          "counts")
     if offset is None and exposure is None and weights is None:
         return None, None
+    if family in LOGIT_SCALAR_PASSES:         # the logistic link's rules, in the model's own words
+        if exposure is not None:
+            raise ValueError("predict: exposure belongs to the Poisson rate model; the %s model takes offset=" % family)
+        return batch_obs(model.ctx, B, offset, weights)
     if family not in ("logistic", "poisson") and family not in SCALAR_PASSES:
         raise ValueError("predict: offset, exposure and weights are for the logistic and Poisson models, not %s" % family)
     check_link("poisson" if family in SCALAR_PASSES else family, offset, exposure, kept="means")   # a log link's rules
@@ -275,6 +287,9 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
                  out["var"], out.get("lpd"), out.get("lpd_sum"))
     elif family in SCALAR_PASSES:  # its own entry point; the offset may be None
         ctx.call(SCALAR_PASSES[family], X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"],
+                 out.get("lpd"), out.get("lpd_sum"))
+    elif family in LOGIT_SCALAR_PASSES:   # the same, behind a logit link
+        ctx.call(LOGIT_SCALAR_PASSES[family], X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"],
                  out.get("lpd"), out.get("lpd_sum"))
     elif offset is None:
         ctx.call("bsc_predict_pass", FAMILIES[family], X, ldx, y, B, model.D, W, logvar, S, out["mean"], out["var"],

@@ -592,6 +592,53 @@ int bsc_glm_gamma_update(bsc_ctx* ctx, const double* stats, const double* lam_in
                          double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
                          int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo, double* grad);
 
+/* ---- Beta regression (logit link) with a learned precision on the same pass (csrc/bsc_glm_beta.hip) ----------------
+ *
+ *      y_n ~ Beta(a_n, b_n),   0 < y_n < 1,   a_n = m_n phi,   b_n = (1 - m_n) phi
+ *      m_n = sigmoid(l_n),   E y_n = m_n,   Var y_n = m_n (1 - m_n) / (1 + phi)
+ *      l[n,s] = sum_d X[n,d] W[s,d] + o[n],   w ~ N(0, I / prior_precision),   phi = e^tau ~ Gamma(a0, b0)
+ * The latent is z = [w (D) | tau], P = D + 1, the guide mean-field: lam = [m (P) | rho (P)].  One precision draw rides
+ * with every weight draw: logprec[s] = tau_s, float32 [S], any 4-byte alignment; phi_s = e^{tau_s} (float32 expf of the
+ * value read); lnGamma(phi_s) and psi(phi_s) are made once per launch in float64 and rounded.  With ly = log y and
+ * l1y = log1p(-y):
+ *      log p(y | l, phi) = lnGamma(phi) - lnGamma(a) - lnGamma(b) + (a - 1) ly + (b - 1) l1y   (the FULL density)
+ *      ell[s]  = sum_n v[n] log p(y[n] | l[n,s], phi_s)
+ *      G[s,d]  = sum_n r[n,s] X[n,d]       r[n,s] = v[n] phi_s m (1 - m) ( (ly - l1y) - psi(a) + psi(b) )       (= d / d l)
+ *      T[s]    = sum_n v[n] phi_s ( psi(phi_s) + m (ly - psi(a)) + (1 - m)(l1y - psi(b)) )          (= d ell[s] / d tau_s)
+ * Outputs float64: ell [S], G [S, D], T [S].  offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0,
+ * v = 1; a row with v[n] = 0 adds EXACTLY nothing to ell, G and T, by a select on the link's inputs: it is evaluated at
+ * y = 1/2, l = 0 whatever it held, as the rows past B are).  m and 1 - m come each from the stable logistic form
+ * (e / (1 + e) and 1 / (1 + e), e = exp(-|l|)), never 1 - m by subtraction; lnGamma and psi at a and b are float32, for
+ * any positive argument: the argument is shifted up to at least 8 by ONE product of at most eight factors carried with
+ * its derivative, then three asymptotic terms (lnGamma = Stirling - log P, psi = asymptotic - P' / P).
+ * y IS NOT CHECKED ON THE DEVICE: a kept row with y <= 0, y >= 1 or a non-finite y makes ell and T of every draw NaN or
+ * infinite (bayesic_amd/svi/glm_beta.py checks y where a batch is set, AFTER rounding to float32).
+ * OVERFLOW: nothing is clamped.  The outputs are finite while m phi, (1 - m) phi and their reciprocals are normal float32
+ * values: |l| <= 80 at tau in [-2, 5] (psi(a) ~ -1 / a reaches 4e35 there and is multiplied by m first).
+ * ACCURACY ENVELOPE: tau in [-2, 5] (phi in [0.135, 148]), |l| <= 80; there a plain float32 evaluation stays within
+ * 1e-6 of  sum_n v ( |lnGamma phi| + S(a) + S(b) + |log min(a, 1)| + |log min(b, 1)| + (a + 1)|ly| + (b + 1)|l1y| + 1 ),
+ * S(x) = max(|lnGamma(max(x, 8))|, 17) the shifted Stirling term, for ell, of  sum_n v ( phi (|psi phi| + m (|ly| +
+ * |psi a|) + (1 - m)(|l1y| + |psi b|)) + 1 )  for T and of max |G|.  T cancels from its terms' size (2e3 per row at
+ * tau = 5) down to O(1): above the envelope float32 does not hold the difference.
+ * The envelope and its refusals are bsc_glm_nb_data_pass's (D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 with eight draws
+ * and their eight tau per launch, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26); logprec == NULL is
+ * refused.  The 16-row MFMA kernel (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned,
+ * else the 8-row kernel.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block partials of
+ * 8 * 256 + 16 floats (ell and T behind G), fixed-order float64 finish, no float atomics. */
+int bsc_glm_beta_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                           const float* weight, int64_t B, int32_t D, const float* W, const float* logprec, int32_t S,
+                           double* ell, double* G, double* T);
+
+/* The finish: bsc_glm_nb_update with logprec in the place of logphi -- the prior on e^tau has the same form, the
+ * likelihood enters through ell, G and T alone, and both entry points run one body (csrc/bsc_meanfield.h), so the same
+ * arguments give the same bits.  stats = [ell (S) | G (S*D) | T (S)]; checks, next draws and requirements as there.
+ * A full-covariance guide finishes with bsc_glm_scalar_fullrank_update. */
+int bsc_glm_beta_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                        double* m2, const double* eps, const float* W, const float* logprec, int32_t D, int32_t S,
+                        double scale, double prior_precision, double a0, double b0, int64_t t, double lr, double beta1,
+                        double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
+                        int32_t eps_next_ready, float* W_next, float* logprec_next, double* elbo, double* grad);
+
 /* ---- Weibull survival regression with right censoring and a learned shape on the same pass (csrc/bsc_glm_weibull.hip)
  *
  *      t_n ~ Weibull(shape k, scale e^{l_n}),   l[n,s] = sum_d X[n,d] W[s,d] + o[n]   (accelerated failure time)
@@ -799,6 +846,21 @@ int bsc_nb_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* 
 int bsc_gamma_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                            int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
                            float* lpd, double* lpd_sum);
+
+/* The predictive of the Beta model (csrc/bsc_glm_beta.hip: bsc_predict_pass's kernel with an eighth family that only
+ * this entry point reaches).  Per draw, with phi_s = exp(logprec[s]), l[n,s] = sum_d X[n,d] W[s,d] + o[n] (offset may be
+ * NULL), m = sigmoid(l), a = m phi_s and b = (1 - m) phi_s:
+ *      mu = m    v = m (1 - m) / (1 + phi_s)
+ *      log p(y | l, phi_s) = lnGamma(phi_s) - lnGamma(a) - lnGamma(b) + (a - 1) log y + (b - 1) log1p(-y)
+ *      mean[n] = 1/S sum_s mu,     var[n] = 1/S sum_s v + 1/S sum_s (mu - mean[n])^2
+ *      lpd[n]  = logsumexp_s log p(y[n] | l[n,s], phi_s) - log S,     lpd_sum = sum_n lpd[n]     (float64 [1])
+ * The density is bsc_glm_beta_data_pass's, complete, in its forms; lnGamma(phi_s) and 1 / (1 + phi_s) are made once per
+ * launch in float64.  mean and var are finite for every finite l; 0 < y < 1 is not checked here.  Outputs, refusals,
+ * envelope and determinism are bsc_nb_predict_pass's; logprec == NULL is BSC_ERR_INVALID.  Accuracy envelope of lpd:
+ * logprec in [-2, 5], |l| <= 80. */
+int bsc_beta_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
+                          int32_t D, const float* W, const float* logprec, int32_t S, float* mean, float* var,
+                          float* lpd, double* lpd_sum);
 
 /* The predictive of the Weibull survival model (csrc/bsc_glm_weibull.hip: bsc_predict_pass's kernel with a sixth family
  * that only this entry point reaches).  y carries bsc_glm_weibull_data_pass's encoding: y[n] > 0 an event at y[n],
