@@ -37,7 +37,7 @@ template <int LINK, bool FULL>
 __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_pass_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, int64_t B, int D,
     const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter) {
-    glm_pass_body<LINK, FULL, false>(X, ldx, y, nullptr, nullptr, B, D, W, S, slab, n_iter);
+    glm_pass_body<GlmFamily<LINK>, FULL, false>(X, ldx, y, nullptr, nullptr, B, D, W, S, slab, n_iter);
 }
 
 // 16-row tiles, both contractions on the MFMA pipe (D == 256, y 16-byte aligned)
@@ -45,7 +45,7 @@ template <int LINK>
 __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_pass_mfma_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, int64_t B,
     const float* __restrict__ W, int S, float* __restrict__ slab, int n_iter) {
-    glm_pass_mfma_body<LINK, false>(X, ldx, y, nullptr, nullptr, B, W, S, slab, n_iter);
+    glm_pass_mfma_body<GlmFamily<LINK>, false>(X, ldx, y, nullptr, nullptr, B, W, S, slab, n_iter);
 }
 
 // ---- float64 reduction of the slab: blr_slab_reduce_kernel's body, ell where that one writes Q -------------------

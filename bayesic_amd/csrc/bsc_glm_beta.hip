@@ -2,7 +2,7 @@
 // with the per-draw scalar flag on and the sixth link, their slab reduction, the finish for the latent z = [w (D) | tau]
 // (csrc/bsc_meanfield.h's bodies with NbModel -- the prior on the scalar has the negative binomial's form, so the finish
 // is the same), and the predictive (csrc/bsc_predict_pass.h's body and envelope with its eighth family).  The kernels and
-// the host side of the three entry points are csrc/bsc_scalar_family.h's, with GLM_BETA and PREDICT_BETA.
+// the host side of the three entry points are csrc/bsc_scalar_family.h's, with the Beta family.
 //
 //     y_n ~ Beta(a_n, b_n),  0 < y_n < 1,  a_n = m_n phi,  b_n = (1 - m_n) phi
 //     m_n = sigmoid(l_n),  E y_n = m_n,  Var y_n = m_n (1 - m_n) / (1 + phi)
@@ -30,8 +30,8 @@ int bsc_glm_beta_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const floa
                            const float* weight, int64_t B, int32_t D, const float* W, const float* logprec, int32_t S,
                            double* ell, double* G, double* T) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_data_pass<GLM_BETA>(ctx, "bsc_glm_beta_data_pass", "logprec", X, ldx, y, nullptr, offset,
-                                             weight, B, D, W, logprec, S, ell, G, T);
+    return scalar_family_data_pass<Beta>(ctx, "bsc_glm_beta_data_pass", "logprec", X, ldx, y, nullptr, offset, weight,
+                                         B, D, W, logprec, S, ell, G, T);
 }
 
 int bsc_glm_beta_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
@@ -40,17 +40,17 @@ int bsc_glm_beta_update(bsc_ctx* ctx, const double* stats, const double* lam_in,
                         double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
                         int32_t eps_next_ready, float* W_next, float* logprec_next, double* elbo, double* grad) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_update<GLM_BETA>(ctx, "bsc_glm_beta_update", stats, lam_in, lam_out, m1, m2, eps, W, logprec,
-                                          D, S, scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps, seed,
-                                          next_step, eps_next, eps_next_ready, W_next, logprec_next, elbo, grad);
+    return scalar_family_update<Beta>(ctx, "bsc_glm_beta_update", stats, lam_in, lam_out, m1, m2, eps, W, logprec, D, S,
+                                      scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps, seed, next_step,
+                                      eps_next, eps_next_ready, W_next, logprec_next, elbo, grad);
 }
 
 int bsc_beta_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                           int32_t D, const float* W, const float* logprec, int32_t S, float* mean, float* var,
                           float* lpd, double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_predict_pass<PREDICT_BETA>(ctx, "bsc_beta_predict_pass", "logprec", X, ldx, y, nullptr, offset,
-                                                    B, D, W, logprec, S, mean, var, lpd, lpd_sum);
+    return scalar_family_predict_pass<Beta>(ctx, "bsc_beta_predict_pass", "logprec", X, ldx, y, nullptr, offset, B, D,
+                                            W, logprec, S, mean, var, lpd, lpd_sum);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // per-draw scalar flag on and the fourth link, their slab reduction, the finish for the latent z = [w (D) | tau]
 // (csrc/bsc_meanfield.h's bodies with NbModel -- the prior on the scalar has the negative binomial's form, so the finish
 // is the same), and the predictive (csrc/bsc_predict_pass.h's body and envelope with its fifth family).  The kernels and
-// the host side of the three entry points are csrc/bsc_scalar_family.h's, with GLM_GAMMA and PREDICT_GAMMA.
+// the host side of the three entry points are csrc/bsc_scalar_family.h's, with the Gamma family.
 //
 //     y_n ~ Gamma(shape alpha, rate alpha / mu_n),  y_n > 0,  E y_n = mu_n = exp(l_n),  Var y_n = mu_n^2 / alpha
 //     l[n,s] = x_n . w_s + o_n,   w ~ N(0, I / prior_precision),   alpha = e^tau ~ Gamma(a0, b0)
@@ -26,8 +26,8 @@ int bsc_glm_gamma_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const flo
                             const float* weight, int64_t B, int32_t D, const float* W, const float* logshape,
                             int32_t S, double* ell, double* G, double* T) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_data_pass<GLM_GAMMA>(ctx, "bsc_glm_gamma_data_pass", "logshape", X, ldx, y, nullptr, offset,
-                                              weight, B, D, W, logshape, S, ell, G, T);
+    return scalar_family_data_pass<Gamma>(ctx, "bsc_glm_gamma_data_pass", "logshape", X, ldx, y, nullptr, offset,
+                                          weight, B, D, W, logshape, S, ell, G, T);
 }
 
 int bsc_glm_gamma_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
@@ -36,18 +36,17 @@ int bsc_glm_gamma_update(bsc_ctx* ctx, const double* stats, const double* lam_in
                          double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
                          int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo, double* grad) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_update<GLM_GAMMA>(ctx, "bsc_glm_gamma_update", stats, lam_in, lam_out, m1, m2, eps, W,
-                                           logshape, D, S, scale, prior_precision, a0, b0, t, lr, beta1, beta2,
-                                           adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, logshape_next,
-                                           elbo, grad);
+    return scalar_family_update<Gamma>(ctx, "bsc_glm_gamma_update", stats, lam_in, lam_out, m1, m2, eps, W, logshape, D,
+                                       S, scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps, seed,
+                                       next_step, eps_next, eps_next_ready, W_next, logshape_next, elbo, grad);
 }
 
 int bsc_gamma_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                            int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
                            float* lpd, double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_predict_pass<PREDICT_GAMMA>(ctx, "bsc_gamma_predict_pass", "logshape", X, ldx, y, nullptr,
-                                                     offset, B, D, W, logshape, S, mean, var, lpd, lpd_sum);
+    return scalar_family_predict_pass<Gamma>(ctx, "bsc_gamma_predict_pass", "logshape", X, ldx, y, nullptr, offset, B,
+                                             D, W, logshape, S, mean, var, lpd, lpd_sum);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Negative-binomial regression with a learned dispersion on the fused pathwise pass: csrc/bsc_glm_pass.h's OBS bodies
 // with the dispersion flag on, their slab reduction, the finish for the latent z = [w (D) | tau] (csrc/bsc_meanfield.h's
 // bodies with NbModel), and the predictive (csrc/bsc_predict_pass.h's body and envelope with its fourth family).  The
-// kernels and the host side of the three entry points are csrc/bsc_scalar_family.h's, with GLM_NEGBIN and PREDICT_NEGBIN.
+// kernels and the host side of the three entry points are csrc/bsc_scalar_family.h's, with the NegBin family.
 //
 //     y_n ~ NegBin(mean exp(l_n), dispersion phi),  Var y_n = mu_n + mu_n^2 / phi,   l[n,s] = x_n . w_s + o_n
 //     w ~ N(0, I / prior_precision),   phi = e^tau ~ Gamma(a0, b0)
@@ -26,8 +26,8 @@ int bsc_glm_nb_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float*
                          const float* weight, int64_t B, int32_t D, const float* W, const float* logphi, int32_t S,
                          double* ell, double* G, double* T) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_data_pass<GLM_NEGBIN>(ctx, "bsc_glm_nb_data_pass", "logphi", X, ldx, y, nullptr, offset,
-                                               weight, B, D, W, logphi, S, ell, G, T);
+    return scalar_family_data_pass<NegBin>(ctx, "bsc_glm_nb_data_pass", "logphi", X, ldx, y, nullptr, offset, weight, B,
+                                           D, W, logphi, S, ell, G, T);
 }
 
 int bsc_glm_nb_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1, double* m2,
@@ -36,17 +36,17 @@ int bsc_glm_nb_update(bsc_ctx* ctx, const double* stats, const double* lam_in, d
                       double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next, int32_t eps_next_ready,
                       float* W_next, float* logphi_next, double* elbo, double* grad) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_update<GLM_NEGBIN>(ctx, "bsc_glm_nb_update", stats, lam_in, lam_out, m1, m2, eps, W, logphi, D,
-                                            S, scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps, seed,
-                                            next_step, eps_next, eps_next_ready, W_next, logphi_next, elbo, grad);
+    return scalar_family_update<NegBin>(ctx, "bsc_glm_nb_update", stats, lam_in, lam_out, m1, m2, eps, W, logphi, D, S,
+                                        scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps, seed, next_step,
+                                        eps_next, eps_next_ready, W_next, logphi_next, elbo, grad);
 }
 
 int bsc_nb_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                         int32_t D, const float* W, const float* logphi, int32_t S, float* mean, float* var, float* lpd,
                         double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_predict_pass<PREDICT_NEGBIN>(ctx, "bsc_nb_predict_pass", "logphi", X, ldx, y, nullptr, offset,
-                                                      B, D, W, logphi, S, mean, var, lpd, lpd_sum);
+    return scalar_family_predict_pass<NegBin>(ctx, "bsc_nb_predict_pass", "logphi", X, ldx, y, nullptr, offset, B, D, W,
+                                              logphi, S, mean, var, lpd, lpd_sum);
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_obs_pass_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, int64_t B, int D, const float* __restrict__ W, int S, float* __restrict__ slab,
     int n_iter) {
-    glm_pass_body<LINK, FULL, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter);
+    glm_pass_body<GlmFamily<LINK>, FULL, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter);
 }
 
 template <int LINK>
@@ -26,7 +26,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_obs_pass_mfma_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, int64_t B, const float* __restrict__ W, int S, float* __restrict__ slab,
     int n_iter) {
-    glm_pass_mfma_body<LINK, true>(X, ldx, y, o, v, B, W, S, slab, n_iter);
+    glm_pass_mfma_body<GlmFamily<LINK>, true>(X, ldx, y, o, v, B, W, S, slab, n_iter);
 }
 
 template <int LINK>

@@ -72,7 +72,7 @@ __device__ __forceinline__ void ord_build_table(float* tab, const float* __restr
 
 // ---- the link --------------------------------------------------------------------------------------------------------
 
-// softplus(x) and sigmoid(x) in glm_link's logistic forms: finite for every finite x
+// softplus(x) and sigmoid(x) in the logistic link's forms (csrc/bsc_families.h): finite for every finite x
 __device__ __forceinline__ void ord_logistic(float x, float& sp, float& sg) {
     const float e = expf(-fabsf(x));
     const float t = 1.0f + e;
@@ -83,7 +83,7 @@ __device__ __forceinline__ void ord_logistic(float x, float& sp, float& sg) {
 }
 
 // `l` already holds the offset, `ybits` the bits of the int32 label, `tabs` this lane's draw's row of the table.
-// The selects sit on the INPUTS (glm_link says why); the H_j take flat selects, one after the other and not nested.
+// The selects sit on the INPUTS (csrc/bsc_families.h says why); the H_j take flat selects, one after the other and not nested.
 __device__ __forceinline__ float ord_link(float l, float ybits, bool real_row, float vv, const float* tabs, int K,
                                           float& ell, float (&H)[ORD_H]) {
     const int yi = (int)__float_as_uint(ybits);
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(RED_BLOCK) void glm_ordinal_slab_reduce_kernel(cons
 template <int NC, bool FULL>
 __global__ __launch_bounds__(P_BLOCK, 2) void predict_ordinal_kernel(PredictArgs a, const float* __restrict__ offset,
                                                                      PredictOrdinal od) {
-    predict_body<PREDICT_ORDINAL, NC, FULL, true>(a, offset, PredictGroups{}, nullptr, od);
+    predict_body<Ordinal, NC, FULL, true>(a, offset, PredictGroups{}, nullptr, od);
 }
 
 __global__ __launch_bounds__(BSC_WAVE) void predict_ordinal_sum_kernel(const double* __restrict__ partial, int n,

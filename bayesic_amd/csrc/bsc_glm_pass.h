@@ -1,5 +1,6 @@
 // The bodies of the GLM training-pass kernels (csrc/bsc_glm.hip's header comment describes the two tile shapes), as
-// __device__ templates with one compile-time flag so that two translation units can instantiate them:
+// __device__ templates over the likelihood family F -- a struct of csrc/bsc_families.h, which holds everything a family
+// is: nothing here names one -- and compile-time flags, so that several translation units can instantiate them:
 //
 //   OBS = false   csrc/bsc_glm.hip: glm_pass_kernel / glm_pass_mfma_kernel, the pass over (X, y) alone.  Every use of
 //                 the offset and the weight is behind `if (OBS)`, the tile structs carry no extra registers, and the
@@ -23,262 +24,29 @@
 //                 past the batch and their stores do not land.  Everything of it is behind `if constexpr (GRP)`; the
 //                 flag defaults to off and the kernels of the two files above compile as they did without it.
 //
-//                 GRP with DSP (csrc/bsc_glm_scalar_group.hip): the link of the GRP branches also gets the draw's
-//                 dispersion and the T accumulator, the slab is DSP's; never with ITV.
+//                 GRP with F::SCALAR (csrc/bsc_glm_scalar_group.hip): the slab is the scalar families'; never with ITV.
 //
-//   DSP = true    csrc/bsc_glm_nb.hip (always with OBS and LINK = GLM_NEGBIN): the negative binomial with one
-//                 dispersion draw per weight draw, tau_s = log phi_s as float32 [S].  A lane owns ONE draw in both tile
-//                 shapes, so tau_s, phi_s = exp(tau_s), lnGamma(phi_s) and psi(phi_s) are made once per launch (the two
-//                 special values in float64, then rounded) and stay in four registers; T[s] = d ell[s] / d tau_s is one
-//                 more lane accumulator next to ell.  The slab has no room for it, so these kernels write block
-//                 partials of NB_SLAB_STRIDE = REG_SLAB_G + 16 floats: ell at [SLAB_G + s], T at [SLAB_G + 8 + s].
-//                 Everything of it is behind `if constexpr (DSP)`; the flag defaults to off.
-//                 csrc/bsc_glm_gamma.hip (LINK = GLM_GAMMA) runs the same flag with a shape alpha_s = exp(tau_s) in the
-//                 place of phi_s: the four registers are tau_s, alpha_s and the two per-draw constants of the Gamma
-//                 density (glm_link below), T[s] and the slab are the same.
-//                 csrc/bsc_glm_weibull.hip (LINK = GLM_WEIBULL) runs it with the Weibull shape k_s = exp(tau_s): only
-//                 tau_s and k_s are kept (the density has no per-draw constant), and the censoring flag of a row is
-//                 the sign of its y, so the tiles carry nothing new.
-//                 csrc/bsc_glm_beta.hip (LINK = GLM_BETA) runs it with the Beta precision phi_s = exp(tau_s): the four
-//                 registers are the negative binomial's (tau_s, phi_s, lnGamma(phi_s), psi(phi_s)); lnGamma and psi at
-//                 m phi and (1 - m) phi are float32, per (row, draw) (csrc/bsc_special_f32.h, bsc_lgamma_psi_f32).
-//   ITV = true    csrc/bsc_glm_weibull_interval.hip (always with DSP and LINK = GLM_WEIBULL): interval and left
+//   F::SCALAR     not a flag: the families with one learned log-scalar per weight draw, tau_s as float32 [S] (always with
+//                 OBS; csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip, csrc/bsc_glm_beta.hip).  A
+//                 lane owns ONE draw in both tile shapes, so F::glm_disp's four values are made once per launch and stay
+//                 in four registers; T[s] = d ell[s] / d tau_s is one more lane accumulator next to ell.  The slab has no
+//                 room for it, so these kernels write block partials of NB_SLAB_STRIDE = REG_SLAB_G + 16 floats: ell at
+//                 [SLAB_G + s], T at [SLAB_G + 8 + s].  Everything of it is behind `if constexpr (F::SCALAR)`.
+//   ITV = true    csrc/bsc_glm_weibull_interval.hip (a family whose link takes upper ends: Weibull): interval and left
 //                 censoring.  One more per-row vector, `upper` [B] float32, rides in the tiles next to y and is loaded
-//                 the way y is (rows past B read 0); glm_link says how it is read.  Everything of it is behind
+//                 the way y is (rows past B read 0); the family's link says how it is read.  Everything of it is behind
 //                 `if constexpr (ITV)`; the flag defaults to off and every other kernel compiles as it did.
 //
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
-#include "bsc_regress.h"
-#include "bsc_special_f32.h"
+#include "bsc_families.h"
 
 namespace {
 
 constexpr int SLAB_G = REG_SLAB_G;            // slab[b][d*8 + s], then ell at [SLAB_G + s]
 constexpr int SLAB_STRIDE = REG_SLAB_STRIDE;  // floats per block partial
-constexpr int NB_SLAB_STRIDE = REG_SLAB_G + 2 * SG;   // DSP: ell at [SLAB_G + s], T at [SLAB_G + 8 + s]
-constexpr int GLM_NEGBIN = 2;                 // the third link; internal: the BSC_GLM_* entry points refuse it
-constexpr int GLM_GAMMA = 3;                  // the fourth, internal as well: csrc/bsc_glm_gamma.hip
-constexpr int GLM_WEIBULL = 4;                // the fifth, internal as well: csrc/bsc_glm_weibull.hip
-constexpr int GLM_BETA = 5;                   // the sixth, internal as well: csrc/bsc_glm_beta.hip
-
-// DSP: what a lane keeps of its draw's dispersion (GLM_GAMMA: of its draw's shape alpha_s; GLM_WEIBULL: of k_s;
-// GLM_BETA: of its draw's precision phi_s).
-struct GlmDisp {
-    float tau, phi;     // log phi_s as the pass read it, exp(tau)
-    float lg, psi;      // lnGamma(phi), psi(phi) (GLM_NEGBIN and GLM_BETA); GLM_GAMMA: c_a = alpha log alpha -
-                        // lnGamma(alpha), c_1 = log alpha + 1 - psi(alpha); GLM_WEIBULL: not used (0)
-};
-
-// Draw s of this launch's chunk (s >= S: a dead slot, phi = 1).  The special values in float64, once per launch.
-template <int LINK = GLM_NEGBIN>
-__device__ __forceinline__ GlmDisp glm_disp_of(const float* __restrict__ logphi, int s, int S) {
-    GlmDisp d;
-    d.tau = s < S ? logphi[s] : 0.0f;
-    d.phi = expf(d.tau);
-    if constexpr (LINK == GLM_WEIBULL) {
-        d.lg = d.psi = 0.0f;       // tau and k alone: the Weibull density has no special function in it
-    } else if constexpr (LINK == GLM_GAMMA) {
-        const double a = (double)d.phi, la = log(a);
-        d.lg = (float)(a * la - bsc_lgamma_f64(a));
-        d.psi = (float)(la + 1.0 - bsc_digamma_f64(a));
-    } else {                       // GLM_NEGBIN and GLM_BETA: lnGamma(phi) and psi(phi) themselves
-        d.lg = (float)bsc_lgamma_f64((double)d.phi);
-        d.psi = (float)bsc_digamma_f64((double)d.phi);
-    }
-    return d;
-}
-
-// ---- the link: ell += y l - A(l) for a real row, resid = y - A'(l) ------------------------------------------
-//
-// Logistic: A = softplus in the stable form max(l, 0) + log1p(e), e = exp(-|l|) <= 1 (exp at full float32 accuracy:
-// the tails at |l| = 80 are compared at rtol 1e-6), and A' = sigmoid from the
-// same e (1 / (1 + e) for l >= 0, e / (1 + e) below): finite for every finite l.  Poisson: A = A' = exp(l),
-// NOT clamped (a clamp would change the gradient silently): finite for l <= 88.
-// OBS: `l` already holds the offset; both terms are scaled by the weight vv where vv > 0 and are exactly 0 elsewhere.
-// GLM_NEGBIN (always OBS; dp and T set): with u = l - tau, phi = e^tau, z = y + phi and the logistic forms at u,
-//     ell  += v [ dlnGamma(y, phi) + y u - z softplus(u) ]          dlnGamma = lnGamma(z) - lnGamma(phi)
-//     resid = v [ y - z sigmoid(u) ]                                                           (= d / d l)
-//     T    += v [ phi dpsi(y, phi) - phi softplus(u) ] - resid       dpsi = psi(z) - psi(phi)   (= d / d tau)
-// finite for every finite l; both differences are exactly 0 at y = 0 (csrc/bsc_special_f32.h: an empty product).
-// GLM_GAMMA (always OBS; dp and T set): y > 0, alpha = e^tau, ly = log y, q = y e^{-l}, and dp's c_a, c_1:
-//     ell  += v [ c_a + alpha (ly - l - q) - ly ]                    (the full density, nothing left out)
-//     resid = v alpha (q - 1)                                                                  (= d / d l)
-//     T    += v alpha (c_1 + ly - l - q)                                                       (= d / d tau)
-// NOT clamped, like the Poisson link: finite while e^{-l} and y e^{-l} are below the float32 maximum (l > -88 at
-// y = 1).  One exp and one log per (row, draw), both at full float32 accuracy: ly enters ell multiplied by alpha.
-// GLM_WEIBULL (always OBS; dp and T set): the sign of y is the censoring flag -- y > 0 an event at y, y < 0 right-censored
-// at -y -- so delta = (y > 0), t = |y|; k = e^tau, ly = log t, z = k (ly - l), l the log SCALE:
-//     ell  += v [ delta (tau + z - ly) - e^z ]            (log f = tau + z - ly - e^z, log S = -e^z: nothing left out)
-//     resid = v k (e^z - delta)                                                                (= d / d l)
-//     T    += v [ delta (1 + z) - z e^z ]                                                      (= d / d tau)
-// NOT clamped, like the Poisson and Gamma links: finite while z stays below about 88 (e^z and z e^z below the float32
-// maximum).  One log and one exp per (row, draw) at full float32 accuracy; z is rounded before the exponential, which
-// costs |z| eps of e^z (the tests' bounds count (1 + |z|) e^z per row).  y = 0 or a non-finite y on a kept row is the
-// caller's to keep out.
-// GLM_BETA (always OBS; dp and T set): 0 < y < 1, phi = e^tau, ly = log y, l1y = log1p(-y), m = sigmoid(l) and
-// 1 - m = sigmoid(-l) EACH from the stable logistic forms e / (1 + e), 1 / (1 + e) with e = exp(-|l|) (never 1 - m by
-// subtraction), a = m phi, b = (1 - m) phi, and dp's lnGamma(phi), psi(phi):
-//     ell  += v [ lnGamma(phi) - lnGamma(a) - lnGamma(b) + (a - 1) ly + (b - 1) l1y ]    (the full density, nothing left out)
-//     resid = v phi m (1 - m) [ (ly - l1y) - psi(a) + psi(b) ]                                (= d / d l)
-//     T    += v phi [ psi(phi) + m (ly - psi(a)) + (1 - m)(l1y - psi(b)) ]                     (= d / d tau)
-// lnGamma and psi of a and of b from csrc/bsc_special_f32.h's bsc_lgamma_psi_f32, one evaluation after the other: four
-// logs, four reciprocals and two shifted products per (row, draw) on top of the logistic link's exp.  l1y through
-// log(w) (-y) / (w - 1), w = 1 - y, which undoes the rounding of w (y = 1e-6: log(1 - y) alone is 6 % off).  NOT
-// clamped: finite while a, b and their reciprocals are normal float32 values -- |l| <= 80 at tau in [-2, 5], where
-// psi(a) ~ -1 / a reaches 4e35 and is multiplied by m before anything else.  y = 0, y = 1 or a non-finite y on a kept
-// row is the caller's to keep out.
-// GLM_WEIBULL with ITV (csrc/bsc_glm_weibull_interval.hip): `uv` is the row's entry of the vector `upper` -- 0: the row is
-// what y says, as above; uv > 0 (with y < 0): interval-censored on (a, b] = (-y, uv]; uv < 0: left-censored at b = -uv,
-// the magnitude of y not read.  With z = k (log a - l), E = e^z, d = log b - log a and Delta = E expm1(k d) = E_b - E_a
-// (a left-censored row: z = k (log b - l), Delta = E, and E_a = 0 in what follows), e = e^{-Delta}, p = -expm1(-Delta):
-// (d through log1p((b - a) / a) where b < 2 a: the difference of two rounded logarithms would lose a narrow interval)
-//     ell  += v [ -E_a + log p ]                                       (= log(S(a) - S(b)): nothing left out)
-//     resid = v k ( E_a - Delta e / p )                                (Delta e / p = Delta / expm1(Delta), in (0, 1))
-//     T    += v [ -z E_a + (z Delta + k d E_b) e / p ]                 E_b = E_a + Delta
-// all three in ONE form with the rows above: an indicator `ic` (1 on such a row, else 0) multiplies the new terms, which
-// a row without an upper end evaluates at Delta = 1, k d = 0.  OVERFLOW: where Delta >= ITV_BIG -- e^{-Delta} is zero in
-// float32 (csrc/bsc_special_f32.h), or the upper end is so far out that e^{k d} or Delta is infinite (upper = 1e30 for "no bound") -- the row is
-// the right-censored one at a (the left-censored one adds nothing: its probability is 1), by the same select on the
-// inputs; a NaN Delta (0 times infinity) goes the same way.  Seven transcendentals per (row, draw) for two.
-
-template <int LINK, bool OBS = false, bool ITV = false>
-__device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv = 1.0f,
-                                          const GlmDisp* dp = nullptr, float* T = nullptr, float uv = 0.0f) {
-    static_assert(!ITV || LINK == GLM_WEIBULL, "the upper end belongs to the Weibull link");
-    if constexpr (LINK == GLM_WEIBULL && ITV) {
-        // The selects sit on the INPUTS, as below: a dropped row is evaluated at a = b = 1, l = 0, delta = 0, ic = 0.
-        // Each select is flat, between values at hand: a nested one (keep ? (left ? .. : ..) : ..) comes out as a branch
-        // that the logit's last additions sink into, which splits the loop body and spills 150 bytes per lane.
-        const bool keep = real_row && vv > 0.0f;
-        const float vq = keep ? vv : 0.0f;
-        const bool left = keep && uv < 0.0f;
-        const bool itv = keep && uv > 0.0f;
-        const float tq = keep ? fabsf(uv < 0.0f ? uv : yv) : 1.0f;     // one select after the other, not nested
-        const float bq = itv ? uv : tq;
-        const float dl = (keep && uv == 0.0f && yv > 0.0f) ? 1.0f : 0.0f;
-        const float lq = keep ? l : 0.0f;
-        const float ly = logf(tq);
-        const float z = dp->phi * (ly - lq);
-        const float ez = expf(z);
-        const float kd = dp->phi * bsc_logratio_f32(bq, tq, ly);   // exactly 0 unless the row is an interval
-        const float dlt = ez * (bsc_expm1_f32(kd) + (left ? 1.0f : 0.0f));   // expm1(0) = 0 on a left-censored row
-        const bool on = (left || itv) && dlt < ITV_BIG;      // false for a NaN as well
-        const float ic = on ? 1.0f : 0.0f;
-        const float dq = on ? dlt : 1.0f;
-        const float kq = on ? kd : 0.0f;
-        const float ea = left ? 0.0f : ez;
-        const float p = -bsc_expm1_f32(-dq);
-        const float q = expf(-dq) * __builtin_amdgcn_rcpf(p);                      // 1 / expm1(Delta), never through an infinite expm1
-        const float eb = ea + dq;
-        ell = fmaf(vq, fmaf(dl, (dp->tau + z) - ly, fmaf(ic, logf(p), -ea)), ell);
-        *T = fmaf(vq, fmaf(dl, 1.0f + z, fmaf(ic * q, fmaf(z, dq, kq * eb), -z * ea)), *T);
-        return vq * (dp->phi * (ea - fmaf(ic * q, dq, dl)));
-    }
-    if constexpr (LINK == GLM_NEGBIN) {
-        // The selects sit on the INPUTS: a dropped row (weight 0, or past B) is evaluated at y = 0, u = 0 -- finite
-        // whatever it held -- and its terms are multiplied by an exact 0.  A select on the results turns into a
-        // branch around the whole evaluation, which splits the loop body and spills.
-        const bool keep = real_row && vv > 0.0f;
-        const float vq = keep ? vv : 0.0f;
-        const float yq = keep ? yv : 0.0f;
-        const float u = keep ? l - dp->tau : 0.0f;
-        const float e = expf(-fabsf(u));
-        const float t = 1.0f + e;
-        const float r = __builtin_amdgcn_rcpf(t);
-        const float sig = u >= 0.0f ? r : e * r;
-        // log1p(e) from the full-accuracy log and a true division: softplus is multiplied by y + phi and the products
-        // cancel against lnGamma(y + phi) and y u, so the 3e-7 of the logistic link's fast form would show in ell
-        // (t == 1: log(t) = 0 and the quotient is over 1, e itself is added -- selects between values at hand)
-        const bool tiny = t == 1.0f;
-        const float lp = logf(t) * (e / (tiny ? 1.0f : t - 1.0f)) + (tiny ? e : 0.0f);
-        const float sp = fmaxf(u, 0.0f) + lp;
-        const float z = yq + dp->phi;
-        float dlg, dps;                                  // exactly 0 at y = 0
-        bsc_dlgamma_dpsi_f32(yq, dp->phi, dp->lg, dp->psi, dlg, dps);
-        const float res = fmaf(-z, sig, yq);
-        ell = fmaf(vq, dlg + fmaf(yq, u, -z * sp), ell);
-        *T = fmaf(vq, fmaf(dp->phi, dps - sp, -res), *T);
-        return vq * res;
-    }
-    if constexpr (LINK == GLM_GAMMA) {
-        // The selects sit on the INPUTS, for the reason given above: a dropped row is evaluated at y = 1, l = 0 -- every
-        // term finite, log 0 never formed -- and multiplied by an exact 0.
-        const bool keep = real_row && vv > 0.0f;
-        const float vq = keep ? vv : 0.0f;
-        const float yq = keep ? yv : 1.0f;
-        const float lq = keep ? l : 0.0f;
-        const float ly = logf(yq);
-        // y e^{-l} as a product: expf(ly - l) would round its argument, 4e-6 of the result at |l| = 80.  The difference
-        // ly - l is used in the linear term alone.
-        const float q = yq * expf(-lq);
-        const float d = (ly - lq) - q;
-        ell = fmaf(vq, fmaf(dp->phi, d, dp->lg) - ly, ell);
-        *T = fmaf(vq, dp->phi * (dp->psi + d), *T);
-        return vq * (dp->phi * (q - 1.0f));
-    }
-    if constexpr (LINK == GLM_BETA) {
-        // The selects sit on the INPUTS, for the reason given above: a dropped row is evaluated at y = 1/2, l = 0 -- a = b
-        // = phi / 2, every term finite whatever y and l held -- and multiplied by an exact 0.  Each select is flat.
-        const bool keep = real_row && vv > 0.0f;
-        const float vq = keep ? vv : 0.0f;
-        const float yq = keep ? yv : 0.5f;
-        const float lq = keep ? l : 0.0f;
-        const float e = expf(-fabsf(lq));
-        const float r = __builtin_amdgcn_rcpf(1.0f + e);
-        const float er = e * r;
-        const bool pos = lq >= 0.0f;
-        const float m = pos ? r : er, m1 = pos ? er : r;         // sigmoid(l) and sigmoid(-l), neither by subtraction
-        const float ly = logf(yq);
-        const float w = 1.0f - yq;
-        const bool one = w == 1.0f;                              // (w - 1 is exact; w == 1: -y itself)
-        const float l1y = fmaf(logf(w), yq * __builtin_amdgcn_rcpf(one ? 1.0f : 1.0f - w), one ? -yq : 0.0f);
-        const float a = m * dp->phi, b = m1 * dp->phi;
-        float lga, psa, lgb, psb;
-        bsc_lgamma_psi_f32(a, lga, psa);
-        bsc_lgamma_psi_f32(b, lgb, psb);
-        ell = fmaf(vq, ((dp->lg - lga) - lgb) + fmaf(a - 1.0f, ly, (b - 1.0f) * l1y), ell);
-        *T = fmaf(vq, dp->phi * (dp->psi + fmaf(m, ly - psa, m1 * (l1y - psb))), *T);
-        return vq * ((dp->phi * (er * r)) * (((ly - l1y) - psa) + psb));
-    }
-    if constexpr (LINK == GLM_WEIBULL) {
-        // The selects sit on the INPUTS, for the reason given above: a dropped row is evaluated at t = 1, l = 0,
-        // delta = 0 -- z = 0, every term finite whatever y held (0 and NaN included) -- and multiplied by an exact 0.
-        const bool keep = real_row && vv > 0.0f;
-        const float vq = keep ? vv : 0.0f;
-        const float tq = keep ? fabsf(yv) : 1.0f;
-        const float dl = (keep && yv > 0.0f) ? 1.0f : 0.0f;
-        const float lq = keep ? l : 0.0f;
-        const float ly = logf(tq);
-        const float z = dp->phi * (ly - lq);
-        const float ez = expf(z);
-        ell = fmaf(vq, fmaf(dl, (dp->tau + z) - ly, -ez), ell);
-        *T = fmaf(vq, fmaf(dl, 1.0f + z, -z * ez), *T);
-        return vq * (dp->phi * (ez - dl));
-    }
-    float a, da;
-    if (LINK == BSC_GLM_LOGISTIC) {
-        const float e = expf(-fabsf(l));
-        const float t = 1.0f + e;
-        const float r = __builtin_amdgcn_rcpf(t);
-        da = l >= 0.0f ? r : e * r;
-        // log1p(e) = log(t) e / (t - 1): the quotient undoes the rounding of t = 1 + e (t - 1 is exact); t == 1: e itself.
-        // Within 3e-7 of log1p over e in [0, 1], ten vector instructions where the library's log1pf is ~90.
-        const float lp = t == 1.0f ? e : __logf(t) * e * __builtin_amdgcn_rcpf(t - 1.0f);
-        a = fmaxf(l, 0.0f) + lp;
-    } else {
-        a = expf(l);
-        da = a;
-    }
-    if (OBS) {
-        const bool on = vv > 0.0f;
-        ell += (real_row && on) ? vv * fmaf(yv, l, -a) : 0.0f;
-        return on ? vv * (yv - da) : 0.0f;
-    }
-    ell += real_row ? fmaf(yv, l, -a) : 0.0f;
-    return yv - da;
-}
+constexpr int NB_SLAB_STRIDE = REG_SLAB_G + 2 * SG;   // F::SCALAR: ell at [SLAB_G + s], T at [SLAB_G + 8 + s]
 
 // ---- 8-row tiles on the VALU (any D % 4 == 0 up to 256): blr_pass_kernel<., 8, .>'s tile (csrc/bsc_regress.h) ----
 constexpr int ROWS = 8;
@@ -293,7 +61,7 @@ struct GlmTile<true, false, false> : RowTile<ROWS> {
 template <>
 struct GlmTile<true, false, true> : RowTile<ROWS> {
     float ov, vv;
-    float uv;       // ITV: the upper end of the same row (glm_link says how it is read)
+    float uv;       // ITV: the upper end of the same row (the family's link says how it is read)
 };
 template <>
 struct GlmTile<true, true, false> : RowTile<ROWS> {
@@ -363,12 +131,12 @@ __device__ __forceinline__ void gather_tile(GlmTile<true, true>& t, const GlmGro
 // Forward + link + backward for one tile; `wl` is this wave's LDS region, `rows_left` = B - row0.  has_v: the weights
 // are set (uniform; without them every row weighs 1.0f and real_row alone masks the rows past B).
 // GRP: `row0` is the tile's first row (a multiple of 8), its residuals also go to ga.R.
-// DSP: `dp` is the dispersion of this lane's draw, `T` its accumulator.
-template <int LINK, bool OBS, bool GRP = false, bool DSP = false, bool ITV = false>
+// `dp` is the scalar of this lane's draw, `T` its accumulator (a family without one reads neither).
+template <class F, bool OBS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP, ITV>& t, const float4 (&w)[SG], float4 (&acc)[SG],
                                              float& ell, float* wl, int lane, int64_t rows_left, bool has_v,
-                                             const GlmGroupArgs* ga = nullptr, int64_t row0 = 0,
-                                             const GlmDisp* dp = nullptr, float* T = nullptr) {
+                                             const GlmDisp* dp, float* T, const GlmGroupArgs* ga = nullptr,
+                                             int64_t row0 = 0) {
     // 1. per-lane partial dots, row by row, into this lane's row of the buffer
     float* mine = wl + lane * G8::PSTR;
 #pragma unroll
@@ -406,26 +174,22 @@ __device__ __forceinline__ void compute_tile(const GlmTile<OBS, GRP, ITV>& t, co
     const float t1 = swap_add32(s4.y, s4.w);
     const float logit = swap_add16(t0, t1);
     const int val = lane_value<ROWS>(lane);
-    float resid;
+    float l = logit;     // l = logit [+ intercept] [+ offset], then what the tile carries of the row
+    if constexpr (GRP) l += t.bz;
+    if constexpr (OBS) l += t.ov;
+    GlmRow row;
+    row.y = t.yv;
+    row.real = (int64_t)(val >> 3) < rows_left;
+    if constexpr (OBS) row.v = has_v ? t.vv : 1.0f;
+    if constexpr (ITV) row.u = t.uv;
+    const float resid = glm_link<F, OBS, ITV>(l, row, ell, dp, T);
     if constexpr (GRP) {
-        // (dp and T are null without DSP, and a link without a dispersion never reads them)
-        resid = glm_link<LINK, true>(logit + t.bz + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell,
-                                     has_v ? t.vv : 1.0f, dp, T);
         // row row0 + (val >> 3) of block row0 >> 4, draw val & 7; nothing lands from the block r_blocks on
         const int64_t blk = row0 >> 4;
         auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(resid), rs,
                                               4 * ((val & 7) * 16 + (int)(row0 & 8) + (val >> 3)), 0, 0);
-    } else if constexpr (ITV)
-        resid = glm_link<LINK, true, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell,
-                                           has_v ? t.vv : 1.0f, dp, T, t.uv);
-    else if constexpr (DSP)
-        resid = glm_link<LINK, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell, has_v ? t.vv : 1.0f,
-                                     dp, T);
-    else if constexpr (OBS)
-        resid = glm_link<LINK, true>(logit + t.ov, t.yv, (int64_t)(val >> 3) < rows_left, ell, has_v ? t.vv : 1.0f);
-    else
-        resid = glm_link<LINK>(logit, t.yv, (int64_t)(val >> 3) < rows_left, ell);
+    }
     float* rb = wl + BSC_WAVE * G8::PSTR;
     rb[val] = resid;
     wave_lds_sync();
@@ -457,18 +221,16 @@ __device__ __forceinline__ void write_block_partial(const float* lds, float* __r
 
 // FULL: D == 256.  n_iter: tiles per wave (the same for every wave; tiles past the end read zeros).
 // o, v_: the offset and the weight, each may be null; read only where OBS.
-// DSP: logphi [S] (this launch's chunk of the dispersion draws); the slab is NB_SLAB_STRIDE floats per block.
-// ITV (with DSP and LINK = GLM_WEIBULL): `upper` [B], not null, rides in the tiles next to y.
-template <int LINK, bool FULL, bool OBS, bool GRP = false, bool DSP = false, bool ITV = false>
+// F::SCALAR: logphi [S] (this launch's chunk of the scalar's draws); the slab is NB_SLAB_STRIDE floats per block.
+// ITV (a scalar family whose link takes it, without groups): `upper` [B], not null, rides in the tiles next to y.
+template <class F, bool FULL, bool OBS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const float* y, const float* o,
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
                                               int n_iter, const GlmGroupArgs* ga = nullptr,
                                               const float* logphi = nullptr, const float* upper = nullptr) {
-    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL || LINK == GLM_BETA)),
-                  "the dispersion (the shape) rides with OBS and its own link");
-    static_assert(!ITV || (DSP && !GRP && LINK == GLM_WEIBULL),
-                  "the upper end rides with the Weibull shape, without groups");
-    constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
+    static_assert(!F::SCALAR || OBS, "the dispersion (the shape) rides with OBS");
+    static_assert(!ITV || (F::SCALAR && !GRP), "the upper end rides with a learned shape, without groups");
+    constexpr int STRIDE = F::SCALAR ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (G8::WAVE_LDS > STRIDE ? G8::WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
@@ -476,9 +238,9 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float* wl = lds + wave * G8::WAVE_LDS;
     const bool has_v = OBS && v_ != nullptr;
-    GlmDisp dp;
+    GlmDisp dp;          // (dp and tacc: untouched without F::SCALAR)
     float tacc = 0.f;
-    if constexpr (DSP) dp = glm_disp_of<LINK>(logphi, lane_value<ROWS>(lane) & 7, S);   // before anything fills the file
+    if constexpr (F::SCALAR) dp = F::glm_disp(logphi, lane_value<ROWS>(lane) & 7, S);   // before anything fills the file
 
     float4 w[SG], acc[SG];
 #pragma unroll
@@ -495,41 +257,33 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     if constexpr (GRP) {
         // the same rotation; every tile's gather goes out before the loads of the tile after it
         const int* g_ = ga->g;
-        const GlmDisp* dq = DSP ? &dp : nullptr;   // (null without DSP, as the defaults of compute_tile are)
-        float* tq = DSP ? &tacc : nullptr;
         GlmTile<OBS, GRP> ta, tb;
         load_tile<FULL, OBS, GRP>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane, g_);
         for (int k = 0; k + 1 < n_iter; k += 2) {
             gather_tile(ta, *ga, lane);
             load_tile<FULL, OBS, GRP>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane, g_);
-            compute_tile<LINK, OBS, GRP, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS, dq,
-                                              tq);
+            compute_tile<F, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, &dp, &tacc, ga, tile * ROWS);
             gather_tile(tb, *ga, lane);
             load_tile<FULL, OBS, GRP>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane, g_);
-            compute_tile<LINK, OBS, GRP, DSP>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, ga,
-                                              (tile + stride) * ROWS, dq, tq);
+            compute_tile<F, OBS>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, &dp, &tacc, ga,
+                                 (tile + stride) * ROWS);
             tile += 2 * stride;
         }
         if (n_iter & 1) {
             gather_tile(ta, *ga, lane);
-            compute_tile<LINK, OBS, GRP, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, ga, tile * ROWS, dq,
-                                              tq);
+            compute_tile<F, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, &dp, &tacc, ga, tile * ROWS);
         }
-    } else {   // (dp and tacc: untouched without DSP)
+    } else {
         GlmTile<OBS, false, ITV> ta, tb;
         load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, tile * ROWS, B, D, lane, nullptr, upper);
         for (int k = 0; k + 1 < n_iter; k += 2) {
             load_tile<FULL, OBS>(tb, X, ldx, y, o, v_, (tile + stride) * ROWS, B, D, lane, nullptr, upper);
-            compute_tile<LINK, OBS, false, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, nullptr, 0, &dp,
-                                                &tacc);
+            compute_tile<F, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, &dp, &tacc);
             load_tile<FULL, OBS>(ta, X, ldx, y, o, v_, (tile + 2 * stride) * ROWS, B, D, lane, nullptr, upper);
-            compute_tile<LINK, OBS, false, DSP>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, nullptr,
-                                                0, &dp, &tacc);
+            compute_tile<F, OBS>(tb, w, acc, ell, wl, lane, B - (tile + stride) * ROWS, has_v, &dp, &tacc);
             tile += 2 * stride;
         }
-        if (n_iter & 1)
-            compute_tile<LINK, OBS, false, DSP>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, nullptr, 0, &dp,
-                                                &tacc);
+        if (n_iter & 1) compute_tile<F, OBS>(ta, w, acc, ell, wl, lane, B - tile * ROWS, has_v, &dp, &tacc);
     }
 
     __syncthreads();  // every wave is done with its private region
@@ -542,7 +296,7 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     ev += __shfl_xor(ev, 4);
     ev += __shfl_xor(ev, 8);
     if ((lane & 14) == 0) ep[SLAB_G + (lane_value<ROWS>(lane) & 7)] = ev;
-    if constexpr (DSP) {   // T folds like ell
+    if constexpr (F::SCALAR) {   // T folds like ell
         float tv = tacc;
         tv += __shfl_xor(tv, 2);
         tv += __shfl_xor(tv, 4);
@@ -617,16 +371,14 @@ __device__ __forceinline__ void load_mtile(MTile<OBS, GRP, ITV>& t, const float*
     if constexpr (ITV) t.uv = load_rows4(u_, B, row0, lane);
 }
 
-template <int LINK, bool OBS, bool GRP = false, bool DSP = false, bool ITV = false>
+template <class F, bool OBS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, const float* y, const float* o,
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
                                                    int n_iter, const GlmGroupArgs* ga = nullptr,
                                                    const float* logphi = nullptr, const float* upper = nullptr) {
-    static_assert(!DSP || (OBS && (LINK == GLM_NEGBIN || LINK == GLM_GAMMA || LINK == GLM_WEIBULL || LINK == GLM_BETA)),
-                  "the dispersion (the shape) rides with OBS and its own link");
-    static_assert(!ITV || (DSP && !GRP && LINK == GLM_WEIBULL),
-                  "the upper end rides with the Weibull shape, without groups");
-    constexpr int STRIDE = DSP ? NB_SLAB_STRIDE : SLAB_STRIDE;
+    static_assert(!F::SCALAR || OBS, "the dispersion (the shape) rides with OBS");
+    static_assert(!ITV || (F::SCALAR && !GRP), "the upper end rides with a learned shape, without groups");
+    constexpr int STRIDE = F::SCALAR ? NB_SLAB_STRIDE : SLAB_STRIDE;
     constexpr int LDS_FLOATS = PASS_WAVES * (MT_WAVE_LDS > STRIDE ? MT_WAVE_LDS : STRIDE);
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     const int tid = threadIdx.x;
@@ -638,7 +390,7 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     const bool has_v = OBS && v_ != nullptr;
     GlmDisp dp;
     float tacc = 0.f;
-    if constexpr (DSP) dp = glm_disp_of<LINK>(logphi, i16, S);   // lane (i16, kq) owns draw i16 (live lanes: i16 < 8)
+    if constexpr (F::SCALAR) dp = F::glm_disp(logphi, i16, S);   // lane (i16, kq) owns draw i16 (live lanes: i16 < 8)
 
     // forward B operand: W[draw i16][64 kq + 4 j + c]; MFMA columns 8 .. 15 and draws >= S are zero.  Lane group
     // kq contracts columns 64 kq .. 64 kq + 63, which keeps the 16-byte A reads of a lane group conflict-free.
@@ -711,14 +463,31 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
         // register reg of lane (i16, kq) = logit(row 4 kq + reg, draw i16): the link in the lane, the residuals
         // to rb[draw][row] as one 16-byte store per live lane
         if (live) {
-            float r0, r1, r2, r3;
+            // row 4 kq + k: l = logit [+ intercept] [+ offset], and what the tile carries of the row.  Both are made
+            // HERE and not inside a function around the link: behind one, the compiler moves l's last addition into
+            // a link's selects.
+            const auto logit = [](float l, float b, float o_) {
+                if constexpr (GRP) l += b;
+                if constexpr (OBS) l += o_;
+                return l;
+            };
+            const auto row = [](float y_, float v, float u, bool real) {
+                GlmRow r;
+                r.y = y_;
+                r.real = real;
+                if constexpr (OBS) r.v = v;
+                if constexpr (ITV) r.u = u;
+                return r;
+            };
+            const float r0 = glm_link<F, OBS, ITV>(logit(d0[0] + d1[0], bz.x, ov.x), row(yv.x, vv.x, uv.x, rows_left > 0),
+                                                   ell, &dp, &tacc);
+            const float r1 = glm_link<F, OBS, ITV>(logit(d0[1] + d1[1], bz.y, ov.y), row(yv.y, vv.y, uv.y, rows_left > 1),
+                                                   ell, &dp, &tacc);
+            const float r2 = glm_link<F, OBS, ITV>(logit(d0[2] + d1[2], bz.z, ov.z), row(yv.z, vv.z, uv.z, rows_left > 2),
+                                                   ell, &dp, &tacc);
+            const float r3 = glm_link<F, OBS, ITV>(logit(d0[3] + d1[3], bz.w, ov.w), row(yv.w, vv.w, uv.w, rows_left > 3),
+                                                   ell, &dp, &tacc);
             if constexpr (GRP) {
-                const GlmDisp* dq = DSP ? &dp : nullptr;   // (null without DSP, as the defaults of glm_link are)
-                float* tq = DSP ? &tacc : nullptr;
-                r0 = glm_link<LINK, true>(d0[0] + d1[0] + bz.x + ov.x, yv.x, rows_left > 0, ell, vv.x, dq, tq);
-                r1 = glm_link<LINK, true>(d0[1] + d1[1] + bz.y + ov.y, yv.y, rows_left > 1, ell, vv.y, dq, tq);
-                r2 = glm_link<LINK, true>(d0[2] + d1[2] + bz.z + ov.z, yv.z, rows_left > 2, ell, vv.z, dq, tq);
-                r3 = glm_link<LINK, true>(d0[3] + d1[3] + bz.w + ov.w, yv.w, rows_left > 3, ell, vv.w, dq, tq);
                 // block row0 / 16 of R, [draw][row]: nothing lands from the block r_blocks on
                 const int64_t blk = row0_of(p) >> 4;
                 auto rs = bsc_vec_rsrc(ga->R, ga->r_blocks * R_BLOCK, blk * R_BLOCK);
@@ -726,26 +495,6 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
                 __builtin_amdgcn_raw_buffer_store_b128(
                     u32x4{__float_as_uint(r0), __float_as_uint(r1), __float_as_uint(r2), __float_as_uint(r3)}, rs,
                     4 * (i16 * MT_ROWS + 4 * kq), 0, 0);
-            } else if constexpr (ITV) {
-                r0 = glm_link<LINK, true, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x, &dp, &tacc, uv.x);
-                r1 = glm_link<LINK, true, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y, &dp, &tacc, uv.y);
-                r2 = glm_link<LINK, true, true>(d0[2] + d1[2] + ov.z, yv.z, rows_left > 2, ell, vv.z, &dp, &tacc, uv.z);
-                r3 = glm_link<LINK, true, true>(d0[3] + d1[3] + ov.w, yv.w, rows_left > 3, ell, vv.w, &dp, &tacc, uv.w);
-            } else if constexpr (DSP) {
-                r0 = glm_link<LINK, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x, &dp, &tacc);
-                r1 = glm_link<LINK, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y, &dp, &tacc);
-                r2 = glm_link<LINK, true>(d0[2] + d1[2] + ov.z, yv.z, rows_left > 2, ell, vv.z, &dp, &tacc);
-                r3 = glm_link<LINK, true>(d0[3] + d1[3] + ov.w, yv.w, rows_left > 3, ell, vv.w, &dp, &tacc);
-            } else if constexpr (OBS) {
-                r0 = glm_link<LINK, true>(d0[0] + d1[0] + ov.x, yv.x, rows_left > 0, ell, vv.x);
-                r1 = glm_link<LINK, true>(d0[1] + d1[1] + ov.y, yv.y, rows_left > 1, ell, vv.y);
-                r2 = glm_link<LINK, true>(d0[2] + d1[2] + ov.z, yv.z, rows_left > 2, ell, vv.z);
-                r3 = glm_link<LINK, true>(d0[3] + d1[3] + ov.w, yv.w, rows_left > 3, ell, vv.w);
-            } else {
-                r0 = glm_link<LINK>(d0[0] + d1[0], yv.x, rows_left > 0, ell);
-                r1 = glm_link<LINK>(d0[1] + d1[1], yv.y, rows_left > 1, ell);
-                r2 = glm_link<LINK>(d0[2] + d1[2], yv.z, rows_left > 2, ell);
-                r3 = glm_link<LINK>(d0[3] + d1[3], yv.w, rows_left > 3, ell);
             }
             *reinterpret_cast<float4*>(rb + i16 * MT_ROWS + 4 * kq) = make_float4(r0, r1, r2, r3);
         }
@@ -787,7 +536,7 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     ev += __shfl_xor(ev, 16);
     ev += __shfl_xor(ev, 32);
     if (lane < SG) ep[SLAB_G + lane] = ev;
-    if constexpr (DSP) {
+    if constexpr (F::SCALAR) {
         float tv = live ? tacc : 0.f;
         tv += __shfl_xor(tv, 16);
         tv += __shfl_xor(tv, 32);
@@ -853,7 +602,7 @@ int for_draw_chunks(bsc_ctx* ctx, int S, Pass pass, Reduce reduce) {
     return for_draw_chunks(ctx, S, pass, reduce, [](int) { return (int)BSC_OK; });
 }
 
-// (The data pass of the DSP routes, kernels and host side: csrc/bsc_scalar_family.h.)
+// (The data pass of the scalar families, kernels and host side: csrc/bsc_scalar_family.h.)
 
 }  // namespace
 

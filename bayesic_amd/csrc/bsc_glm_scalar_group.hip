@@ -1,9 +1,9 @@
 // Random intercepts for the regression families with a learned scalar -- the negative binomial's dispersion, the Gamma
 // shape, the Weibull shape with right censoring -- on the fused pathwise pass: csrc/bsc_glm_pass.h's bodies with the
-// group flag AND the dispersion flag on, the per-group sums of the residuals (csrc/bsc_group_sum.h), and the finish for
-// the latent z = [w (D) | b (J) | zeta | tau].
+// group flag on and a scalar family (csrc/bsc_families.h; with_scalar_family maps the public id to it), the per-group
+// sums of the residuals (csrc/bsc_group_sum.h), and the finish for the latent z = [w (D) | b (J) | zeta | tau].
 //
-//     l[n,s] = x_n . w_s + b_s[g_n] + o_n            y_n ~ F(l_ns, e^{tau_s})        (the links of glm_link, unchanged)
+//     l[n,s] = x_n . w_s + b_s[g_n] + o_n            y_n ~ F(l_ns, e^{tau_s})        (the families' links, unchanged)
 //     ell[s], G[s,:] = sum_n r_ns x_n, T[s] = d ell[s] / d tau_s       as csrc/bsc_scalar_family.h's passes leave them
 //     H[s,j] = sum_{n : g_n = j} r_ns                                  as csrc/bsc_glm_group.hip's pass leaves it
 // The intercept enters through l alone, so a link sees nothing new: the GRP branches of the bodies hand it the draw's
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_scalar_group_pass_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, int64_t B, int D, const float* __restrict__ W, const float* __restrict__ logtau, int S,
     float* __restrict__ slab, int n_iter, GlmGroupArgs ga) {
-    glm_pass_body<LINK, FULL, true, true, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, &ga, logtau);
+    glm_pass_body<GlmFamily<LINK>, FULL, true, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, &ga, logtau);
 }
 
 template <int LINK>
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void glm_scalar_group_pass_mfma_kern
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, int64_t B, const float* __restrict__ W, const float* __restrict__ logtau, int S,
     float* __restrict__ slab, int n_iter, GlmGroupArgs ga) {
-    glm_pass_mfma_body<LINK, true, true, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, &ga, logtau);
+    glm_pass_mfma_body<GlmFamily<LINK>, true, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, &ga, logtau);
 }
 
 __global__ __launch_bounds__(RED_BLOCK) void glm_scalar_group_slab_reduce_kernel(
@@ -125,10 +125,11 @@ __global__ __launch_bounds__(MF_BLOCK) void glm_scalar_hier_coord_kernel(HierSca
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-template <int LINK>
+template <class F>
 void launch_scalar_group_link(bsc_ctx* ctx, int rows, const float* X, int64_t ldx, const float* y, const float* o,
                               const float* v, int64_t B, int D, const float* W, const float* logtau, int sg, PassGrid g,
                               float* slab, const GlmGroupArgs& ga) {
+    constexpr int LINK = F::GLM_ID;
     const auto go = [&](auto kernel, auto... tail) {
         hipLaunchKernelGGL(kernel, dim3(g.n_blocks), dim3(PASS_BLOCK), 0, ctx->stream, X, ldx, y, o, v, B, tail...);
     };
@@ -137,10 +138,6 @@ void launch_scalar_group_link(bsc_ctx* ctx, int rows, const float* X, int64_t ld
         [&](auto full) {
             go(glm_scalar_group_pass_kernel<LINK, decltype(full)::value>, D, W, logtau, sg, slab, g.n_iter, ga);
         });
-}
-
-inline bool scalar_family_ok(int32_t family) {
-    return family == BSC_SCALAR_NEGBIN || family == BSC_SCALAR_GAMMA || family == BSC_SCALAR_WEIBULL;
 }
 
 }  // namespace
@@ -202,15 +199,10 @@ int bsc_glm_scalar_data_pass_groups(bsc_ctx* ctx, int32_t family, const float* X
         [&](int s0, int sg) {   // each launch with its chunk of the intercepts and of the scalar
             ga.Bz = Bz + (int64_t)(s0 / SG) * J * SG;
             const float *Ws = W + (int64_t)s0 * D, *lp = logtau + s0;
-            if (family == BSC_SCALAR_NEGBIN)
-                launch_scalar_group_link<GLM_NEGBIN>(ctx, rows, X, ldx, y, offset, weight, B, D, Ws, lp, sg, pg, slab,
-                                                     ga);
-            else if (family == BSC_SCALAR_GAMMA)
-                launch_scalar_group_link<GLM_GAMMA>(ctx, rows, X, ldx, y, offset, weight, B, D, Ws, lp, sg, pg, slab,
-                                                    ga);
-            else
-                launch_scalar_group_link<GLM_WEIBULL>(ctx, rows, X, ldx, y, offset, weight, B, D, Ws, lp, sg, pg, slab,
+            with_scalar_family(family, [&](auto f) {
+                launch_scalar_group_link<decltype(f)>(ctx, rows, X, ldx, y, offset, weight, B, D, Ws, lp, sg, pg, slab,
                                                       ga);
+            });
         },
         [&](int s0) {
             hipLaunchKernelGGL(glm_scalar_group_slab_reduce_kernel, rgrid, dim3(RED_BLOCK), 0, ctx->stream,

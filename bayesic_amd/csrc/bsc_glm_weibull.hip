@@ -3,7 +3,7 @@
 // finish for the latent z = [w (D) | tau] (csrc/bsc_meanfield.h's bodies with NbModel -- the prior on the scalar has the
 // negative binomial's form, so the finish is the same), and the predictive (csrc/bsc_predict_pass.h's body and envelope
 // with its sixth family).  The kernels and the host side of the three entry points are csrc/bsc_scalar_family.h's, with
-// GLM_WEIBULL and PREDICT_WEIBULL.
+// the Weibull family (csrc/bsc_families.h).
 //
 //     t_n ~ Weibull(shape k, scale e^{l_n}),   l[n,s] = x_n . w_s + o_n
 //     w ~ N(0, I / prior_precision),   k = e^tau ~ Gamma(a0, b0)
@@ -31,8 +31,8 @@ int bsc_glm_weibull_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const f
                               const float* weight, int64_t B, int32_t D, const float* W, const float* logshape,
                               int32_t S, double* ell, double* G, double* T) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_data_pass<GLM_WEIBULL>(ctx, "bsc_glm_weibull_data_pass", "logshape", X, ldx, y, nullptr,
-                                                offset, weight, B, D, W, logshape, S, ell, G, T);
+    return scalar_family_data_pass<Weibull>(ctx, "bsc_glm_weibull_data_pass", "logshape", X, ldx, y, nullptr, offset,
+                                            weight, B, D, W, logshape, S, ell, G, T);
 }
 
 int bsc_glm_weibull_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
@@ -42,18 +42,17 @@ int bsc_glm_weibull_update(bsc_ctx* ctx, const double* stats, const double* lam_
                            double* eps_next, int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo,
                            double* grad) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_update<GLM_WEIBULL>(ctx, "bsc_glm_weibull_update", stats, lam_in, lam_out, m1, m2, eps, W,
-                                             logshape, D, S, scale, prior_precision, a0, b0, t, lr, beta1, beta2,
-                                             adam_eps, seed, next_step, eps_next, eps_next_ready, W_next, logshape_next,
-                                             elbo, grad);
+    return scalar_family_update<Weibull>(ctx, "bsc_glm_weibull_update", stats, lam_in, lam_out, m1, m2, eps, W,
+                                         logshape, D, S, scale, prior_precision, a0, b0, t, lr, beta1, beta2, adam_eps,
+                                         seed, next_step, eps_next, eps_next_ready, W_next, logshape_next, elbo, grad);
 }
 
 int bsc_weibull_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                              int32_t D, const float* W, const float* logshape, int32_t S, float* mean, float* var,
                              float* lpd, double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
-    return scalar_family_predict_pass<PREDICT_WEIBULL>(ctx, "bsc_weibull_predict_pass", "logshape", X, ldx, y, nullptr,
-                                                       offset, B, D, W, logshape, S, mean, var, lpd, lpd_sum);
+    return scalar_family_predict_pass<Weibull>(ctx, "bsc_weibull_predict_pass", "logshape", X, ldx, y, nullptr, offset,
+                                               B, D, W, logshape, S, mean, var, lpd, lpd_sum);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // the per-draw scalar flag AND the upper-end flag on, their slab reduction, and csrc/bsc_predict_pass.h's body with the
 // interval variant of its sixth family.  The finishes (bsc_glm_weibull_update, bsc_glm_scalar_fullrank_update) see
 // [ell | G | T] alone and are shared as they are.  The kernels and the host side of the two entry points are
-// csrc/bsc_scalar_family.h's `upper` variants (UPPER = true), with GLM_WEIBULL and PREDICT_WEIBULL.
+// csrc/bsc_scalar_family.h's `upper` variants (UPPER = true), with the Weibull family.
 //
 // One more per-row vector, upper [B] float32, next to the signed y of csrc/bsc_glm_weibull.hip:
 //     upper[n] == 0             the row is what y[n] says: y > 0 an event at y, y < 0 right-censored at -y
@@ -17,8 +17,8 @@
 // and a left-censored row the same with E_a = 0, z_a E_a = 0, Delta = E_b:  log P = log(-expm1(-E_b)),
 // d / dl = -k E_b / expm1(E_b),  d / dtau = z_b E_b / expm1(E_b).  Where Delta >= 103 (e^{-Delta} is zero in float32), or
 // e^{k d} is infinite in float32 (upper = 1e30 for "no bound"), the row is the right-censored one at a -- a left-censored
-// one adds nothing -- by selects on the link's inputs (glm_link).  Apart from that the link is NOT clamped: finite while
-// z_a stays below about 88.
+// one adds nothing -- by selects on the link's inputs (csrc/bsc_families.h).  Apart from that the link is NOT clamped:
+// finite while z_a stays below about 88.
 //
 // A translation unit of its own so that every other one keeps its kernels, their names, their count and their code.
 #include "bsc_scalar_family.h"
@@ -31,8 +31,8 @@ int bsc_glm_weibull_data_pass_interval(bsc_ctx* ctx, const float* X, int64_t ldx
     BSC_CHECK_CTX(ctx);
     if (!upper)   // the kernels of csrc/bsc_glm_weibull.hip: the same bits
         return bsc_glm_weibull_data_pass(ctx, X, ldx, y, offset, weight, B, D, W, logshape, S, ell, G, T);
-    return scalar_family_data_pass<GLM_WEIBULL, true>(ctx, "bsc_glm_weibull_data_pass_interval", "logshape", X, ldx, y,
-                                                      upper, offset, weight, B, D, W, logshape, S, ell, G, T);
+    return scalar_family_data_pass<Weibull, true>(ctx, "bsc_glm_weibull_data_pass_interval", "logshape", X, ldx, y,
+                                                  upper, offset, weight, B, D, W, logshape, S, ell, G, T);
 }
 
 int bsc_weibull_predict_pass_interval(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* upper,
@@ -40,9 +40,8 @@ int bsc_weibull_predict_pass_interval(bsc_ctx* ctx, const float* X, int64_t ldx,
                                       int32_t S, float* mean, float* var, float* lpd, double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
     if (!upper) return bsc_weibull_predict_pass(ctx, X, ldx, y, offset, B, D, W, logshape, S, mean, var, lpd, lpd_sum);
-    return scalar_family_predict_pass<PREDICT_WEIBULL, true>(ctx, "bsc_weibull_predict_pass_interval", "logshape", X,
-                                                             ldx, y, upper, offset, B, D, W, logshape, S, mean, var,
-                                                             lpd, lpd_sum);
+    return scalar_family_predict_pass<Weibull, true>(ctx, "bsc_weibull_predict_pass_interval", "logshape", X, ldx, y,
+                                                     upper, offset, B, D, W, logshape, S, mean, var, lpd, lpd_sum);
 }
 
 }  // extern "C"

@@ -31,7 +31,7 @@ namespace {
 // FULL: D == 256 (two strips, 32 columns per lane group, everything unrolled).
 template <int FAM, int NC, bool FULL>
 __global__ __launch_bounds__(P_BLOCK, 2) void predict_kernel(PredictArgs a) {
-    predict_body<FAM, NC, FULL, false>(a, nullptr);
+    predict_body<PredictFamily<FAM>, NC, FULL, false>(a, nullptr);
 }
 
 // lpd_sum = the block partials in block order

@@ -17,7 +17,7 @@ namespace {
 template <int FAM, int NC, bool FULL>
 __global__ __launch_bounds__(P_BLOCK, 2) void predict_group_kernel(PredictArgs a, const float* __restrict__ offset,
                                                                    PredictGroups gr) {
-    predict_body<FAM, NC, FULL, /*OFFS=*/true, /*GRP=*/true>(a, offset, gr);
+    predict_body<PredictFamily<FAM>, NC, FULL, /*OFFS=*/true, /*GRP=*/true>(a, offset, gr);
 }
 
 __global__ __launch_bounds__(BSC_WAVE) void predict_group_sum_kernel(const double* __restrict__ partial, int n,

@@ -8,7 +8,7 @@ namespace {
 
 template <int FAM, int NC, bool FULL>
 __global__ __launch_bounds__(P_BLOCK, 2) void predict_offset_kernel(PredictArgs a, const float* __restrict__ offset) {
-    predict_body<FAM, NC, FULL, true>(a, offset);
+    predict_body<PredictFamily<FAM>, NC, FULL, true>(a, offset);
 }
 
 template <int FAM, int NC>

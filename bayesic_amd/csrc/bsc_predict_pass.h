@@ -1,5 +1,7 @@
-// The body of the predictive pass (csrc/bsc_predict.hip's header comment describes it), as a __device__ template with
-// one compile-time flag so that two translation units can instantiate it: OFFS = false is predict_kernel of
+// The body of the predictive pass (csrc/bsc_predict.hip's header comment describes it), as a __device__ template over
+// the likelihood family F -- a struct of csrc/bsc_families.h, which holds everything a family is: nothing here names one
+// but the ordinal family, which keeps a branch of its own -- and compile-time flags, so that several translation units
+// can instantiate it: OFFS = false is predict_kernel of
 // csrc/bsc_predict.hip, unchanged; OFFS = true is predict_offset_kernel of csrc/bsc_predict_offset.hip, which adds a
 // per-row offset o_n to l_ns = x_n . w_s before the link (logistic and Poisson families: log E[y_n] = x_n . w +
 // log exposure_n).  GRP = true (always with OFFS) is predict_group_kernel of csrc/bsc_predict_group.hip: a per-draw,
@@ -7,35 +9,15 @@
 // below).  With GRP off nothing of it is compiled: the shipped instantiations keep their code.  The host side at the end
 // is the envelope of the entry points (predict_check_batch, predict_setup, predict_launch_chunks), shared by
 // csrc/bsc_predict.hip, csrc/bsc_glm_nb.hip, csrc/bsc_glm_gamma.hip, csrc/bsc_glm_weibull.hip,
-// csrc/bsc_glm_weibull_interval.hip, csrc/bsc_glm_beta.hip, csrc/bsc_glm_ordinal.hip and csrc/bsc_predict_group.hip.  Header-only, internal linkage, like csrc/bsc_regress.h.
+// csrc/bsc_glm_weibull_interval.hip, csrc/bsc_glm_beta.hip, csrc/bsc_glm_ordinal.hip and csrc/bsc_predict_group.hip.
+// Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
-#include "bsc_regress.h"
-#include "bsc_special_f32.h"
+#include "bsc_families.h"
 
 namespace {
 
-// The fourth family, internal: csrc/bsc_glm_nb.hip's scalar_predict_kernel (bsc_nb_predict_pass).  bsc_predict_pass and
-// bsc_predict_pass_offset refuse it.  Always with OFFS (a null offset reads 0 through an empty descriptor); `logvar`
-// carries tau_s = log phi_s.
-constexpr int PREDICT_NEGBIN = 3;
-// The fifth, internal as well: csrc/bsc_glm_gamma.hip's scalar_predict_kernel (bsc_gamma_predict_pass), the Gamma
-// likelihood with a per-draw shape; `logvar` carries tau_s = log alpha_s.  Always with OFFS, the offset may be null.
-constexpr int PREDICT_GAMMA = 4;
-// The sixth, internal as well: csrc/bsc_glm_weibull.hip's scalar_predict_kernel (bsc_weibull_predict_pass), the Weibull
-// likelihood with a per-draw shape and right censoring in the sign of y; `logvar` carries tau_s = log k_s.  Always with
-// OFFS, the offset may be null.
-constexpr int PREDICT_WEIBULL = 5;
-// The seventh, internal as well: csrc/bsc_glm_ordinal.hip's predict_ordinal_kernel (bsc_ordinal_predict_pass), the
-// cumulative-logit likelihood with K - 1 cutpoints per draw.  Always with OFFS, the offset may be null; y holds the bits of
-// int32 labels; the outputs are prob [B, K] (PredictOrdinal below) and lpd, no mean and no var.
-constexpr int PREDICT_ORDINAL = 6;
-constexpr int P_ORD_K = 8;                     // classes at most
-// The eighth, internal as well: csrc/bsc_glm_beta.hip's scalar_predict_kernel (bsc_beta_predict_pass), the Beta
-// likelihood in its mean / precision form with a per-draw precision; `logvar` carries tau_s = log phi_s.  Always with
-// OFFS, the offset may be null.
-constexpr int PREDICT_BETA = 7;
-
+constexpr int P_ORD_K = 8;                     // classes of the ordinal family at most
 constexpr int P_BLOCK = 512;
 constexpr int P_WAVES = P_BLOCK / BSC_WAVE;
 constexpr int T_ROWS = 16;                     // rows per tile = the MFMA's N
@@ -43,7 +25,6 @@ constexpr int STRIP = 128;                     // columns per strip
 constexpr int XS = STRIP + 2;                  // LDS row stride of a strip (floats)
 constexpr int WCOLS = 256;                     // column capacity
 constexpr int WS = WCOLS + 2;                  // LDS row stride of the draws
-constexpr int P_MAX_S = 64;
 constexpr int LD_STRIP = STRIP * T_ROWS / (4 * BSC_WAVE);   // 16-byte loads per lane and strip: 8
 
 typedef float p_f32x4 __attribute__((ext_vector_type(4)));
@@ -54,8 +35,7 @@ struct PredictArgs {
     const float* y;          // may be null
     int64_t B;
     const float* W;
-    const float* logvar;     // Gaussian: log s2 per draw; PREDICT_NEGBIN: log phi per draw; PREDICT_GAMMA: log alpha;
-                             // PREDICT_WEIBULL: log k; PREDICT_BETA: log phi
+    const float* logvar;     // F::PER_DRAW: the family's scalar per draw (Gaussian: log s2; a scalar family: tau)
     float* mean;            // outputs, each may be null
     float* var;
     float* lpd;
@@ -133,125 +113,6 @@ __device__ __forceinline__ void load_intercepts(p_f32x4 (&bt)[NC], const Predict
     }
 }
 
-// mu, v and log p(y | l) of one draw.  p4 = (logvar, exp(logvar), exp(-logvar)) for the Gaussian family.
-// Logistic: csrc/bsc_glm.hip's stable forms from e = exp(-|l|) <= 1 -- sigmoid = 1 / (1 + e) or e / (1 + e),
-// v = mu (1 - mu) = e / (1 + e)^2 without the cancellation, softplus = max(l, 0) + log1p(e) with log1p(e) =
-// log(t) e / (t - 1), t = 1 + e (the quotient undoes the rounding of t): finite for every finite l.
-// Poisson: exp(l), not clamped; the row constant lnGamma(y + 1) is taken off after the log-mean-exp.
-// PREDICT_NEGBIN: p4 = (tau, phi = exp(tau), 1 / phi) and lgp = lnGamma(phi).  mu = exp(l) (not clamped),
-// v = mu + mu^2 / phi; log p from the logistic forms at u = l - tau, finite for every finite l:
-// lnGamma(y + phi) - lnGamma(phi) + y u - (y + phi) softplus(u), the difference exactly 0 at y = 0; the row
-// constant lnGamma(y + 1) is taken off after the log-mean-exp.
-// PREDICT_GAMMA: p4 = (tau, alpha = exp(tau), 1 / alpha) and lgp = c_a = alpha log alpha - lnGamma(alpha).
-// mu = exp(l) (not clamped), v = mu^2 / alpha; log p = c_a + alpha (log y - l - y e^{-l}) - log y, the full density
-// (csrc/bsc_glm_pass.h's forms: the exponential as the product y e^{-l}); y > 0 is the caller's to see to.
-// PREDICT_WEIBULL: p4 = (tau, k = exp(tau), g1 = Gamma(1 + 1/k)) and lgp = g2 = Gamma(1 + 2/k) - Gamma(1 + 1/k)^2, both
-// made once per launch in float64 (the exp(-logvar) slot is not needed and carries g1).  l is the log SCALE:
-// mu = e^l g1, v = e^{2l} g2 (not clamped); with t = |y|, z = k (log t - l):  log p = tau + z - log t - e^z for y > 0 (an
-// event at y), log p = -e^z for y < 0 (right-censored at -y: the log survival), so the lpd of a censored row is the log of
-// the posterior-predictive survival probability.  y = 0 is the caller's to keep out.
-// FLOAT32 ENVELOPE OF THE MOMENTS: Gamma(1 + 2/k) overflows float32 near k = 0.06 (tau = -2.8); accuracy envelope tau in
-// [-2, 4].  g2 is a difference of float64 values, 5e-4 at tau = 4: no digit of the float32 result is lost to it.
-// PREDICT_BETA: p4 = (tau, phi = exp(tau), 1 / (1 + phi)) and lgp = lnGamma(phi), both made once per launch in float64.
-// mu = m = sigmoid(l), v = m (1 - m) / (1 + phi) with m (1 - m) = e / (1 + e)^2; log p = lnGamma(phi) - lnGamma(a) -
-// lnGamma(b) + (a - 1) log y + (b - 1) log1p(-y), a = m phi, b = (1 - m) phi, the full density in csrc/bsc_glm_pass.h's
-// forms (m and 1 - m each from the stable logistic form, bsc_lgamma_psi_f32 whose psi half folds away); 0 < y < 1 is
-// the caller's to see to.
-template <int FAM>
-__device__ __forceinline__ void predict_link(float l, float yv, float lv, float ev, float iv, float& mu, float& v,
-                                             float& lp, float lgp = 0.0f) {
-    if constexpr (FAM == PREDICT_NEGBIN) {
-        mu = expf(l);
-        v = fmaf(mu * iv, mu, mu);
-        const float u = l - lv;
-        const float e = expf(-fabsf(u));
-        const float t = 1.0f + e;
-        const float l1p = t == 1.0f ? e : logf(t) * e / (t - 1.0f);
-        float dlg, dps;
-        bsc_dlgamma_dpsi_f32(yv, ev, lgp, 0.0f, dlg, dps);      // (dpsi is not used and folds away)
-        lp = dlg + fmaf(yv, u, -(yv + ev) * (fmaxf(u, 0.0f) + l1p));
-        return;
-    }
-    if constexpr (FAM == PREDICT_GAMMA) {
-        mu = expf(l);
-        v = mu * iv * mu;
-        const float ly = logf(yv);
-        lp = fmaf(ev, (ly - l) - yv * expf(-l), lgp) - ly;
-        return;
-    }
-    if constexpr (FAM == PREDICT_WEIBULL) {
-        const float el = expf(l);
-        mu = el * iv;
-        v = el * lgp * el;
-        const float ly = logf(fabsf(yv));
-        const float z = ev * (ly - l);
-        const float ez = expf(z);
-        lp = yv > 0.0f ? ((lv + z) - ly) - ez : -ez;
-        return;
-    }
-    if constexpr (FAM == PREDICT_BETA) {
-        const float e = expf(-fabsf(l));
-        const float r = __builtin_amdgcn_rcpf(1.0f + e);
-        const float er = e * r;
-        const bool pos = l >= 0.0f;
-        const float m = pos ? r : er, m1 = pos ? er : r;
-        mu = m;
-        v = er * r * iv;
-        const float ly = logf(yv);
-        const float w = 1.0f - yv;
-        const bool one = w == 1.0f;
-        const float l1y = fmaf(logf(w), yv * __builtin_amdgcn_rcpf(one ? 1.0f : 1.0f - w), one ? -yv : 0.0f);
-        const float a = m * ev, b = m1 * ev;
-        float lga, psa, lgb, psb;                               // (psi is not used and folds away)
-        bsc_lgamma_psi_f32(a, lga, psa);
-        bsc_lgamma_psi_f32(b, lgb, psb);
-        lp = ((lgp - lga) - lgb) + fmaf(a - 1.0f, ly, (b - 1.0f) * l1y);
-        return;
-    }
-    if (FAM == BSC_PREDICT_GAUSSIAN) {
-        const float r = yv - l;
-        mu = l;
-        v = ev;
-        lp = fmaf(-0.5f * iv * r, r, -0.5f * (lv + (float)BSC_LOG_2PI));
-    } else if (FAM == BSC_PREDICT_LOGISTIC) {
-        const float e = expf(-fabsf(l));
-        const float t = 1.0f + e;
-        const float r = 1.0f / t;
-        mu = l >= 0.0f ? r : e * r;
-        v = e * r * r;
-        const float l1p = t == 1.0f ? e : logf(t) * e / (t - 1.0f);
-        lp = fmaf(yv, l, -(fmaxf(l, 0.0f) + l1p));
-    } else {
-        mu = expf(l);
-        v = mu;
-        lp = fmaf(yv, l, -mu);
-    }
-}
-
-// PREDICT_WEIBULL with interval and left censoring (csrc/bsc_glm_weibull_interval.hip): `uv` is the row's entry of
-// `upper`, read as csrc/bsc_glm_pass.h's glm_link reads it (0: what y says; > 0: the interval (-y, uv]; < 0: left-censored
-// at -uv), the same forms and the same overflow rule: log p = -E_a + log(-expm1(-Delta)), the log of the row's
-// probability, so its lpd is the log of the draw average of that probability.  mu and v do not depend on the row's kind.
-__device__ __forceinline__ void predict_link_weibull_itv(float l, float yv, float uv, float lv, float ev, float iv,
-                                                         float& mu, float& v, float& lp, float lgp) {
-    const float el = expf(l);
-    mu = el * iv;
-    v = el * lgp * el;
-    const bool left = uv < 0.0f, itv = uv > 0.0f;
-    const float tq = fabsf(left ? uv : yv);
-    const float bq = itv ? uv : tq;
-    const float ly = logf(tq);
-    const float z = ev * (ly - l);
-    const float ez = expf(z);
-    const float kd = ev * bsc_logratio_f32(bq, tq, ly);    // exactly 0 unless the row is an interval
-    const float dlt = ez * (bsc_expm1_f32(kd) + (left ? 1.0f : 0.0f));   // expm1(0) = 0 on a left-censored row
-    const bool on = (left || itv) && dlt < ITV_BIG;         // false for a NaN as well
-    const float dq = on ? dlt : 1.0f;
-    const float ea = left ? 0.0f : ez;
-    const float lpc = fmaf(on ? 1.0f : 0.0f, logf(-bsc_expm1_f32(-dq)), -ea);
-    lp = (uv == 0.0f && yv > 0.0f) ? ((lv + z) - ly) - ez : lpc;
-}
-
 // PREDICT_ORDINAL: what the family needs besides PredictArgs.  The draws are a.W = Z [S, ldz] with the weights in
 // columns 0 .. D-1 and theta_0 = c_0, theta_j = log(c_j - c_{j-1}) behind them (4-byte aligned).
 struct PredictOrdinal {
@@ -307,27 +168,24 @@ __device__ __forceinline__ float predict_link_ordinal(float l, const float (&cut
 }
 
 // FULL: D == 256 (two strips, 32 columns per lane group, everything unrolled).
-// PREDICT_ORDINAL (with OFFS; a null offset reads 0): `od` says where prob goes and how the draws are laid out; everything
-// of it is behind `if constexpr`, and with another family nothing of it is compiled.
+// The ordinal family (with OFFS; a null offset reads 0): `od` says where prob goes and how the draws are laid out;
+// everything of it is behind `if constexpr`, and with another family nothing of it is compiled.
 // OFFS: `offset` [B] (not null) is loaded like y and added to every draw's l of its row before the link.
 // GRP (with OFFS; a null offset reads 0): the tile's ids are loaded with its y and offset, at `last` of the tile before;
 // its intercepts are requested at the top of its first strip, ahead of that strip's LDS store, and land behind the
 // tile's MFMAs.  Both loads are unconditional within their (wave-uniform) branch, so the X prefetch stays in flight.
-// ITV (PREDICT_WEIBULL with OFFS): `upper` [B] (not null) is loaded like y and the offset; with the flag off nothing of
-// it is compiled.
-template <int FAM, int NC, bool FULL, bool OFFS, bool GRP = false, bool ITV = false>
+// ITV (a family whose link takes upper ends, with OFFS): `upper` [B] (not null) is loaded like y and the offset; with the
+// flag off nothing of it is compiled.
+template <class F, int NC, bool FULL, bool OFFS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset, PredictGroups gr = PredictGroups{},
                                              const float* upper = nullptr, PredictOrdinal od = PredictOrdinal{}) {
     static_assert(!GRP || OFFS, "the grouped body adds its intercept next to the offset");
-    static_assert(!ITV || (FAM == PREDICT_WEIBULL && OFFS && !GRP), "the upper end belongs to the Weibull family");
-    constexpr bool ORD = FAM == PREDICT_ORDINAL;
+    static_assert(!ITV || (F::UPPER && OFFS && !GRP), "the upper end belongs to a family whose link takes one");
+    constexpr bool ORD = F::PREDICT_ID == PREDICT_ORDINAL;
     static_assert(!ORD || (OFFS && !GRP && !ITV), "the ordinal family takes an offset and nothing else");
     constexpr int W_FLOATS = NC * 16 * WS;
     constexpr int X_FLOATS = P_WAVES * T_ROWS * XS;
-    constexpr bool OWN4 = FAM == PREDICT_NEGBIN || FAM == PREDICT_GAMMA || FAM == PREDICT_WEIBULL ||
-                          FAM == PREDICT_BETA;                                                        // a fourth value
-    constexpr bool PER_DRAW = FAM == BSC_PREDICT_GAUSSIAN || OWN4;        // a scalar rides with every draw
-    constexpr int GP_SLOTS = OWN4 ? 4 : 3;                                 // ... and lnGamma(phi), or c_a
+    constexpr int GP_SLOTS = F::SCALAR ? 4 : 3;                           // F::predict_slots fills them, F::PER_DRAW
     constexpr int ORD_FLOATS = ORD ? 2 * P_ORD_K * P_MAX_S : 0;           // the cutpoints and log(-expm1(-g)), [draw][class]
     __shared__ __attribute__((aligned(16))) float lds[W_FLOATS + X_FLOATS + GP_SLOTS * P_MAX_S + ORD_FLOATS];
     __shared__ double red[P_WAVES];
@@ -337,7 +195,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     const int i16 = lane & 15, kq = lane >> 4;
     float* wl = lds;                                    // draws [16 NC][WS], zero-padded
     float* xl = lds + W_FLOATS + wave * (T_ROWS * XS);  // this wave's strip [16][XS]
-    float* gp = lds + W_FLOATS + X_FLOATS;              // logvar | exp(logvar) | exp(-logvar), [64] each
+    float* gp = lds + W_FLOATS + X_FLOATS;              // the family's slots, [64] each
     [[maybe_unused]] float* ct = gp + GP_SLOTS * P_MAX_S;   // ORD: c_k, [64][8]
     [[maybe_unused]] float* lt = ct + P_ORD_K * P_MAX_S;    // ORD: log(-expm1(-g_k)), [64][8]
     const int S = a.S, D = a.D;
@@ -347,25 +205,11 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
             wl[row * WS + col] = (row < S && col < D) ? a.W[(int64_t)row * (ORD ? od.ldz : (int64_t)D) + col] : 0.f;
     if constexpr (ORD) predict_ordinal_tables(ct, lt, a, od, tid);
     if (tid < P_MAX_S) {
-        const float lv = (PER_DRAW && tid < S) ? a.logvar[tid] : 0.f;
-        gp[tid] = lv;
-        gp[P_MAX_S + tid] = expf(lv);
-        gp[2 * P_MAX_S + tid] = expf(-lv);
-        if constexpr (FAM == PREDICT_NEGBIN) gp[3 * P_MAX_S + tid] = (float)bsc_lgamma_f64((double)expf(lv));
-        if constexpr (FAM == PREDICT_GAMMA) {
+        const float lv = (F::PER_DRAW && tid < S) ? a.logvar[tid] : 0.f;
+        F::predict_slots(gp, tid, lv);
+        if constexpr (F::PREDICT_ID == Gamma::PREDICT_ID) {   // (csrc/bsc_families.h says why this one slot is made here)
             const double al = (double)expf(lv);
             gp[3 * P_MAX_S + tid] = (float)(al * log(al) - bsc_lgamma_f64(al));
-        }
-        if constexpr (FAM == PREDICT_WEIBULL) {   // Gamma(1 + 1/k) in the exp(-logvar) slot, the variance factor behind
-            const double ik = 1.0 / (double)expf(lv);
-            const double g1 = exp(bsc_lgamma_f64(1.0 + ik));
-            gp[2 * P_MAX_S + tid] = (float)g1;
-            gp[3 * P_MAX_S + tid] = (float)(exp(bsc_lgamma_f64(1.0 + 2.0 * ik)) - g1 * g1);
-        }
-        if constexpr (FAM == PREDICT_BETA) {      // 1 / (1 + phi) in the exp(-logvar) slot, the variance factor
-            const double ph = (double)expf(lv);
-            gp[2 * P_MAX_S + tid] = (float)(1.0 / (1.0 + ph));
-            gp[3 * P_MAX_S + tid] = (float)bsc_lgamma_f64(ph);
         }
     }
     __syncthreads();
@@ -390,7 +234,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     load_strip(t, a, row0_of(0), 0, lane);
     float y_cur = load_y(a, row0_of(0), i16);
     float o_cur = 0.f;
-    [[maybe_unused]] const int64_t o_rows = ((OWN4 || GRP || ORD) && !offset) ? 0 : a.B;   // a null offset: no records, reads 0
+    [[maybe_unused]] const int64_t o_rows = ((F::SCALAR || GRP || ORD) && !offset) ? 0 : a.B;   // null: no records, reads 0
     if constexpr (OFFS) o_cur = load_offset(offset, o_rows, row0_of(0), i16);
     [[maybe_unused]] float u_cur = 0.f;
     if constexpr (ITV) u_cur = load_offset(upper, a.B, row0_of(0), i16);
@@ -538,12 +382,12 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
                 const int d0 = 16 * c + 4 * kq;
                 float4 lv4 = make_float4(0.f, 0.f, 0.f, 0.f), ev4 = lv4, iv4 = lv4;
                 [[maybe_unused]] float4 lg4 = lv4;
-                if (PER_DRAW) {
+                if (F::PER_DRAW) {
                     lv4 = *reinterpret_cast<const float4*>(gp + d0);
                     ev4 = *reinterpret_cast<const float4*>(gp + P_MAX_S + d0);
                     iv4 = *reinterpret_cast<const float4*>(gp + 2 * P_MAX_S + d0);
                 }
-                if constexpr (OWN4) lg4 = *reinterpret_cast<const float4*>(gp + 3 * P_MAX_S + d0);
+                if constexpr (F::SCALAR) lg4 = *reinterpret_cast<const float4*>(gp + 3 * P_MAX_S + d0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float l = acc[c][0][r] + acc[c][1][r];
@@ -552,15 +396,9 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
                     const float lv = r == 0 ? lv4.x : r == 1 ? lv4.y : r == 2 ? lv4.z : lv4.w;
                     const float ev = r == 0 ? ev4.x : r == 1 ? ev4.y : r == 2 ? ev4.z : ev4.w;
                     const float iv = r == 0 ? iv4.x : r == 1 ? iv4.y : r == 2 ? iv4.z : iv4.w;
-                    float m_i, v_i, lp_i;
-                    if constexpr (ITV)
-                        predict_link_weibull_itv(l, yv, u_cur, lv, ev, iv, m_i, v_i, lp_i,
-                                                 r == 0 ? lg4.x : r == 1 ? lg4.y : r == 2 ? lg4.z : lg4.w);
-                    else if constexpr (OWN4)
-                        predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i,
-                                          r == 0 ? lg4.x : r == 1 ? lg4.y : r == 2 ? lg4.z : lg4.w);
-                    else
-                        predict_link<FAM>(l, yv, lv, ev, iv, m_i, v_i, lp_i);
+                    float m_i, v_i, lp_i, lg = 0.f;      // (u_cur and lg: 0 without ITV, without F::SCALAR; not read then)
+                    if constexpr (F::SCALAR) lg = r == 0 ? lg4.x : r == 1 ? lg4.y : r == 2 ? lg4.z : lg4.w;
+                    F::template predict_link<ITV>(l, yv, u_cur, lv, ev, iv, m_i, v_i, lp_i, lg);
                     const bool valid = d0 + r < S;
                     mu[4 * c + r] = valid ? m_i : 0.f;
                     lp[4 * c + r] = valid ? lp_i : -INFINITY;
@@ -593,8 +431,7 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
                 for (int i = 0; i < 4 * NC; ++i) se += __expf(lp[i] - ms);
                 se = fold4_sum(se);
                 lpd = ms + logf(se) - log_S;
-                if (FAM == BSC_PREDICT_POISSON || FAM == PREDICT_NEGBIN)
-                    lpd -= (float)bsc_lgamma_f64((double)yv + 1.0);   // once per row
+                if (F::ROW_LGAMMA) lpd -= (float)bsc_lgamma_f64((double)yv + 1.0);   // once per row
             }
             const int64_t row = row0_of(p) + i16;
             if (kq == 0 && row < B) {     // lanes 0 .. 15: one row each, 64 contiguous bytes per output

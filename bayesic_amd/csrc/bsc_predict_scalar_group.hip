@@ -15,7 +15,7 @@ template <int FAM, int NC, bool FULL>
 __global__ __launch_bounds__(P_BLOCK, 2) void scalar_predict_group_kernel(PredictArgs a,
                                                                           const float* __restrict__ offset,
                                                                           PredictGroups gr) {
-    predict_body<FAM, NC, FULL, /*OFFS=*/true, /*GRP=*/true>(a, offset, gr);
+    predict_body<PredictFamily<FAM>, NC, FULL, /*OFFS=*/true, /*GRP=*/true>(a, offset, gr);
 }
 
 __global__ __launch_bounds__(BSC_WAVE) void scalar_predict_group_sum_kernel(const double* __restrict__ partial, int n,
@@ -48,7 +48,7 @@ int bsc_scalar_predict_pass_groups(bsc_ctx* ctx, int32_t family, const float* X,
                                    float* mean, float* var, float* lpd, double* lpd_sum) {
     BSC_CHECK_CTX(ctx);
     const char* who = "bsc_scalar_predict_pass_groups";
-    PREDICT_UNSUPPORTED(family == BSC_SCALAR_NEGBIN || family == BSC_SCALAR_GAMMA || family == BSC_SCALAR_WEIBULL,
+    PREDICT_UNSUPPORTED(scalar_family_ok(family),
                         "%s: family=%d must be BSC_SCALAR_NEGBIN (0), BSC_SCALAR_GAMMA (1) or BSC_SCALAR_WEIBULL (2)",
                         who, family);
     int rc = predict_check_batch(who, X, y, B, W, mean, var, lpd, lpd_sum);
@@ -67,9 +67,8 @@ int bsc_scalar_predict_pass_groups(bsc_ctx* ctx, int32_t family, const float* X,
     gr.g = groups; gr.Bt = Bt; gr.J = J; gr.ldb = ldb;
     {
         bsc_prof_scope prof(ctx);
-        if (family == BSC_SCALAR_NEGBIN) launch_group<PREDICT_NEGBIN>(ctx, a, offset, gr, n_blocks);
-        else if (family == BSC_SCALAR_GAMMA) launch_group<PREDICT_GAMMA>(ctx, a, offset, gr, n_blocks);
-        else launch_group<PREDICT_WEIBULL>(ctx, a, offset, gr, n_blocks);
+        with_scalar_family(family,
+                           [&](auto f) { launch_group<decltype(f)::PREDICT_ID>(ctx, a, offset, gr, n_blocks); });
     }
     BSC_LAUNCH_CHECK();
     if (lpd_sum) {

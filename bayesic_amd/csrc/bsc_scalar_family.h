@@ -2,20 +2,21 @@
 // z = [w (D) | tau]: the negative binomial's dispersion (csrc/bsc_glm_nb.hip), the Gamma shape (csrc/bsc_glm_gamma.hip),
 // the Weibull shape (csrc/bsc_glm_weibull.hip), the Weibull route with upper ends (csrc/bsc_glm_weibull_interval.hip)
 // and the Beta precision (csrc/bsc_glm_beta.hip).
-// A family is two constants -- its LINK of csrc/bsc_glm_pass.h and its FAMILY of csrc/bsc_predict_pass.h -- and the
-// bodies are those headers' and csrc/bsc_meanfield.h's; what is here is the shell the four units used to repeat:
+// A family is one struct F of csrc/bsc_families.h -- its two ids (LINK = F::GLM_ID, FAMILY = F::PREDICT_ID), its
+// constants and its links -- and the bodies are csrc/bsc_glm_pass.h's, csrc/bsc_predict_pass.h's and
+// csrc/bsc_meanfield.h's; what is here is the shell the four units used to repeat:
 //
 //   kernels   scalar_pass_kernel<LINK, FULL>, scalar_pass_mfma_kernel<LINK>, scalar_slab_reduce_kernel<LINK>,
 //             scalar_mf_scalars_kernel<LINK>, scalar_mf_coord_kernel<LINK> (NbModel), scalar_predict_kernel<FAMILY, NC,
 //             FULL>, scalar_predict_sum_kernel<FAMILY>; with one more pointer, `upper` [B], behind the weight / the
 //             offset: scalar_upper_pass_kernel<LINK, FULL>, scalar_upper_pass_mfma_kernel<LINK>,
 //             scalar_upper_predict_kernel<FAMILY, NC, FULL>.
-//   host      scalar_family_data_pass<LINK, UPPER>, scalar_family_update<LINK>, scalar_family_predict_pass<FAMILY, UPPER>:
+//   host      scalar_family_data_pass<F, UPPER>, scalar_family_update<F>, scalar_family_predict_pass<F, UPPER>:
 //             the checks, the grid, the workspace and the launches of an entry point, naming their kernels themselves.
 //
 // A translation unit gets exactly the kernels of the host templates it calls (anonymous namespace, so each unit's are its
 // own): a unit that never asks for UPPER has no `upper` kernel, the interval unit has no finish.  The next family with a
-// learned scalar is a link in glm_link, a family in predict_link and three extern "C" functions of a few lines.
+// learned scalar is a struct in csrc/bsc_families.h, its id, and three extern "C" functions of a few lines.
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void scalar_pass_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, int64_t B, int D, const float* __restrict__ W, const float* __restrict__ logtau, int S,
     float* __restrict__ slab, int n_iter) {
-    glm_pass_body<LINK, FULL, true, false, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, nullptr, logtau);
+    glm_pass_body<GlmFamily<LINK>, FULL, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, nullptr, logtau);
 }
 
 template <int LINK>
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void scalar_pass_mfma_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, int64_t B, const float* __restrict__ W, const float* __restrict__ logtau, int S,
     float* __restrict__ slab, int n_iter) {
-    glm_pass_mfma_body<LINK, true, false, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, nullptr, logtau);
+    glm_pass_mfma_body<GlmFamily<LINK>, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, nullptr, logtau);
 }
 
 // `u`: the upper ends (csrc/bsc_glm_pass.h, ITV), not null
@@ -52,7 +53,8 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void scalar_upper_pass_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, const float* __restrict__ u, int64_t B, int D, const float* __restrict__ W,
     const float* __restrict__ logtau, int S, float* __restrict__ slab, int n_iter) {
-    glm_pass_body<LINK, FULL, true, false, true, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, nullptr, logtau, u);
+    glm_pass_body<GlmFamily<LINK>, FULL, true, false, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, nullptr, logtau,
+                                                            u);
 }
 
 template <int LINK>
@@ -60,7 +62,8 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void scalar_upper_pass_mfma_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
     const float* __restrict__ v, const float* __restrict__ u, int64_t B, const float* __restrict__ W,
     const float* __restrict__ logtau, int S, float* __restrict__ slab, int n_iter) {
-    glm_pass_mfma_body<LINK, true, false, true, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, nullptr, logtau, u);
+    glm_pass_mfma_body<GlmFamily<LINK>, true, false, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, nullptr, logtau,
+                                                           u);
 }
 
 template <int LINK>
@@ -75,11 +78,12 @@ __global__ __launch_bounds__(RED_BLOCK) void scalar_slab_reduce_kernel(const flo
 // reduction of the NB_SLAB_STRIDE slab, all S draws in chunks of eight.  `logtau` [S] is the per-draw scalar under the
 // name `what`.  UPPER: `upper` (not null) joins the vectors whose alignment decides the MFMA route and is handed to the
 // kernels behind the weight; without the flag it is not read.
-template <int LINK, bool UPPER = false>
+template <class F, bool UPPER = false>
 int scalar_family_data_pass(bsc_ctx* ctx, const char* who, const char* what, const float* X, int64_t ldx,
                             const float* y, const float* upper, const float* offset, const float* weight, int64_t B,
                             int32_t D, const float* W, const float* logtau, int32_t S, double* ell, double* G,
                             double* T) {
+    constexpr int LINK = F::GLM_ID;
     const int rc0 = check_glm_obs_args(who, BSC_GLM_LOGISTIC, X, ldx, y, offset, weight, B, D, W, S, SCALAR_MAX_S);
     if (rc0 != BSC_OK) return rc0;
     if constexpr (UPPER) BSC_REQUIRE((((uintptr_t)upper) & 3) == 0, "%s: upper must be 4-byte aligned", who);
@@ -133,14 +137,15 @@ template <int LINK>
 __global__ __launch_bounds__(MF_BLOCK) void scalar_mf_coord_kernel(NbModel a) { meanfield_coord_body(a); }
 
 // The checks, the next step's noise, the arguments and the two launches.  The likelihood enters through
-// stats = [ell | G | T] alone, so LINK only says whose kernels these are.
-template <int LINK>
+// stats = [ell | G | T] alone, so F only says whose kernels these are.
+template <class F>
 int scalar_family_update(bsc_ctx* ctx, const char* who, const double* stats, const double* lam_in, double* lam_out,
                          double* m1, double* m2, const double* eps, const float* W, const float* logtau, int32_t D,
                          int32_t S, double scale, double prior_precision, double a0, double b0, int64_t t, double lr,
                          double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
                          double* eps_next, int32_t eps_next_ready, float* W_next, float* logtau_next, double* elbo,
                          double* grad) {
+    constexpr int LINK = F::GLM_ID;
     BSC_REQUIRE(stats, "%s: stats is null (pending pass partials are not read: pass [ell | G | T])", who);
     int rc = check_meanfield_update(who, lam_in && lam_out && m1 && m2 && eps && W && logtau && elbo && grad, lam_in,
                                     lam_out, D, S, MF_MAX_S, prior_precision, /*has_gamma=*/true, a0, b0, scale, t);
@@ -175,7 +180,7 @@ int scalar_family_update(bsc_ctx* ctx, const char* who, const double* stats, con
 // FULL: D == 256.  offset may be null.
 template <int FAMILY, int NC, bool FULL>
 __global__ __launch_bounds__(P_BLOCK, 2) void scalar_predict_kernel(PredictArgs a, const float* __restrict__ offset) {
-    predict_body<FAMILY, NC, FULL, true>(a, offset);
+    predict_body<PredictFamily<FAMILY>, NC, FULL, true>(a, offset);
 }
 
 // ... and upper is set
@@ -183,7 +188,7 @@ template <int FAMILY, int NC, bool FULL>
 __global__ __launch_bounds__(P_BLOCK, 2) void scalar_upper_predict_kernel(PredictArgs a,
                                                                           const float* __restrict__ offset,
                                                                           const float* __restrict__ upper) {
-    predict_body<FAMILY, NC, FULL, true, false, true>(a, offset, PredictGroups{}, upper);
+    predict_body<PredictFamily<FAMILY>, NC, FULL, true, false, true>(a, offset, PredictGroups{}, upper);
 }
 
 template <int FAMILY>
@@ -210,11 +215,12 @@ void launch_scalar_predict(bsc_ctx* ctx, const PredictArgs& a, const float* offs
 // The predictive entry point `who` of a family with a per-draw scalar of its own (`logtau` [S], named `what` in the
 // messages) and an offset that may be null.  UPPER: `upper` (not null) rides with the offset; without the flag it is
 // not read.
-template <int FAMILY, bool UPPER = false>
+template <class F, bool UPPER = false>
 int scalar_family_predict_pass(bsc_ctx* ctx, const char* who, const char* what, const float* X, int64_t ldx,
                                const float* y, const float* upper, const float* offset, int64_t B, int32_t D,
                                const float* W, const float* logtau, int32_t S, float* mean, float* var, float* lpd,
                                double* lpd_sum) {
+    constexpr int FAMILY = F::PREDICT_ID;
     if constexpr (UPPER) BSC_REQUIRE((((uintptr_t)upper) & 3) == 0, "%s: upper must be 4-byte aligned", who);
     int rc = predict_check_batch(who, X, y, B, W, mean, var, lpd, lpd_sum);
     if (rc != BSC_OK) return rc;

@@ -76,7 +76,7 @@ __device__ __forceinline__ void bsc_lgamma_psi_f32(float x, float& lg, float& ps
     ps = fmaf(-dP, __builtin_amdgcn_rcpf(P), asym);
 }
 
-// Interval censoring (csrc/bsc_glm_pass.h's glm_link and csrc/bsc_predict_pass.h's predict_link_weibull_itv, ONE value for
+// Interval censoring (csrc/bsc_families.h: Weibull's glm_link_upper and predict_link_upper, ONE value for
 // the training pass and the predictive): from Delta = ITV_BIG on the upper end of a row is read as absent.
 constexpr float ITV_BIG = 103.0f;              // e^{-103} = 1.8e-45: at most one denormal step from 1 - e^{-Delta} = 1
 

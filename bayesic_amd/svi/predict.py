@@ -55,6 +55,8 @@ row's ``mean``, ``var`` and ``lpd`` are correct Monte-Carlo estimates of its mar
 two rows of the same new group are not (one call cannot tell two new groups apart, and ``lpd_sum`` adds the rows'
 marginal log densities, as it does for every model here).  offset, exposure and weights behave as for GLMReparamSVI.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -63,14 +65,26 @@ from ._reparam_base import first_draw, float_batch
 
 # include/bayesic_hip.h: BSC_PREDICT_*
 FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
-# families with an entry point of their own: a per-draw log-scalar behind the weights, the offset may be None
-SCALAR_PASSES = {"negbin": "bsc_nb_predict_pass", "gamma": "bsc_gamma_predict_pass",
-                 "weibull": "bsc_weibull_predict_pass"}
-# include/bayesic_hip.h: BSC_SCALAR_*, the same families with groups (svi/hier_scalar.py)
-SCALAR_FAMILIES = {"negbin": 0, "gamma": 1, "weibull": 2}
-# the same kind of entry point behind a LOGIT link (the logistic model's rules: offset allowed, exposure refused); no
-# groups
-LOGIT_SCALAR_PASSES = {"beta": "bsc_beta_predict_pass"}
+# One row per family (csrc/bsc_families.h holds the device side of each):
+#   entry    its own entry point (the offset may be None), or None: bsc_predict_pass[_offset] with its FAMILIES id
+#   link     "log" or "logit": the offset / exposure rules (a logit link takes offset and refuses exposure); None: neither
+#   scalar   a per-draw log-scalar rides behind the weights
+#   grouped  include/bayesic_hip.h: BSC_SCALAR_*, its id with groups (svi/hier_scalar.py), or None: not built
+Family = namedtuple("Family", "entry link scalar grouped")
+FAMILY_TABLE = {
+    "gaussian": Family(None, None, True, None),
+    "logistic": Family(None, "logit", False, None),
+    "poisson": Family(None, "log", False, None),
+    "negbin": Family("bsc_nb_predict_pass", "log", True, 0),
+    "gamma": Family("bsc_gamma_predict_pass", "log", True, 1),
+    "weibull": Family("bsc_weibull_predict_pass", "log", True, 2),
+    "beta": Family("bsc_beta_predict_pass", "logit", True, None),
+}
+NO_FAMILY = Family(None, None, False, None)      # softmax and ordinal: their own passes and their own rules
+# the table's columns under their earlier names
+SCALAR_PASSES = {f: r.entry for f, r in FAMILY_TABLE.items() if r.entry and r.link == "log"}
+LOGIT_SCALAR_PASSES = {f: r.entry for f, r in FAMILY_TABLE.items() if r.entry and r.link == "logit"}
+SCALAR_FAMILIES = {f: r.grouped for f, r in FAMILY_TABLE.items() if r.grouped is not None}
 PREDICT_STREAM = 2     # Philox stream of the predictive draws
 MAX_SAMPLES = 64       # draws per bsc_predict_pass call
 
@@ -131,10 +145,11 @@ def posterior_draws(model, n_samples=64, seed=None):
     docstring), and for the drivers of svi/hier_scalar.py the triple (W, Bt, logtau float32 [S])."""
     S = _check_samples(n_samples)
     family = family_of(model)
+    row = FAMILY_TABLE.get(family, NO_FAMILY)
     ctx, D = model.ctx, model.D
     if grouped(model):
         J = model.J
-        scalar = family in SCALAR_FAMILIES       # svi/hier_scalar.py: tau sits behind zeta
+        scalar = row.grouped is not None         # svi/hier_scalar.py: tau sits behind zeta
         P = D + J + (2 if scalar else 1)
         seed = model.seed if seed is None else int(seed)
         eps_d = torch.zeros((S, P + 1), dtype=torch.float64, device=ctx.device)
@@ -152,8 +167,7 @@ def posterior_draws(model, n_samples=64, seed=None):
     elif family == "ordinal":
         D = model.P                            # z = [w | theta], returned whole: the pass reads both from Z [S, P]
     seed = model.seed if seed is None else int(seed)
-    # a scalar latent rides behind the weights
-    scalar = family == "gaussian" or family in SCALAR_PASSES or family in LOGIT_SCALAR_PASSES
+    scalar = row.scalar                        # a scalar latent rides behind the weights
     P = D + 1 if scalar else D
     eps_d = torch.zeros((S, P), dtype=torch.float64, device=ctx.device)
     ctx.call("bsc_philox_normal", seed, PREDICT_STREAM, 0, S, P, eps_d)
@@ -189,13 +203,14 @@ def _obs(model, family, B, offset, exposure, weights):
                          "counts")
     if offset is None and exposure is None and weights is None:
         return None, None
-    if family in LOGIT_SCALAR_PASSES:         # the logistic link's rules, in the model's own words
+    row = FAMILY_TABLE.get(family, NO_FAMILY)
+    if row.entry and row.link == "logit":     # the logistic link's rules, in the model's own words
         if exposure is not None:
             raise ValueError("predict: exposure belongs to the Poisson rate model; the %s model takes offset=" % family)
         return batch_obs(model.ctx, B, offset, weights)
-    if family not in ("logistic", "poisson") and family not in SCALAR_PASSES:
+    if row.link is None:
         raise ValueError("predict: offset, exposure and weights are for the logistic and Poisson models, not %s" % family)
-    check_link("poisson" if family in SCALAR_PASSES else family, offset, exposure, kept="means")   # a log link's rules
+    check_link("poisson" if row.entry else family, offset, exposure, kept="means")   # (its own entry: a log link)
     return batch_obs(model.ctx, B, offset, weights, exposure)
 
 
@@ -245,8 +260,9 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     offset, weights = _obs(model, family, int(X.shape[0]), offset, exposure, weights)
     if draws is None:
         draws = posterior_draws(model, n_samples, seed)
+    row = FAMILY_TABLE.get(family, NO_FAMILY)
     logtau = None
-    if groups is not None and family in SCALAR_FAMILIES:     # svi/hier_scalar.py: (W, Bt, logtau [S])
+    if groups is not None and row.grouped is not None:       # svi/hier_scalar.py: (W, Bt, logtau [S])
         if len(draws) != 3:
             raise ValueError("draws of a random-intercept model with a learned scalar are (W [S, D], Bt float32 "
                              "[J + 1, ldb], logtau float32 [S]) as posterior_draws returns them")
@@ -276,7 +292,7 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
             raise ValueError("draws of the random-intercept model are (W [S, D], Bt float32 [J + 1, ldb]) as "
                              "posterior_draws returns them")
         if logtau is not None:
-            ctx.call("bsc_scalar_predict_pass_groups", SCALAR_FAMILIES[family], X, ldx, y, offset, groups, B, model.D,
+            ctx.call("bsc_scalar_predict_pass_groups", row.grouped, X, ldx, y, offset, groups, B, model.D,
                      model.J, W, Bt, int(Bt.stride(0)), logtau, S, out["mean"], out["var"], out.get("lpd"),
                      out.get("lpd_sum"))
         else:
@@ -285,12 +301,9 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     elif upper is not None:        # the Weibull model with interval and left censoring; the offset may be None
         ctx.call("bsc_weibull_predict_pass_interval", X, ldx, y, upper, offset, B, model.D, W, logvar, S, out["mean"],
                  out["var"], out.get("lpd"), out.get("lpd_sum"))
-    elif family in SCALAR_PASSES:  # its own entry point; the offset may be None
-        ctx.call(SCALAR_PASSES[family], X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"],
-                 out.get("lpd"), out.get("lpd_sum"))
-    elif family in LOGIT_SCALAR_PASSES:   # the same, behind a logit link
-        ctx.call(LOGIT_SCALAR_PASSES[family], X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"],
-                 out.get("lpd"), out.get("lpd_sum"))
+    elif row.entry:                # its own entry point, behind a log or a logit link; the offset may be None
+        ctx.call(row.entry, X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"], out.get("lpd"),
+                 out.get("lpd_sum"))
     elif offset is None:
         ctx.call("bsc_predict_pass", FAMILIES[family], X, ldx, y, B, model.D, W, logvar, S, out["mean"], out["var"],
                  out.get("lpd"), out.get("lpd_sum"))
