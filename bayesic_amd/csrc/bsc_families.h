@@ -485,6 +485,74 @@ struct Beta : ScalarFamily {
     }
 };
 
+// ---- log-normal: tau = log(1 / sigma), the log of the INVERSE scale; internal ids: csrc/bsc_glm_lognormal.hip
+// (bsc_lognormal_predict_pass) ------------------------------------------------------------------------------------------
+// glm_disp: (tau, k = 1 / sigma = e^tau, 0, 0) -- the density has no per-draw constant.  The sign of y is the censoring
+// flag as in the Weibull family -- y > 0 an event at y, y < 0 right-censored at -y -- so delta = (y > 0), t = |y|,
+// ly = log t, z = k (ly - l), l the LOCATION of log t (the Weibull link's z, rounded the same way); with
+// (lsf, h) = (log Phi(-z), phi(z) / Phi(-z)) from csrc/bsc_special_f32.h's bsc_lognormsf_hazard_f32:
+//     ell  += v [ delta (tau - ly - z^2 / 2 - log(2 pi) / 2) + (1 - delta) lsf ]    (log f and log S: nothing left out)
+//     resid = v k [ delta z + (1 - delta) h ]                                                  (= d / d l)
+//     T    += v [ delta (1 - z^2) - (1 - delta) z h ]                                          (= d / d tau)
+// NOT clamped and no need to be: every term is finite for every finite z whose square is (|z| < 1.8e19), both tails of
+// the censored rows included -- the Weibull link's z < 88 does not apply.  One log, one erfcx, one exp, one more log and
+// one reciprocal per (row, draw).  y = 0 or a non-finite y on a kept row is the caller's to keep out.
+// Prediction: slots (tau, k, m1 = e^{sigma^2 / 2}, m2 = (e^{sigma^2} - 1) e^{sigma^2}), sigma^2 = e^{-2 tau}, both made
+// once per launch in float64 from tau itself (the exp(-logvar) slot is not needed and carries m1).  mu = e^l m1,
+// v = e^{2l} m2 (not clamped); log p = tau - log t - z^2 / 2 - log(2 pi) / 2 for y > 0 (an event at y), log p = lsf for
+// y < 0 (right-censored at -y: the log survival), so the lpd of a censored row is the log of the posterior-predictive
+// survival probability.  y = 0 is the caller's to keep out.
+// FLOAT32 ENVELOPE OF THE MOMENTS: m2 ~ e^{2 sigma^2} overflows float32 at sigma^2 = 44.4 (tau = -1.90; at tau = -2
+// sigma^2 = 54.6); accuracy envelope tau in [-1.5, 4] (sigma from 4.5 down to 0.018, m2 = 2.8e17 at the lower end).  m2
+// through expm1 in float64: 3e-4 at tau = 4 with every digit.
+struct LogNormal : ScalarFamily {
+    static constexpr int GLM_ID = 6, PREDICT_ID = 8;
+    static constexpr bool UPPER = false;           // right censoring alone: no upper ends
+    static __device__ __forceinline__ GlmDisp glm_disp(const float* __restrict__ logphi, int s, int S) {
+        GlmDisp d = glm_disp_tau(logphi, s, S);
+        d.lg = d.psi = 0.0f;
+        return d;
+    }
+    template <bool OBS, bool ITV>
+    static __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv,
+                                                     const GlmDisp* dp, float* T, float uv) {
+        // a dropped row is evaluated at t = 1, l = 0, delta = 0 -- z = 0, every term finite whatever y held (0 and NaN
+        // included)
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const float tq = keep ? fabsf(yv) : 1.0f;
+        const float dl = (keep && yv > 0.0f) ? 1.0f : 0.0f;
+        const float lq = keep ? l : 0.0f;
+        const float ly = logf(tq);
+        const float z = dp->phi * (ly - lq);
+        float lsf, hz;
+        bsc_lognormsf_hazard_f32(z, lsf, hz);
+        const float cs = 1.0f - dl;
+        const float zz = z * z;
+        ell = fmaf(vq, fmaf(dl, (dp->tau - ly) - fmaf(0.5f, zz, 0.5f * (float)BSC_LOG_2PI), cs * lsf), ell);
+        *T = fmaf(vq, fmaf(dl, 1.0f - zz, -cs * (z * hz)), *T);
+        return vq * (dp->phi * fmaf(dl, z, cs * hz));
+    }
+    static __device__ __forceinline__ void predict_slots(float* gp, int s, float lv) {
+        predict_slots3(gp, s, lv);
+        const double s2 = exp(-2.0 * (double)lv);
+        gp[2 * P_MAX_S + s] = (float)exp(0.5 * s2);
+        gp[3 * P_MAX_S + s] = (float)(expm1(s2) * exp(s2));
+    }
+    template <bool ITV>
+    static __device__ __forceinline__ void predict_link(float l, float yv, float uv, float lv, float ev, float iv,
+                                                        float& mu, float& v, float& lp, float lgp) {
+        const float el = expf(l);
+        mu = el * iv;
+        v = el * lgp * el;
+        const float ly = logf(fabsf(yv));
+        const float z = ev * (ly - l);
+        float lsf, hz;                                          // (the hazard is not used and folds away)
+        bsc_lognormsf_hazard_f32(z, lsf, hz);
+        lp = yv > 0.0f ? (lv - ly) - fmaf(0.5f * z, z, 0.5f * (float)BSC_LOG_2PI) : lsf;
+    }
+};
+
 // ---- the ids to the structs ------------------------------------------------------------------------------------------
 template <int ID, class... Fs>
 struct FamilyById {
@@ -497,7 +565,7 @@ struct FamilyById<ID, F, Fs...> {
     using predict = std::conditional_t<F::PREDICT_ID == ID, F, typename FamilyById<ID, Fs...>::predict>;
 };
 template <int ID>
-using FamilyOf = FamilyById<ID, Logistic, Poisson, Gaussian, NegBin, Gamma, Weibull, Beta, Ordinal>;
+using FamilyOf = FamilyById<ID, Logistic, Poisson, Gaussian, NegBin, Gamma, Weibull, Beta, LogNormal, Ordinal>;
 template <int LINK>
 using GlmFamily = typename FamilyOf<LINK>::glm;
 template <int FAM>

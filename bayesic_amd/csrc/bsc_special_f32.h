@@ -16,7 +16,8 @@
 // +1 / -1, all finite, so that the compiler has no expensive operand to branch around.
 // Callers state the range of phi over which the differences are good enough (include/bayesic_hip.h,
 // bsc_glm_nb_data_pass).  bsc_lgamma_psi_f32 below is the pair itself, not a difference, for any positive argument (the
-// Beta link).  Device only, header-only, internal linkage.
+// Beta link); bsc_lognormsf_hazard_f32 at the end is the normal log survival function and hazard (the log-normal link).
+// Device only, header-only, internal linkage.
 #pragma once
 
 namespace {
@@ -102,6 +103,66 @@ __device__ __forceinline__ float bsc_logratio_f32(float b, float a, float la) {
     const float lg = logf(near ? w : b);
     const float ratio = near ? r * __builtin_amdgcn_rcpf(one ? 1.0f : w - 1.0f) : 1.0f;
     return fmaf(lg, ratio, one ? r : 0.0f) - (near ? 0.0f : la);
+}
+
+// erfcx(a) = e^{a^2} erfc(a) for a finite a >= 0, in (0, 1], straight-line (with the library's erfcxf, which serves
+// negative arguments too, the 8-row pass of the log-normal link spills 140 bytes per lane; with this one it keeps 233
+// registers and no scratch).  The half line is mapped to t = (a - 2) / (a + 2) in [-1, 1), where
+// (1 + 2 a) erfcx(a) - 1 is smooth up to its limit 2 / sqrt(pi) - 1 at t = 1: a polynomial of degree 11 in t
+// (interpolated at the Chebyshev nodes in float64 against a float64 erfcx, 1.9e-8 off at most, rounded to float32), then
+// the division by 1 + 2 a.  Both quotients are a reciprocal with ONE correction step from their exact residuals (fmaf),
+// so neither costs more than a rounding.  Within 1.8 float32 roundings of erfcx over [0, 1e19]:
+// tests/test_glm_lognormal_cpu.py replays these steps and these coefficients in float32 on the host
+// (tests/_glm_lognormal_ref.erfcx_pos_f32).
+__device__ __forceinline__ float bsc_erfcx_pos_f32(float a) {
+    const float r2 = __builtin_amdgcn_rcpf(a + 2.0f);
+    const float t0 = (a - 2.0f) * r2;
+    const float t = fmaf(r2, fmaf(t0, -a, fmaf(t0 + 1.0f, -2.0f, a)), t0);     // + r2 ((a - 2) - t0 (a + 2))
+    float p = 6.807514728279784e-05f;
+    p = fmaf(p, t, 1.6084033995866776e-04f);
+    p = fmaf(p, t, -3.709284064825624e-04f);
+    p = fmaf(p, t, -1.3958050403743982e-03f);
+    p = fmaf(p, t, 1.230503199622035e-03f);
+    p = fmaf(p, t, 8.68925265967846e-03f);
+    p = fmaf(p, t, -8.024739101529121e-03f);
+    p = fmaf(p, t, -5.4211996495723724e-02f);
+    p = fmaf(p, t, 1.6405050456523895e-01f);
+    p = fmaf(p, t, -1.660310924053192e-01f);
+    p = fmaf(p, t, -9.276381880044937e-02f);
+    p = fmaf(p, t, 2.7697840332984924e-01f);
+    const float r = 0.5f * __builtin_amdgcn_rcpf(a + 0.5f);                    // 1 / (1 + 2 a)
+    const float q = fmaf(p, r, r);
+    return fmaf((p - q) + fmaf(q + q, -a, 1.0f), r, q);                        // + r ((1 + p) - q (1 + 2 a))
+}
+
+// The log survival function and the hazard of the standard normal together, for any finite float32 z with z^2 finite
+// (the log-normal link's censored rows, csrc/bsc_glm_lognormal.hip):
+//     lsf = log Phi(-z),     hz = phi(z) / Phi(-z)
+// from ONE scaled complementary error function E = erfcx(|z| / sqrt 2) in (0, 1] (bsc_erfcx_pos_f32 above), which
+// neither tail can overflow or cancel, and g = e^{-z^2 / 2} (the exponential of the ROUNDED square times one minus the
+// square's rounding error, which an fmaf gives exactly: without it g is off by z^2 / 2 roundings, 32 at z = -13):
+//   z >= 0:  Phi(-z) = g E / 2, so    lsf = -z^2 / 2 + log(E / 2),     hz = sqrt(2 / pi) / E       (g itself is not used:
+//            at z = 60 it is 0 in float32 and lsf = -1805.01 all the same)
+//   z <  0:  q = Phi(z) = g E / 2 in (0, 1/2), so    lsf = log1p(-q),     hz = phi(z) / (1 - q)
+//            with log1p(-q) = log(w) q / (1 - w), w = 1 - q in [1/2, 1): 1 - w is exact and the quotient undoes the
+//            rounding of w; -q itself where w == 1.  hz runs to 0 with g.
+// The one form -z^2 / 2 + log(E(z) / 2) for every z would lose the left tail to cancellation (both terms ~ z^2 / 2, the
+// result ~ -q).  ONE log and ONE reciprocal, the selects on their inputs and between values at hand; both results within
+// a few roundings of max(|lsf|, z^2 / 2) and of hz.  The hz half folds away where it is not used.
+__device__ __forceinline__ void bsc_lognormsf_hazard_f32(float z, float& lsf, float& hz) {
+    const bool pos = z >= 0.0f;
+    const float E = bsc_erfcx_pos_f32(fabsf(z) * 0.70710678118654752f);
+    const float hz2 = 0.5f * z * z;
+    const float g0 = expf(-hz2);
+    const float g = fmaf(-g0, fmaf(0.5f * z, z, -hz2), g0);    // e^{-(hz2 + d)} = g0 (1 - d), d the rounding of hz2
+    const float q = 0.5f * g * E;
+    const float w = 1.0f - q;
+    const bool tiny = !pos && w == 1.0f;
+    const float lg = logf(pos ? 0.5f * E : w);
+    const float ratio = pos ? 1.0f : q * __builtin_amdgcn_rcpf(tiny ? 1.0f : 1.0f - w);
+    const float add0 = pos ? -hz2 : 0.0f;
+    lsf = fmaf(lg, ratio, tiny ? -q : add0);
+    hz = (pos ? 0.79788456080286536f : 0.39894228040143268f * g) * __builtin_amdgcn_rcpf(pos ? E : w);
 }
 
 }  // namespace

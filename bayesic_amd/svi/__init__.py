@@ -3,6 +3,7 @@
 from .glm import GLMReparamSVI  # noqa: E402,F401
 from .glm_beta import BetaReparamSVI  # noqa: E402,F401
 from .glm_gamma import GammaReparamSVI  # noqa: E402,F401
+from .glm_lognormal import LogNormalReparamSVI  # noqa: E402,F401
 from .glm_nb import NegBinReparamSVI  # noqa: E402,F401
 from .glm_ordinal import OrdinalReparamSVI  # noqa: E402,F401
 from .glm_weibull import WeibullReparamSVI  # noqa: E402,F401
@@ -13,5 +14,5 @@ from . import predict  # noqa: E402,F401  (the module: predict.predict(model, X,
 from .predict import heldout_lpd, posterior_draws  # noqa: E402,F401
 
 __all__ = ["BetaReparamSVI", "GLMReparamSVI", "GammaReparamSVI", "HierGLMReparamSVI", "HierGammaReparamSVI",
-           "HierNegBinReparamSVI", "HierWeibullReparamSVI", "NegBinReparamSVI", "OrdinalReparamSVI", "SoftmaxReparamSVI",
-           "WeibullReparamSVI", "predict", "posterior_draws", "heldout_lpd"]
+           "HierNegBinReparamSVI", "HierWeibullReparamSVI", "LogNormalReparamSVI", "NegBinReparamSVI",
+           "OrdinalReparamSVI", "SoftmaxReparamSVI", "WeibullReparamSVI", "predict", "posterior_draws", "heldout_lpd"]

@@ -725,6 +725,65 @@ int bsc_glm_weibull_update(bsc_ctx* ctx, const double* stats, const double* lam_
                            double* eps_next, int32_t eps_next_ready, float* W_next, float* logshape_next, double* elbo,
                            double* grad);
 
+/* ---- Log-normal survival regression with right censoring and a learned scale on the same pass
+ * (csrc/bsc_glm_lognormal.hip)
+ *
+ *      t_n ~ LogNormal(location l_n, scale sigma),   l[n,s] = sum_d X[n,d] W[s,d] + o[n]   (accelerated failure time)
+ *      w ~ N(0, I / prior_precision),   k = 1 / sigma = e^tau ~ Gamma(a0, b0)
+ * The latent is z = [w (D) | tau], P = D + 1, the guide mean-field: lam = [m (P) | rho (P)].  tau is the log of the
+ * INVERSE scale, so that the prior on e^tau has the form the shared finish knows.  One draw of it rides with every weight
+ * draw: loginvscale[s] = tau_s, float32 [S], any 4-byte alignment; k_s = e^{tau_s} (float32 expf of the value read).  l is
+ * the location of log t (the log median), not the log mean: E t = e^{l + sigma^2 / 2}, Var t = (e^{sigma^2} - 1)
+ * e^{2l + sigma^2}.  The model next to bsc_glm_weibull_data_pass's: its hazard rises and falls where the Weibull one is
+ * monotone.
+ * ENCODING: bsc_glm_weibull_data_pass's.  The censoring flag of a row is the SIGN of y:  y[n] > 0 is an event seen at
+ * y[n];  y[n] < 0 is right-censored at -y[n] (the event is later);  0, NaN and +-infinity are invalid.  With
+ * delta = (y > 0), t = |y|, ly = log t, z = k (ly - l), Phi and phi the standard normal distribution function and density
+ * and h(z) = phi(z) / Phi(-z) the normal hazard:
+ *      log f(t) = tau - ly - z^2 / 2 - log(2 pi) / 2        log S(t) = log Phi(-z)        (the FULL density)
+ *      ell[s]  = sum_n v[n] ( delta[n] (tau_s - ly[n] - z[n,s]^2 / 2 - log(2 pi) / 2) + (1 - delta[n]) log Phi(-z[n,s]) )
+ *      G[s,d]  = sum_n r[n,s] X[n,d]        r[n,s] = v[n] k_s ( delta[n] z[n,s] + (1 - delta[n]) h(z[n,s]) )     (= d / d l)
+ *      T[s]    = sum_n v[n] ( delta[n] (1 - z[n,s]^2) - (1 - delta[n]) z[n,s] h(z[n,s]) )          (= d ell[s] / d tau_s)
+ * With every row an event this is the Gaussian regression of log t.
+ * Outputs float64: ell [S], G [S, D], T [S].  offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0,
+ * v = 1; a row with v[n] = 0 adds EXACTLY nothing to ell, G and T, by a select on the link's inputs: it is evaluated at
+ * t = 1, l = 0, delta = 0 whatever it held -- 0 and NaN included -- as the rows past B are).
+ * log Phi(-z) and h(z) are float32, per (row, draw), from ONE scaled complementary error function E = erfcx(|z| / sqrt 2)
+ * in (0, 1] (a degree-11 polynomial on the half line, within 2 roundings): for z >= 0, log Phi(-z) = -z^2 / 2 + log(E / 2)
+ * and h = sqrt(2 / pi) / E; for z < 0, with q = e^{-z^2 / 2} E / 2, log Phi(-z) = log1p(-q) and h = phi(z) / (1 - q).
+ * Neither tail cancels or overflows: log Phi(-60) = -1805.01 with h = 60.02, log Phi(60) = -0 with h = 0.
+ * y IS NOT CHECKED ON THE DEVICE: a kept row with y = 0 or a non-finite y makes ell and T of every draw NaN or infinite
+ * (bayesic_amd/svi/glm_lognormal.py checks time and event where a batch is set).
+ * OVERFLOW: nothing is clamped and nothing needs to be: every term is finite for every finite z whose square is
+ * (|z| < 1.8e19); bsc_glm_weibull_data_pass's z < 88 does not apply.
+ * ACCURACY ENVELOPE: tau in [-1.5, 4] (sigma from 4.5 down to 0.018; the lower end is the predictive variance's, see
+ * bsc_lognormal_predict_pass).  z inherits the rounding of k, ly and l: with c = |z| + k (|ly| + sum_d |x_d w_d| + |o|) a
+ * plain float32 evaluation stays within 1e-6 of
+ *      sum_n v ( delta (|tau| + |ly| + z^2 / 2 + |z| c + 1) + (1 - delta)(|log Phi(-z)| + h c + 1) )           for ell,
+ *      sum_n v ( delta (1 + z^2 + 2 |z| c) + (1 - delta)(|z| h + (h + |z| h |h - z|) c) + 1 )                   for T,
+ *      sum_n v k ( delta (|z| + c) + (1 - delta) h (1 + |h - z| c) ) |x_d|                                      for G[., d]
+ * (h' = h (h - z)), |z| = 60 in both tails included, and the device within 2e-5.
+ * The envelope and its refusals are bsc_glm_nb_data_pass's (D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 with eight draws
+ * and their eight tau per launch, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26); loginvscale == NULL is
+ * refused.  The 16-row MFMA kernel (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned,
+ * else the 8-row kernel.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block partials of
+ * 8 * 256 + 16 floats (ell and T behind G), fixed-order float64 finish, no float atomics.
+ * Not built: interval and left censoring (no `upper`), left truncation, random intercepts. */
+int bsc_glm_lognormal_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                                const float* weight, int64_t B, int32_t D, const float* W, const float* loginvscale,
+                                int32_t S, double* ell, double* G, double* T);
+
+/* The finish: bsc_glm_nb_update with loginvscale in the place of logphi -- the prior on e^tau = 1 / sigma has the same
+ * form, the likelihood enters through ell, G and T alone, and the entry points run one body (csrc/bsc_meanfield.h), so
+ * the same arguments give the same bits as bsc_glm_nb_update.  stats = [ell (S) | G (S*D) | T (S)]; checks, next draws
+ * and requirements as there.  A full-covariance guide finishes with bsc_glm_scalar_fullrank_update. */
+int bsc_glm_lognormal_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                             double* m2, const double* eps, const float* W, const float* loginvscale, int32_t D,
+                             int32_t S, double scale, double prior_precision, double a0, double b0, int64_t t, double lr,
+                             double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
+                             double* eps_next, int32_t eps_next_ready, float* W_next, float* loginvscale_next,
+                             double* elbo, double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
@@ -888,6 +947,26 @@ int bsc_weibull_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const fl
 int bsc_weibull_predict_pass_interval(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* upper,
                                       const float* offset, int64_t B, int32_t D, const float* W, const float* logshape,
                                       int32_t S, float* mean, float* var, float* lpd, double* lpd_sum);
+
+/* The predictive of the log-normal survival model (csrc/bsc_glm_lognormal.hip: bsc_predict_pass's kernel with a family
+ * that only this entry point reaches).  y carries bsc_glm_lognormal_data_pass's encoding: y[n] > 0 an event at y[n],
+ * y[n] < 0 right-censored at -y[n].  Per draw, with k_s = exp(loginvscale[s]), sigma_s = 1 / k_s, l[n,s] =
+ * sum_d X[n,d] W[s,d] + o[n] (offset may be NULL), t = |y| and z = k_s (log t - l), the three outputs are
+ *      mu = e^l e^{sigma_s^2 / 2}        v = e^{2l} (e^{sigma_s^2} - 1) e^{sigma_s^2}
+ *      log p(y | l, k_s) = tau_s - log t - z^2 / 2 - log(2 pi) / 2   (y > 0: the density)
+ *                        = log Phi(-z)                                (y < 0: the log survival)
+ *      mean[n] = 1/S sum_s mu,     var[n] = 1/S sum_s v + 1/S sum_s (mu - mean[n])^2
+ *      lpd[n]  = logsumexp_s log p(y[n] | l[n,s], k_s) - log S,     lpd_sum = sum_n lpd[n]     (float64 [1])
+ * The lpd of a censored row is therefore the log of the posterior-predictive survival probability at that time, and a
+ * batch with every row censored at t_n gives log S(t_n | x_n).  log Phi(-z) is the training pass's, in its forms.  Both
+ * moment factors are made once per launch in float64 from tau_s itself and rounded.  exp is NOT clamped: mean stops being
+ * finite at l + sigma^2 / 2 > 88, var at 2 l + 2 sigma^2 > 88; y = 0 is not checked here.  FLOAT32 ENVELOPE OF THE
+ * MOMENTS: the variance factor ~ e^{2 sigma^2} overflows float32 at sigma^2 = 44.4 (tau = -1.90; sigma^2 = 54.6 at
+ * tau = -2); accuracy envelope loginvscale in [-1.5, 4], where the factor is 2.8e17 at most.  Outputs, refusals, envelope
+ * and determinism are bsc_nb_predict_pass's; loginvscale == NULL is BSC_ERR_INVALID. */
+int bsc_lognormal_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                               int64_t B, int32_t D, const float* W, const float* loginvscale, int32_t S, float* mean,
+                               float* var, float* lpd, double* lpd_sum);
 
 /* The predictive of the random-intercept model (csrc/bsc_predict_group.hip: bsc_predict_pass_offset's kernel with a
  * per-draw, per-group intercept; bsc_glm_data_pass_groups is its training pass):
