@@ -19,7 +19,7 @@ class BayesicHipError(RuntimeError):
 
 
 # The argument types of the three entry points of a family with a learned log-scalar behind the weights
-# (csrc/bsc_scalar_family.h): the negative-binomial, Gamma, Weibull, Beta and log-normal routes have the same signatures, the interval pair
+# (csrc/bsc_scalar_family.h): the negative-binomial, Gamma, Weibull, Beta, log-normal and zero-inflated Poisson routes have the same signatures, the interval pair
 # one more pointer behind y.  Tuples: every entry of SIGNATURES gets a list of its own (_scalar).
 _SCALAR_DATA_PASS = (c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                      c_int32, c_void_p, c_void_p, c_void_p)
@@ -149,6 +149,8 @@ SIGNATURES = {
     "bsc_glm_beta_update": _scalar(_SCALAR_UPDATE),
     "bsc_glm_lognormal_data_pass": _scalar(_SCALAR_DATA_PASS),
     "bsc_glm_lognormal_update": _scalar(_SCALAR_UPDATE),
+    "bsc_glm_zip_data_pass": _scalar(_SCALAR_DATA_PASS),
+    "bsc_glm_zip_update": _scalar(_SCALAR_UPDATE),
     "bsc_glm_weibull_data_pass": _scalar(_SCALAR_DATA_PASS),
     "bsc_glm_weibull_data_pass_interval": _scalar(_SCALAR_DATA_PASS, upper=True),
     "bsc_glm_weibull_update": _scalar(_SCALAR_UPDATE),
@@ -167,6 +169,7 @@ SIGNATURES = {
     "bsc_gamma_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
     "bsc_beta_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
     "bsc_lognormal_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
+    "bsc_zip_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
     "bsc_weibull_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
     "bsc_weibull_predict_pass_interval": _scalar(_SCALAR_PREDICT_PASS, upper=True),
     "bsc_predict_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,

@@ -553,6 +553,93 @@ struct LogNormal : ScalarFamily {
     }
 };
 
+// ---- zero-inflated Poisson: tau = log omega, the log ODDS of a structural zero, pi = sigmoid(tau); internal ids:
+// csrc/bsc_glm_zip.hip (bsc_zip_predict_pass) -----------------------------------------------------------------------------
+// glm_disp: (tau, omega = e^tau, L1 = log1p(omega) = softplus(tau), pi = sigmoid(tau)), the last two made once per launch
+// in float64 and rounded, in the two slots the negative binomial fills with lnGamma and psi.  y is a count; mu = e^l,
+// u = tau + mu, e = e^{-|u|}, and sigmoid(u), sigmoid(-u) EACH from the stable logistic forms 1 / (1 + e), e / (1 + e)
+// (never one by subtraction from the other).  The two branches are chosen by y == 0:
+//                     y == 0                                             y > 0
+//     log p    max(tau, -mu) + log1p(e) - L1                             y l - mu - L1
+//     d / d l  -mu r,   r = sigmoid(-u) = P(Poisson | y = 0)             y - mu
+//     d / d tau  sigmoid(u) (1 - pi) (-expm1(-mu))                       -pi
+//     ell  += v log p,    resid = v d / d l,    T += v d / d tau
+// The zero branch is log(omega + e^{-mu}) - log1p(omega), written so that softplus(u) - mu is never formed; its tau
+// derivative is sigmoid(u) - sigmoid(tau), which cancels at small mu, as the product of three factors in [0, 1]: never
+// negative.  Training leaves the row constant -lnGamma(y + 1) out, as the Poisson and negative-binomial links do.  Both
+// branches are evaluated for every row and chosen by flat selects between values at hand (y l = 0 on a zero row, so the
+// positive branch is finite there, and the zero branch is finite everywhere).  NOT clamped, like the Poisson link: finite
+// while e^l is.  At l = +80 a zero row gives e = 0, so log p = tau - L1 = log pi, d / d l = -mu 0 = 0 and d / d tau =
+// 1 - pi, each exactly.  Per (row, draw) on top of the Poisson link's exp: e^{-|u|} with its reciprocal, log1p (a log and
+// a division) and expm1 (e^{-mu}, a log and a reciprocal).
+// Prediction: slots (tau, omega, pi, L1), pi and L1 made once per launch in float64 (the exp(-logvar) slot carries pi).
+// mu = (1 - pi) e^l, v = (1 - pi) e^l (1 + pi e^l) (not clamped); log p in the training forms; the row constant
+// lnGamma(y + 1) is taken off after the log-mean-exp (lnGamma(1) = 0 keeps the zero rows right).
+struct ZeroInflPoisson : ScalarFamily {
+    static constexpr int GLM_ID = 7, PREDICT_ID = 9;
+    static constexpr bool ROW_LGAMMA = true;
+    static constexpr bool UPPER = false;
+    static __device__ __forceinline__ GlmDisp glm_disp(const float* __restrict__ logphi, int s, int S) {
+        GlmDisp d = glm_disp_tau(logphi, s, S);
+        const double t = (double)d.tau, e = exp(-fabs(t));
+        d.lg = (float)(fmax(t, 0.0) + log1p(e));
+        d.psi = (float)((t >= 0.0 ? 1.0 : e) / (1.0 + e));
+        return d;
+    }
+    template <bool OBS, bool ITV>
+    static __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv,
+                                                     const GlmDisp* dp, float* T, float uv) {
+        // a dropped row is evaluated at y = 0, l = 0 -- every term finite whatever y held (NaN and negatives included)
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const float yq = keep ? yv : 0.0f;
+        const float lq = keep ? l : 0.0f;
+        const float mu = expf(lq);
+        const float u = dp->tau + mu;
+        const float e = expf(-fabsf(u));
+        const float t = 1.0f + e;
+        const float rc = __builtin_amdgcn_rcpf(t);
+        const float er = e * rc;
+        const bool pos = u >= 0.0f;
+        const float su = pos ? rc : er, sn = pos ? er : rc;      // sigmoid(u) and sigmoid(-u), neither by subtraction
+        // log1p(e) from the full-accuracy log and a true division, as in the negative-binomial link
+        const bool tiny = t == 1.0f;
+        const float lp = logf(t) * (e / (tiny ? 1.0f : t - 1.0f)) + (tiny ? e : 0.0f);
+        const float em = -bsc_expm1_f32(-mu);                    // 1 - e^{-mu}, every digit at small mu
+        // the branch as an indicator on the input (z0 = 1 on a zero row, zp = 1 on a positive one) that multiplies both
+        // branches' terms, as delta does in the Weibull link: a select between the results becomes a branch around the
+        // zero row's evaluation, which splits the loop body and spills 140 bytes per lane
+        const float z0 = yq == 0.0f ? 1.0f : 0.0f;
+        const float zp = 1.0f - z0;
+        const float lp0 = fmaxf(dp->tau, -mu) + lp;
+        const float lpp = fmaf(yq, lq, -mu);
+        const float res = fmaf(-mu, fmaf(z0, sn, zp), yq);
+        const float dt0 = su * (1.0f - dp->psi) * em;
+        ell = fmaf(vq, fmaf(z0, lp0, zp * lpp) - dp->lg, ell);
+        *T = fmaf(vq, fmaf(z0, dt0, -zp * dp->psi), *T);
+        return vq * res;
+    }
+    static __device__ __forceinline__ void predict_slots(float* gp, int s, float lv) {
+        predict_slots3(gp, s, lv);
+        const double t = (double)lv, e = exp(-fabs(t));
+        gp[2 * P_MAX_S + s] = (float)((t >= 0.0 ? 1.0 : e) / (1.0 + e));
+        gp[3 * P_MAX_S + s] = (float)(fmax(t, 0.0) + log1p(e));
+    }
+    template <bool ITV>
+    static __device__ __forceinline__ void predict_link(float l, float yv, float uv, float lv, float ev, float iv,
+                                                        float& mu, float& v, float& lp, float lgp) {
+        const float el = expf(l);
+        const float q = (1.0f - iv) * el;
+        mu = q;
+        v = fmaf(q * iv, el, q);
+        const float u = lv + el;
+        const float e = expf(-fabsf(u));
+        const float t = 1.0f + e;
+        const float l1p = t == 1.0f ? e : logf(t) * e / (t - 1.0f);
+        lp = (yv == 0.0f ? fmaxf(lv, -el) + l1p : fmaf(yv, l, -el)) - lgp;
+    }
+};
+
 // ---- the ids to the structs ------------------------------------------------------------------------------------------
 template <int ID, class... Fs>
 struct FamilyById {
@@ -565,7 +652,8 @@ struct FamilyById<ID, F, Fs...> {
     using predict = std::conditional_t<F::PREDICT_ID == ID, F, typename FamilyById<ID, Fs...>::predict>;
 };
 template <int ID>
-using FamilyOf = FamilyById<ID, Logistic, Poisson, Gaussian, NegBin, Gamma, Weibull, Beta, LogNormal, Ordinal>;
+using FamilyOf =
+    FamilyById<ID, Logistic, Poisson, Gaussian, NegBin, Gamma, Weibull, Beta, LogNormal, ZeroInflPoisson, Ordinal>;
 template <int LINK>
 using GlmFamily = typename FamilyOf<LINK>::glm;
 template <int FAM>

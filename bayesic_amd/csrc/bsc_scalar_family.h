@@ -1,7 +1,8 @@
 // The kernels and the host envelopes of the regression families with ONE learned log-scalar behind the weights,
 // z = [w (D) | tau]: the negative binomial's dispersion (csrc/bsc_glm_nb.hip), the Gamma shape (csrc/bsc_glm_gamma.hip),
 // the Weibull shape (csrc/bsc_glm_weibull.hip), the Weibull route with upper ends (csrc/bsc_glm_weibull_interval.hip),
-// the Beta precision (csrc/bsc_glm_beta.hip) and the log-normal inverse scale (csrc/bsc_glm_lognormal.hip).
+// the Beta precision (csrc/bsc_glm_beta.hip), the log-normal inverse scale (csrc/bsc_glm_lognormal.hip) and the
+// zero-inflated Poisson's inflation odds (csrc/bsc_glm_zip.hip).
 // A family is one struct F of csrc/bsc_families.h -- its two ids (LINK = F::GLM_ID, FAMILY = F::PREDICT_ID), its
 // constants and its links -- and the bodies are csrc/bsc_glm_pass.h's, csrc/bsc_predict_pass.h's and
 // csrc/bsc_meanfield.h's; what is here is the shell the four units used to repeat:

@@ -31,6 +31,9 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
     LogNormalReparamSVI               eps [S, D + 1]:  the same transform, tau = log(1 / sigma), the inverse scale
                                       (bsc_lognormal_predict_pass; y is the signed response as for the Weibull model;
                                       offset allowed, exposure, upper= and groups= refused)
+    ZIPoissonReparamSVI               eps [S, D + 1]:  the same transform, tau = log omega, the log odds of a structural
+                                      zero (bsc_zip_predict_pass; a log link: offset or exposure; upper= and groups=
+                                      refused)
     HierNegBin/Gamma/WeibullReparamSVI  eps [S, D + J + 3]: the transform below over z = [w | b | zeta | tau], b_new
                                       from the last column; returned as (W, Bt, logtau float32 [S])
                                       (bsc_scalar_predict_pass_groups)
@@ -47,7 +50,8 @@ of the negative binomial, or the log-shape of the Gamma model, and travels in th
 Offsets and weights (logistic, Poisson, negative-binomial, Gamma and Weibull models): ``offset`` (or, with a log link, ``exposure`` = e^offset) is added to the
 linear predictor in the pass (bsc_predict_pass_offset), so a Poisson ``mean`` is the expected count at that exposure.
 The Beta model takes ``offset`` and ``weights`` the same way and, its link being a logit, no ``exposure``; so does the
-log-normal model, whose linear predictor is the location of log t.
+log-normal model, whose linear predictor is the location of log t.  The zero-inflated Poisson model follows the Poisson
+rules (offset or exposure): its ``mean`` is (1 - pi) times the expected count at that exposure.
 A model fitted with an offset refuses to predict without one.  ``weights`` leave every per-row output alone and make
 ``lpd_sum`` the weighted sum_n v_n lpd_n (float64, on the device, from the lpd vector).
 
@@ -72,7 +76,9 @@ FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
 # One row per family (csrc/bsc_families.h holds the device side of each):
 #   entry    its own entry point (the offset may be None), or None: bsc_predict_pass[_offset] with its FAMILIES id
 #   link     "log" or "logit": the offset / exposure rules (a logit link takes offset and refuses exposure); "location":
-#            the location of log t, offset allowed and exposure refused as for a logit; None: neither
+#            the location of log t, offset allowed and exposure refused as for a logit; "count": the log mean of the
+#            Poisson part of a mixture, the rules of "log" under a word of its own (the views below keep their
+#            contents); None: neither
 #   scalar   a per-draw log-scalar rides behind the weights
 #   grouped  include/bayesic_hip.h: BSC_SCALAR_*, its id with groups (svi/hier_scalar.py), or None: not built
 Family = namedtuple("Family", "entry link scalar grouped")
@@ -85,6 +91,7 @@ FAMILY_TABLE = {
     "weibull": Family("bsc_weibull_predict_pass", "log", True, 2),
     "beta": Family("bsc_beta_predict_pass", "logit", True, None),
     "lognormal": Family("bsc_lognormal_predict_pass", "location", True, None),
+    "zip": Family("bsc_zip_predict_pass", "count", True, None),
 }
 NO_FAMILY = Family(None, None, False, None)      # softmax and ordinal: their own passes and their own rules
 # the table's columns under their earlier names
@@ -99,8 +106,8 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 
 def family_of(model):
     """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI, "gamma" for GammaReparamSVI,
-    "weibull" for WeibullReparamSVI, "beta" for BetaReparamSVI, "lognormal" for LogNormalReparamSVI, "ordinal" for
-    OrdinalReparamSVI; HierGLMReparamSVI's link
+    "weibull" for WeibullReparamSVI, "beta" for BetaReparamSVI, "lognormal" for LogNormalReparamSVI, "zip" for
+    ZIPoissonReparamSVI, "ordinal" for OrdinalReparamSVI; HierGLMReparamSVI's link
     too -- ``grouped`` tells that model apart), "softmax" for SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
     if getattr(model, "n_classes", None) is not None:
         return "softmax"
@@ -148,7 +155,8 @@ def posterior_draws(model, n_samples=64, seed=None):
     SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d) and Z [S, D + K - 1] = [w | theta] for
     OrdinalReparamSVI; for NegBinReparamSVI the second
     entry is logphi float32 [S], for GammaReparamSVI and WeibullReparamSVI logshape float32 [S], for BetaReparamSVI
-    logprec float32 [S], for LogNormalReparamSVI loginvscale float32 [S]; for HierGLMReparamSVI it is the intercept
+    logprec float32 [S], for LogNormalReparamSVI loginvscale float32 [S], for ZIPoissonReparamSVI logodds float32
+    [S]; for HierGLMReparamSVI it is the intercept
     table Bt float32 [J + 1, ldb] (module
     docstring), and for the drivers of svi/hier_scalar.py the triple (W, Bt, logtau float32 [S])."""
     S = _check_samples(n_samples)
@@ -218,7 +226,8 @@ def _obs(model, family, B, offset, exposure, weights):
         return batch_obs(model.ctx, B, offset, weights)
     if row.link is None:
         raise ValueError("predict: offset, exposure and weights are for the logistic and Poisson models, not %s" % family)
-    check_link("poisson" if row.entry else family, offset, exposure, kept="means")   # (its own entry: a log link)
+    # (its own entry: a log link, "log" or "count")
+    check_link("poisson" if row.entry else family, offset, exposure, kept="means")
     return batch_obs(model.ctx, B, offset, weights, exposure)
 
 

@@ -784,6 +784,61 @@ int bsc_glm_lognormal_update(bsc_ctx* ctx, const double* stats, const double* la
                              double* eps_next, int32_t eps_next_ready, float* W_next, float* loginvscale_next,
                              double* elbo, double* grad);
 
+/* ---- Zero-inflated Poisson regression with a learned inflation odds on the same pass (csrc/bsc_glm_zip.hip)
+ *
+ *      y_n ~ ZIP(pi, mu_n): with probability pi a structural zero, else Poisson(mu_n)
+ *      mu_n = e^{l_n},   l[n,s] = sum_d X[n,d] W[s,d] + o[n]          (offset or log exposure, as in the Poisson route)
+ *      w ~ N(0, I / prior_precision),   omega = pi / (1 - pi) = e^tau ~ Gamma(a0, b0)
+ * The latent is z = [w (D) | tau], P = D + 1, the guide mean-field: lam = [m (P) | rho (P)].  tau is the log ODDS of a
+ * structural zero, pi = sigmoid(tau), so that the prior on e^tau has the form the shared finish knows.  One draw of it
+ * rides with every weight draw: logodds[s] = tau_s, float32 [S], any 4-byte alignment.  Per draw L1 = log1p(omega) =
+ * softplus(tau_s) and pi = sigmoid(tau_s) are made once per launch in float64 from the value read and rounded.  With
+ * u = tau + mu and the branch of a row chosen by y == 0:
+ *                   y == 0                                                   y > 0
+ *      log p        max(tau, -mu) + log1p(e^{-|u|}) - L1                      y l - mu - L1
+ *      d / d l      -mu sigmoid(-u)                                           y - mu
+ *      d / d tau    sigmoid(u) (1 - pi) (1 - e^{-mu})                         -pi
+ *      ell[s]  = sum_n v[n] log p        G[s,d] = sum_n r[n,s] X[n,d],  r = v d / d l        T[s] = sum_n v[n] d / d tau
+ * The zero branch is log(omega + e^{-mu}) - log1p(omega); softplus(u) - mu is never formed.  sigmoid(-u) is the
+ * probability that a zero came from the Poisson part.  sigmoid(u) and sigmoid(-u) each come from the stable logistic
+ * form on e^{-|u|}; the tau derivative of a zero row is the product above (= sigmoid(u) - sigmoid(tau), which would cancel
+ * at small mu), never negative; 1 - e^{-mu} through expm1.  The positive branch leaves the row constant -lnGamma(y + 1)
+ * out, as bsc_glm_data_pass(BSC_GLM_POISSON) and bsc_glm_nb_data_pass do.
+ * Outputs float64: ell [S], G [S, D], T [S].  offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0,
+ * v = 1; a row with v[n] = 0 adds EXACTLY nothing to ell, G and T, by a select on the link's inputs: it is evaluated at
+ * y = 0, l = 0 whatever it held -- NaN, infinity and negative values included -- as the rows past B are).
+ * y IS NOT CHECKED ON THE DEVICE: a kept row with a negative or non-finite y is read as a positive count
+ * (bayesic_amd/svi/glm_zip.py checks y finite, >= 0 and whole where a batch is set).
+ * OVERFLOW: nothing is clamped, like the Poisson link: every term is finite while e^l is (l <= 88).  At l = +80 a zero
+ * row gives exactly log p = tau - L1 (= log pi), d / d l = 0 and d / d tau = 1 - pi; at l = -80 every term is finite (a zero row's
+ * log p is -(1 - pi) mu to first order, within a rounding of L1 of 0; a positive row's is y l - L1).
+ * ACCURACY: a plain float32 evaluation stays within 1e-6, and the device within 2e-5, of
+ *      sum_n v ( |tau| + mu + L1 + |y l| + 1 )          for ell,
+ *      sum_n v ( |d / d tau| + pi + 1 )                  for T,
+ *      sum_n v ( y + (1 + a) mu r + a mu^2 r (1 - r) [y == 0] ) |x_d|                        for G[., d]
+ * (a = sum_d |x_d w_d| + |o| the size of the logit's float32 terms; r = sigmoid(-u) on a zero row and 1 on a positive
+ * one, so that mu r is the size of the residual's second term and the rest its conditioning on l) over tau in [-8, 8]
+ * and l in [-80, 80].
+ * The envelope and its refusals are bsc_glm_nb_data_pass's (D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 with eight draws
+ * and their eight tau per launch, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26); logodds == NULL is
+ * refused.  The 16-row MFMA kernel (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned,
+ * else the 8-row kernel.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block partials of
+ * 8 * 256 + 16 floats (ell and T behind G), fixed-order float64 finish, no float atomics.
+ * Not built: covariates on the zero share, a zero-inflated negative binomial, hurdle models, random intercepts. */
+int bsc_glm_zip_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                          const float* weight, int64_t B, int32_t D, const float* W, const float* logodds, int32_t S,
+                          double* ell, double* G, double* T);
+
+/* The finish: bsc_glm_nb_update with logodds in the place of logphi -- the prior on e^tau = pi / (1 - pi) has the same
+ * form, the likelihood enters through ell, G and T alone, and the entry points run one body (csrc/bsc_meanfield.h), so
+ * the same arguments give the same bits as bsc_glm_nb_update.  stats = [ell (S) | G (S*D) | T (S)]; checks, next draws
+ * and requirements as there.  A full-covariance guide finishes with bsc_glm_scalar_fullrank_update. */
+int bsc_glm_zip_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                       double* m2, const double* eps, const float* W, const float* logodds, int32_t D, int32_t S,
+                       double scale, double prior_precision, double a0, double b0, int64_t t, double lr, double beta1,
+                       double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
+                       int32_t eps_next_ready, float* W_next, float* logodds_next, double* elbo, double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
@@ -967,6 +1022,23 @@ int bsc_weibull_predict_pass_interval(bsc_ctx* ctx, const float* X, int64_t ldx,
 int bsc_lognormal_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
                                int64_t B, int32_t D, const float* W, const float* loginvscale, int32_t S, float* mean,
                                float* var, float* lpd, double* lpd_sum);
+
+/* The predictive of the zero-inflated Poisson model (csrc/bsc_glm_zip.hip: bsc_predict_pass's kernel with a family that
+ * only this entry point reaches).  Per draw, with pi_s = sigmoid(logodds[s]), L1_s = softplus(logodds[s]) (both made once
+ * per launch in float64 and rounded), l[n,s] = sum_d X[n,d] W[s,d] + o[n] (offset may be NULL) and mu = e^l, the three
+ * outputs are
+ *      m = (1 - pi_s) mu        v = (1 - pi_s) mu (1 + pi_s mu)
+ *      log p(y | l, tau_s) = max(tau_s, -mu) + log1p(e^{-|tau_s + mu|}) - L1_s     (y == 0: log(pi + (1 - pi) e^{-mu}))
+ *                          = y l - mu - L1_s - lnGamma(y + 1)                      (y > 0)
+ *      mean[n] = 1/S sum_s m,     var[n] = 1/S sum_s v + 1/S sum_s (m - mean[n])^2
+ *      lpd[n]  = logsumexp_s log p(y[n] | l[n,s], tau_s) - log S,     lpd_sum = sum_n lpd[n]     (float64 [1])
+ * log p in the training pass's forms; lnGamma(y + 1) is taken off once per row after the log-mean-exp (lnGamma(1) = 0
+ * keeps the zero rows right).  A batch with y = 0 in every row gives the log of the predictive P(y = 0 | x).  exp is NOT
+ * clamped: mean stops being finite at l > 88, var at 2 l > 88; lpd is finite for |l| <= 80.  y is not checked here.
+ * Outputs, refusals, envelope and determinism are bsc_nb_predict_pass's; logodds == NULL is BSC_ERR_INVALID. */
+int bsc_zip_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
+                         int32_t D, const float* W, const float* logodds, int32_t S, float* mean, float* var,
+                         float* lpd, double* lpd_sum);
 
 /* The predictive of the random-intercept model (csrc/bsc_predict_group.hip: bsc_predict_pass_offset's kernel with a
  * per-draw, per-group intercept; bsc_glm_data_pass_groups is its training pass):
