@@ -224,6 +224,9 @@ SIGNATURES = {
     "bsc_mog_log_normalizer": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "bsc_mog_natgrad_elbo": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_double,
                                      c_double, c_void_p, c_void_p, c_void_p]),
+    "bsc_mog_predictive_params": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "bsc_mog_predict_pass": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "bsc_bbvi_sample": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_uint32,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsc_logreg_bbvi_loglik": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,

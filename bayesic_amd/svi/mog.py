@@ -6,6 +6,14 @@ mini-batching) + README.md:36,75-77 (VMP == unit-step natural gradient; SVI, ref
 [4]).  One update = expected-parameter kernel -> fused E-step/statistics pass
 (fp32 MFMA) -> float64 reduction -> (all-reduce of the K(1+2D) statistics + the
 bound term when data-parallel) -> natural-gradient step.  All on the device.
+
+After (or during) the fit the model answers for rows it has not seen: ``predict`` gives the exact posterior
+predictive of the fitted mixture under the mean-field q -- a mixture of products of Student-t laws, the Dirichlet and
+the Normal-Gamma factors integrated out -- as a per-row log density, the predictive membership probabilities and the
+label, in ONE fused pass over X (csrc/bsc_mog_predict.hip); ``heldout_lpd`` is its mean log density, the figure the
+regression drivers compare models by (and what decides K).  The pass reads only ``eta``, so both routes of the local
+step have it; it is limited to K <= 64 and D <= 16 and evaluates the rows of this rank only.  It is NOT the variational
+responsibility of the training E-step (that one plugs E_q[log .] into the logits) and has no row weights.
 """
 import numpy as np
 import torch
@@ -53,6 +61,9 @@ def unpack(eta, K, D):
     e1, e2, e3, e4 = (eta[K + i * K * D: K + (i + 1) * K * D].reshape(K, D) for i in range(4))
     m = e1 / e2
     return alpha, m, e2, 0.5 * (e3 + 1.0), 0.5 * (e4 - e2 * m * m)
+
+
+PREDICT_MAX_K, PREDICT_MAX_D = 64, 16     # the fused predictive pass (PK, PD of csrc/bsc_mog_predict.hip)
 
 
 class MoGNatGradSVI:
@@ -158,3 +169,67 @@ class MoGNatGradSVI:
         self.exchange.all_reduce(self.buf)
         self.ctx.call("bsc_mog_natgrad_elbo", self.eta, self.eta0, self.stats, self.K,
                       self.D, self.n_total / self.batch_rows, float(rho), self.lse, self._bound, self.elbo)
+
+    # -- the posterior predictive at the current eta (csrc/bsc_mog_predict.hip) -------------------------------------
+    def _predict_limits(self):
+        if self.K > PREDICT_MAX_K or self.D > PREDICT_MAX_D:
+            raise NotImplementedError(
+                "the fused predictive pass takes K <= %d components and D <= %d columns; this model has K=%d, D=%d"
+                % (PREDICT_MAX_K, PREDICT_MAX_D, self.K, self.D))
+
+    def _predict_rows(self, X):
+        """-> (device tensor, ldx): X as the pass reads it.  Checked before anything reaches the device."""
+        if isinstance(X, torch.Tensor):
+            if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1:
+                raise ValueError("X must be a row-major float32 [N, D] tensor")
+        else:
+            X = np.asarray(X)
+            if X.ndim != 2:
+                raise ValueError("X must be a [N, D] array")
+        if X.shape[1] != self.D:
+            raise ValueError("X has %d columns, the model has D=%d" % (X.shape[1], self.D))
+        if not isinstance(X, torch.Tensor):
+            X = self.ctx.to_device(X, torch.float32)
+        elif not X.is_cuda:
+            X = X.contiguous().to(self.ctx.device)
+        ldx = X.stride(0) if X.shape[0] > 1 else self.D
+        if ldx < self.D:
+            raise ValueError("the rows of X overlap (row stride %d < D=%d)" % (ldx, self.D))
+        return X, ldx
+
+    def predictive_params(self):
+        """(Pt float32 [K, 3D] = [m | q | h], c float32 [K]) of the predictive's logits at the current eta:
+        logit_k(x) = c_k - sum_d h_kd log1p(q_kd (x_d - m_kd)^2).  Device tensors."""
+        Pt = self.ctx.empty((self.K, 3 * self.D))
+        c = self.ctx.empty(self.K)
+        self.ctx.call("bsc_mog_predictive_params", self.eta, self.K, self.D, Pt, c)
+        return Pt, c
+
+    def predict(self, X, responsibilities=False):
+        """The posterior predictive of the rows of X (a host array, or a row-major float32 device tensor: strided views
+        are read in place) at the current eta, one pass.  -> dict of device tensors: ``lpd`` float32 [N] (log density),
+        ``label`` int32 [N] (argmax_k, the lowest index among equal maxima), ``lpd_sum`` float64 [1] (fixed-order sum)
+        and, with ``responsibilities``, ``resp`` float32 [N, K] (the predictive membership probabilities)."""
+        self._predict_limits()
+        X, ldx = self._predict_rows(X)
+        N = X.shape[0]
+        Pt, c = self.predictive_params()
+        out = dict(lpd=self.ctx.empty(N), label=self.ctx.empty(N, torch.int32), lpd_sum=self.ctx.empty(1, torch.float64))
+        R = self.ctx.empty((N, self.K)) if responsibilities else None
+        self.ctx.call("bsc_mog_predict_pass", X, ldx, N, self.D, self.K, Pt, c, out["lpd"], out["label"], R, self.K,
+                      out["lpd_sum"])
+        if responsibilities:
+            out["resp"] = R
+        return out
+
+    def heldout_lpd(self, X):
+        """Mean log posterior-predictive density of the rows of X (host float): lpd_sum / N."""
+        self._predict_limits()
+        X, ldx = self._predict_rows(X)
+        N = X.shape[0]
+        if N == 0:
+            raise ValueError("heldout_lpd needs at least one row")
+        Pt, c = self.predictive_params()
+        lpd_sum = self.ctx.empty(1, torch.float64)
+        self.ctx.call("bsc_mog_predict_pass", X, ldx, N, self.D, self.K, Pt, c, None, None, None, self.K, lpd_sum)
+        return float(lpd_sum.item()) / N

@@ -1390,6 +1390,34 @@ int bsc_mog_natgrad_elbo(bsc_ctx* ctx, double* eta, const double* eta0, const do
                          int32_t D, double scale, double rho, const double* lse, const double* bound,
                          double* elbo);
 
+/* The exact posterior predictive of the fitted mixture under the mean-field q (ABSENT in the reference;
+ * README.md:43,72 -- marginalise the discrete latent by summation -- for a NEW row, with the Dirichlet and the
+ * Normal-Gamma factors integrated out in closed form).  With (alpha [K], m, kappa, a, b [K, D]) read from eta as
+ * above, the predictive is a mixture of products of Student-t laws,
+ *     p(x*) = sum_k alpha_k / sum(alpha) prod_d St(x_d; location m_kd, scale^2 = b_kd (kappa_kd + 1) / (a_kd kappa_kd),
+ *                                                   dof 2 a_kd),
+ *     logit_k(x) = c_k - sum_d h_kd log1p(q_kd (x_d - m_kd)^2),
+ *         h_kd = a_kd + 1/2,   q_kd = kappa_kd / (2 b_kd (kappa_kd + 1)),
+ *         c_k  = log alpha_k - log sum(alpha) + sum_d [lnGamma(a_kd + 1/2) - lnGamma(a_kd) + log(q_kd / pi) / 2],
+ *     lpd(x)   = logsumexp_k logit_k(x)        (the log posterior-predictive density),
+ *     R_k(x)   = exp(logit_k(x) - lpd(x))      (the predictive probability that the row belongs to component k),
+ *     label(x) = argmax_k logit_k(x)           (the lowest index among equal float32 maxima).
+ * The logit is formed from (x - m)^2, not from the expanded quadratic (which loses digits on data that are not
+ * centred), and log1p as log(w) u / (w - 1), w = 1 + u: h ~ N_k / 2 multiplies whatever log(1 + u) would lose.
+ *
+ * bsc_mog_predictive_params writes the table Pt float32 [K, 3D] = [m | q | h] and c float32 [K]: everything in
+ * float64, rounded once.  K <= 1024; the validity of eta is the caller's, as for bsc_mog_expected_params.
+ *
+ * bsc_mog_predict_pass is ONE pass over X (float32 [N, D], rows ldx apart).  Each of lpd [N], label [N],
+ * R [N, K] (rows ldr >= K apart) and lpd_sum [1] may be NULL, not all four.  lpd_sum = sum_n lpd(x_n) in float64 in a
+ * fixed order (no float atomics: two runs give the same bits); N = 0 is BSC_OK and gives lpd_sum = 0.  Nothing is
+ * written past N rows, and the pass reads no environment variable.  Limits, the fused E-step's: D <= 16 and K <= 64
+ * (BSC_ERR_UNSUPPORTED otherwise); X 4-byte aligned, D <= ldx < 2^25. */
+int bsc_mog_predictive_params(bsc_ctx* ctx, const double* eta, int32_t K, int32_t D, float* Pt, float* c);
+int bsc_mog_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, int64_t N, int32_t D, int32_t K,
+                         const float* Pt, const float* c, float* lpd, int32_t* label, float* R, int64_t ldr,
+                         double* lpd_sum);
+
 /* ---- black-box VI, score-function gradient with control variate ------------
  * (ABSENT in reference; README.md:52 -> ref [3]; config 5: hierarchical logistic
  * regression y_n ~ Bernoulli(sigmoid(x_n.w + b_{g_n})), z = [w (D) | b (G) | log tau],
