@@ -20,7 +20,7 @@ class BayesicHipError(RuntimeError):
 
 # The argument types of the three entry points of a family with a learned log-scalar behind the weights
 # (csrc/bsc_scalar_family.h): the negative-binomial, Gamma, Weibull, Beta, log-normal and zero-inflated Poisson routes have the same signatures, the interval pair
-# one more pointer behind y.  Tuples: every entry of SIGNATURES gets a list of its own (_scalar).
+# one more pointer behind y, the Student-t pass and predictive one double behind S.  Tuples: every entry of SIGNATURES gets a list of its own (_scalar).
 _SCALAR_DATA_PASS = (c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                      c_int32, c_void_p, c_void_p, c_void_p)
 _SCALAR_UPDATE = (c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
@@ -30,8 +30,13 @@ _SCALAR_PREDICT_PASS = (c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64
                         c_void_p, c_void_p, c_void_p, c_void_p)
 
 
-def _scalar(argtypes, upper=False):
-    """The entry of SIGNATURES; ``upper``: (ctx, X, ldx, y, ...) -> (ctx, X, ldx, y, upper, ...)."""
+def _scalar(argtypes, upper=False, df=False):
+    """The entry of SIGNATURES; ``upper``: (ctx, X, ldx, y, ...) -> (ctx, X, ldx, y, upper, ...); ``df``: one double, the
+    Student-t route's degrees of freedom, behind S -- (..., S, ell, ...) -> (..., S, df, ell, ...), and the same in the
+    predictive, where S is the tenth argument."""
+    if df:
+        at = argtypes.index(c_int32, 8) + 1          # S: the last 32-bit integer of both argument lists
+        return c_int, list(argtypes[:at] + (c_double,) + argtypes[at:])
     return c_int, list(argtypes[:4] + (c_void_p,) + argtypes[4:] if upper else argtypes)
 
 
@@ -151,6 +156,8 @@ SIGNATURES = {
     "bsc_glm_lognormal_update": _scalar(_SCALAR_UPDATE),
     "bsc_glm_zip_data_pass": _scalar(_SCALAR_DATA_PASS),
     "bsc_glm_zip_update": _scalar(_SCALAR_UPDATE),
+    "bsc_glm_studentt_data_pass": _scalar(_SCALAR_DATA_PASS, df=True),
+    "bsc_glm_studentt_update": _scalar(_SCALAR_UPDATE),
     "bsc_glm_weibull_data_pass": _scalar(_SCALAR_DATA_PASS),
     "bsc_glm_weibull_data_pass_interval": _scalar(_SCALAR_DATA_PASS, upper=True),
     "bsc_glm_weibull_update": _scalar(_SCALAR_UPDATE),
@@ -170,6 +177,7 @@ SIGNATURES = {
     "bsc_beta_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
     "bsc_lognormal_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
     "bsc_zip_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
+    "bsc_studentt_predict_pass": _scalar(_SCALAR_PREDICT_PASS, df=True),
     "bsc_weibull_predict_pass": _scalar(_SCALAR_PREDICT_PASS),
     "bsc_weibull_predict_pass_interval": _scalar(_SCALAR_PREDICT_PASS, upper=True),
     "bsc_predict_pass_groups": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,

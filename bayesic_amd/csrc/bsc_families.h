@@ -14,6 +14,9 @@
 //   predict_link  prediction: mu, v and log p(y | l) of one (row, draw): (l, y, the row's `upper` entry, slots 0 .. 2,
 //                 outputs, slot 3)
 //   ROW_LGAMMA    prediction: lnGamma(y + 1) is taken off once per row, after the log-mean-exp
+//   PARAM         a constant of the model (the Student-t's degrees of freedom) rides with the launch as one float: glm_disp
+//                 and predict_slots take it as a last argument, and the kernels are the scalar_par_* ones
+//                 (csrc/bsc_scalar_family.h), which have it as theirs
 //
 // The kernels are compared instruction by instruction when a family moves (profiles/family_refactor_isa.txt).  What
 // keeps them as they are: a link is ONE function (the compiler simplifies every function on its own before it inlines
@@ -68,6 +71,7 @@ __device__ __forceinline__ void predict_slots3(float* gp, int s, float lv) {
 struct PlainFamily {
     static constexpr int GLM_ID = -1;              // no training pass of csrc/bsc_glm_pass.h
     static constexpr bool SCALAR = false, PER_DRAW = false, ROW_LGAMMA = false, UPPER = false;
+    static constexpr bool PARAM = false;           // no per-model constant rides with the launch
     static __device__ __forceinline__ void predict_slots(float* gp, int s, float lv) { predict_slots3(gp, s, lv); }
 };
 
@@ -167,6 +171,7 @@ struct Ordinal : PlainFamily {
 struct ScalarFamily {
     static constexpr bool SCALAR = true, PER_DRAW = true, ROW_LGAMMA = false;
     static constexpr bool UPPER = false;           // the links take no upper ends
+    static constexpr bool PARAM = false;           // no per-model constant: glm_disp and predict_slots take none
     // (tau, phi = e^tau, lnGamma(phi), psi(phi)): the negative binomial's and the Beta family's
     static __device__ __forceinline__ GlmDisp glm_disp(const float* __restrict__ logphi, int s, int S) {
         GlmDisp d = glm_disp_tau(logphi, s, S);
@@ -640,6 +645,81 @@ struct ZeroInflPoisson : ScalarFamily {
     }
 };
 
+// ---- Student-t: tau = log(1 / sigma), the log of the INVERSE scale, as in the log-normal family; nu > 0, the degrees of
+// freedom, is a constant of the MODEL and rides with every launch as one more kernel argument (PARAM); internal ids:
+// csrc/bsc_glm_studentt.hip (bsc_studentt_predict_pass) ----------------------------------------------------------------
+// glm_disp: (tau, k = 1 / sigma = e^tau, tau + c_nu, nu) with c_nu = lnGamma((nu + 1) / 2) - lnGamma(nu / 2) -
+// log(nu pi) / 2 made once per launch in float64 from the float32 nu the kernel was handed, added to tau there and
+// rounded once.  y any finite float, l the LOCATION, z = k (y - l):
+//     ell  += v [ tau + c_nu - ((nu + 1) / 2) log1p(z^2 / nu) ]                    (the full density, nothing left out)
+//     resid = v k (nu + 1) z / (nu + z^2)                                 (= d / d l; BOUNDED in z: the robustness)
+//     T    += v nu (1 - z^2) / (nu + z^2)                                 (= d / d tau; not 1 - (nu + 1) z^2 / (nu + z^2),
+//                                                                          which cancels near z^2 = 1)
+// log1p(r), r = z^2 / nu, through the quotient form log(t) r / (t - 1), t = 1 + r, with the full-accuracy log and a true
+// division (t == 1: r itself): the quotient undoes the rounding of t, so that at nu = 1e6, where r is 1e-6 z^2 and the
+// product with (nu + 1) / 2 is z^2 / 2, every digit is kept.  1 / nu is a correctly rounded division, the same for every
+// row; the two derivatives share one hardware reciprocal of nu + z^2.  NOT clamped and nothing to clamp: every term is
+// finite while z^2 is (|z| < 1.8e19), outliers at |z| = 1e4 included.  One log and one reciprocal (and the quotient's
+// division) per (row, draw).  A non-finite y on a kept row is the caller's to keep out.
+// Prediction: slots (tau + c_nu, k, nu / ((nu - 2) k^2), nu), the first and the third made once per launch in float64 (the
+// exp(-logvar) slot carries the variance, +infinity for nu <= 2).  mu = l -- the location: the mean for nu > 1, the
+// median always --, v = the third slot; log p in the training forms.
+struct StudentT : ScalarFamily {
+    static constexpr int GLM_ID = 8, PREDICT_ID = 10;
+    static constexpr bool UPPER = false;
+    static constexpr bool PARAM = true;            // nu: the last argument of the scalar_par_* kernels
+    static __device__ __forceinline__ double log_norm(double nu) {
+        return bsc_lgamma_f64(0.5 * (nu + 1.0)) - bsc_lgamma_f64(0.5 * nu) - 0.5 * log(nu * 3.14159265358979323846);
+    }
+    static __device__ __forceinline__ GlmDisp glm_disp(const float* __restrict__ logphi, int s, int S, float nu) {
+        GlmDisp d = glm_disp_tau(logphi, s, S);
+        d.lg = (float)((double)d.tau + log_norm((double)nu));
+        d.psi = nu;
+        return d;
+    }
+    template <bool OBS, bool ITV>
+    static __device__ __forceinline__ float glm_link(float l, float yv, bool real_row, float& ell, float vv,
+                                                     const GlmDisp* dp, float* T, float uv) {
+        // a dropped row is evaluated at y = 0, l = 0 -- z = 0, every term finite whatever y held (NaN and infinity
+        // included)
+        const bool keep = real_row && vv > 0.0f;
+        const float vq = keep ? vv : 0.0f;
+        const float yq = keep ? yv : 0.0f;
+        const float lq = keep ? l : 0.0f;
+        const float nu = dp->psi;
+        const float np1 = nu + 1.0f;
+        const float z = dp->phi * (yq - lq);
+        const float zz = z * z;
+        const float r = zz * (1.0f / nu);
+        const float t = 1.0f + r;
+        // (t == 1: log(t) = 0 and the quotient is over 1, r itself is added -- selects between values at hand)
+        const bool tiny = t == 1.0f;
+        const float lp = logf(t) * (r / (tiny ? 1.0f : t - 1.0f)) + (tiny ? r : 0.0f);
+        const float q = __builtin_amdgcn_rcpf(fmaf(z, z, nu));
+        ell = fmaf(vq, fmaf(-0.5f * np1, lp, dp->lg), ell);
+        *T = fmaf(vq, (nu * (1.0f - zz)) * q, *T);
+        return vq * ((dp->phi * np1) * (z * q));
+    }
+    static __device__ __forceinline__ void predict_slots(float* gp, int s, float lv, float nu) {
+        predict_slots3(gp, s, lv);
+        const double n = (double)nu, k = (double)expf(lv);
+        gp[s] = (float)((double)lv + log_norm(n));
+        gp[2 * P_MAX_S + s] = nu > 2.0f ? (float)(n / ((n - 2.0) * k * k)) : INFINITY;
+        gp[3 * P_MAX_S + s] = nu;
+    }
+    template <bool ITV>
+    static __device__ __forceinline__ void predict_link(float l, float yv, float uv, float lv, float ev, float iv,
+                                                        float& mu, float& v, float& lp, float lgp) {
+        mu = l;
+        v = iv;
+        const float z = ev * (yv - l);
+        const float r = z * z * (1.0f / lgp);
+        const float t = 1.0f + r;
+        const float l1p = t == 1.0f ? r : logf(t) * r / (t - 1.0f);
+        lp = fmaf(-0.5f * (lgp + 1.0f), l1p, lv);
+    }
+};
+
 // ---- the ids to the structs ------------------------------------------------------------------------------------------
 template <int ID, class... Fs>
 struct FamilyById {
@@ -653,7 +733,8 @@ struct FamilyById<ID, F, Fs...> {
 };
 template <int ID>
 using FamilyOf =
-    FamilyById<ID, Logistic, Poisson, Gaussian, NegBin, Gamma, Weibull, Beta, LogNormal, ZeroInflPoisson, Ordinal>;
+    FamilyById<ID, Logistic, Poisson, Gaussian, NegBin, Gamma, Weibull, Beta, LogNormal, ZeroInflPoisson, StudentT,
+               Ordinal>;
 template <int LINK>
 using GlmFamily = typename FamilyOf<LINK>::glm;
 template <int FAM>

@@ -36,6 +36,10 @@
 //                 censoring.  One more per-row vector, `upper` [B] float32, rides in the tiles next to y and is loaded
 //                 the way y is (rows past B read 0); the family's link says how it is read.  Everything of it is behind
 //                 `if constexpr (ITV)`; the flag defaults to off and every other kernel compiles as it did.
+//   F::PARAM      not a flag either: a scalar family with one constant per MODEL (csrc/bsc_glm_studentt.hip: the degrees of
+//                 freedom).  It is the bodies' last argument `par`, a kernel argument of the scalar_par_* kernels
+//                 (csrc/bsc_scalar_family.h), and is read once, by F::glm_disp, which keeps what the link needs of it in
+//                 the draw's four registers.  Behind `if constexpr (F::PARAM)`; every other kernel compiles as it did.
 //
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
@@ -223,11 +227,13 @@ __device__ __forceinline__ void write_block_partial(const float* lds, float* __r
 // o, v_: the offset and the weight, each may be null; read only where OBS.
 // F::SCALAR: logphi [S] (this launch's chunk of the scalar's draws); the slab is NB_SLAB_STRIDE floats per block.
 // ITV (a scalar family whose link takes it, without groups): `upper` [B], not null, rides in the tiles next to y.
+// F::PARAM: `par`, the family's per-model constant (uniform over the launch), goes to F::glm_disp and nowhere else.
 template <class F, bool FULL, bool OBS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const float* y, const float* o,
                                               const float* v_, int64_t B, int D, const float* W, int S, float* slab,
                                               int n_iter, const GlmGroupArgs* ga = nullptr,
-                                              const float* logphi = nullptr, const float* upper = nullptr) {
+                                              const float* logphi = nullptr, const float* upper = nullptr,
+                                              float par = 0.f) {
     static_assert(!F::SCALAR || OBS, "the dispersion (the shape) rides with OBS");
     static_assert(!ITV || (F::SCALAR && !GRP), "the upper end rides with a learned shape, without groups");
     constexpr int STRIDE = F::SCALAR ? NB_SLAB_STRIDE : SLAB_STRIDE;
@@ -240,7 +246,10 @@ __device__ __forceinline__ void glm_pass_body(const float* X, int64_t ldx, const
     const bool has_v = OBS && v_ != nullptr;
     GlmDisp dp;          // (dp and tacc: untouched without F::SCALAR)
     float tacc = 0.f;
-    if constexpr (F::SCALAR) dp = F::glm_disp(logphi, lane_value<ROWS>(lane) & 7, S);   // before anything fills the file
+    if constexpr (F::SCALAR) {   // before anything fills the file
+        if constexpr (F::PARAM) dp = F::glm_disp(logphi, lane_value<ROWS>(lane) & 7, S, par);
+        else dp = F::glm_disp(logphi, lane_value<ROWS>(lane) & 7, S);
+    }
 
     float4 w[SG], acc[SG];
 #pragma unroll
@@ -375,7 +384,8 @@ template <class F, bool OBS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, const float* y, const float* o,
                                                    const float* v_, int64_t B, const float* W, int S, float* slab,
                                                    int n_iter, const GlmGroupArgs* ga = nullptr,
-                                                   const float* logphi = nullptr, const float* upper = nullptr) {
+                                                   const float* logphi = nullptr, const float* upper = nullptr,
+                                                   float par = 0.f) {
     static_assert(!F::SCALAR || OBS, "the dispersion (the shape) rides with OBS");
     static_assert(!ITV || (F::SCALAR && !GRP), "the upper end rides with a learned shape, without groups");
     constexpr int STRIDE = F::SCALAR ? NB_SLAB_STRIDE : SLAB_STRIDE;
@@ -390,7 +400,10 @@ __device__ __forceinline__ void glm_pass_mfma_body(const float* X, int64_t ldx, 
     const bool has_v = OBS && v_ != nullptr;
     GlmDisp dp;
     float tacc = 0.f;
-    if constexpr (F::SCALAR) dp = F::glm_disp(logphi, i16, S);   // lane (i16, kq) owns draw i16 (live lanes: i16 < 8)
+    if constexpr (F::SCALAR) {   // lane (i16, kq) owns draw i16 (live lanes: i16 < 8)
+        if constexpr (F::PARAM) dp = F::glm_disp(logphi, i16, S, par);
+        else dp = F::glm_disp(logphi, i16, S);
+    }
 
     // forward B operand: W[draw i16][64 kq + 4 j + c]; MFMA columns 8 .. 15 and draws >= S are zero.  Lane group
     // kq contracts columns 64 kq .. 64 kq + 63, which keeps the 16-byte A reads of a lane group conflict-free.

@@ -176,9 +176,12 @@ __device__ __forceinline__ float predict_link_ordinal(float l, const float (&cut
 // tile's MFMAs.  Both loads are unconditional within their (wave-uniform) branch, so the X prefetch stays in flight.
 // ITV (a family whose link takes upper ends, with OFFS): `upper` [B] (not null) is loaded like y and the offset; with the
 // flag off nothing of it is compiled.
+// F::PARAM (a scalar family with one constant per model): `par` goes to F::predict_slots, which puts what the link needs
+// of it into the draws' slots; PredictArgs does not carry it.
 template <class F, int NC, bool FULL, bool OFFS, bool GRP = false, bool ITV = false>
 __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset, PredictGroups gr = PredictGroups{},
-                                             const float* upper = nullptr, PredictOrdinal od = PredictOrdinal{}) {
+                                             const float* upper = nullptr, PredictOrdinal od = PredictOrdinal{},
+                                             float par = 0.f) {
     static_assert(!GRP || OFFS, "the grouped body adds its intercept next to the offset");
     static_assert(!ITV || (F::UPPER && OFFS && !GRP), "the upper end belongs to a family whose link takes one");
     constexpr bool ORD = F::PREDICT_ID == PREDICT_ORDINAL;
@@ -206,7 +209,8 @@ __device__ __forceinline__ void predict_body(PredictArgs a, const float* offset,
     if constexpr (ORD) predict_ordinal_tables(ct, lt, a, od, tid);
     if (tid < P_MAX_S) {
         const float lv = (F::PER_DRAW && tid < S) ? a.logvar[tid] : 0.f;
-        F::predict_slots(gp, tid, lv);
+        if constexpr (F::PARAM) F::predict_slots(gp, tid, lv, par);
+        else F::predict_slots(gp, tid, lv);
         if constexpr (F::PREDICT_ID == Gamma::PREDICT_ID) {   // (csrc/bsc_families.h says why this one slot is made here)
             const double al = (double)expf(lv);
             gp[3 * P_MAX_S + tid] = (float)(al * log(al) - bsc_lgamma_f64(al));

@@ -1,8 +1,9 @@
 // The kernels and the host envelopes of the regression families with ONE learned log-scalar behind the weights,
 // z = [w (D) | tau]: the negative binomial's dispersion (csrc/bsc_glm_nb.hip), the Gamma shape (csrc/bsc_glm_gamma.hip),
 // the Weibull shape (csrc/bsc_glm_weibull.hip), the Weibull route with upper ends (csrc/bsc_glm_weibull_interval.hip),
-// the Beta precision (csrc/bsc_glm_beta.hip), the log-normal inverse scale (csrc/bsc_glm_lognormal.hip) and the
-// zero-inflated Poisson's inflation odds (csrc/bsc_glm_zip.hip).
+// the Beta precision (csrc/bsc_glm_beta.hip), the log-normal inverse scale (csrc/bsc_glm_lognormal.hip), the
+// zero-inflated Poisson's inflation odds (csrc/bsc_glm_zip.hip) and the Student-t inverse scale
+// (csrc/bsc_glm_studentt.hip).
 // A family is one struct F of csrc/bsc_families.h -- its two ids (LINK = F::GLM_ID, FAMILY = F::PREDICT_ID), its
 // constants and its links -- and the bodies are csrc/bsc_glm_pass.h's, csrc/bsc_predict_pass.h's and
 // csrc/bsc_meanfield.h's; what is here is the shell the four units used to repeat:
@@ -11,13 +12,18 @@
 //             scalar_mf_scalars_kernel<LINK>, scalar_mf_coord_kernel<LINK> (NbModel), scalar_predict_kernel<FAMILY, NC,
 //             FULL>, scalar_predict_sum_kernel<FAMILY>; with one more pointer, `upper` [B], behind the weight / the
 //             offset: scalar_upper_pass_kernel<LINK, FULL>, scalar_upper_pass_mfma_kernel<LINK>,
-//             scalar_upper_predict_kernel<FAMILY, NC, FULL>.
-//   host      scalar_family_data_pass<F, UPPER>, scalar_family_update<F>, scalar_family_predict_pass<F, UPPER>:
-//             the checks, the grid, the workspace and the launches of an entry point, naming their kernels themselves.
+//             scalar_upper_predict_kernel<FAMILY, NC, FULL>; with one more float, the family's per-model constant
+//             `par` (F::PARAM: the Student-t's degrees of freedom, csrc/bsc_glm_studentt.hip), as the last argument:
+//             scalar_par_pass_kernel<LINK, FULL>, scalar_par_pass_mfma_kernel<LINK>, scalar_par_predict_kernel<FAMILY, NC,
+//             FULL>.
+//   host      scalar_family_data_pass<F, UPPER, PARAM>, scalar_family_update<F>, scalar_family_predict_pass<F, UPPER,
+//             PARAM>: the checks, the grid, the workspace and the launches of an entry point, naming their kernels
+//             themselves.
 //
 // A translation unit gets exactly the kernels of the host templates it calls (anonymous namespace, so each unit's are its
-// own): a unit that never asks for UPPER has no `upper` kernel, the interval unit has no finish.  The next family with a
-// learned scalar is a struct in csrc/bsc_families.h, its id, and three extern "C" functions of a few lines.
+// own): a unit that never asks for UPPER has no `upper` kernel and one that never asks for PARAM no `par` kernel, the
+// interval unit has no finish.  The next family with a learned scalar is a struct in csrc/bsc_families.h, its id, and
+// three extern "C" functions of a few lines.
 // Header-only, internal linkage, like csrc/bsc_regress.h.
 #pragma once
 
@@ -67,6 +73,24 @@ __global__ __launch_bounds__(PASS_BLOCK, 2) void scalar_upper_pass_mfma_kernel(
                                                            u);
 }
 
+// `par`: the family's per-model constant (F::PARAM), the same for every draw and every launch of a pass
+template <int LINK, bool FULL>
+__global__ __launch_bounds__(PASS_BLOCK, 2) void scalar_par_pass_kernel(
+    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
+    const float* __restrict__ v, int64_t B, int D, const float* __restrict__ W, const float* __restrict__ logtau, int S,
+    float* __restrict__ slab, int n_iter, float par) {
+    glm_pass_body<GlmFamily<LINK>, FULL, true>(X, ldx, y, o, v, B, D, W, S, slab, n_iter, nullptr, logtau, nullptr,
+                                               par);
+}
+
+template <int LINK>
+__global__ __launch_bounds__(PASS_BLOCK, 2) void scalar_par_pass_mfma_kernel(
+    const float* __restrict__ X, int64_t ldx, const float* __restrict__ y, const float* __restrict__ o,
+    const float* __restrict__ v, int64_t B, const float* __restrict__ W, const float* __restrict__ logtau, int S,
+    float* __restrict__ slab, int n_iter, float par) {
+    glm_pass_mfma_body<GlmFamily<LINK>, true>(X, ldx, y, o, v, B, W, S, slab, n_iter, nullptr, logtau, nullptr, par);
+}
+
 template <int LINK>
 __global__ __launch_bounds__(RED_BLOCK) void scalar_slab_reduce_kernel(const float* __restrict__ slab, int n_blocks,
                                                                        int D, int S, int s_base,
@@ -78,13 +102,15 @@ __global__ __launch_bounds__(RED_BLOCK) void scalar_slab_reduce_kernel(const flo
 // The data pass of an entry point `who`: the 16-row MFMA kernel, the 8-row kernel with D == 256 and with any D, and the
 // reduction of the NB_SLAB_STRIDE slab, all S draws in chunks of eight.  `logtau` [S] is the per-draw scalar under the
 // name `what`.  UPPER: `upper` (not null) joins the vectors whose alignment decides the MFMA route and is handed to the
-// kernels behind the weight; without the flag it is not read.
-template <class F, bool UPPER = false>
+// kernels behind the weight; without the flag it is not read.  PARAM: `par`, the family's per-model constant (checked by
+// the entry point), is the kernels' last argument; without the flag it is not read.
+template <class F, bool UPPER = false, bool PARAM = false>
 int scalar_family_data_pass(bsc_ctx* ctx, const char* who, const char* what, const float* X, int64_t ldx,
                             const float* y, const float* upper, const float* offset, const float* weight, int64_t B,
                             int32_t D, const float* W, const float* logtau, int32_t S, double* ell, double* G,
-                            double* T) {
+                            double* T, float par = 0.f) {
     constexpr int LINK = F::GLM_ID;
+    static_assert(PARAM == F::PARAM && !(UPPER && PARAM), "the constant rides with the family that declares one");
     const int rc0 = check_glm_obs_args(who, BSC_GLM_LOGISTIC, X, ldx, y, offset, weight, B, D, W, S, SCALAR_MAX_S);
     if (rc0 != BSC_OK) return rc0;
     if constexpr (UPPER) BSC_REQUIRE((((uintptr_t)upper) & 3) == 0, "%s: upper must be 4-byte aligned", who);
@@ -115,11 +141,14 @@ int scalar_family_data_pass(bsc_ctx* ctx, const char* who, const char* what, con
                 rows, D,
                 [&] {
                     if constexpr (UPPER) go(scalar_upper_pass_mfma_kernel<LINK>, Ws, lp, sg, slab, g.n_iter);
+                    else if constexpr (PARAM) go(scalar_par_pass_mfma_kernel<LINK>, Ws, lp, sg, slab, g.n_iter, par);
                     else go(scalar_pass_mfma_kernel<LINK>, Ws, lp, sg, slab, g.n_iter);
                 },
                 [&](auto full) {
                     constexpr bool FULL = decltype(full)::value;
                     if constexpr (UPPER) go(scalar_upper_pass_kernel<LINK, FULL>, (int)D, Ws, lp, sg, slab, g.n_iter);
+                    else if constexpr (PARAM)
+                        go(scalar_par_pass_kernel<LINK, FULL>, (int)D, Ws, lp, sg, slab, g.n_iter, par);
                     else go(scalar_pass_kernel<LINK, FULL>, (int)D, Ws, lp, sg, slab, g.n_iter);
                 });
         },
@@ -192,20 +221,31 @@ __global__ __launch_bounds__(P_BLOCK, 2) void scalar_upper_predict_kernel(Predic
     predict_body<PredictFamily<FAMILY>, NC, FULL, true, false, true>(a, offset, PredictGroups{}, upper);
 }
 
+// ... or the family's per-model constant `par` (F::PARAM)
+template <int FAMILY, int NC, bool FULL>
+__global__ __launch_bounds__(P_BLOCK, 2) void scalar_par_predict_kernel(PredictArgs a, const float* __restrict__ offset,
+                                                                        float par) {
+    predict_body<PredictFamily<FAMILY>, NC, FULL, true>(a, offset, PredictGroups{}, nullptr, PredictOrdinal{}, par);
+}
+
 template <int FAMILY>
 __global__ __launch_bounds__(BSC_WAVE) void scalar_predict_sum_kernel(const double* __restrict__ partial, int n,
                                                                       double* __restrict__ out) {
     block_partial_sum(partial, n, out);
 }
 
-template <int FAMILY, bool UPPER, int NC>
-void launch_scalar_predict(bsc_ctx* ctx, const PredictArgs& a, const float* offset, const float* upper, int n_blocks) {
+template <int FAMILY, bool UPPER, bool PARAM, int NC>
+void launch_scalar_predict(bsc_ctx* ctx, const PredictArgs& a, const float* offset, const float* upper, float par,
+                           int n_blocks) {
     const dim3 grid(n_blocks), block(P_BLOCK);
     const auto go = [&](auto full) {
         constexpr bool FULL = decltype(full)::value;
         if constexpr (UPPER)
             hipLaunchKernelGGL((scalar_upper_predict_kernel<FAMILY, NC, FULL>), grid, block, 0, ctx->stream, a, offset,
                                upper);
+        else if constexpr (PARAM)
+            hipLaunchKernelGGL((scalar_par_predict_kernel<FAMILY, NC, FULL>), grid, block, 0, ctx->stream, a, offset,
+                               par);
         else
             hipLaunchKernelGGL((scalar_predict_kernel<FAMILY, NC, FULL>), grid, block, 0, ctx->stream, a, offset);
     };
@@ -215,13 +255,14 @@ void launch_scalar_predict(bsc_ctx* ctx, const PredictArgs& a, const float* offs
 
 // The predictive entry point `who` of a family with a per-draw scalar of its own (`logtau` [S], named `what` in the
 // messages) and an offset that may be null.  UPPER: `upper` (not null) rides with the offset; without the flag it is
-// not read.
-template <class F, bool UPPER = false>
+// not read.  PARAM: `par`, the family's per-model constant (checked by the entry point), is the kernels' last argument.
+template <class F, bool UPPER = false, bool PARAM = false>
 int scalar_family_predict_pass(bsc_ctx* ctx, const char* who, const char* what, const float* X, int64_t ldx,
                                const float* y, const float* upper, const float* offset, int64_t B, int32_t D,
                                const float* W, const float* logtau, int32_t S, float* mean, float* var, float* lpd,
-                               double* lpd_sum) {
+                               double* lpd_sum, float par = 0.f) {
     constexpr int FAMILY = F::PREDICT_ID;
+    static_assert(PARAM == F::PARAM && !(UPPER && PARAM), "the constant rides with the family that declares one");
     if constexpr (UPPER) BSC_REQUIRE((((uintptr_t)upper) & 3) == 0, "%s: upper must be 4-byte aligned", who);
     int rc = predict_check_batch(who, X, y, B, W, mean, var, lpd, lpd_sum);
     if (rc != BSC_OK) return rc;
@@ -235,7 +276,7 @@ int scalar_family_predict_pass(bsc_ctx* ctx, const char* who, const char* what, 
     {
         bsc_prof_scope prof(ctx);
         predict_launch_chunks(S, [&](auto nc) {
-            launch_scalar_predict<FAMILY, UPPER, decltype(nc)::value>(ctx, a, offset, upper, n_blocks);
+            launch_scalar_predict<FAMILY, UPPER, PARAM, decltype(nc)::value>(ctx, a, offset, upper, par, n_blocks);
         });
     }
     BSC_LAUNCH_CHECK();

@@ -6,6 +6,7 @@ from .glm_gamma import GammaReparamSVI  # noqa: E402,F401
 from .glm_lognormal import LogNormalReparamSVI  # noqa: E402,F401
 from .glm_nb import NegBinReparamSVI  # noqa: E402,F401
 from .glm_ordinal import OrdinalReparamSVI  # noqa: E402,F401
+from .glm_studentt import StudentTReparamSVI  # noqa: E402,F401
 from .glm_weibull import WeibullReparamSVI  # noqa: E402,F401
 from .glm_zip import ZIPoissonReparamSVI  # noqa: E402,F401
 from .hier_glm import HierGLMReparamSVI  # noqa: E402,F401
@@ -16,5 +17,5 @@ from .predict import heldout_lpd, posterior_draws  # noqa: E402,F401
 
 __all__ = ["BetaReparamSVI", "GLMReparamSVI", "GammaReparamSVI", "HierGLMReparamSVI", "HierGammaReparamSVI",
            "HierNegBinReparamSVI", "HierWeibullReparamSVI", "LogNormalReparamSVI", "NegBinReparamSVI",
-           "OrdinalReparamSVI", "SoftmaxReparamSVI", "WeibullReparamSVI", "ZIPoissonReparamSVI", "predict",
-           "posterior_draws", "heldout_lpd"]
+           "OrdinalReparamSVI", "SoftmaxReparamSVI", "StudentTReparamSVI", "WeibullReparamSVI", "ZIPoissonReparamSVI",
+           "predict", "posterior_draws", "heldout_lpd"]

@@ -34,6 +34,10 @@ The transform is parameter-sized and runs once per call: ``_reparam_base.first_d
     ZIPoissonReparamSVI               eps [S, D + 1]:  the same transform, tau = log omega, the log odds of a structural
                                       zero (bsc_zip_predict_pass; a log link: offset or exposure; upper= and groups=
                                       refused)
+    StudentTReparamSVI                eps [S, D + 1]:  the same transform, tau = log(1 / sigma), the inverse scale
+                                      (bsc_studentt_predict_pass, which also takes the model's df; ``mean`` is the
+                                      location -- the mean for df > 1, the median always --, ``var`` +inf for df <= 2;
+                                      offset allowed, exposure, upper= and groups= refused)
     HierNegBin/Gamma/WeibullReparamSVI  eps [S, D + J + 3]: the transform below over z = [w | b | zeta | tau], b_new
                                       from the last column; returned as (W, Bt, logtau float32 [S])
                                       (bsc_scalar_predict_pass_groups)
@@ -76,9 +80,9 @@ FAMILIES = {"gaussian": 0, "logistic": 1, "poisson": 2}
 # One row per family (csrc/bsc_families.h holds the device side of each):
 #   entry    its own entry point (the offset may be None), or None: bsc_predict_pass[_offset] with its FAMILIES id
 #   link     "log" or "logit": the offset / exposure rules (a logit link takes offset and refuses exposure); "location":
-#            the location of log t, offset allowed and exposure refused as for a logit; "count": the log mean of the
-#            Poisson part of a mixture, the rules of "log" under a word of its own (the views below keep their
-#            contents); None: neither
+#            the location of log t (of y itself for the Student-t family), offset allowed and exposure refused as for a
+#            logit; "count": the log mean of the Poisson part of a mixture, the rules of "log" under a word of its own
+#            (the views below keep their contents); None: neither
 #   scalar   a per-draw log-scalar rides behind the weights
 #   grouped  include/bayesic_hip.h: BSC_SCALAR_*, its id with groups (svi/hier_scalar.py), or None: not built
 Family = namedtuple("Family", "entry link scalar grouped")
@@ -92,6 +96,7 @@ FAMILY_TABLE = {
     "beta": Family("bsc_beta_predict_pass", "logit", True, None),
     "lognormal": Family("bsc_lognormal_predict_pass", "location", True, None),
     "zip": Family("bsc_zip_predict_pass", "count", True, None),
+    "studentt": Family("bsc_studentt_predict_pass", "location", True, None),
 }
 NO_FAMILY = Family(None, None, False, None)      # softmax and ordinal: their own passes and their own rules
 # the table's columns under their earlier names
@@ -107,7 +112,7 @@ __all__ = ["posterior_draws", "predict", "heldout_lpd", "family_of", "PREDICT_ST
 def family_of(model):
     """The likelihood family of a driver: its GLM link ("negbin" for NegBinReparamSVI, "gamma" for GammaReparamSVI,
     "weibull" for WeibullReparamSVI, "beta" for BetaReparamSVI, "lognormal" for LogNormalReparamSVI, "zip" for
-    ZIPoissonReparamSVI, "ordinal" for OrdinalReparamSVI; HierGLMReparamSVI's link
+    ZIPoissonReparamSVI, "studentt" for StudentTReparamSVI, "ordinal" for OrdinalReparamSVI; HierGLMReparamSVI's link
     too -- ``grouped`` tells that model apart), "softmax" for SoftmaxReparamSVI, or "gaussian" for BLRReparamSVI."""
     if getattr(model, "n_classes", None) is not None:
         return "softmax"
@@ -155,8 +160,8 @@ def posterior_draws(model, n_samples=64, seed=None):
     SoftmaxReparamSVI (its guide is over the K D entries, flattened p = k D + d) and Z [S, D + K - 1] = [w | theta] for
     OrdinalReparamSVI; for NegBinReparamSVI the second
     entry is logphi float32 [S], for GammaReparamSVI and WeibullReparamSVI logshape float32 [S], for BetaReparamSVI
-    logprec float32 [S], for LogNormalReparamSVI loginvscale float32 [S], for ZIPoissonReparamSVI logodds float32
-    [S]; for HierGLMReparamSVI it is the intercept
+    logprec float32 [S], for LogNormalReparamSVI and StudentTReparamSVI loginvscale float32 [S], for
+    ZIPoissonReparamSVI logodds float32 [S]; for HierGLMReparamSVI it is the intercept
     table Bt float32 [J + 1, ldb] (module
     docstring), and for the drivers of svi/hier_scalar.py the triple (W, Bt, logtau float32 [S])."""
     S = _check_samples(n_samples)
@@ -318,6 +323,9 @@ def predict(model, X, y=None, n_samples=64, seed=None, draws=None, offset=None, 
     elif upper is not None:        # the Weibull model with interval and left censoring; the offset may be None
         ctx.call("bsc_weibull_predict_pass_interval", X, ldx, y, upper, offset, B, model.D, W, logvar, S, out["mean"],
                  out["var"], out.get("lpd"), out.get("lpd_sum"))
+    elif family == "studentt":     # its own entry point and the model's degrees of freedom; the offset may be None
+        ctx.call(row.entry, X, ldx, y, offset, B, model.D, W, logvar, S, float(model.df), out["mean"], out["var"],
+                 out.get("lpd"), out.get("lpd_sum"))
     elif row.entry:                # its own entry point, behind a log or a logit link; the offset may be None
         ctx.call(row.entry, X, ldx, y, offset, B, model.D, W, logvar, S, out["mean"], out["var"], out.get("lpd"),
                  out.get("lpd_sum"))

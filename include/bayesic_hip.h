@@ -839,6 +839,63 @@ int bsc_glm_zip_update(bsc_ctx* ctx, const double* stats, const double* lam_in, 
                        double beta2, double adam_eps, uint64_t seed, uint32_t next_step, double* eps_next,
                        int32_t eps_next_ready, float* W_next, float* logodds_next, double* elbo, double* grad);
 
+/* ---- Student-t robust regression with a learned scale and fixed degrees of freedom on the same pass
+ * (csrc/bsc_glm_studentt.hip)
+ *
+ *      y_n ~ StudentT(df = nu, location l_n, scale sigma),   l[n,s] = sum_d X[n,d] W[s,d] + o[n]
+ *      w ~ N(0, I / prior_precision),   k = 1 / sigma = e^tau ~ Gamma(a0, b0),   nu = df > 0 fixed by the caller
+ * The latent is z = [w (D) | tau], P = D + 1, the guide mean-field: lam = [m (P) | rho (P)].  tau is the log of the
+ * INVERSE scale, as in bsc_glm_lognormal_data_pass, so that the prior on e^tau has the form the shared finish knows.  One
+ * draw of it rides with every weight draw: loginvscale[s] = tau_s, float32 [S], any 4-byte alignment; k_s = e^{tau_s}
+ * (float32 expf of the value read).  y is any finite float.  With z = k (y - l) and
+ * c_nu = lnGamma((nu + 1) / 2) - lnGamma(nu / 2) - log(nu pi) / 2:
+ *      log p   = tau + c_nu - ((nu + 1) / 2) log1p(z^2 / nu)                                     (the FULL density)
+ *      ell[s]  = sum_n v[n] log p(y[n] | l[n,s], k_s)
+ *      G[s,d]  = sum_n r[n,s] X[n,d]        r[n,s] = v[n] k_s (nu + 1) z[n,s] / (nu + z[n,s]^2)                  (= d / d l)
+ *      T[s]    = sum_n v[n] nu (1 - z[n,s]^2) / (nu + z[n,s]^2)                              (= d ell[s] / d tau_s)
+ * The residual is BOUNDED in z (k (nu + 1) / (2 sqrt nu) at most, at z^2 = nu): one gross outlier cannot move the fit as
+ * far as it likes, which it can under the Gaussian likelihood, the limit nu -> infinity of this one.
+ * df: the degrees of freedom, finite and > 0 (BSC_ERR_INVALID otherwise, the message naming the entry point); the kernels
+ * take it rounded to float32, and c_nu is made once per launch in float64 from the rounded value and added to tau_s there,
+ * so the density is normalised for the nu the link uses.  It is read at every call: two calls on one context may differ
+ * in it.
+ * Outputs float64: ell [S], G [S, D], T [S].  offset and weight are bsc_glm_data_pass_obs's (each may be NULL: o = 0,
+ * v = 1; a row with v[n] = 0 adds EXACTLY nothing to ell, G and T, by a select on the link's inputs: it is evaluated at
+ * y = 0, l = 0 whatever it held -- NaN and infinity included -- as the rows past B are).
+ * log1p(r), r = z^2 / nu, is log(t) r / (t - 1) with t = 1 + r (r itself where t == 1): the quotient undoes the rounding
+ * of t, so at nu = 1e6, where r = 1e-6 z^2 and ((nu + 1) / 2) log1p(r) = z^2 / 2, every digit is kept.
+ * y IS NOT CHECKED ON THE DEVICE: a kept row with a non-finite y makes ell, G and T of every draw NaN
+ * (bayesic_amd/svi/glm_studentt.py checks y where a batch is set).
+ * OVERFLOW: nothing is clamped and nothing needs to be: every term is finite while z^2 is (|z| < 1.8e19).
+ * ACCURACY: z inherits the rounding of k, y and l: with a = sum_d |x_d w_d| + |o| and c = |z| + k (|y| + a) a plain
+ * float32 evaluation stays within 1e-6, and the device within 2e-5, of
+ *      sum_n v ( |tau| + |c_nu| + ((nu + 1) / 2) log1p(z^2 / nu) + (nu + 1) |z| c / (nu + z^2) + 1 )              for ell,
+ *      sum_n v ( nu |1 - z^2| / (nu + z^2) + 2 nu (nu + 1) |z| c / (nu + z^2)^2 + 1 )                             for T,
+ *      sum_n v k (nu + 1) ( |z| + c |nu - z^2| / (nu + z^2) ) / (nu + z^2) |x_d|                                 for G[., d]
+ * (each derivative's size times c) over tau in [-3, 5], nu from 1 to 1e6 and |z| from 1e-3 to 1e4 and beyond.  Where the
+ * data are many sigma away from 0 (k |y| large against |z|) the term in c is the whole bound: y - l cancels.
+ * The envelope and its refusals are bsc_glm_nb_data_pass's (D % 4 == 0, 4 <= D <= 256, 1 <= S <= 64 with eight draws
+ * and their eight tau per launch, X and W 16-byte aligned, ldx >= D, ldx % 4 == 0, ldx < 2^26); loginvscale == NULL is
+ * refused.  The 16-row MFMA kernel (D == 256) is taken when y and the set ones of offset and weight are 16-byte aligned,
+ * else the 8-row kernel.  B = 0 gives zeros.  Deterministic: fixed partition, float32 block partials of
+ * 8 * 256 + 16 floats (ell and T behind G), fixed-order float64 finish, no float atomics.
+ * Not built: a learned nu, random intercepts, a one-call pass + finish form. */
+int bsc_glm_studentt_data_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                               const float* weight, int64_t B, int32_t D, const float* W, const float* loginvscale,
+                               int32_t S, double df, double* ell, double* G, double* T);
+
+/* The finish: bsc_glm_nb_update with loginvscale in the place of logphi -- the prior on e^tau = 1 / sigma has the same
+ * form, the likelihood enters through ell, G and T alone, and the entry points run one body (csrc/bsc_meanfield.h), so
+ * the same arguments give the same bits as bsc_glm_nb_update.  The finish never sees nu.  stats = [ell (S) | G (S*D) |
+ * T (S)]; checks, next draws and requirements as there.  A full-covariance guide finishes with
+ * bsc_glm_scalar_fullrank_update. */
+int bsc_glm_studentt_update(bsc_ctx* ctx, const double* stats, const double* lam_in, double* lam_out, double* m1,
+                            double* m2, const double* eps, const float* W, const float* loginvscale, int32_t D,
+                            int32_t S, double scale, double prior_precision, double a0, double b0, int64_t t, double lr,
+                            double beta1, double beta2, double adam_eps, uint64_t seed, uint32_t next_step,
+                            double* eps_next, int32_t eps_next_ready, float* W_next, float* loginvscale_next,
+                            double* elbo, double* grad);
+
 /* The finish of bsc_glm_update for a FULL-COVARIANCE Gaussian guide (csrc/bsc_glm_full.hip; full-rank ADVI, Kucukelbir
  * et al.): q(w) = N(mu, L L^T) over w in R^D (no scalar latent: P = D), L lower-triangular with L_ii = e^{rho_i}.
  *     lam = [mu (D) | L packed row-major, lower triangle incl. the diagonal (D(D+1)/2)]
@@ -1039,6 +1096,23 @@ int bsc_lognormal_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const 
 int bsc_zip_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset, int64_t B,
                          int32_t D, const float* W, const float* logodds, int32_t S, float* mean, float* var,
                          float* lpd, double* lpd_sum);
+
+/* The predictive of the Student-t model (csrc/bsc_glm_studentt.hip: bsc_predict_pass's kernel with a family that only
+ * this entry point reaches).  Per draw, with k_s = exp(loginvscale[s]), nu = df (bsc_glm_studentt_data_pass's: finite and
+ * > 0, rounded to float32), l[n,s] = sum_d X[n,d] W[s,d] + o[n] (offset may be NULL) and z = k_s (y - l), the three
+ * outputs are
+ *      mu = l        v = nu / ((nu - 2) k_s^2)  for nu > 2,   +infinity for nu <= 2
+ *      log p(y | l, k_s) = tau_s + c_nu - ((nu + 1) / 2) log1p(z^2 / nu)
+ *      mean[n] = 1/S sum_s mu,     var[n] = 1/S sum_s v + 1/S sum_s (mu - mean[n])^2
+ *      lpd[n]  = logsumexp_s log p(y[n] | l[n,s], k_s) - log S,     lpd_sum = sum_n lpd[n]     (float64 [1])
+ * mu is the LOCATION: the mean of the distribution for nu > 1 and its median for every nu (at nu <= 1 the distribution
+ * has no mean and `mean` is the draw average of the median).  var is +infinity in every row at nu <= 2, exactly.  tau_s +
+ * c_nu and v are made once per launch in float64 and rounded; log p is the training pass's, in its forms.  Nothing is
+ * clamped; y is not checked here.  Outputs, refusals, envelope and determinism are bsc_nb_predict_pass's;
+ * loginvscale == NULL and a df that is not finite and > 0 are BSC_ERR_INVALID. */
+int bsc_studentt_predict_pass(bsc_ctx* ctx, const float* X, int64_t ldx, const float* y, const float* offset,
+                              int64_t B, int32_t D, const float* W, const float* loginvscale, int32_t S, double df,
+                              float* mean, float* var, float* lpd, double* lpd_sum);
 
 /* The predictive of the random-intercept model (csrc/bsc_predict_group.hip: bsc_predict_pass_offset's kernel with a
  * per-draw, per-group intercept; bsc_glm_data_pass_groups is its training pass):
